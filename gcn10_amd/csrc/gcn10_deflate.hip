@@ -1586,6 +1586,14 @@ int deflate_launch_codes(gcn10_gpu_ctx *ctx, const TileJob &job, uint32_t nblock
     return GCN10_OK;
 }
 
+int deflate_launch_place(gcn10_gpu_ctx *ctx, const TileJob &job, hipStream_t s)
+{
+    hipLaunchKernelGGL(deflate_place_kernel, dim3(1), dim3(kPlaceThreads), 0, s, job, job.across * job.down,
+                       (uint32_t)ctx->arena_segment_align);
+    HIP_TRY(hipGetLastError());
+    return GCN10_OK;
+}
+
 }  // namespace gcn10
 
 extern "C" {

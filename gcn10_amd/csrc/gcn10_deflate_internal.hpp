@@ -212,6 +212,9 @@ int deflate_workspace(gcn10_gpu_ctx *ctx, size_t need);
 // Pass B for `nblocks` (raster, tile) pairs whose statistics are in job.hist: code books to job.books,
 // sizes to job.table; with `place`, pass B' (deflate_place_kernel) behind it lays the streams out in the arena.
 int deflate_launch_codes(gcn10_gpu_ctx *ctx, const TileJob &job, uint32_t nblocks, hipStream_t s, bool place = true);
+// pass B' alone: places streams whose sizes lie in job.sizes (= job.table: { 0, bytes } per stream) -- the LZW
+// encoder (gcn10_lzw.hip) lays its streams out exactly as the tile encoders do
+int deflate_launch_place(gcn10_gpu_ctx *ctx, const TileJob &job, hipStream_t s);
 
 }  // namespace gcn10
 

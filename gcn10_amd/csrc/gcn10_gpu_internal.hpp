@@ -86,6 +86,8 @@ struct gcn10_gpu_ctx {
     size_t deflate_ws_cap = 0;
     void *inflate_ws = nullptr;     // linear slots of the tiles being decoded (gcn10_inflate.hip)
     size_t inflate_ws_cap = 0;
+    void *lzw_ws = nullptr;         // segment bit strings + their lengths of the LZW tile encoder (gcn10_lzw.hip)
+    size_t lzw_ws_cap = 0;
 };
 
 #endif

@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <strings.h>
 
 static char *strip(char *s)
 {
@@ -97,6 +98,19 @@ int gcn10_parse_conditions(const char *text, unsigned *mask)
     return 0;
 }
 
+int gcn10_parse_compress(const char *text, int *codec)
+{
+    if (!text)
+        return -1;
+    if (!strcasecmp(text, "deflate"))
+        *codec = GCN10_COMPRESS_DEFLATE;
+    else if (!strcasecmp(text, "lzw"))
+        *codec = GCN10_COMPRESS_LZW;
+    else
+        return -1;
+    return 0;
+}
+
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap)
 {
     char line[512];                                     /* src/config.c:47 */
@@ -168,6 +182,12 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
                 return -3;
             }
         }
+        else if (!strcmp(key, "compress") && gcn10_parse_compress(val, &cfg->compress) != 0) {
+            fclose(f);
+            snprintf(err, errcap, "bad value for compress: '%s' (deflate or lzw)", val);
+            gcn10_config_free(cfg);
+            return -3;
+        }
         if (rc != 0) {
             fclose(f);
             snprintf(err, errcap, "malloc failed for %s", key);     /* src/config.c:71 */
@@ -176,6 +196,12 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
         }
     }
     fclose(f);
+    if (cfg->compress == GCN10_COMPRESS_LZW && cfg->gpu_deflate == 0) {
+        snprintf(err, errcap, "bad value for compress: 'lzw' with gpu_deflate=0 (LZW tiles are encoded on the GPU "
+                              "only; there is no host LZW encoder)");
+        gcn10_config_free(cfg);
+        return -3;
+    }
 
     if (!cfg->hysogs_data_path || !cfg->esa_data_path || !cfg->blocks_shp_path ||
         !cfg->lookup_table_path || !cfg->log_dir) {

@@ -81,6 +81,9 @@ static void load_once(void)
     BIND(deflate_fused_strip); BIND(deflate_fused_available); BIND(inflate_tiles);
 #undef BIND
     *(void **)(&g_api.set_option) = dlsym(h, "gcn10_gpu_set_option");    /* tuning only: may be absent (tests' stand-in) */
+    /* the LZW encoder: needed by compress=lzw runs only, which check for it (may be absent: tests' stand-in) */
+    *(void **)(&g_api.lzw_arena_bound) = dlsym(h, "gcn10_gpu_lzw_arena_bound");
+    *(void **)(&g_api.lzw_strip) = dlsym(h, "gcn10_gpu_lzw_strip");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

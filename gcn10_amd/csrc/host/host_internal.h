@@ -104,6 +104,9 @@ struct gcn10_gpu_api {
     int (*deflate_strip)(gcn10_gpu_ctx *, const uint8_t *const *, int, int, int, uint8_t *, size_t,
                          uint32_t *, unsigned long long *, gcn10_stream_t);
     int (*set_option)(gcn10_gpu_ctx *, const char *, int);     /* optional (tuning): NULL when the library has none */
+    size_t (*lzw_arena_bound)(int, int, int);                   /* optional: NULL when the library has none */
+    int (*lzw_strip)(gcn10_gpu_ctx *, const uint8_t *const *, int, int, int, uint8_t *, size_t,
+                     uint32_t *, unsigned long long *, gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -4,7 +4,8 @@
  *   gcn10 -c|--config <file> [-l|--blocks <file>] [-o|--overwrite] [-h|--help] [-v|--version]
  * plus -b as a synonym of -l (the reference's usage text advertises -b,
  * src/main.c:28, while its parser only takes -l, src/main.c:90), --gpus N, and --lookups /
- * --conditions to produce a subset of the 18 rasters (BASELINE config 3: "single lookup").
+ * --conditions to produce a subset of the 18 rasters (BASELINE config 3: "single lookup"), and --compress to
+ * write LZW instead of DEFLATE GeoTIFFs.
  * No mpirun: one process drives every GPU of the node.
  */
 #include "gcn10_host.h"
@@ -19,7 +20,7 @@ static void usage(FILE *fp)
             "gcn10 - high-resolution curve number generator, MI355X edition\n"
             "usage:\n"
             "  gcn10 --config <config.txt> [--blocks <blocks.txt>] [--overwrite] [--gpus <n>]\n"
-            "        [--lookups <names>] [--conditions drained|undrained|both]\n"
+            "        [--lookups <names>] [--conditions drained|undrained|both] [--compress deflate|lzw]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -29,6 +30,7 @@ static void usage(FILE *fp)
             "  --gpus <n>\t\tnumber of GPUs to use (default: all visible)\n"
             "  --lookups <names>\tonly these lookups, e.g. g_ii or p_i,f_iii (default: all nine)\n"
             "  --conditions <c>\tdrained, undrained or both (default: both)\n"
+            "  --compress <c>\tdeflate or lzw: compression of the GeoTIFFs (default: deflate)\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -67,6 +69,8 @@ int main(int argc, char **argv)
             opt.lookups = argv[++i];
         else if (!strcmp(argv[i], "--conditions") && i + 1 < argc)
             opt.conditions = argv[++i];
+        else if (!strcmp(argv[i], "--compress") && i + 1 < argc)
+            opt.compress = argv[++i];
     }
     return gcn10_run(&opt);
 }

@@ -411,7 +411,8 @@ static int ensure_strip_buffers(struct worker *w, int W)
         if (w->run->gpu_deflate) {
             size_t tiles = n_tiles;
 
-            b->arena_cap = g->deflate_arena_bound(W, w->strip_rows, GCN10_N_RASTERS);
+            b->arena_cap = w->run->lzw ? g->lzw_arena_bound(W, w->strip_rows, GCN10_N_RASTERS)
+                                       : g->deflate_arena_bound(W, w->strip_rows, GCN10_N_RASTERS);
             GPU_TRY(w, g->malloc(w->ctx, b->arena_cap + 4096, (void **)&b->d_arena));
             b->h_arena_cap = b->arena_cap / 8 > ((size_t)32 << 20) ? b->arena_cap / 8 : ((size_t)32 << 20);
             if (getenv("GCN10_PINNED_ARENA_BYTES"))        /* tests: force the spill path */
@@ -534,6 +535,8 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
             w->t_create += now_seconds() - t_mark;
             return 1;
         }
+        if (r->lzw)
+            (void)gcn10_tiff_set_compression(in->tifs[k], 5);
         if (r->direct_io && r->gpu_deflate)
             gcn10_tiff_set_direct(in->tifs[k], true);   /* best effort: a file system that refuses writes buffered */
     }
@@ -628,8 +631,8 @@ static int encode_block(struct worker *w, struct block_in *in)
                 goto gpu_fail;
             /* encode the selected strips where they are */
             if (r->gpu_deflate &&
-                g->deflate_strip(w->ctx, b->d_ptrs, r->n_sel, W, rows, b->d_arena, b->arena_cap,
-                                 b->d_table, b->d_cursor, w->s_kernel) != 0)
+                (r->lzw ? g->lzw_strip : g->deflate_strip)(w->ctx, b->d_ptrs, r->n_sel, W, rows, b->d_arena,
+                                                           b->arena_cap, b->d_table, b->d_cursor, w->s_kernel) != 0)
                 goto gpu_fail;
         }
         if (g->event_record(w->ctx, b->ev_kernel, w->s_kernel) != 0 ||
@@ -1080,6 +1083,19 @@ int gcn10_run(const gcn10_run_options *opt)
         free(r);
         return 1;
     }
+    if (opt->compress && gcn10_parse_compress(opt->compress, &r->cfg.compress) != 0) {
+        fprintf(stderr, "[rank 0] bad value for compress: '%s' (deflate or lzw)\n", opt->compress);
+        gcn10_config_free(&r->cfg);
+        free(r);
+        return 1;
+    }
+    if (r->cfg.compress == GCN10_COMPRESS_LZW && r->cfg.gpu_deflate == 0) {
+        fprintf(stderr, "[rank 0] bad value for compress: 'lzw' with gpu_deflate=0 (LZW tiles are encoded on the GPU "
+                        "only; there is no host LZW encoder)\n");
+        gcn10_config_free(&r->cfg);
+        free(r);
+        return 1;
+    }
     for (int k = 0; k < GCN10_N_RASTERS; k++)
         if ((r->cond_mask >> (k / 9)) & 1u && (r->table_mask >> (k % 9)) & 1u)
             r->sel[r->n_sel++] = k;
@@ -1097,7 +1113,8 @@ int gcn10_run(const gcn10_run_options *opt)
         r->strip_rows = MAX_STRIP_ROWS;
     r->deflate_level = r->cfg.deflate_level;
     r->gpu_deflate = r->cfg.gpu_deflate != 0;
-    r->fused = r->cfg.gpu_deflate == 2;
+    r->lzw = r->cfg.compress == GCN10_COMPRESS_LZW;
+    r->fused = r->cfg.gpu_deflate == 2 && !r->lzw;     /* the fused encoder is DEFLATE-only */
     r->gpu_inflate = r->cfg.gpu_inflate != 0;
     r->direct_io = r->cfg.direct_io != 0 || (getenv("GCN10_DIRECT_IO") && atoi(getenv("GCN10_DIRECT_IO")) != 0);
     r->prefetch = r->cfg.prefetch_blocks != 0 && !(getenv("GCN10_PREFETCH_BLOCKS") && atoi(getenv("GCN10_PREFETCH_BLOCKS")) == 0);
@@ -1120,6 +1137,10 @@ int gcn10_run(const gcn10_run_options *opt)
     r->gpu = gcn10_gpu_api_get(err, sizeof err);
     if (!r->gpu) {
         fprintf(stderr, "[rank 0] %s\n", err);
+        goto done;
+    }
+    if (r->lzw && (!r->gpu->lzw_strip || !r->gpu->lzw_arena_bound)) {
+        fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_lzw_strip (needed by compress=lzw)\n", gcn10_gpu_library_path());
         goto done;
     }
     n_dev = r->gpu->device_count();
@@ -1357,7 +1378,7 @@ int gcn10_run(const gcn10_run_options *opt)
                  "soil window %.3f, creating outputs %.3f, finishing outputs %.3f, device setup %.3f, "
                  "waiting for input %.3f; input thread seconds: %.3f%s",
                  done_blocks, now_seconds() - t_start, steady, r->n_workers, r->null_sink ? ", null sink" : "",
-                 r->gpu_deflate ? (r->fused ? ", fused gpu deflate" : ", gpu deflate") : ", host zlib",
+                 r->lzw ? ", gpu lzw" : r->gpu_deflate ? (r->fused ? ", fused gpu deflate" : ", gpu deflate") : ", host zlib",
                  r->gpu_inflate ? ", gpu inflate of deflate landcover" : "", busy, rd, gw, sw, so, cr, fi, dv, iw, ib,
                  r->prefetch ? " (one block ahead of the encoder)" : " (in turn with the encoder)");
         gcn10_log_message(log0, "INFO", msg, false);

@@ -141,6 +141,7 @@ struct run {
     bool null_sink;                         /* GCN10_SINK=null: no compression, no files */
     bool gpu_deflate;                       /* tiles are encoded on the GPU */
     bool fused;                             /* ... straight from landcover + soil (no CN rasters in HBM) */
+    bool lzw;                               /* ... as TIFF LZW streams (compress=lzw: per-raster, never fused) */
     bool gpu_inflate;                       /* DEFLATE landcover tiles are decoded on the GPU */
     bool direct_io;                         /* tile data is written with O_DIRECT */
     bool prefetch;                          /* input threads stage block N+1 while block N is encoded */

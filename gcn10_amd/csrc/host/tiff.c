@@ -1045,6 +1045,7 @@ struct gcn10_tiff_writer {
     pthread_mutex_t mu;
     bool failed;
     bool direct;                /* O_DIRECT is set on fd: extents go out at 4096-aligned positions */
+    int compression;            /* TIFF Compression tag: 8 (Adobe deflate, default) or 5 (LZW) */
 };
 
 static int write_all(int fd, const void *buf, size_t n, uint64_t off)
@@ -1108,6 +1109,14 @@ static int copy_georef(gcn10_georef *dst, const gcn10_georef *src)
     return 0;
 }
 
+int gcn10_tiff_set_compression(gcn10_tiff_writer *w, int compression)
+{
+    if (compression != 8 && compression != 5)
+        return -1;
+    w->compression = compression;
+    return 0;
+}
+
 gcn10_tiff_writer *gcn10_tiff_create(const char *path, int xsize, int ysize, const double gt[6],
                                      const gcn10_georef *georef, char *err, size_t errcap)
 {
@@ -1123,6 +1132,7 @@ gcn10_tiff_writer *gcn10_tiff_create(const char *path, int xsize, int ysize, con
     if (!w)
         goto oom;
     w->fd = -1;
+    w->compression = 8;
     pthread_mutex_init(&w->mu, NULL);
     w->xsize = xsize;
     w->ysize = ysize;
@@ -1380,7 +1390,7 @@ int gcn10_tiff_finish(gcn10_tiff_writer *w, char *err, size_t errcap)
     put32(s_w, (uint32_t)w->xsize);
     put32(s_h, (uint32_t)w->ysize);
     put16(s_bps, 8);
-    put16(s_comp, 8);           /* COMPRESS=DEFLATE -> Adobe deflate */
+    put16(s_comp, (unsigned)w->compression);     /* COMPRESS=DEFLATE -> Adobe deflate (8); COMPRESS=LZW -> 5 */
     put16(s_phot, 1);           /* MinIsBlack */
     put16(s_spp, 1);
     put16(s_plan, 1);

@@ -42,7 +42,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_pci_bus_id", "gcn10_gpu_deflate_fused_strip",
     "gcn10_gpu_deflate_fused_available",
     "gcn10_gpu_inflate_tiles", "gcn10_gpu_stream_copy", "gcn10_gpu_tune_single_raster",
-    "gcn10_gpu_soil_words_state",
+    "gcn10_gpu_soil_words_state", "gcn10_gpu_lzw_arena_bound", "gcn10_gpu_lzw_strip",
 )
 
 
@@ -112,6 +112,8 @@ def lib():
             "gcn10_gpu_inflate_tiles": (i, [vp, vp, vp, i, u, vp, sz, vp, vp]),
             "gcn10_gpu_deflate_arena_bound": (sz, [i, i, i]),
             "gcn10_gpu_deflate_strip": (i, [vp, vp, i, i, i, vp, sz, vp, vp, vp]),
+            "gcn10_gpu_lzw_arena_bound": (sz, [i, i, i]),
+            "gcn10_gpu_lzw_strip": (i, [vp, vp, i, i, i, vp, sz, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -356,6 +358,33 @@ class Engine:
             self._chk(lib().gcn10_gpu_deflate_strip(self._ctx, ptrs.ptr, n, W, rows, arena.ptr, cap,
                                                     table.ptr, cursor.ptr, stream),
                       "gcn10_gpu_deflate_strip")
+            used = int(self.download(cursor.ptr, (1,), dtype=np.uint64, stream=stream)[0])
+            tab = self.download(table.ptr, (n, down, across, 2), dtype=np.uint32, stream=stream)
+            data = self.download(arena.ptr, (min(used, cap),), stream=stream)
+        finally:
+            for b in (ptrs, arena, table, cursor):
+                b.close()
+        return data, tab, used
+
+    def lzw_arena_bound(self, W: int, rows: int, n_rasters: int) -> int:
+        """Worst-case arena bytes of gcn10_gpu_lzw_strip for n_rasters strips of W x rows."""
+        return int(lib().gcn10_gpu_lzw_arena_bound(W, rows, n_rasters))
+
+    def lzw_strip(self, raster_ptrs: Sequence[int], W: int, rows: int, stream=None, arena_cap: Optional[int] = None):
+        """TIFF-LZW-encodes every 256x256 tile of the given device rasters (gcn10_gpu_lzw_strip).
+
+        Returns (arena bytes as uint8 array, table uint32[n, down, across, 2], used).
+        arena_cap: an arena smaller than lzw_arena_bound (tests: streams that do not fit)."""
+        n = len(raster_ptrs)
+        across, down = (W + 255) // 256, (rows + 255) // 256
+        cap = self.lzw_arena_bound(W, rows, n) if arena_cap is None else int(arena_cap)
+        ptrs = self.upload(np.array(raster_ptrs, dtype=np.uint64))
+        arena = self.alloc(max(cap, 16))
+        table = self.alloc(n * across * down * 8)
+        cursor = self.alloc(8)
+        try:
+            self._chk(lib().gcn10_gpu_lzw_strip(self._ctx, ptrs.ptr, n, W, rows, arena.ptr, cap, table.ptr,
+                                                cursor.ptr, stream), "gcn10_gpu_lzw_strip")
             used = int(self.download(cursor.ptr, (1,), dtype=np.uint64, stream=stream)[0])
             tab = self.download(table.ptr, (n, down, across, 2), dtype=np.uint32, stream=stream)
             data = self.download(arena.ptr, (min(used, cap),), stream=stream)

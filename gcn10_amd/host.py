@@ -87,7 +87,7 @@ class Config(C.Structure):
                 ("io_threads", C.c_int), ("deflate_level", C.c_int), ("esa_tile_dir", C.c_char_p),
                 ("gpu_deflate", C.c_int), ("gpu_inflate", C.c_int), ("direct_io", C.c_int),
                 ("prefetch_blocks", C.c_int),
-                ("table_mask", C.c_uint), ("cond_mask", C.c_uint)]
+                ("table_mask", C.c_uint), ("cond_mask", C.c_uint), ("compress", C.c_int)]
 
 
 class Blocks(C.Structure):

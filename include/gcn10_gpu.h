@@ -203,6 +203,17 @@ int gcn10_gpu_deflate_strip(gcn10_gpu_ctx *ctx, const uint8_t *const *rasters_de
                             size_t arena_cap, uint32_t *table_dev,
                             unsigned long long *cursor_dev, gcn10_stream_t stream);
 
+/* The same contract with TIFF LZW streams (TIFF 6.0 section 13, Compression 5; config key compress=lzw): every
+ * 256x256 tile (edge tiles zero padded) becomes one complete LZW stream -- MSB-first 9..12-bit codes, early
+ * change, starting with ClearCode, ending with EndOfInformation, padded to a byte -- and streams, table and
+ * cursor are laid out exactly as by gcn10_gpu_deflate_strip (offset 0xffffffff: the arena was too small; nothing
+ * is written past arena_cap).  gcn10_gpu_lzw_arena_bound covers incompressible tiles.  Added in ABI 3 without a
+ * version change: a caller that needs them looks them up (the host program does, and only for LZW runs). */
+size_t gcn10_gpu_lzw_arena_bound(int W, int rows, int n_rasters);
+int gcn10_gpu_lzw_strip(gcn10_gpu_ctx *ctx, const uint8_t *const *rasters_dev, int n_rasters, int W, int rows,
+                        uint8_t *arena_dev, size_t arena_cap, uint32_t *table_dev,
+                        unsigned long long *cursor_dev, gcn10_stream_t stream);
+
 /* The same encoding WITHOUT materialising the CN rasters: the strip's landcover and the
  * block's x-expanded soil (gcn10_gpu_prepare_tile) are reduced to pixel classes once per
  * tile position, tokenised once, and the selected rasters' streams are produced from that

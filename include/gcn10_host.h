@@ -111,14 +111,21 @@ typedef struct gcn10_config {
                                order p,f,g x i,ii,iii (src/cn.c:146-147) */
     unsigned cond_mask;     /* "conditions": "drained", "undrained" or "both" (absent = both);
                                bit 0 = drained, bit 1 = undrained (src/cn.c:145) */
+    int compress;           /* "compress": GCN10_COMPRESS_DEFLATE (default, "deflate") or GCN10_COMPRESS_LZW ("lzw"),
+                               case-insensitive as GDAL's COMPRESS=; LZW tiles are encoded on the GPU only, so
+                               "lzw" with gpu_deflate=0 is refused */
 } gcn10_config;
+
+enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
 
 /* "g_ii", "p_i,f_iii", "all" -> table mask; "drained" | "undrained" | "both" | "all" -> condition mask.
  * Return 0 and set *mask, or -1 for a name that is not a lookup / condition. */
 int gcn10_parse_lookups(const char *text, unsigned *mask);
 int gcn10_parse_conditions(const char *text, unsigned *mask);
+/* "deflate" | "lzw" (any case) -> GCN10_COMPRESS_*.  0, or -1 for another name. */
+int gcn10_parse_compress(const char *text, int *codec);
 
-/* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" value; -2 a required key is missing
+/* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -200,6 +207,8 @@ int gcn10_tiff_put_tiles(gcn10_tiff_writer *w, int n, const int *tx, const int *
  * them.  What the GPU encoders produce for a raster and a strip. */
 int gcn10_tiff_put_extent(gcn10_tiff_writer *w, const void *data, size_t extent_bytes, int n, const int *tx,
                           const int *ty, const uint32_t *rel_off, const uint32_t *nbytes);
+/* TIFF Compression tag of the file: 8 (default, Adobe deflate: zlib streams) or 5 (LZW streams).  0 or -1. */
+int gcn10_tiff_set_compression(gcn10_tiff_writer *w, int compression);
 /* O_DIRECT for the tile data (config key "direct_io"): extents must then be 4096-aligned in memory and
  * readable to the next multiple of 4096.  0 = on, -1 = the file system refuses (nothing changed). */
 int gcn10_tiff_set_direct(gcn10_tiff_writer *w, bool on);
@@ -231,6 +240,7 @@ typedef struct gcn10_run_options {
     int gpus;                   /* --gpus N, 0 = config key "gpus" or all visible */
     const char *lookups;        /* --lookups g_ii[,..]: overrides the config key "lookups"       */
     const char *conditions;     /* --conditions drained|undrained|both: overrides "conditions" */
+    const char *compress;       /* --compress deflate|lzw: overrides the config key "compress"   */
 } gcn10_run_options;
 
 /* Runs the whole job: config, logs, block ids, lookup tables, one worker thread

@@ -80,17 +80,8 @@ enum {
     kErrWindow = 8,         // the descriptor's window does not lie inside its chunk
 };
 
-// the wanted window must lie inside the decoded chunk (and the chunk inside its slot)
-__device__ __forceinline__ bool window_ok(uint32_t out_len, uint32_t chunk_w, uint32_t src_x, uint32_t src_y,
-                                          uint32_t copy_w, uint32_t copy_h, uint32_t slot_bytes)
-{
-    if (copy_w == 0 || copy_h == 0)
-        return true;
-    if (chunk_w == 0 || out_len > slot_bytes || src_x > chunk_w || copy_w > chunk_w - src_x)
-        return false;
-    const unsigned long long last = (unsigned long long)(src_y + copy_h - 1u) * chunk_w + src_x + copy_w;
-    return (unsigned long long)src_y + copy_h <= 0xffffffffull && last <= out_len;
-}
+// the wanted window must lie inside the decoded chunk (and the chunk inside its slot): gcn10::inflate_window_ok
+using gcn10::inflate_window_ok;
 
 struct Code {               // canonical code, by length
     uint16_t count[16];
@@ -1262,7 +1253,7 @@ __device__ __forceinline__ uint32_t copy_batch(Shared &sh, Output &o, const uint
 __device__ __forceinline__ bool tile_in_place(const TileIn &t, uint32_t slot_bytes, const uint8_t *dst, unsigned long long dst_stride)
 {
     const uint32_t w = t.chunk_w;
-    return !(t.flags & (GCN10_TILE_RAW | GCN10_TILE_PREDICTOR2)) && w >= 16u && (w & (w - 1u)) == 0u && t.src_x == 0u &&
+    return !(t.flags & (GCN10_TILE_RAW | GCN10_TILE_PREDICTOR2 | GCN10_TILE_LZW)) && w >= 16u && (w & (w - 1u)) == 0u && t.src_x == 0u &&
            t.src_y == 0u && t.copy_w == w && t.copy_h > 0u && (unsigned long long)t.copy_h * w == t.out_len &&
            t.out_len <= slot_bytes && ((reinterpret_cast<uintptr_t>(dst) | t.dst_off | dst_stride) & 15u) == 0u;
 }
@@ -1284,11 +1275,13 @@ __global__ __launch_bounds__(128) void inflate_kernel(const uint8_t *comp, const
     if (tile >= n_tiles)
         return;
     const TileIn tin = tiles[tile];
+    if (tin.flags & GCN10_TILE_LZW)
+        return;                                 // lzw_decode_kernel's (gcn10_lzw_decode.hip)
     if (tin.flags & GCN10_TILE_RAW) {
         // not a zlib stream: the chunk's bytes lie in `comp` as they are; untile_kernel copies the window
         if (threadIdx.x == 0)
             status[tile] = tin.in_len >= tin.out_len &&
-                                   window_ok(tin.out_len, tin.chunk_w, tin.src_x, tin.src_y, tin.copy_w, tin.copy_h,
+                                   inflate_window_ok(tin.out_len, tin.chunk_w, tin.src_x, tin.src_y, tin.copy_w, tin.copy_h,
                                              0xffffffffu)
                                ? 0u
                                : (uint32_t)kErrWindow;
@@ -1367,7 +1360,7 @@ __global__ __launch_bounds__(128) void inflate_kernel(const uint8_t *comp, const
     if (wave == 0)
         return;
     uint32_t err = c_err ? c_err : uniform(sh.err);
-    if (!err && !window_ok(tin.out_len, tin.chunk_w, tin.src_x, tin.src_y, tin.copy_w, tin.copy_h, slot_bytes))
+    if (!err && !inflate_window_ok(tin.out_len, tin.chunk_w, tin.src_x, tin.src_y, tin.copy_w, tin.copy_h, slot_bytes))
         err = kErrWindow;
 
     // what is still in the window, then zeros up to the tile's size (as a short stream reads on the host)
@@ -1392,8 +1385,10 @@ __global__ __launch_bounds__(256) void untile_kernel(const TileIn *tiles, const 
 {
     typedef uint32_t u32_u __attribute__((aligned(1)));
     const TileIn tin = tiles[blockIdx.x];
+    if ((tin.flags & (GCN10_TILE_RAW | GCN10_TILE_LZW)) == (GCN10_TILE_RAW | GCN10_TILE_LZW))
+        return;                                 // no such tile: lzw_decode_kernel has set the status
     const bool raw = (tin.flags & GCN10_TILE_RAW) != 0;
-    if (!window_ok(tin.out_len, tin.chunk_w, tin.src_x, tin.src_y, tin.copy_w, tin.copy_h, raw ? 0xffffffffu : slot_bytes) ||
+    if (!inflate_window_ok(tin.out_len, tin.chunk_w, tin.src_x, tin.src_y, tin.copy_w, tin.copy_h, raw ? 0xffffffffu : slot_bytes) ||
         (raw && tin.in_len < tin.out_len))
         return;                                 // inflate_kernel has set the status
     if (tile_in_place(tin, slot_bytes, dst, dst_stride))
@@ -1498,11 +1493,18 @@ int gcn10_gpu_inflate_tiles(gcn10_gpu_ctx *ctx, const uint8_t *comp_dev, const g
     hipLaunchKernelGGL(inflate_kernel, dim3((uint32_t)n_tiles), dim3(128), sizeof(Shared), s, comp_dev,
                        reinterpret_cast<const TileIn *>(tiles_dev), (uint32_t)n_tiles, scratch, slot, status_dev,
                        (uint32_t)ctx->inflate_diag, dst_dev, (unsigned long long)dst_stride);
+    // LZW tiles (GCN10_TILE_LZW) into their slots; every other tile leaves at once
+    gcn10::launch_lzw_decode(comp_dev, tiles_dev, (uint32_t)n_tiles, scratch, slot, status_dev, s);
     hipLaunchKernelGGL(untile_kernel, dim3((uint32_t)n_tiles, 16), dim3(256), 0, s,
                        reinterpret_cast<const TileIn *>(tiles_dev), scratch, slot, comp_dev, dst_dev,
                        (unsigned long long)dst_stride);
     HIP_TRY(hipGetLastError());
     return GCN10_OK;
+}
+
+int gcn10_gpu_inflate_codecs(void)
+{
+    return (int)(GCN10_CODEC_DEFLATE | GCN10_CODEC_RAW | GCN10_CODEC_LZW);
 }
 
 }  // extern "C"

@@ -119,6 +119,7 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
     memset(cfg, 0, sizeof *cfg);
     cfg->gpu_deflate = 2;
     cfg->gpu_inflate = 1;
+    cfg->gpu_inflate_lzw = 1;
     cfg->prefetch_blocks = 1;
     cfg->table_mask = 0x1ffu;
     cfg->cond_mask = 3u;
@@ -161,6 +162,8 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             cfg->strip_rows = atoi(val);
         else if (!strcmp(key, "gpu_inflate"))
             cfg->gpu_inflate = atoi(val) != 0;
+        else if (!strcmp(key, "gpu_inflate_lzw"))
+            cfg->gpu_inflate_lzw = atoi(val) != 0;
         else if (!strcmp(key, "io_threads"))
             cfg->io_threads = atoi(val);
         else if (!strcmp(key, "direct_io"))

@@ -84,6 +84,8 @@ static void load_once(void)
     /* the LZW encoder: needed by compress=lzw runs only, which check for it (may be absent: tests' stand-in) */
     *(void **)(&g_api.lzw_arena_bound) = dlsym(h, "gcn10_gpu_lzw_arena_bound");
     *(void **)(&g_api.lzw_strip) = dlsym(h, "gcn10_gpu_lzw_strip");
+    /* the chunk codecs of gcn10_gpu_inflate_tiles (may be absent: then LZW landcover goes through the host reader) */
+    *(void **)(&g_api.inflate_codecs) = dlsym(h, "gcn10_gpu_inflate_codecs");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -43,7 +43,7 @@ struct gcn10_chunk_ref {
     uint32_t src_x, src_y;      /* first wanted pixel of the chunk */
     uint32_t copy_w, copy_h;
     uint32_t dst_x, dst_y;      /* where it goes in the window */
-    uint32_t flags;             /* GCN10_TILE_RAW | GCN10_TILE_PREDICTOR2 (gcn10_inflate_tile.flags) */
+    uint32_t flags;             /* GCN10_TILE_RAW | GCN10_TILE_PREDICTOR2 | GCN10_TILE_LZW (gcn10_inflate_tile.flags) */
     uint32_t out_len;           /* bytes the chunk stands for on the device: decoded size, or nbytes of a raw one */
 };
 struct gcn10_read_plan {
@@ -59,8 +59,13 @@ struct gcn10_read_plan {
  * sources, full-width raw strips of a much wider raster ...): use gcn10_raster_read_mt; -1 = error (err is set). */
 int gcn10_raster_plan_window(gcn10_raster *r, int xoff, int yoff, int xcount, int ycount,
                              struct gcn10_read_plan *plan, char *err, size_t errcap);
+/* the same for the chunk codecs in `codecs` (GCN10_CODEC_* of gcn10_gpu.h): with GCN10_CODEC_LZW, LZW chunks
+ * are planned too (flags GCN10_TILE_LZW, plus GCN10_TILE_PREDICTOR2 as the file says), under the rules of
+ * DEFLATE chunks; gcn10_raster_plan_window = DEFLATE | RAW */
+int gcn10_raster_plan_window_codecs(gcn10_raster *r, int xoff, int yoff, int xcount, int ycount, unsigned codecs,
+                                    struct gcn10_read_plan *plan, char *err, size_t errcap);
 int gcn10_tiff_plan_window(struct gcn10_tiff *t, int xoff, int yoff, int xcount, int ycount, int dst_x,
-                           int dst_y, struct gcn10_read_plan *plan, char *err, size_t errcap);
+                           int dst_y, unsigned codecs, struct gcn10_read_plan *plan, char *err, size_t errcap);
 void gcn10_read_plan_free(struct gcn10_read_plan *plan);
 
 /* gpuapi.c: include/gcn10_gpu.h bound with dlopen */
@@ -107,6 +112,7 @@ struct gcn10_gpu_api {
     size_t (*lzw_arena_bound)(int, int, int);                   /* optional: NULL when the library has none */
     int (*lzw_strip)(gcn10_gpu_ctx *, const uint8_t *const *, int, int, int, uint8_t *, size_t,
                      uint32_t *, unsigned long long *, gcn10_stream_t);
+    int (*inflate_codecs)(void);    /* optional: NULL = DEFLATE and raw chunks only (LZW windows stay on the host) */
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -1143,6 +1143,9 @@ int gcn10_run(const gcn10_run_options *opt)
         fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_lzw_strip (needed by compress=lzw)\n", gcn10_gpu_library_path());
         goto done;
     }
+    r->inflate_codecs = GCN10_CODEC_DEFLATE | GCN10_CODEC_RAW;
+    if (r->cfg.gpu_inflate_lzw && r->gpu->inflate_codecs && (r->gpu->inflate_codecs() & GCN10_CODEC_LZW))
+        r->inflate_codecs |= GCN10_CODEC_LZW;
     n_dev = r->gpu->device_count();
     if (n_dev <= 0) {
         fprintf(stderr, "[rank 0] no MI355X (gfx950) device visible; the CN path has no CPU fallback\n");
@@ -1382,6 +1385,18 @@ int gcn10_run(const gcn10_run_options *opt)
                  r->gpu_inflate ? ", gpu inflate of deflate landcover" : "", busy, rd, gw, sw, so, cr, fi, dv, iw, ib,
                  r->prefetch ? " (one block ahead of the encoder)" : " (in turn with the encoder)");
         gcn10_log_message(log0, "INFO", msg, false);
+        {
+            long n_gpu = 0, n_lzw = 0, n_host = 0;
+
+            for (int i = 0; i < r->n_workers; i++) {
+                n_gpu += r->workers[i].n_win_gpu;
+                n_lzw += r->workers[i].n_win_gpu_lzw;
+                n_host += r->workers[i].n_win_host;
+            }
+            snprintf(msg, sizeof msg, "timing: landcover windows: %ld through the gpu decoder (of them %ld with lzw chunks), "
+                     "%ld through the host reader", n_gpu, n_lzw, n_host);
+            gcn10_log_message(log0, "INFO", msg, false);
+        }
         {
             /* CPU seconds of the whole process (all threads): against the wall time this says whether the host
              * side is what bounds the run (a cgroup CPU quota shows as user + system ~ quota x wall) */

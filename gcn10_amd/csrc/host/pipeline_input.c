@@ -12,10 +12,11 @@
  *     has the I/O pool pread the chunks -- compressed or raw, as they lie in the files -- into
  *     a ring of pinned buffers, and copies batch k to HBM (hipMemcpyAsync on its stream) while the
  *     pool fills batch k+1: the "pinned-host staging, double-buffered" of the north star,
- *   - launches gcn10_gpu_inflate_tiles on them: DEFLATE tiles are decoded, raw tiles untiled, TIFF
- *     predictor 2 undone, all in HBM, into the row-major window d_block,
- *   - (windows the GPU side cannot take -- LZW, PackBits, overlapping mosaic sources -- are read by
- *     the host reader strip by strip into the same ring and copied up the same way),
+ *   - launches gcn10_gpu_inflate_tiles on them: DEFLATE and LZW tiles are decoded, raw tiles untiled, TIFF
+ *     predictor 2 undone, all in HBM, into the row-major window d_block (LZW with gpu_inflate_lzw=1, the
+ *     default, when the GPU library reports the codec),
+ *   - (windows the GPU side cannot take -- PackBits, overlapping mosaic sources, LZW with gpu_inflate_lzw=0
+ *     -- are read by the host reader strip by strip into the same ring and copied up the same way),
  *   - records one event behind all of it and hands the slot to the worker.
  * Two slots per worker: the block being encoded and the one being staged, so at most two blocks'
  * input are resident per worker.  prefetch_blocks=0 runs the same code on the worker thread itself.
@@ -158,7 +159,7 @@ static int stage_planned(struct worker *w, struct block_in *in)
     const int W = in->W, H = in->H;
     double t0 = now_seconds();
 
-    rc = gcn10_raster_plan_window(w->esa, in->xoff, in->yoff, W, H, &plan, err, sizeof err);
+    rc = gcn10_raster_plan_window_codecs(w->esa, in->xoff, in->yoff, W, H, r->inflate_codecs, &plan, err, sizeof err);
     if (rc > 0)
         return 1;
     if (rc < 0) {
@@ -284,6 +285,12 @@ static int stage_planned(struct worker *w, struct block_in *in)
          g->memcpy_d2h(w->in_ctx, in->h_status, in->d_status, plan.n * 4, w->s_in) != 0))
         goto gpu_fail;
     in->n_inflate = plan.n;
+    w->n_win_gpu++;
+    for (size_t i = 0; i < plan.n; i++)
+        if (plan.chunks[i].flags & GCN10_TILE_LZW) {
+            w->n_win_gpu_lzw++;
+            break;
+        }
     rc = 0;
     goto out;
 
@@ -417,8 +424,10 @@ static int fill_block(struct worker *w, struct block_in *in, int block_id)
     /* the landcover window: chunks as they lie in the files -> HBM -> decoded / untiled there; what the GPU
      * side cannot take, and everything with gpu_inflate=0, through the host reader */
     rc = r->gpu_inflate ? stage_planned(w, in) : 1;
-    if (rc == 1)
+    if (rc == 1) {
+        w->n_win_host++;
         rc = stage_host(w, in);
+    }
     if (rc == 0 && g->event_record(w->in_ctx, in->ev_ready, w->s_in) != 0) {
         wlog(w, "ERROR", true, "gpu: %s", g->last_error());
         rc = -2;

@@ -117,6 +117,8 @@ struct worker {
     double t_gpu_wait, t_sink_wait;         /* where the worker thread's time goes */
     double t_create, t_finish, t_device, t_in_wait;
     double t_read, t_soil, t_in_busy;       /* ... and the input thread's */
+    long n_win_gpu, n_win_gpu_lzw, n_win_host;  /* landcover windows through the GPU decoder (of them with LZW chunks),
+                                                   through the host reader */
 };
 
 struct run {
@@ -143,6 +145,8 @@ struct run {
     bool fused;                             /* ... straight from landcover + soil (no CN rasters in HBM) */
     bool lzw;                               /* ... as TIFF LZW streams (compress=lzw: per-raster, never fused) */
     bool gpu_inflate;                       /* DEFLATE landcover tiles are decoded on the GPU */
+    unsigned inflate_codecs;                /* GCN10_CODEC_* the read plans hand to the GPU decoder (LZW: gpu_inflate_lzw=1
+                                               and a library that decodes it) */
     bool direct_io;                         /* tile data is written with O_DIRECT */
     bool prefetch;                          /* input threads stage block N+1 while block N is encoded */
     int n_devices;                          /* GPUs of the run; worker i belongs to GPU i % n_devices */

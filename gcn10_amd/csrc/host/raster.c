@@ -394,6 +394,13 @@ void gcn10_read_plan_free(struct gcn10_read_plan *plan)
 int gcn10_raster_plan_window(gcn10_raster *r, int xoff, int yoff, int xcount, int ycount,
                              struct gcn10_read_plan *plan, char *err, size_t errcap)
 {
+    return gcn10_raster_plan_window_codecs(r, xoff, yoff, xcount, ycount, GCN10_CODEC_DEFLATE | GCN10_CODEC_RAW,
+                                           plan, err, errcap);
+}
+
+int gcn10_raster_plan_window_codecs(gcn10_raster *r, int xoff, int yoff, int xcount, int ycount, unsigned codecs,
+                                    struct gcn10_read_plan *plan, char *err, size_t errcap)
+{
     int rc = 0;
 
     memset(plan, 0, sizeof *plan);
@@ -404,7 +411,7 @@ int gcn10_raster_plan_window(gcn10_raster *r, int xoff, int yoff, int xcount, in
         return -1;
     }
     if (r->tiff) {
-        rc = gcn10_tiff_plan_window(r->tiff, xoff, yoff, xcount, ycount, 0, 0, plan, err, errcap);
+        rc = gcn10_tiff_plan_window(r->tiff, xoff, yoff, xcount, ycount, 0, 0, codecs, plan, err, errcap);
         if (rc != 0)
             gcn10_read_plan_free(plan);
         return rc;
@@ -451,7 +458,7 @@ int gcn10_raster_plan_window(gcn10_raster *r, int xoff, int yoff, int xcount, in
         plan->opened = g;
         plan->opened[plan->n_opened++] = t;
         rc = gcn10_tiff_plan_window(t, s->sx + (x0 - s->dx), s->sy + (y0 - s->dy), x1 - x0, y1 - y0,
-                                    x0 - xoff, y0 - yoff, plan, err, errcap);
+                                    x0 - xoff, y0 - yoff, codecs, plan, err, errcap);
     }
     if (rc != 0)
         gcn10_read_plan_free(plan);

@@ -457,8 +457,11 @@ static int lzw_decode(const unsigned char *src, size_t n, unsigned char *dst, si
         }
         code = (int)((bits >> (nbits - width)) & ((1u << width) - 1));
         nbits -= width;
-        if (code == EOI)
+        if (code == EOI) {
+            if (op < cap)               /* an early EOI leaves zeros, as a short DEFLATE chunk does */
+                memset(dst + op, 0, cap - op);
             break;
+        }
         if (code == CLEAR) {
             width = 9;
             next = FIRST;
@@ -929,17 +932,19 @@ int gcn10_tiff_read_window(struct gcn10_tiff *t, int xoff, int yoff, int xcount,
 }
 
 /* The chunks of a window as they lie in the file, for the GPU side: DEFLATE chunks are inflated
- * there, uncompressed chunks are only untiled there, and TIFF predictor 2 (horizontal differencing)
- * is undone there in either case.  LZW and PackBits stay with the host reader (return 1).  Mirrors
- * the clipping of read_chunk().  Of an uncompressed chunk only the bytes from the first wanted pixel
- * to the last wanted pixel are staged. */
+ * there, LZW chunks decoded there when `codecs` has GCN10_CODEC_LZW, uncompressed chunks are only
+ * untiled there, and TIFF predictor 2 (horizontal differencing) is undone there in every case.  Other
+ * codecs (PackBits; LZW without the bit) stay with the host reader (return 1).  Mirrors the clipping
+ * of read_chunk().  Of an uncompressed chunk only the bytes from the first wanted pixel to the last
+ * wanted pixel are staged. */
 int gcn10_tiff_plan_window(struct gcn10_tiff *t, int xoff, int yoff, int xcount, int ycount, int dst_x,
-                           int dst_y, struct gcn10_read_plan *plan, char *err, size_t errcap)
+                           int dst_y, unsigned codecs, struct gcn10_read_plan *plan, char *err, size_t errcap)
 {
-    const bool raw = t->compression == 1;
-    const bool deflate = t->compression == 8 || t->compression == 32946;
+    const bool raw = t->compression == 1 && (codecs & GCN10_CODEC_RAW);
+    const bool deflate = (t->compression == 8 || t->compression == 32946) && (codecs & GCN10_CODEC_DEFLATE);
+    const bool lzw = t->compression == 5 && (codecs & GCN10_CODEC_LZW);
 
-    if ((!raw && !deflate) || (t->predictor != 1 && t->predictor != 2) || t->spp != 1 ||
+    if ((!raw && !deflate && !lzw) || (t->predictor != 1 && t->predictor != 2) || t->spp != 1 ||
         t->bps != 8 || (uint64_t)t->cw * t->ch > ((uint64_t)1 << 28))
         return 1;
     if (xoff < 0 || yoff < 0 || xcount <= 0 || ycount <= 0 ||
@@ -994,7 +999,8 @@ int gcn10_tiff_plan_window(struct gcn10_tiff *t, int xoff, int yoff, int xcount,
             c->dst_y = (uint32_t)dst_y + (ys - (uint32_t)yoff);
             /* (the Predictor tag belongs to the LZW / DEFLATE codecs: libtiff, and with it GDAL, ignores it on
              * uncompressed data, and so does decode_chunk()) */
-            c->flags = raw ? GCN10_TILE_RAW : (t->predictor == 2 ? GCN10_TILE_PREDICTOR2 : 0u);
+            c->flags = raw ? GCN10_TILE_RAW
+                           : (t->predictor == 2 ? GCN10_TILE_PREDICTOR2 : 0u) | (lzw ? GCN10_TILE_LZW : 0u);
             c->out_len = t->cw * rows;
             if (raw) {
                 /* the bytes that matter: from the first wanted pixel to the last one */

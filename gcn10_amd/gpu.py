@@ -43,11 +43,15 @@ ABI_SYMBOLS = (
     "gcn10_gpu_deflate_fused_available",
     "gcn10_gpu_inflate_tiles", "gcn10_gpu_stream_copy", "gcn10_gpu_tune_single_raster",
     "gcn10_gpu_soil_words_state", "gcn10_gpu_lzw_arena_bound", "gcn10_gpu_lzw_strip",
+    "gcn10_gpu_inflate_codecs",
 )
 
 
 # struct gcn10_inflate_tile (include/gcn10_gpu.h)
-TILE_RAW, TILE_PREDICTOR2 = 1, 2          # gcn10_inflate_tile.flags (include/gcn10_gpu.h)
+TILE_RAW, TILE_PREDICTOR2, TILE_LZW = 1, 2, 4     # gcn10_inflate_tile.flags (include/gcn10_gpu.h)
+CODEC_DEFLATE, CODEC_RAW, CODEC_LZW = 1, 2, 4       # gcn10_gpu_inflate_codecs() bits
+# gcn10_inflate_tiles status words of LZW tiles (GCN10_INFLATE_E_LZW_*)
+INFLATE_E_LZW_CODE, INFLATE_E_LZW_FIRST, INFLATE_E_LZW_INPUT = 9, 10, 11
 INFLATE_TILE_DTYPE = np.dtype([("in_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("chunk_w", "<u4"),
                                ("src_x", "<u4"), ("src_y", "<u4"), ("copy_w", "<u4"), ("copy_h", "<u4"),
                                ("flags", "<u4"), ("dst_off", "<u8")])
@@ -110,6 +114,7 @@ def lib():
             "gcn10_gpu_deflate_fused_strip": (i, [vp, vp, i, i, vp, u, u, vp, sz, vp, vp, vp]),
             "gcn10_gpu_deflate_fused_available": (i, [vp]),
             "gcn10_gpu_inflate_tiles": (i, [vp, vp, vp, i, u, vp, sz, vp, vp]),
+            "gcn10_gpu_inflate_codecs": (i, []),
             "gcn10_gpu_deflate_arena_bound": (sz, [i, i, i]),
             "gcn10_gpu_deflate_strip": (i, [vp, vp, i, i, i, vp, sz, vp, vp, vp]),
             "gcn10_gpu_lzw_arena_bound": (sz, [i, i, i]),
@@ -416,14 +421,20 @@ class Engine:
                 b.close()
         return data, tab, used
 
+    @staticmethod
+    def inflate_codecs() -> int:
+        """CODEC_* bits of the chunk codecs inflate_tiles decodes (gcn10_gpu_inflate_codecs)."""
+        return int(lib().gcn10_gpu_inflate_codecs())
+
     def inflate_tiles(self, streams: Sequence[bytes], chunk_w: int, chunk_rows: Sequence[int],
                       windows: Sequence[tuple], dst_shape: tuple, stream=None, flags: Optional[Sequence[int]] = None,
                       out_lens: Optional[Sequence[int]] = None):
-        """Decodes zlib streams on the GPU (gcn10_gpu_inflate_tiles).
+        """Decodes zlib and TIFF LZW streams on the GPU (gcn10_gpu_inflate_tiles).
 
         streams[i] decodes to a chunk of chunk_rows[i] x chunk_w pixels; windows[i] =
         (src_x, src_y, copy_w, copy_h, dst_x, dst_y) places part of it in a zero-filled uint8
-        raster of dst_shape.  flags[i]: TILE_RAW (streams[i] is the chunk's pixels as they are) |
+        raster of dst_shape.  flags[i]: TILE_RAW (streams[i] is the chunk's pixels as they are) or
+        TILE_LZW (a TIFF LZW stream; 0 = a zlib stream), either with
         TILE_PREDICTOR2 (rows are horizontal differences); out_lens[i] overrides the decoded size
         (a raw chunk staged from its first wanted row on).  Returns (raster, status uint32[n])."""
         n = len(streams)

@@ -87,7 +87,8 @@ class Config(C.Structure):
                 ("io_threads", C.c_int), ("deflate_level", C.c_int), ("esa_tile_dir", C.c_char_p),
                 ("gpu_deflate", C.c_int), ("gpu_inflate", C.c_int), ("direct_io", C.c_int),
                 ("prefetch_blocks", C.c_int),
-                ("table_mask", C.c_uint), ("cond_mask", C.c_uint), ("compress", C.c_int)]
+                ("table_mask", C.c_uint), ("cond_mask", C.c_uint), ("compress", C.c_int),
+                ("gpu_inflate_lzw", C.c_int)]
 
 
 class Blocks(C.Structure):
@@ -164,6 +165,10 @@ class _ReadPlan(C.Structure):
                 ("max_chunk_bytes", C.c_uint32), ("staged_bytes", C.c_uint64)]
 
 
+# GCN10_CODEC_DEFLATE | GCN10_CODEC_RAW | GCN10_CODEC_LZW (include/gcn10_gpu.h)
+PLAN_CODECS_LZW = 1 | 2 | 4
+
+
 class Raster:
     """An open GeoTIFF / VRT (``gcn10_raster``)."""
 
@@ -188,20 +193,29 @@ class Raster:
     def georef_ptr(self):
         return lib().gcn10_raster_georef(self._h)
 
-    def plan(self, xoff, yoff, xcount, ycount):
+    def plan(self, xoff, yoff, xcount, ycount, lzw=False):
         """The read plan the pipeline hands to the GPU decoder (gcn10_raster_plan_window,
         host_internal.h): None when the window has to go through the host reader, else
         (chunks, covered_pixels, max_chunk_bytes) with chunks = list of dicts holding the
-        compressed bytes of a tile or strip and where its wanted part goes."""
+        compressed bytes of a tile or strip and where its wanted part goes.  lzw=True: LZW chunks
+        are planned too (gcn10_raster_plan_window_codecs with the LZW codec, what the pipeline
+        asks for with gpu_inflate_lzw=1)."""
         plan = _ReadPlan()
         err = C.create_string_buffer(1024)
         L = lib()
         L.gcn10_raster_plan_window.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                C.POINTER(_ReadPlan), C.c_char_p, C.c_size_t]
         L.gcn10_raster_plan_window.restype = C.c_int
+        L.gcn10_raster_plan_window_codecs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint,
+                                                      C.POINTER(_ReadPlan), C.c_char_p, C.c_size_t]
+        L.gcn10_raster_plan_window_codecs.restype = C.c_int
         L.gcn10_read_plan_free.argtypes = [C.POINTER(_ReadPlan)]
         L.gcn10_read_plan_free.restype = None
-        rc = L.gcn10_raster_plan_window(self._h, xoff, yoff, xcount, ycount, C.byref(plan), err, 1024)
+        if lzw:
+            rc = L.gcn10_raster_plan_window_codecs(self._h, xoff, yoff, xcount, ycount, PLAN_CODECS_LZW,
+                                                   C.byref(plan), err, 1024)
+        else:
+            rc = L.gcn10_raster_plan_window(self._h, xoff, yoff, xcount, ycount, C.byref(plan), err, 1024)
         if rc < 0:
             raise HostError(err.value.decode(errors="replace"))
         if rc > 0:

@@ -36,7 +36,9 @@ extern "C" {
 /* 1: round 1.  2: + gcn10_gpu_tune_single_raster, gcn10_gpu_stream_copy, gcn10_gpu_soil_words_state (round 2).
  * 3: gcn10_inflate_tile.reserved became .flags (raw and predictor-2 chunks), the tile encoders lay a raster's
  *    streams of a strip out as one extent (option "arena_segment_align"), gcn10_gpu_deflate_arena_bound grew by
- *    the extents' pads (round 3).  A caller built against an older header must be rebuilt: check at start-up. */
+ *    the extents' pads (round 3).  A caller built against an older header must be rebuilt: check at start-up.
+ *    Added within 3: the LZW encoder (gcn10_gpu_lzw_*), LZW tiles of gcn10_gpu_inflate_tiles (GCN10_TILE_LZW)
+ *    and gcn10_gpu_inflate_codecs. */
 #define GCN10_GPU_ABI_VERSION 3
 
 enum {
@@ -254,18 +256,32 @@ typedef struct gcn10_inflate_tile {
  * from the first wanted pixel on: src_x = src_y = 0 then, chunk_w still the chunk's row pitch).
  * PREDICTOR2 = the chunk was written with TIFF Predictor 2 (horizontal differencing): every chunk row is
  * summed back, byte-wise modulo 256, from the row's first pixel while it is copied (tiff.c decode_chunk does
- * the same on the host). */
+ * the same on the host).
+ * LZW = the chunk is a TIFF LZW stream (Compression 5: MSB-first codes, early change), decoded as tiff.c
+ * lzw_decode does (an early EOI leaves zeros, codes past out_len are ignored); same alignment rule as a zlib
+ * stream.  May be combined with PREDICTOR2, not with RAW (status GCN10_INFLATE_E_HEADER).  One call may mix
+ * zlib, raw and LZW tiles. */
 #define GCN10_TILE_RAW 1u
 #define GCN10_TILE_PREDICTOR2 2u
+#define GCN10_TILE_LZW 4u
 enum {
     GCN10_INFLATE_E_HEADER = 1, GCN10_INFLATE_E_BLOCK_TYPE = 2, GCN10_INFLATE_E_STORED = 3,
     GCN10_INFLATE_E_LENGTHS = 4, GCN10_INFLATE_E_CODE = 5, GCN10_INFLATE_E_DISTANCE = 6,
-    GCN10_INFLATE_E_INPUT = 7, GCN10_INFLATE_E_WINDOW = 8
+    GCN10_INFLATE_E_INPUT = 7, GCN10_INFLATE_E_WINDOW = 8,
+    /* LZW tiles: a code beyond the dictionary (code > next); the first code of the stream or after a
+     * ClearCode is not a literal; the input ends without EndOfInformation before out_len bytes */
+    GCN10_INFLATE_E_LZW_CODE = 9, GCN10_INFLATE_E_LZW_FIRST = 10, GCN10_INFLATE_E_LZW_INPUT = 11
 };
 int gcn10_gpu_inflate_tiles(gcn10_gpu_ctx *ctx, const uint8_t *comp_dev,
                             const gcn10_inflate_tile *tiles_dev, int n_tiles, uint32_t chunk_bytes,
                             uint8_t *dst_dev, size_t dst_stride, uint32_t *status_dev,
                             gcn10_stream_t stream);
+/* The chunk codecs gcn10_gpu_inflate_tiles decodes, GCN10_CODEC_* bits (a library without this symbol
+ * decodes DEFLATE and raw chunks only). */
+#define GCN10_CODEC_DEFLATE 1u
+#define GCN10_CODEC_RAW 2u
+#define GCN10_CODEC_LZW 4u
+int gcn10_gpu_inflate_codecs(void);
 
 /* Launch-shape knobs of the strip kernels, for tuning runs; results never
  * depend on them.  Names: "grid_blocks_per_cu" (1..64), "ilp16" (0 = by raster count | 1 | 2),

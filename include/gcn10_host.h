@@ -114,6 +114,9 @@ typedef struct gcn10_config {
     int compress;           /* "compress": GCN10_COMPRESS_DEFLATE (default, "deflate") or GCN10_COMPRESS_LZW ("lzw"),
                                case-insensitive as GDAL's COMPRESS=; LZW tiles are encoded on the GPU only, so
                                "lzw" with gpu_deflate=0 is refused */
+    int gpu_inflate_lzw;    /* "gpu_inflate_lzw": 1 (default) with gpu_inflate=1, LZW-compressed landcover tiles
+                               cross PCIe compressed and are decoded on the GPU too (when the GPU library has the
+                               decoder: gcn10_gpu_inflate_codecs); 0 = LZW windows through the host reader */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };

@@ -41,6 +41,7 @@ def main():
     ap.add_argument("--compress", default="deflate", help='config key "compress": deflate | lzw')
     ap.add_argument("--workers-per-gpu", type=int, default=0)
     ap.add_argument("--gpu-inflate", type=int, default=1)
+    ap.add_argument("--gpu-inflate-lzw", type=int, default=1, help='config key "gpu_inflate_lzw" (0 = LZW landcover through the host reader)')
     ap.add_argument("--io-threads", type=int, default=0, help='config key "io_threads" (0 = the program\'s choice)')
     ap.add_argument("--lookups", default="", help='config key "lookups" (e.g. g_ii): BASELINE config 3, single lookup')
     ap.add_argument("--conditions", default="", help='config key "conditions" (drained | undrained | both)')
@@ -76,9 +77,10 @@ def main():
     with open(os.path.join(wd, "config.txt"), "w") as f:
         f.write("hysogs_data_path=%s/soil.tif\nesa_data_path=%s/esa.tif\nblocks_shp_path=%s/blocks.shp\n"
                 "lookup_table_path=%s\nlog_dir=%s/logs\nstrip_rows=%d\ndeflate_level=%d\ngpu_deflate=%d\n"
-                "workers_per_gpu=%d\ngpu_inflate=%d\nio_threads=%d\ncompress=%s\n%s%s"
+                "workers_per_gpu=%d\ngpu_inflate=%d\ngpu_inflate_lzw=%d\nio_threads=%d\ncompress=%s\n%s%s"
                 % (wd, wd, wd, os.path.join(ROOT, "tests", "golden", "lookups"), wd, a.strip_rows,
-                   a.deflate_level, a.gpu_deflate, a.workers_per_gpu, a.gpu_inflate, a.io_threads, a.compress,
+                   a.deflate_level, a.gpu_deflate, a.workers_per_gpu, a.gpu_inflate, a.gpu_inflate_lzw, a.io_threads,
+                   a.compress,
                    "lookups=%s\n" % a.lookups if a.lookups else "", "conditions=%s\n" % a.conditions if a.conditions else ""))
     build_s = time.time() - t0
     run_modes(a, wd, size, nb, build_s)
@@ -114,7 +116,7 @@ def run_modes(a, wd, size, nb, build_s):
     if a.lookups or a.conditions:
         n_rasters = (len([x for x in a.lookups.split(",") if x]) if a.lookups and a.lookups != "all" else 9) * \
             (1 if a.conditions in ("drained", "undrained") else 2)
-    res = {"size": size, "blocks": nb, "rasters_per_block": n_rasters, "strip_rows": a.strip_rows, "gpus": a.gpus, "pattern": a.pattern, "gpu_deflate": a.gpu_deflate, "compress": a.compress, "gpu_inflate": a.gpu_inflate, "workers_per_gpu": a.workers_per_gpu, "esa_compression": a.esa_compression, "dual_soil_fraction": a.dual_soil_fraction,
+    res = {"size": size, "blocks": nb, "rasters_per_block": n_rasters, "strip_rows": a.strip_rows, "gpus": a.gpus, "pattern": a.pattern, "gpu_deflate": a.gpu_deflate, "compress": a.compress, "gpu_inflate": a.gpu_inflate, "gpu_inflate_lzw": a.gpu_inflate_lzw, "workers_per_gpu": a.workers_per_gpu, "esa_compression": a.esa_compression, "dual_soil_fraction": a.dual_soil_fraction,
            "world_build_seconds": round(build_s, 1), "modes": {}}
     for mode in a.modes.split(","):
         env = dict(os.environ)
@@ -138,8 +140,10 @@ def run_modes(a, wd, size, nb, build_s):
             if os.path.isdir(p):
                 nbytes += sum(os.path.getsize(os.path.join(p, f)) for f in os.listdir(p))
         mt = re.search(r"worker seconds: (.*)", log)
+        mw = re.search(r"timing: landcover windows: (.*)", log)
         mc = re.search(r"host cpu seconds: user ([0-9.]+), system ([0-9.]+), over [0-9.]+ s wall \(([0-9.]+) per block\).*?pinned host memory allocated ([0-9.]+) MB; peak resident set ([0-9.]+) MB", log)
         res["modes"][mode] = {"rc": out.returncode, "worker_seconds": mt.group(1) if mt else None, "blocks_done": done, "seconds": round(secs, 3),
+                              "landcover_windows": mw.group(1) if mw else None,
                               "cn_gpx_per_s": round(done * size * size * n_rasters / secs / 1e9, 3) if secs else None,
                               "seconds_per_block": round(secs / done, 3) if done else None,
                               "seconds_after_startup": steady,

@@ -111,6 +111,27 @@ int gcn10_parse_compress(const char *text, int *codec)
     return 0;
 }
 
+int gcn10_parse_overview_resampling(const char *text, int *method)
+{
+    if (!text)
+        return -1;
+    if (!strcasecmp(text, "nearest"))
+        *method = GCN10_OVERVIEW_NEAREST;
+    else if (!strcasecmp(text, "average"))
+        *method = GCN10_OVERVIEW_AVERAGE;
+    else
+        return -1;
+    return 0;
+}
+
+int gcn10_parse_cog(const char *text, int *cog)
+{
+    if (!text || (strcmp(text, "0") != 0 && strcmp(text, "1") != 0))
+        return -1;
+    *cog = text[0] == '1';
+    return 0;
+}
+
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap)
 {
     char line[512];                                     /* src/config.c:47 */
@@ -191,6 +212,19 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             gcn10_config_free(cfg);
             return -3;
         }
+        else if (!strcmp(key, "cog") && gcn10_parse_cog(val, &cfg->cog) != 0) {
+            fclose(f);
+            snprintf(err, errcap, "bad value for cog: '%s' (0 or 1)", val);
+            gcn10_config_free(cfg);
+            return -3;
+        }
+        else if (!strcmp(key, "overview_resampling") &&
+                 gcn10_parse_overview_resampling(val, &cfg->overview_resampling) != 0) {
+            fclose(f);
+            snprintf(err, errcap, "bad value for overview_resampling: '%s' (nearest or average)", val);
+            gcn10_config_free(cfg);
+            return -3;
+        }
         if (rc != 0) {
             fclose(f);
             snprintf(err, errcap, "malloc failed for %s", key);     /* src/config.c:71 */
@@ -202,6 +236,12 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
     if (cfg->compress == GCN10_COMPRESS_LZW && cfg->gpu_deflate == 0) {
         snprintf(err, errcap, "bad value for compress: 'lzw' with gpu_deflate=0 (LZW tiles are encoded on the GPU "
                               "only; there is no host LZW encoder)");
+        gcn10_config_free(cfg);
+        return -3;
+    }
+    if (cfg->cog && cfg->gpu_deflate == 0) {
+        snprintf(err, errcap, "bad value for cog: '1' with gpu_deflate=0 (overviews are built and encoded on the GPU "
+                              "only; there is no host fallback)");
         gcn10_config_free(cfg);
         return -3;
     }

@@ -86,6 +86,8 @@ static void load_once(void)
     *(void **)(&g_api.lzw_strip) = dlsym(h, "gcn10_gpu_lzw_strip");
     /* the chunk codecs of gcn10_gpu_inflate_tiles (may be absent: then LZW landcover goes through the host reader) */
     *(void **)(&g_api.inflate_codecs) = dlsym(h, "gcn10_gpu_inflate_codecs");
+    *(void **)(&g_api.overview_nearest) = dlsym(h, "gcn10_gpu_overview_nearest");
+    *(void **)(&g_api.overview_average) = dlsym(h, "gcn10_gpu_overview_average");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -113,6 +113,10 @@ struct gcn10_gpu_api {
     int (*lzw_strip)(gcn10_gpu_ctx *, const uint8_t *const *, int, int, int, uint8_t *, size_t,
                      uint32_t *, unsigned long long *, gcn10_stream_t);
     int (*inflate_codecs)(void);    /* optional: NULL = DEFLATE and raw chunks only (LZW windows stay on the host) */
+    /* optional: NULL when the library has none (needed by cog=1 only) */
+    int (*overview_nearest)(gcn10_gpu_ctx *, const uint8_t *, int, int, int, uint8_t *, gcn10_stream_t);
+    int (*overview_average)(gcn10_gpu_ctx *, const uint8_t *, int, int, int, int, const int32_t *, unsigned, unsigned,
+                            int, uint8_t *const *, gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -21,6 +21,7 @@ static void usage(FILE *fp)
             "usage:\n"
             "  gcn10 --config <config.txt> [--blocks <blocks.txt>] [--overwrite] [--gpus <n>]\n"
             "        [--lookups <names>] [--conditions drained|undrained|both] [--compress deflate|lzw]\n"
+            "        [--cog] [--overview-resampling nearest|average]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -31,6 +32,8 @@ static void usage(FILE *fp)
             "  --lookups <names>\tonly these lookups, e.g. g_ii or p_i,f_iii (default: all nine)\n"
             "  --conditions <c>\tdrained, undrained or both (default: both)\n"
             "  --compress <c>\tdeflate or lzw: compression of the GeoTIFFs (default: deflate)\n"
+            "  --cog\t\t\tCloud Optimized GeoTIFFs with overviews built on the GPU (config key cog=1)\n"
+            "  --overview-resampling <m>\tnearest or average: how the overviews are made (default: nearest)\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -71,6 +74,10 @@ int main(int argc, char **argv)
             opt.conditions = argv[++i];
         else if (!strcmp(argv[i], "--compress") && i + 1 < argc)
             opt.compress = argv[++i];
+        else if (!strcmp(argv[i], "--cog"))
+            opt.cog = true;
+        else if (!strcmp(argv[i], "--overview-resampling") && i + 1 < argc)
+            opt.overview_resampling = argv[++i];
     }
     return gcn10_run(&opt);
 }

@@ -190,6 +190,7 @@ struct gate_job {
     struct strip_buf *b;
     gcn10_tiff_writer *tifs[GCN10_N_RASTERS];
     int ty0, across, down;
+    long seq;                               /* COG: this strip's turn among the worker's strips */
 };
 
 static void strip_gate_job(void *arg)
@@ -200,6 +201,14 @@ static void strip_gate_job(void *arg)
 
     if (!arrived)
         atomic_store(&g->w->failed, true);
+    if (r->cog) {
+        /* a COG takes its tile data in file order: this strip's extents go after the previous strip's, here on
+         * this thread (gate jobs are queued in strip order and the pool is FIFO, so the turn before is running) */
+        pthread_mutex_lock(&g->w->gate_mu);
+        while (g->w->gate_turn != g->seq)
+            pthread_cond_wait(&g->w->gate_cv, &g->w->gate_mu);
+        pthread_mutex_unlock(&g->w->gate_mu);
+    }
     for (int q = 0; arrived && q < r->n_sel; q++) {       /* stream q of the table = the q-th selected raster */
         struct put_job *j = malloc(sizeof *j);
 
@@ -211,7 +220,16 @@ static void strip_gate_job(void *arg)
         pthread_mutex_lock(&g->b->mu);
         g->b->pending++;
         pthread_mutex_unlock(&g->b->mu);
-        gcn10_pool_submit(r->pool, put_tiles_job, j);
+        if (r->cog)
+            put_tiles_job(j);
+        else
+            gcn10_pool_submit(r->pool, put_tiles_job, j);
+    }
+    if (r->cog) {
+        pthread_mutex_lock(&g->w->gate_mu);
+        g->w->gate_turn++;
+        pthread_cond_broadcast(&g->w->gate_cv);
+        pthread_mutex_unlock(&g->w->gate_mu);
     }
     pthread_mutex_lock(&g->b->mu);
     if (--g->b->pending == 0)
@@ -306,6 +324,7 @@ static int drain_strip_inner(struct worker *w, struct strip_buf *b, gcn10_tiff_w
             j->ty0 = b->y0 / TILE;
             j->across = across;
             j->down = down;
+            j->seq = w->gate_seq++;
             pthread_mutex_lock(&b->mu);
             b->pending++;
             pthread_mutex_unlock(&b->mu);
@@ -498,6 +517,15 @@ static void output_path(char *out, size_t cap, const char *cond, const char *hc,
     }
 }
 
+/* overview levels of a COG block; a window that would need more than GCN10_COG_MAX_LEVELS gets none here (the
+ * encoder refuses the block) */
+static int cog_levels_of(int W, int H)
+{
+    int L = gcn10_cog_levels(W, H);
+
+    return L > GCN10_COG_MAX_LEVELS ? 0 : L;
+}
+
 /* output directories (src/cn.c:237-256) and the files of the run's rasters, for block `in` */
 int gcn10_create_outputs(struct worker *w, struct block_in *in)
 {
@@ -528,7 +556,11 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
 
         output_path(path, sizeof path, gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3],
                     in->block_id, r->opt.overwrite);
-        in->tifs[k] = gcn10_tiff_create(path, in->W, in->H, in->gt, gcn10_raster_georef(w->esa), err, sizeof err);
+        if (r->cog)
+            in->tifs[k] = gcn10_tiff_create_cog(path, in->W, in->H, in->gt, gcn10_raster_georef(w->esa),
+                                                cog_levels_of(in->W, in->H), err, sizeof err);
+        else
+            in->tifs[k] = gcn10_tiff_create(path, in->W, in->H, in->gt, gcn10_raster_georef(w->esa), err, sizeof err);
         if (!in->tifs[k]) {
             wlog(w, "ERROR", true, "%s", err);          /* save_raster logs and goes on, src/raster.c:220-223 */
             gcn10_abort_outputs(in);
@@ -555,78 +587,53 @@ void gcn10_abort_outputs(struct block_in *in)
     in->tifs_ok = false;
 }
 
-/* The back half of process_block (src/cn.c:236-384) for a block whose input the input side has put on its
- * way to HBM.  Returns 0 (done, or skipped like the reference skips) or -1 for errors the
- * reference answers with MPI_Abort */
-static int encode_block(struct worker *w, struct block_in *in)
+/* The strips of one raster (a block, or a level of its overviews) through the encoder and the sink.  d_block / d_cj:
+ * its landcover and soil rows, for the prepared tile of width W.  premade (device, [strip][GCN10_N_RASTERS]): the
+ * selected rasters are already made (average overviews), strip s's n_sel pointers at premade + s * GCN10_N_RASTERS,
+ * and only the per-raster encoder runs.  Every strip has been handed to the sink, and the sink is done, on return.
+ * 0, or -1 (logged) for errors the reference answers with MPI_Abort. */
+static int run_strips(struct worker *w, int W, int H, const uint8_t *d_block, const int32_t *d_cj,
+                      const uint8_t *const *premade, gcn10_tiff_writer *tifs[GCN10_N_RASTERS])
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
-    char err[1024] = "";
-    const int W = in->W, H = in->H, block_id = in->block_id;
-    gcn10_tiff_writer *tifs[GCN10_N_RASTERS] = { 0 };
-    int rc = 0, n_strips;
-    bool ok = false;
-    double t_mark = now_seconds();
-
-    if (getenv("GCN10_TEST_FAIL_BLOCK") && atoi(getenv("GCN10_TEST_FAIL_BLOCK")) == block_id) {
-        /* test hook (tools/r03/run_rehearse_8gpu.sh): one worker meets an error of the kind the reference answers
-         * with MPI_Abort -- the whole run must stop and exit with code 1 (src/main.c:175, src/cn.c:25, 216) */
-        wlog(w, "ERROR", true, "malloc failed for block %d (GCN10_TEST_FAIL_BLOCK)", block_id);
-        return -1;
-    }
-    /* the 18 files were created by the input side (gcn10_create_outputs), one block ahead */
-    memcpy(tifs, in->tifs, sizeof tifs);
-    memset(in->tifs, 0, sizeof in->tifs);
-    if (!r->null_sink && !in->tifs_ok)
-        goto out;                       /* save_raster logs and goes on, src/raster.c:220-223: logged at creation */
-    t_mark = now_seconds();
-
-    /* device side of the block: the encoder waits (on the device) for the input side's copies and kernels */
-    w->strip_rows = r->strip_rows;
-    if (ensure_strip_buffers(w, W) != 0) {
-        rc = -1;
-        goto out;
-    }
-    atomic_store(&w->failed, false);
-    if (g->stream_wait_event(w->ctx, w->s_kernel, in->ev_ready) != 0 ||
-        g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, W, w->s_kernel) != 0) {
-        wlog(w, "ERROR", true, "gpu: %s", g->last_error());
-        rc = -1;
-        goto out;
-    }
-    w->t_device += now_seconds() - t_mark;
+    int n_strips;
 
     /* strips: rows are multiples of 256 (whole GeoTIFF tile rows) and of 16
      * (16-byte aligned strip starts for any W) */
     n_strips = (H + w->strip_rows - 1) / w->strip_rows;
+
     for (int s = 0; s < n_strips; s++) {
         struct strip_buf *b = &w->buf[s % r->nbuf];
         int y0 = s * w->strip_rows;
         int rows = H - y0 < w->strip_rows ? H - y0 : w->strip_rows;
         size_t px = (size_t)W * (size_t)rows;
         uint8_t *outs[GCN10_N_RASTERS];
-        const uint8_t *d_esa = in->d_block + (size_t)y0 * (size_t)W;
+        const uint8_t *d_esa = d_block ? d_block + (size_t)y0 * (size_t)W : NULL;
 
         /* this buffer's previous strip: its D2H must be done and handed to the sink,
          * and the sink must be done with the pinned buffers */
-        if (drain_strip(w, b, tifs, W, H) != 0) {
-            rc = -1;
-            goto out;
-        }
+        if (drain_strip(w, b, tifs, W, H) != 0)
+            return -1;
         wait_sink(b);
 
         /* the strip's kernels on the compute stream */
-        if (w->fused) {
+        if (premade) {
+            if ((r->lzw ? g->lzw_strip : g->deflate_strip)(w->ctx, premade + (size_t)s * GCN10_N_RASTERS, r->n_sel, W,
+                                                           rows, b->d_arena, b->arena_cap, b->d_table, b->d_cursor,
+                                                           w->s_kernel) != 0)
+                goto gpu_fail;
+        }
+        else if (w->fused) {
             /* landcover + soil -> 18 x compressed tiles in one device pass, no CN strip in HBM */
-            if (g->deflate_fused_strip(w->ctx, d_esa, W, rows, in->d_cj + y0, r->cond_mask, r->table_mask, b->d_arena,
+            if (g->deflate_fused_strip(w->ctx, d_esa, W, rows, d_cj + y0, r->cond_mask, r->table_mask, b->d_arena,
                                        b->arena_cap, b->d_table, b->d_cursor, w->s_kernel) != 0)
                 goto gpu_fail;
         }
         else {
             for (int k = 0; k < GCN10_N_RASTERS; k++)
                 outs[k] = b->d_out[k];             /* NULL for a raster this run does not produce */
-            if (g->cn_strip(w->ctx, d_esa, W, rows, in->d_cj + y0, r->cond_mask, r->table_mask, outs,
+            if (g->cn_strip(w->ctx, d_esa, W, rows, d_cj + y0, r->cond_mask, r->table_mask, outs,
                             w->s_kernel) != 0)
                 goto gpu_fail;
             /* encode the selected strips where they are */
@@ -665,18 +672,228 @@ static int encode_block(struct worker *w, struct block_in *in)
          * worker had exactly one strip queued behind the running one and could submit the next only when the
          * previous had finished -- the trace of round 3 shows the compute stream idle ~0.5 ms between strips
          * whose kernels take 0.2-0.3 ms.  With 2 the queue holds two strips while the host waits. */
-        if (s >= r->drain_lag && drain_strip(w, &w->buf[(s - r->drain_lag) % r->nbuf], tifs, W, H) != 0) {
+        if (s >= r->drain_lag && drain_strip(w, &w->buf[(s - r->drain_lag) % r->nbuf], tifs, W, H) != 0)
+            return -1;
+    }
+    if (r->cog) {
+        /* a COG's strips reach the sink in strip order */
+        for (int s = n_strips > r->nbuf ? n_strips - r->nbuf : 0; s < n_strips; s++)
+            if (drain_strip(w, &w->buf[s % r->nbuf], tifs, W, H) != 0)
+                return -1;
+    }
+    for (int i = 0; i < w->run->nbuf; i++)
+        if (drain_strip(w, &w->buf[i], tifs, W, H) != 0)
+            return -1;
+    for (int i = 0; i < w->run->nbuf; i++)
+        wait_sink(&w->buf[i]);
+    return 0;
+
+gpu_fail:
+    wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+    return -1;
+}
+
+/* The overview phase of a COG block (levels L .. 1, smallest first): made on the GPU, encoded by the run's encoders,
+ * appended to the files before any full-resolution tile.  nearest: every level is a block of its own -- its
+ * landcover gathered from the block's, its soil index maps the block's composed with the same sampling -- through
+ * prepare_tile and the strip encoder of the run; the block's own tile is prepared again afterwards.  average: the
+ * whole pyramid of the selected rasters from landcover + soil in one pass per strip (gcn10_gpu_overview_average on
+ * the block's prepared tile), then every level through the per-raster encoder.  0, or -1 (logged). */
+static int encode_overviews(struct worker *w, struct block_in *in, gcn10_tiff_writer *tifs[GCN10_N_RASTERS], int L)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    const int W = in->W, H = in->H;
+    gcn10_tiff_writer *lv[GCN10_N_RASTERS];
+
+    if (!r->ov_average) {
+        const int W1 = (W + 1) / 2, H1 = (H + 1) / 2;
+        /* a level's ci, padded to a multiple of 4 entries, then its cj: at most W1 + 3 + H1 entries */
+        const size_t n_idx = (size_t)W1 + 4 + (size_t)H1;
+        int32_t *idx = malloc(n_idx * sizeof *idx);
+
+        if (!idx) {
+            wlog(w, "ERROR", true, "malloc failed for overview index maps");
+            return -1;
+        }
+        if (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov, &w->ov_cap, (size_t)W1 * (size_t)H1 + 16) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov_idx, &w->ov_idx_cap, n_idx * sizeof *idx) != 0) {
+            free(idx);
+            return -1;
+        }
+        for (int k = L; k >= 1; k--) {
+            const int Wk = (int)(((int64_t)W + ((int64_t)1 << k) - 1) >> k);
+            const int Hk = (int)(((int64_t)H + ((int64_t)1 << k) - 1) >> k);
+            const int half = 1 << (k - 1);
+            /* cj of the level right after its ci, 16-byte aligned */
+            const size_t cj_at = ((size_t)Wk + 3) & ~(size_t)3;
+            int32_t *d_ci = w->d_ov_idx, *d_cj = w->d_ov_idx + cj_at;
+
+            for (int x = 0; x < Wk; x++)
+                idx[x] = in->h_ci[(int64_t)x * (1 << k) + half < W ? (int64_t)x * (1 << k) + half : W - 1];
+            for (int y = 0; y < Hk; y++)
+                idx[cj_at + y] = in->h_cj[(int64_t)y * (1 << k) + half < H ? (int64_t)y * (1 << k) + half : H - 1];
+            if (g->overview_nearest(w->ctx, in->d_block, W, H, k, w->d_ov, w->s_kernel) != 0 ||
+                g->memcpy_h2d(w->ctx, w->d_ov_idx, idx, (cj_at + (size_t)Hk) * sizeof *idx, w->s_kernel) != 0 ||
+                g->stream_sync(w->ctx, w->s_kernel) != 0 ||
+                g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, d_ci, Wk, w->s_kernel) != 0) {
+                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+                free(idx);
+                return -1;
+            }
+            for (int q = 0; q < GCN10_N_RASTERS; q++)
+                lv[q] = tifs[q] ? gcn10_tiff_level(tifs[q], k) : NULL;
+            if (run_strips(w, Wk, Hk, w->d_ov, d_cj, NULL, lv) != 0) {
+                free(idx);
+                return -1;
+            }
+            /* the next level overwrites the index maps and the level's landcover: this one's kernels are done */
+            if (g->stream_sync(w->ctx, w->s_kernel) != 0) {
+                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+                free(idx);
+                return -1;
+            }
+        }
+        free(idx);
+        if (g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, W, w->s_kernel) != 0) {
+            wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+            return -1;
+        }
+        return 0;
+    }
+
+    /* average: the pyramid of the selected rasters, level by level, raster by raster */
+    {
+        size_t lvl_off[GCN10_COG_MAX_LEVELS + 1], total = 0;
+        uint8_t *levels[GCN10_N_RASTERS * GCN10_COG_MAX_LEVELS];
+        size_t n_ptrs = 0;
+
+        for (int k = 1; k <= L; k++) {
+            const size_t Wk = (size_t)(((int64_t)W + ((int64_t)1 << k) - 1) >> k);
+            const size_t Hk = (size_t)(((int64_t)H + ((int64_t)1 << k) - 1) >> k);
+            const int n_strips = (int)((Hk + (size_t)w->strip_rows - 1) / (size_t)w->strip_rows);
+
+            lvl_off[k] = total;
+            total += (Wk * Hk + 255) & ~(size_t)255;
+            n_ptrs = (size_t)n_strips > n_ptrs ? (size_t)n_strips : n_ptrs;
+        }
+        if (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov, &w->ov_cap, total * (size_t)r->n_sel + 16) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, &w->d_ov_ptrs, &w->ov_ptrs_cap,
+                                n_ptrs * GCN10_N_RASTERS * sizeof(void *)) != 0)
+            return -1;
+        for (int q = 0; q < r->n_sel; q++)
+            for (int k = 1; k <= L; k++)
+                levels[q * L + k - 1] = w->d_ov + (size_t)q * total + lvl_off[k];
+        for (int y0 = 0; y0 < H; y0 += w->strip_rows) {
+            const int rows = H - y0 < w->strip_rows ? H - y0 : w->strip_rows;
+
+            if (g->overview_average(w->ctx, in->d_block, W, H, y0, rows, in->d_cj, r->cond_mask, r->table_mask, L,
+                                    levels, w->s_kernel) != 0) {
+                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+                return -1;
+            }
+        }
+        for (int k = L; k >= 1; k--) {
+            const int Wk = (int)(((int64_t)W + ((int64_t)1 << k) - 1) >> k);
+            const int Hk = (int)(((int64_t)H + ((int64_t)1 << k) - 1) >> k);
+            const int n_strips = (Hk + w->strip_rows - 1) / w->strip_rows;
+            const uint8_t **tab = calloc((size_t)n_strips * GCN10_N_RASTERS, sizeof *tab);
+
+            if (!tab) {
+                wlog(w, "ERROR", true, "malloc failed for overview strips");
+                return -1;
+            }
+            for (int s = 0; s < n_strips; s++)
+                for (int q = 0; q < r->n_sel; q++)
+                    tab[(size_t)s * GCN10_N_RASTERS + q] =
+                        levels[q * L + k - 1] + (size_t)s * (size_t)w->strip_rows * (size_t)Wk;
+            if (g->memcpy_h2d(w->ctx, w->d_ov_ptrs, tab, (size_t)n_strips * GCN10_N_RASTERS * sizeof *tab,
+                              w->s_kernel) != 0 ||
+                g->stream_sync(w->ctx, w->s_kernel) != 0) {
+                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+                free(tab);
+                return -1;
+            }
+            free(tab);
+            for (int q = 0; q < GCN10_N_RASTERS; q++)
+                lv[q] = tifs[q] ? gcn10_tiff_level(tifs[q], k) : NULL;
+            if (run_strips(w, Wk, Hk, NULL, NULL, (const uint8_t *const *)w->d_ov_ptrs, lv) != 0)
+                return -1;
+            if (g->stream_sync(w->ctx, w->s_kernel) != 0) {       /* the pointer table is rewritten next */
+                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+                return -1;
+            }
+        }
+    }
+    return 0;
+}
+
+/* The back half of process_block (src/cn.c:236-384) for a block whose input the input side has put on its
+ * way to HBM.  Returns 0 (done, or skipped like the reference skips) or -1 for errors the
+ * reference answers with MPI_Abort */
+static int encode_block(struct worker *w, struct block_in *in)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    char err[1024] = "";
+    const int W = in->W, H = in->H, block_id = in->block_id;
+    gcn10_tiff_writer *tifs[GCN10_N_RASTERS] = { 0 };
+    int rc = 0;
+    bool ok = false;
+    double t_mark = now_seconds();
+    /* COG: the block's overview levels; nearest ones are encoded as blocks of their own (encode_overviews) */
+    const int L = r->cog ? gcn10_cog_levels(W, H) : 0;
+    const bool nearest_levels = r->cog && !r->ov_average && L > 0 && L <= GCN10_COG_MAX_LEVELS;
+
+    if (getenv("GCN10_TEST_FAIL_BLOCK") && atoi(getenv("GCN10_TEST_FAIL_BLOCK")) == block_id) {
+        /* test hook (tools/r03/run_rehearse_8gpu.sh): one worker meets an error of the kind the reference answers
+         * with MPI_Abort -- the whole run must stop and exit with code 1 (src/main.c:175, src/cn.c:25, 216) */
+        wlog(w, "ERROR", true, "malloc failed for block %d (GCN10_TEST_FAIL_BLOCK)", block_id);
+        return -1;
+    }
+    /* the 18 files were created by the input side (gcn10_create_outputs), one block ahead */
+    memcpy(tifs, in->tifs, sizeof tifs);
+    memset(in->tifs, 0, sizeof in->tifs);
+    if (!r->null_sink && !in->tifs_ok)
+        goto out;                       /* save_raster logs and goes on, src/raster.c:220-223: logged at creation */
+    t_mark = now_seconds();
+
+    /* device side of the block: the encoder waits (on the device) for the input side's copies and kernels */
+    w->strip_rows = r->strip_rows;
+    if (ensure_strip_buffers(w, W) != 0) {
+        rc = -1;
+        goto out;
+    }
+    atomic_store(&w->failed, false);
+    /* nearest overviews prepare their levels' tiles first and the block's after them (encode_overviews); every
+     * other block -- average overviews, no levels (a window of at most 256 px), a refused one -- is prepared here */
+    if (g->stream_wait_event(w->ctx, w->s_kernel, in->ev_ready) != 0 ||
+        (!nearest_levels &&
+         g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, W, w->s_kernel) != 0)) {
+        wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+        rc = -1;
+        goto out;
+    }
+    w->t_device += now_seconds() - t_mark;
+
+    if (r->cog) {
+        if (!atomic_exchange(&r->cog_logged, true))
+            wlog(w, "INFO", true, "cog: Cloud Optimized GeoTIFFs, overviews by %s resampling, %d levels (block %d, "
+                 "%dx%d)", r->ov_average ? "average" : "nearest", L, block_id, W, H);
+        if (L > GCN10_COG_MAX_LEVELS) {
+            wlog(w, "ERROR", true, "cog: block %d (%dx%d) would need %d overview levels, more than %d: block skipped",
+                 block_id, W, H, L, GCN10_COG_MAX_LEVELS);
+            goto out;
+        }
+        if (L > 0 && encode_overviews(w, in, tifs, L) != 0) {
             rc = -1;
             goto out;
         }
     }
-    for (int i = 0; i < w->run->nbuf; i++)
-        if (drain_strip(w, &w->buf[i], tifs, W, H) != 0) {
-            rc = -1;
-            goto out;
-        }
-    for (int i = 0; i < w->run->nbuf; i++)
-        wait_sink(&w->buf[i]);
+    if (run_strips(w, W, H, in->d_block, in->d_cj, NULL, tifs) != 0) {
+        rc = -1;
+        goto out;
+    }
     ok = !atomic_load(&w->failed);
     if (in->n_inflate > 0) {
         /* every landcover chunk must have been a valid one (the statuses came back behind ev_ready) */
@@ -783,6 +1000,12 @@ static void worker_teardown(struct worker *w)
             if (b->ev_d2h) g->event_destroy(w->ctx, b->ev_d2h);
             if (b->ev_meta) g->event_destroy(w->ctx, b->ev_meta);
         }
+        if (w->d_ov) g->free(w->ctx, w->d_ov);
+        if (w->d_ov_idx) g->free(w->ctx, w->d_ov_idx);
+        if (w->d_ov_ptrs) g->free(w->ctx, w->d_ov_ptrs);
+        w->d_ov = NULL;
+        w->d_ov_idx = NULL;
+        w->d_ov_ptrs = NULL;
         if (w->s_kernel) g->stream_destroy(w->ctx, w->s_kernel);
         if (w->s_d2h) g->stream_destroy(w->ctx, w->s_d2h);
         g->destroy(w->ctx);
@@ -795,6 +1018,8 @@ static void worker_teardown(struct worker *w)
         pthread_mutex_destroy(&w->buf[i].mu);
         pthread_cond_destroy(&w->buf[i].cv);
     }
+    pthread_mutex_destroy(&w->gate_mu);
+    pthread_cond_destroy(&w->gate_cv);
 }
 
 /* Keeps a worker thread (and the pinned buffers it is about to allocate: first touch)
@@ -868,6 +1093,8 @@ static int worker_setup(struct worker *w)
         pthread_cond_init(&w->buf[i].cv, NULL);
         w->buf[i].owner = w;
     }
+    pthread_mutex_init(&w->gate_mu, NULL);
+    pthread_cond_init(&w->gate_cv, NULL);
     bind_to_gpu_numa_node(w, (w->index % r->n_devices) % r->n_physical);
     if (g->init(w->device, &w->ctx) != 0) {
         wlog(w, "ERROR", true, "gpu %d: %s", w->device, g->last_error());
@@ -1096,6 +1323,23 @@ int gcn10_run(const gcn10_run_options *opt)
         free(r);
         return 1;
     }
+    if (opt->overview_resampling &&
+        gcn10_parse_overview_resampling(opt->overview_resampling, &r->cfg.overview_resampling) != 0) {
+        fprintf(stderr, "[rank 0] bad value for overview_resampling: '%s' (nearest or average)\n",
+                opt->overview_resampling);
+        gcn10_config_free(&r->cfg);
+        free(r);
+        return 1;
+    }
+    if (opt->cog)
+        r->cfg.cog = 1;
+    if (r->cfg.cog && r->cfg.gpu_deflate == 0) {
+        fprintf(stderr, "[rank 0] bad value for cog: '1' with gpu_deflate=0 (overviews are built and encoded on the GPU "
+                        "only; there is no host fallback)\n");
+        gcn10_config_free(&r->cfg);
+        free(r);
+        return 1;
+    }
     for (int k = 0; k < GCN10_N_RASTERS; k++)
         if ((r->cond_mask >> (k / 9)) & 1u && (r->table_mask >> (k % 9)) & 1u)
             r->sel[r->n_sel++] = k;
@@ -1114,6 +1358,8 @@ int gcn10_run(const gcn10_run_options *opt)
     r->deflate_level = r->cfg.deflate_level;
     r->gpu_deflate = r->cfg.gpu_deflate != 0;
     r->lzw = r->cfg.compress == GCN10_COMPRESS_LZW;
+    r->cog = r->cfg.cog != 0;
+    r->ov_average = r->cfg.overview_resampling == GCN10_OVERVIEW_AVERAGE;
     r->fused = r->cfg.gpu_deflate == 2 && !r->lzw;     /* the fused encoder is DEFLATE-only */
     r->gpu_inflate = r->cfg.gpu_inflate != 0;
     r->direct_io = r->cfg.direct_io != 0 || (getenv("GCN10_DIRECT_IO") && atoi(getenv("GCN10_DIRECT_IO")) != 0);
@@ -1137,6 +1383,10 @@ int gcn10_run(const gcn10_run_options *opt)
     r->gpu = gcn10_gpu_api_get(err, sizeof err);
     if (!r->gpu) {
         fprintf(stderr, "[rank 0] %s\n", err);
+        goto done;
+    }
+    if (r->cog && (!r->gpu->overview_nearest || !r->gpu->overview_average)) {
+        fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_overview_* (needed by cog=1)\n", gcn10_gpu_library_path());
         goto done;
     }
     if (r->lzw && (!r->gpu->lzw_strip || !r->gpu->lzw_arena_bound)) {

@@ -117,6 +117,17 @@ struct worker {
     double t_gpu_wait, t_sink_wait;         /* where the worker thread's time goes */
     double t_create, t_finish, t_device, t_in_wait;
     double t_read, t_soil, t_in_busy;       /* ... and the input thread's */
+    /* COG output: the overview phase's device buffers, and the order in which strips reach the files (a COG takes
+     * tile data in file order only: the gate jobs of a worker's strips append their extents in turn) */
+    uint8_t *d_ov;                          /* nearest: one level's landcover; average: the whole pyramid */
+    size_t ov_cap;
+    int32_t *d_ov_idx;                      /* nearest: a level's ci then cj */
+    size_t ov_idx_cap;
+    void *d_ov_ptrs;                        /* average: per strip of a level, the n_sel raster pointers */
+    size_t ov_ptrs_cap;
+    pthread_mutex_t gate_mu;
+    pthread_cond_t gate_cv;
+    long gate_seq, gate_turn;
     long n_win_gpu, n_win_gpu_lzw, n_win_host;  /* landcover windows through the GPU decoder (of them with LZW chunks),
                                                    through the host reader */
 };
@@ -148,6 +159,9 @@ struct run {
     unsigned inflate_codecs;                /* GCN10_CODEC_* the read plans hand to the GPU decoder (LZW: gpu_inflate_lzw=1
                                                and a library that decodes it) */
     bool direct_io;                         /* tile data is written with O_DIRECT */
+    bool cog;                               /* Cloud Optimized GeoTIFFs with overviews (cog=1) */
+    bool ov_average;                        /* ... made by averaging (overview_resampling=average), else nearest */
+    atomic_bool cog_logged;                 /* the run log has its COG line */
     bool prefetch;                          /* input threads stage block N+1 while block N is encoded */
     int n_devices;                          /* GPUs of the run; worker i belongs to GPU i % n_devices */
     int n_physical;                         /* ... and the devices behind them: GPU d is device d % n_physical (all the

@@ -1052,6 +1052,16 @@ struct gcn10_tiff_writer {
     bool failed;
     bool direct;                /* O_DIRECT is set on fd: extents go out at 4096-aligned positions */
     int compression;            /* TIFF Compression tag: 8 (Adobe deflate, default) or 5 (LZW) */
+    /* Cloud Optimized GeoTIFF layout (gcn10_tiff_create_cog).  A COG writer owns one view per overview
+     * level; a view has its own size and tile arrays and shares the file (fd, pos, mu, failed, direct) with
+     * its root.  A plain writer is its own root with no levels. */
+    struct gcn10_tiff_writer *root;
+    struct gcn10_tiff_writer **levels;  /* root of a COG: views of levels 1 .. n_levels, [k - 1] */
+    int n_levels, level;
+    bool cog;
+    int cur_level;              /* root of a COG: the level tile data goes to now (starts at n_levels) */
+    long long last_idx;         /* COG: highest tile index of this level written so far (-1: none) */
+    uint64_t data_start;        /* root of a COG: first byte after the IFDs, where tile data begins */
 };
 
 static int write_all(int fd, const void *buf, size_t n, uint64_t off)
@@ -1119,7 +1129,7 @@ int gcn10_tiff_set_compression(gcn10_tiff_writer *w, int compression)
 {
     if (compression != 8 && compression != 5)
         return -1;
-    w->compression = compression;
+    w->root->compression = compression;     /* every IFD of a COG has the same Compression */
     return 0;
 }
 
@@ -1139,6 +1149,8 @@ gcn10_tiff_writer *gcn10_tiff_create(const char *path, int xsize, int ysize, con
         goto oom;
     w->fd = -1;
     w->compression = 8;
+    w->root = w;
+    w->last_idx = -1;
     pthread_mutex_init(&w->mu, NULL);
     w->xsize = xsize;
     w->ysize = ysize;
@@ -1181,29 +1193,152 @@ int gcn10_tiff_tiles_down(const gcn10_tiff_writer *w)
     return w->down;
 }
 
+int gcn10_cog_levels(int xsize, int ysize)
+{
+    int k = 0;
+
+    if (xsize <= 0 || ysize <= 0)
+        return -1;
+    while (xsize > TILE || ysize > TILE) {
+        xsize = (xsize + 1) / 2;        /* ceil(W / 2^k) step by step: ceil(ceil(a/2)/2) = ceil(a/4) */
+        ysize = (ysize + 1) / 2;
+        k++;
+    }
+    return k;
+}
+
+static int cog_layout(gcn10_tiff_writer *R, int fd, uint64_t *first, uint64_t *end);
+
+gcn10_tiff_writer *gcn10_tiff_create_cog(const char *path, int xsize, int ysize, const double gt[6],
+                                         const gcn10_georef *georef, int n_levels, char *err, size_t errcap)
+{
+    gcn10_tiff_writer *w;
+    uint64_t first, end;
+
+    if (n_levels < 0 || n_levels > 30 || xsize <= 0 || ysize <= 0) {
+        snprintf(err, errcap, "write error: bad overview level count %d for %dx%d (%s)", n_levels, xsize, ysize, path);
+        return NULL;
+    }
+    w = gcn10_tiff_create(path, xsize, ysize, gt, georef, err, errcap);
+    if (!w)
+        return NULL;
+    w->cog = true;
+    w->n_levels = n_levels;
+    w->cur_level = n_levels;
+    w->levels = calloc(n_levels > 0 ? (size_t)n_levels : 1, sizeof *w->levels);
+    if (!w->levels)
+        goto oom;
+    for (int k = 1; k <= n_levels; k++) {
+        gcn10_tiff_writer *v = calloc(1, sizeof *v);
+        size_t nt;
+
+        if (!v)
+            goto oom;
+        w->levels[k - 1] = v;
+        v->root = w;
+        v->level = k;
+        v->last_idx = -1;
+        v->fd = -1;
+        v->xsize = (int)(((int64_t)xsize + ((int64_t)1 << k) - 1) >> k);
+        v->ysize = (int)(((int64_t)ysize + ((int64_t)1 << k) - 1) >> k);
+        v->across = (v->xsize + TILE - 1) / TILE;
+        v->down = (v->ysize + TILE - 1) / TILE;
+        nt = (size_t)v->across * (size_t)v->down;
+        v->offsets = calloc(nt, sizeof *v->offsets);
+        v->counts = calloc(nt, sizeof *v->counts);
+        if (!v->offsets || !v->counts)
+            goto oom;
+    }
+    /* the IFDs' room: their sizes depend only on the level sizes and the georeferencing */
+    if (cog_layout(w, -1, &first, &end) != 0) {
+        snprintf(err, errcap, "write error: directories of %s do not fit classic TIFF", path);
+        gcn10_tiff_abort(w);
+        return NULL;
+    }
+    w->data_start = end;
+    w->pos = end;
+    return w;
+
+oom:
+    snprintf(err, errcap, "out of memory creating %s", path);
+    gcn10_tiff_abort(w);
+    return NULL;
+}
+
+int gcn10_tiff_n_levels(const gcn10_tiff_writer *w)
+{
+    return w->root->n_levels;
+}
+
+gcn10_tiff_writer *gcn10_tiff_level(gcn10_tiff_writer *w, int level)
+{
+    w = w->root;
+    if (level == 0)
+        return w;
+    if (level < 0 || level > w->n_levels)
+        return NULL;
+    return w->levels[level - 1];
+}
+
+/* COG order rule (called with root->mu held): tile data is appended level L first, full resolution last, and in
+ * each level in row-major tile order, so every IFD's offsets increase.  0 = the tiles idx[0..n) (ascending) may go
+ * next; -1 = they would break the order.  Always 0 for a plain file. */
+static int cog_order_ok(gcn10_tiff_writer *w, int n, const int *tx, const int *ty)
+{
+    long long prev = w->last_idx;
+
+    if (!w->root->cog)
+        return 0;
+    if (w->level > w->root->cur_level)
+        return -1;
+    if (w->level < w->root->cur_level)
+        prev = -1;                      /* the first put of a finer level */
+    for (int i = 0; i < n; i++) {
+        long long idx = (long long)ty[i] * w->across + tx[i];
+
+        if (idx <= prev)
+            return -1;
+        prev = idx;
+    }
+    return 0;
+}
+
+static void cog_order_advance(gcn10_tiff_writer *w, int n, const int *tx, const int *ty)
+{
+    if (!w->root->cog || n <= 0)
+        return;
+    w->root->cur_level = w->level;
+    w->last_idx = (long long)ty[n - 1] * w->across + tx[n - 1];
+}
+
 int gcn10_tiff_put_tile(gcn10_tiff_writer *w, int tx, int ty, const void *zdata, size_t nbytes)
 {
+    gcn10_tiff_writer *R = w->root;
     int rc = 0;
     size_t idx;
 
     if (tx < 0 || ty < 0 || tx >= w->across || ty >= w->down || nbytes == 0)
         return -1;
     idx = (size_t)ty * (size_t)w->across + (size_t)tx;
-    pthread_mutex_lock(&w->mu);
-    if (w->pos + nbytes + (1u << 20) > 0xffffffffull) {
-        w->failed = true;           /* classic TIFF offsets are 32 bit */
+    pthread_mutex_lock(&R->mu);
+    if (cog_order_ok(w, 1, &tx, &ty) != 0) {
+        rc = -1;                        /* refused; the file itself is still intact */
+    }
+    else if (R->pos + nbytes + (1u << 20) > 0xffffffffull) {
+        R->failed = true;           /* classic TIFF offsets are 32 bit */
         rc = -1;
     }
-    else if (write_all(w->fd, zdata, nbytes, w->pos) != 0) {
-        w->failed = true;
+    else if (write_all(R->fd, zdata, nbytes, R->pos) != 0) {
+        R->failed = true;
         rc = -1;
     }
     else {
-        w->offsets[idx] = (uint32_t)w->pos;
+        w->offsets[idx] = (uint32_t)R->pos;
         w->counts[idx] = (uint32_t)nbytes;
-        w->pos += nbytes;
+        R->pos += nbytes;
+        cog_order_advance(w, 1, &tx, &ty);
     }
-    pthread_mutex_unlock(&w->mu);
+    pthread_mutex_unlock(&R->mu);
     return rc;
 }
 
@@ -1212,13 +1347,18 @@ int gcn10_tiff_put_tile(gcn10_tiff_writer *w, int tx, int ty, const void *zdata,
 int gcn10_tiff_put_tiles(gcn10_tiff_writer *w, int n, const int *tx, const int *ty, const void *const *zdata,
                          const uint32_t *nbytes)
 {
+    gcn10_tiff_writer *R = w->root;
     struct iovec iov[512];
     int rc = 0;
 
-    pthread_mutex_lock(&w->mu);
+    pthread_mutex_lock(&R->mu);
+    if (cog_order_ok(w, n, tx, ty) != 0) {
+        pthread_mutex_unlock(&R->mu);
+        return -1;
+    }
     for (int i = 0; i < n && rc == 0;) {
         int m = 0;
-        uint64_t total = 0, at = w->pos;
+        uint64_t total = 0, at = R->pos;
 
         for (; i + m < n && m < 512; m++) {
             if (tx[i + m] < 0 || ty[i + m] < 0 || tx[i + m] >= w->across || ty[i + m] >= w->down ||
@@ -1232,12 +1372,12 @@ int gcn10_tiff_put_tiles(gcn10_tiff_writer *w, int n, const int *tx, const int *
         }
         if (rc != 0)
             break;
-        if (w->pos + total + (1u << 20) > 0xffffffffull) {
+        if (R->pos + total + (1u << 20) > 0xffffffffull) {
             rc = -1;                    /* classic TIFF offsets are 32 bit */
             break;
         }
         for (int k = 0; k < m;) {       /* pwritev may stop short */
-            ssize_t got = pwritev(w->fd, iov + k, m - k, (off_t)at);
+            ssize_t got = pwritev(R->fd, iov + k, m - k, (off_t)at);
 
             if (got < 0 && errno == EINTR)
                 continue;
@@ -1258,15 +1398,17 @@ int gcn10_tiff_put_tiles(gcn10_tiff_writer *w, int n, const int *tx, const int *
         for (int k = 0; k < m; k++) {
             size_t idx = (size_t)ty[i + k] * (size_t)w->across + (size_t)tx[i + k];
 
-            w->offsets[idx] = (uint32_t)w->pos;
+            w->offsets[idx] = (uint32_t)R->pos;
             w->counts[idx] = nbytes[i + k];
-            w->pos += nbytes[i + k];
+            R->pos += nbytes[i + k];
         }
         i += m;
     }
     if (rc != 0)
-        w->failed = true;
-    pthread_mutex_unlock(&w->mu);
+        R->failed = true;
+    else
+        cog_order_advance(w, n, tx, ty);
+    pthread_mutex_unlock(&R->mu);
     return rc;
 }
 
@@ -1279,7 +1421,10 @@ enum { DIRECT_ALIGN = 4096 };
 
 int gcn10_tiff_set_direct(gcn10_tiff_writer *w, bool on)
 {
-    int fl = fcntl(w->fd, F_GETFL);
+    int fl;
+
+    w = w->root;
+    fl = fcntl(w->fd, F_GETFL);
 
     if (fl < 0)
         return -1;
@@ -1302,30 +1447,35 @@ int gcn10_tiff_set_direct(gcn10_tiff_writer *w, bool on)
 int gcn10_tiff_put_extent(gcn10_tiff_writer *w, const void *data, size_t extent_bytes, int n, const int *tx,
                           const int *ty, const uint32_t *rel_off, const uint32_t *nbytes)
 {
+    gcn10_tiff_writer *R = w->root;
     int rc = 0;
 
     for (int i = 0; i < n; i++)
         if (tx[i] < 0 || ty[i] < 0 || tx[i] >= w->across || ty[i] >= w->down || nbytes[i] == 0 ||
-            (size_t)rel_off[i] + nbytes[i] > extent_bytes)
+            (size_t)rel_off[i] + nbytes[i] > extent_bytes || (R->cog && i > 0 && rel_off[i] <= rel_off[i - 1]))
             return -1;
-    pthread_mutex_lock(&w->mu);
+    pthread_mutex_lock(&R->mu);
+    if (cog_order_ok(w, n, tx, ty) != 0) {
+        pthread_mutex_unlock(&R->mu);
+        return -1;
+    }
     {
-        uint64_t at = w->pos;
+        uint64_t at = R->pos;
         size_t len = extent_bytes;
 
-        if (w->direct) {
+        if (R->direct) {
             at = (at + DIRECT_ALIGN - 1) / DIRECT_ALIGN * DIRECT_ALIGN;
             len = (len + DIRECT_ALIGN - 1) / DIRECT_ALIGN * DIRECT_ALIGN;
         }
         if (at + len + (1u << 20) > 0xffffffffull) {
             rc = -1;                    /* classic TIFF offsets are 32 bit */
         }
-        else if (write_all(w->fd, data, len, at) != 0) {
-            if (w->direct && errno == EINVAL && gcn10_tiff_set_direct(w, false) != 0 && !w->direct) {
+        else if (write_all(R->fd, data, len, at) != 0) {
+            if (R->direct && errno == EINVAL && gcn10_tiff_set_direct(R, false) != 0 && !R->direct) {
                 /* this file system takes the flag and then refuses the write: once more without it */
-                at = w->pos;
+                at = R->pos;
                 len = extent_bytes;
-                rc = write_all(w->fd, data, len, at) != 0 ? -1 : 0;
+                rc = write_all(R->fd, data, len, at) != 0 ? -1 : 0;
             }
             else {
                 rc = -1;
@@ -1338,12 +1488,13 @@ int gcn10_tiff_put_extent(gcn10_tiff_writer *w, const void *data, size_t extent_
                 w->offsets[idx] = (uint32_t)(at + rel_off[i]);
                 w->counts[idx] = nbytes[i];
             }
-            w->pos = at + len;
+            R->pos = at + len;
+            cog_order_advance(w, n, tx, ty);
         }
     }
     if (rc != 0)
-        w->failed = true;
-    pthread_mutex_unlock(&w->mu);
+        R->failed = true;
+    pthread_mutex_unlock(&R->mu);
     return rc;
 }
 
@@ -1368,119 +1519,225 @@ struct dirent_w {
     size_t nbytes;
 };
 
+/* the values the entries of one IFD point at */
+struct ifd_vals {
+    unsigned char s_sub[4], s_w[4], s_h[4], s_bps[2], s_comp[2], s_phot[2], s_spp[2], s_plan[2], s_tw[2], s_th[2],
+        s_fmt[2];
+    double scale[3], tie[6], xform[16];
+};
+
+/* Directory entries of level view v of root R, ascending tags.  v == R: the full-resolution IFD, the tag set of a
+ * plain file; an overview level: NewSubfileType = 1 (reduced resolution), its own size and tiles, the same
+ * Compression, no geo tags (readers take the georeferencing of overviews from the main IFD). */
+static int ifd_entries(const gcn10_tiff_writer *R, const gcn10_tiff_writer *v, struct ifd_vals *x,
+                       struct dirent_w ents[24])
+{
+    const size_t nt = (size_t)v->across * (size_t)v->down;
+    int ne = 0;
+
+    memset(x, 0, sizeof *x);
+    x->scale[0] = R->gt[1];
+    x->scale[1] = -R->gt[5];
+    x->tie[3] = R->gt[0];
+    x->tie[4] = R->gt[3];
+    put32(x->s_sub, 1);
+    put32(x->s_w, (uint32_t)v->xsize);
+    put32(x->s_h, (uint32_t)v->ysize);
+    put16(x->s_bps, 8);
+    put16(x->s_comp, (unsigned)R->compression);     /* COMPRESS=DEFLATE -> Adobe deflate (8); COMPRESS=LZW -> 5 */
+    put16(x->s_phot, 1);            /* MinIsBlack */
+    put16(x->s_spp, 1);
+    put16(x->s_plan, 1);
+    put16(x->s_tw, TILE);
+    put16(x->s_th, TILE);
+    put16(x->s_fmt, 1);             /* unsigned integer */
+#define ENT(tag_, type_, count_, data_, nbytes_) \
+    ents[ne++] = (struct dirent_w){ tag_, type_, (uint32_t)(count_), data_, nbytes_ }
+    if (v != R)
+        ENT(254, T_LONG, 1, x->s_sub, 4);
+    ENT(256, T_LONG, 1, x->s_w, 4);
+    ENT(257, T_LONG, 1, x->s_h, 4);
+    ENT(258, T_SHORT, 1, x->s_bps, 2);
+    ENT(259, T_SHORT, 1, x->s_comp, 2);
+    ENT(262, T_SHORT, 1, x->s_phot, 2);
+    ENT(277, T_SHORT, 1, x->s_spp, 2);
+    ENT(284, T_SHORT, 1, x->s_plan, 2);
+    ENT(322, T_SHORT, 1, x->s_tw, 2);
+    ENT(323, T_SHORT, 1, x->s_th, 2);
+    ENT(324, T_LONG, nt, v->offsets, nt * 4);      /* host is little endian (x86-64) */
+    ENT(325, T_LONG, nt, v->counts, nt * 4);
+    ENT(339, T_SHORT, 1, x->s_fmt, 2);
+    if (v != R)
+        return ne;
+    if (R->gt[2] == 0.0 && R->gt[4] == 0.0) {
+        ENT(33550, T_DOUBLE, 3, x->scale, sizeof x->scale);
+        ENT(33922, T_DOUBLE, 6, x->tie, sizeof x->tie);
+    }
+    else {
+        /* a rotated or sheared geotransform: ModelTransformationTag, the 4x4 matrix GDAL's
+         * GTiff driver writes for GDALSetGeoTransform in that case (src/raster.c:210) */
+        x->xform[0] = R->gt[1]; x->xform[1] = R->gt[2]; x->xform[3] = R->gt[0];
+        x->xform[4] = R->gt[4]; x->xform[5] = R->gt[5]; x->xform[7] = R->gt[3];
+        x->xform[15] = 1.0;
+        ENT(34264, T_DOUBLE, 16, x->xform, sizeof x->xform);
+    }
+    if (R->georef.n_geokeys > 0 && R->georef.geokeys)
+        ENT(34735, T_SHORT, R->georef.n_geokeys, R->georef.geokeys, (size_t)R->georef.n_geokeys * 2);
+    if (R->georef.geodoubles)
+        ENT(34736, T_DOUBLE, R->georef.n_geodoubles, R->georef.geodoubles, (size_t)R->georef.n_geodoubles * 8);
+    if (R->georef.geoascii)
+        ENT(34737, T_ASCII, strlen(R->georef.geoascii) + 1, R->georef.geoascii, strlen(R->georef.geoascii) + 1);
+#undef ENT
+    return ne;
+}
+
+/* One IFD: its out-of-line values from *val_pos on (word aligned; *val_pos is advanced past them) and the
+ * directory itself at dir_pos, chained to `next`.  fd < 0: sizes only.  0 or -1. */
+static int write_ifd(int fd, const struct dirent_w *ents, int ne, uint64_t dir_pos, uint64_t *val_pos, uint32_t next)
+{
+    const size_t dirbytes = 2 + (size_t)ne * 12 + 4;
+    unsigned char *dir = fd >= 0 ? calloc(1, dirbytes) : NULL;
+    uint64_t pos = (*val_pos + 1) & ~1ull;
+    int rc = -1;
+
+    if (fd >= 0 && !dir)
+        return -1;
+    if (dir)
+        put16(dir, (unsigned)ne);
+    for (int i = 0; i < ne; i++) {
+        unsigned char *e = dir ? dir + 2 + i * 12 : NULL;
+
+        if (e) {
+            put16(e, ents[i].tag);
+            put16(e + 2, ents[i].type);
+            put32(e + 4, ents[i].count);
+        }
+        if (ents[i].nbytes <= 4) {
+            if (e)
+                memcpy(e + 8, ents[i].data, ents[i].nbytes);
+            continue;
+        }
+        if (pos + ents[i].nbytes > 0xffffffffull || (fd >= 0 && write_all(fd, ents[i].data, ents[i].nbytes, pos) != 0))
+            goto done;
+        if (e)
+            put32(e + 8, (uint32_t)pos);
+        pos = (pos + ents[i].nbytes + 1) & ~1ull;
+    }
+    if (dir)
+        put32(dir + dirbytes - 4, next);
+    if (dir_pos + dirbytes > 0xffffffffull || (fd >= 0 && write_all(fd, dir, dirbytes, dir_pos) != 0))
+        goto done;
+    *val_pos = pos;
+    rc = 0;
+done:
+    free(dir);
+    return rc;
+}
+
+static size_t ifd_bytes(int ne)
+{
+    return 2 + (size_t)ne * 12 + 4;
+}
+
+/* COG: GDAL's ghost area (structural metadata) at offset 8, then every IFD with its values.  Returns the position
+ * of the first byte after them; with fd >= 0 the IFDs are written (tile arrays as they are now). */
+static const char cog_ghost_body[] = "LAYOUT=IFDS_BEFORE_DATA\nBLOCK_ORDER=ROW_MAJOR\nKNOWN_INCOMPATIBLE_EDITION=NO\n";
+
+static int cog_layout(gcn10_tiff_writer *R, int fd, uint64_t *first, uint64_t *end)
+{
+    char ghost[128];
+    int n = snprintf(ghost, sizeof ghost, "GDAL_STRUCTURAL_METADATA_SIZE=%06d bytes\n%s",
+                     (int)(sizeof cog_ghost_body - 1), cog_ghost_body);
+    uint64_t pos = (8 + (uint64_t)n + 1) & ~1ull;
+
+    if (fd >= 0 && write_all(fd, ghost, (size_t)n, 8) != 0)
+        return -1;
+    *first = pos;
+    for (int k = 0; k <= R->n_levels; k++) {
+        gcn10_tiff_writer *v = k == 0 ? R : R->levels[k - 1];
+        struct ifd_vals x;
+        struct dirent_w ents[24];
+        const int ne = ifd_entries(R, v, &x, ents);
+        const uint64_t dir_pos = pos;
+        uint64_t val_pos = dir_pos + ifd_bytes(ne);
+        uint64_t next;
+
+        /* the next IFD follows this one's values: their end is known from a dry run */
+        if (write_ifd(-1, ents, ne, dir_pos, &val_pos, 0) != 0)
+            return -1;
+        next = k < R->n_levels ? val_pos : 0;
+        val_pos = dir_pos + ifd_bytes(ne);
+        if (write_ifd(fd, ents, ne, dir_pos, &val_pos, (uint32_t)next) != 0)
+            return -1;
+        pos = val_pos;
+    }
+    *end = pos;
+    return 0;
+}
+
 int gcn10_tiff_finish(gcn10_tiff_writer *w, char *err, size_t errcap)
 {
-    size_t nt = (size_t)w->across * (size_t)w->down;
-    double scale[3] = { w->gt[1], -w->gt[5], 0.0 };
-    double tie[6] = { 0, 0, 0, w->gt[0], w->gt[3], 0 };
-    double xform[16] = { 0 };
-    unsigned char s_w[4], s_h[4], s_bps[2], s_comp[2], s_phot[2], s_spp[2], s_plan[2], s_tw[2],
-        s_th[2], s_fmt[2];
-    struct dirent_w ents[20];
-    int ne = 0, rc = -1;
-    unsigned char *dir = NULL;
-    uint64_t data_pos, dir_pos;
-    size_t dirbytes;
+    struct ifd_vals x;
+    struct dirent_w ents[24];
+    int ne, rc = -1;
 
+    w = w->root;
     if (w->failed) {
         snprintf(err, errcap, "write error on %s", w->path);
         goto done;
     }
     if (w->direct)
         gcn10_tiff_set_direct(w, false);        /* the directory is not sector sized */
-    for (size_t i = 0; i < nt; i++)
-        if (w->counts[i] == 0) {
-            snprintf(err, errcap, "write error on %s: tile %zu was never written", w->path, i);
-            goto done;
-        }
-    put32(s_w, (uint32_t)w->xsize);
-    put32(s_h, (uint32_t)w->ysize);
-    put16(s_bps, 8);
-    put16(s_comp, (unsigned)w->compression);     /* COMPRESS=DEFLATE -> Adobe deflate (8); COMPRESS=LZW -> 5 */
-    put16(s_phot, 1);           /* MinIsBlack */
-    put16(s_spp, 1);
-    put16(s_plan, 1);
-    put16(s_tw, TILE);
-    put16(s_th, TILE);
-    put16(s_fmt, 1);            /* unsigned integer */
-#define ENT(tag_, type_, count_, data_, nbytes_) \
-    ents[ne++] = (struct dirent_w){ tag_, type_, (uint32_t)(count_), data_, nbytes_ }
-    ENT(256, T_LONG, 1, s_w, 4);
-    ENT(257, T_LONG, 1, s_h, 4);
-    ENT(258, T_SHORT, 1, s_bps, 2);
-    ENT(259, T_SHORT, 1, s_comp, 2);
-    ENT(262, T_SHORT, 1, s_phot, 2);
-    ENT(277, T_SHORT, 1, s_spp, 2);
-    ENT(284, T_SHORT, 1, s_plan, 2);
-    ENT(322, T_SHORT, 1, s_tw, 2);
-    ENT(323, T_SHORT, 1, s_th, 2);
-    ENT(324, T_LONG, nt, w->offsets, nt * 4);      /* host is little endian (x86-64) */
-    ENT(325, T_LONG, nt, w->counts, nt * 4);
-    ENT(339, T_SHORT, 1, s_fmt, 2);
-    if (w->gt[2] == 0.0 && w->gt[4] == 0.0) {
-        ENT(33550, T_DOUBLE, 3, scale, sizeof scale);
-        ENT(33922, T_DOUBLE, 6, tie, sizeof tie);
-    }
-    else {
-        /* a rotated or sheared geotransform: ModelTransformationTag, the 4x4 matrix GDAL's
-         * GTiff driver writes for GDALSetGeoTransform in that case (src/raster.c:210) */
-        xform[0] = w->gt[1]; xform[1] = w->gt[2]; xform[3] = w->gt[0];
-        xform[4] = w->gt[4]; xform[5] = w->gt[5]; xform[7] = w->gt[3];
-        xform[15] = 1.0;
-        ENT(34264, T_DOUBLE, 16, xform, sizeof xform);
-    }
-    if (w->georef.n_geokeys > 0 && w->georef.geokeys)
-        ENT(34735, T_SHORT, w->georef.n_geokeys, w->georef.geokeys, (size_t)w->georef.n_geokeys * 2);
-    if (w->georef.geodoubles)
-        ENT(34736, T_DOUBLE, w->georef.n_geodoubles, w->georef.geodoubles,
-            (size_t)w->georef.n_geodoubles * 8);
-    if (w->georef.geoascii)
-        ENT(34737, T_ASCII, strlen(w->georef.geoascii) + 1, w->georef.geoascii,
-            strlen(w->georef.geoascii) + 1);
-#undef ENT
+    for (int k = 0; k <= w->n_levels; k++) {
+        const gcn10_tiff_writer *v = k == 0 ? w : w->levels[k - 1];
+        const size_t nt = (size_t)v->across * (size_t)v->down;
 
-    /* out-of-line payloads first, then the directory, both word aligned */
-    data_pos = (w->pos + 1) & ~1ull;
-    dirbytes = 2 + (size_t)ne * 12 + 4;
-    dir = calloc(1, dirbytes);
-    if (!dir) {
-        snprintf(err, errcap, "out of memory finishing %s", w->path);
-        goto done;
-    }
-    put16(dir, (unsigned)ne);
-    for (int i = 0; i < ne; i++) {
-        unsigned char *e = dir + 2 + i * 12;
-
-        put16(e, ents[i].tag);
-        put16(e + 2, ents[i].type);
-        put32(e + 4, ents[i].count);
-        if (ents[i].nbytes <= 4) {
-            memcpy(e + 8, ents[i].data, ents[i].nbytes);
-        }
-        else {
-            if (data_pos + ents[i].nbytes > 0xffffffffull ||
-                write_all(w->fd, ents[i].data, ents[i].nbytes, data_pos) != 0) {
-                snprintf(err, errcap, "write error on %s", w->path);
+        for (size_t i = 0; i < nt; i++)
+            if (v->counts[i] == 0) {
+                if (k == 0)
+                    snprintf(err, errcap, "write error on %s: tile %zu was never written", w->path, i);
+                else
+                    snprintf(err, errcap, "write error on %s: tile %zu of overview level %d was never written",
+                             w->path, i, k);
                 goto done;
             }
-            put32(e + 8, (uint32_t)data_pos);
-            data_pos = (data_pos + ents[i].nbytes + 1) & ~1ull;
-        }
     }
-    dir_pos = data_pos;
+    if (w->cog) {
+        unsigned char off[4];
+        uint64_t first, end;
+
+        /* the IFDs go into the room create left for them: same entries, same sizes, now with the tile arrays */
+        if (cog_layout(w, w->fd, &first, &end) != 0 || end != w->data_start) {
+            snprintf(err, errcap, "write error on %s", w->path);
+            goto done;
+        }
+        put32(off, (uint32_t)first);
+        if (write_all(w->fd, off, 4, 4) != 0) {
+            snprintf(err, errcap, "write error on %s", w->path);
+            goto done;
+        }
+        rc = 0;
+        goto done;
+    }
+    ne = ifd_entries(w, w, &x, ents);
     {
+        /* out-of-line payloads first, then the directory, both word aligned */
+        uint64_t val_pos = (w->pos + 1) & ~1ull, dir_pos = val_pos;
         unsigned char off[4];
 
+        if (write_ifd(-1, ents, ne, 0, &dir_pos, 0) != 0 ||
+            write_ifd(w->fd, ents, ne, dir_pos, &val_pos, 0) != 0) {
+            snprintf(err, errcap, "write error on %s", w->path);
+            goto done;
+        }
         put32(off, (uint32_t)dir_pos);
-        if (dir_pos + dirbytes > 0xffffffffull || write_all(w->fd, dir, dirbytes, dir_pos) != 0 ||
-            write_all(w->fd, off, 4, 4) != 0) {
+        if (write_all(w->fd, off, 4, 4) != 0) {
             snprintf(err, errcap, "write error on %s", w->path);
             goto done;
         }
     }
     rc = 0;
 done:
-    free(dir);
     if (w->fd >= 0 && close(w->fd) != 0 && rc == 0) {
         snprintf(err, errcap, "write error closing %s: %s", w->path, strerror(errno));
         rc = -1;
@@ -1498,10 +1755,24 @@ done:
     return rc;
 }
 
+static void free_level_view(gcn10_tiff_writer *v)
+{
+    if (!v)
+        return;
+    free(v->offsets);
+    free(v->counts);
+    free(v);
+}
+
 void gcn10_tiff_abort(gcn10_tiff_writer *w)
 {
     if (!w)
         return;
+    w = w->root ? w->root : w;
+    if (w->levels)
+        for (int k = 0; k < w->n_levels; k++)
+            free_level_view(w->levels[k]);
+    free(w->levels);
     if (w->fd >= 0)
         close(w->fd);
     if (w->part)

@@ -43,7 +43,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_deflate_fused_available",
     "gcn10_gpu_inflate_tiles", "gcn10_gpu_stream_copy", "gcn10_gpu_tune_single_raster",
     "gcn10_gpu_soil_words_state", "gcn10_gpu_lzw_arena_bound", "gcn10_gpu_lzw_strip",
-    "gcn10_gpu_inflate_codecs",
+    "gcn10_gpu_inflate_codecs", "gcn10_gpu_overview_nearest", "gcn10_gpu_overview_average",
 )
 
 
@@ -119,6 +119,8 @@ def lib():
             "gcn10_gpu_deflate_strip": (i, [vp, vp, i, i, i, vp, sz, vp, vp, vp]),
             "gcn10_gpu_lzw_arena_bound": (sz, [i, i, i]),
             "gcn10_gpu_lzw_strip": (i, [vp, vp, i, i, i, vp, sz, vp, vp, vp]),
+            "gcn10_gpu_overview_nearest": (i, [vp, vp, i, i, i, vp, vp]),
+            "gcn10_gpu_overview_average": (i, [vp, vp, i, i, i, i, vp, u, u, i, C.POINTER(vp), vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -370,6 +372,19 @@ class Engine:
             for b in (ptrs, arena, table, cursor):
                 b.close()
         return data, tab, used
+
+    def overview_nearest(self, src_ptr: int, W: int, H: int, level: int, dst_ptr: int, stream=None):
+        """Level `level` of a W x H device landcover, nearest sampling, into dst (gcn10_gpu_overview_nearest)."""
+        self._chk(lib().gcn10_gpu_overview_nearest(self._ctx, src_ptr, W, H, level, dst_ptr, stream),
+                  "gcn10_gpu_overview_nearest")
+
+    def overview_average(self, esa_ptr: int, W: int, H: int, y0: int, rows: int, cj_ptr: int, cond_mask: int,
+                         table_mask: int, n_levels: int, level_ptrs: Sequence[int], stream=None):
+        """Average overview levels 1..n_levels of the selected rasters for full-resolution rows [y0, y0+rows)
+        (gcn10_gpu_overview_average).  level_ptrs: [q * n_levels + k - 1] device pointers."""
+        arr = (C.c_void_p * len(level_ptrs))(*[int(p) for p in level_ptrs])
+        self._chk(lib().gcn10_gpu_overview_average(self._ctx, esa_ptr, W, H, y0, rows, cj_ptr, cond_mask, table_mask,
+                                                   n_levels, arr, stream), "gcn10_gpu_overview_average")
 
     def lzw_arena_bound(self, W: int, rows: int, n_rasters: int) -> int:
         """Worst-case arena bytes of gcn10_gpu_lzw_strip for n_rasters strips of W x rows."""

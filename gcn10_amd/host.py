@@ -71,6 +71,33 @@ def lib():
         L.gcn10_raster_georef.restype = vp
         L.gcn10_save_raster.argtypes = [vp, C.c_int, C.c_int, _f64p, vp, cp, C.c_int, cp, C.c_size_t]
         L.gcn10_save_raster.restype = C.c_int
+        L.gcn10_tiff_create_cog.argtypes = [cp, C.c_int, C.c_int, _f64p, vp, C.c_int, cp, C.c_size_t]
+        L.gcn10_tiff_create_cog.restype = vp
+        L.gcn10_tiff_create.argtypes = [cp, C.c_int, C.c_int, _f64p, vp, cp, C.c_size_t]
+        L.gcn10_tiff_create.restype = vp
+        L.gcn10_cog_levels.argtypes = [C.c_int, C.c_int]
+        L.gcn10_cog_levels.restype = C.c_int
+        L.gcn10_tiff_level.argtypes = [vp, C.c_int]
+        L.gcn10_tiff_level.restype = vp
+        L.gcn10_tiff_n_levels.argtypes = [vp]
+        L.gcn10_tiff_n_levels.restype = C.c_int
+        L.gcn10_tiff_tiles_across.argtypes = [vp]
+        L.gcn10_tiff_tiles_across.restype = C.c_int
+        L.gcn10_tiff_tiles_down.argtypes = [vp]
+        L.gcn10_tiff_tiles_down.restype = C.c_int
+        L.gcn10_tiff_put_tile.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
+        L.gcn10_tiff_put_tile.restype = C.c_int
+        L.gcn10_tiff_put_extent.argtypes = [vp, vp, C.c_size_t, C.c_int, ip, ip, C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint32)]
+        L.gcn10_tiff_put_extent.restype = C.c_int
+        L.gcn10_tiff_set_compression.argtypes = [vp, C.c_int]
+        L.gcn10_tiff_set_compression.restype = C.c_int
+        L.gcn10_tiff_set_direct.argtypes = [vp, C.c_bool]
+        L.gcn10_tiff_set_direct.restype = C.c_int
+        L.gcn10_tiff_finish.argtypes = [vp, cp, C.c_size_t]
+        L.gcn10_tiff_finish.restype = C.c_int
+        L.gcn10_tiff_abort.argtypes = [vp]
+        L.gcn10_tiff_abort.restype = None
         L.free_ = C.CDLL(None).free
         L.free_.argtypes = [vp]
         L.free_.restype = None
@@ -88,7 +115,7 @@ class Config(C.Structure):
                 ("gpu_deflate", C.c_int), ("gpu_inflate", C.c_int), ("direct_io", C.c_int),
                 ("prefetch_blocks", C.c_int),
                 ("table_mask", C.c_uint), ("cond_mask", C.c_uint), ("compress", C.c_int),
-                ("gpu_inflate_lzw", C.c_int)]
+                ("gpu_inflate_lzw", C.c_int), ("cog", C.c_int), ("overview_resampling", C.c_int)]
 
 
 class Blocks(C.Structure):
@@ -251,6 +278,81 @@ def save_raster(data: np.ndarray, gt, path: str, georef_ptr=None, level: int = 0
                                  os.fsencode(path), level, err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
+
+
+def cog_levels(xsize: int, ysize: int) -> int:
+    """Overview levels of a COG of that size (GDAL's rule with BLOCKSIZE=256)."""
+    return lib().gcn10_cog_levels(xsize, ysize)
+
+
+class TiffWriter:
+    """The streaming GeoTIFF writer (``gcn10_tiff_create`` / ``gcn10_tiff_create_cog``): tiles go in already
+    compressed.  ``n_levels=None``: a plain file; an int: a COG with that many overview levels.  ``put_*`` return
+    the C result (0 or -1) so that refused puts can be seen."""
+
+    def __init__(self, path: str, xsize: int, ysize: int, gt, n_levels=None, georef_ptr=None,
+                 compression: int = 8, direct: bool = False):
+        err = C.create_string_buffer(1024)
+        L = lib()
+        if n_levels is None:
+            self._h = L.gcn10_tiff_create(os.fsencode(path), xsize, ysize, _f(gt, 6), georef_ptr, err, 1024)
+        else:
+            self._h = L.gcn10_tiff_create_cog(os.fsencode(path), xsize, ysize, _f(gt, 6), georef_ptr, n_levels,
+                                              err, 1024)
+        if not self._h:
+            raise HostError(err.value.decode(errors="replace"))
+        if compression != 8 and L.gcn10_tiff_set_compression(self._h, compression) != 0:
+            self.abort()
+            raise HostError("bad compression %d" % compression)
+        self.direct = bool(direct) and L.gcn10_tiff_set_direct(self._h, True) == 0
+
+    def _level(self, level):
+        v = lib().gcn10_tiff_level(self._h, level)
+        if not v:
+            raise HostError("no overview level %d" % level)
+        return v
+
+    @property
+    def n_levels(self):
+        return lib().gcn10_tiff_n_levels(self._h)
+
+    def tiles(self, level=0):
+        v = self._level(level)
+        return lib().gcn10_tiff_tiles_across(v), lib().gcn10_tiff_tiles_down(v)
+
+    def put_tile(self, tx, ty, data: bytes, level=0) -> int:
+        return lib().gcn10_tiff_put_tile(self._level(level), tx, ty, data, len(data))
+
+    def put_extent(self, tiles, level=0) -> int:
+        """tiles: [(tx, ty, bytes)] laid out back to back (16-byte slots, as the GPU encoders do) and put
+        with one gcn10_tiff_put_extent.  The extent buffer is 4096-aligned and padded for direct I/O."""
+        rel, off = [], 0
+        for _tx, _ty, d in tiles:
+            rel.append(off)
+            off = (off + len(d) + 15) & ~15
+        size = max(off, 1)
+        buf = np.zeros(((size + 4095) // 4096 + 2) * 4096, np.uint8)
+        base = (-buf.ctypes.data) % 4096
+        for (_tx, _ty, d), r in zip(tiles, rel):
+            buf[base + r:base + r + len(d)] = np.frombuffer(d, np.uint8)
+        n = len(tiles)
+        txs = (C.c_int * n)(*[t[0] for t in tiles])
+        tys = (C.c_int * n)(*[t[1] for t in tiles])
+        rels = (C.c_uint32 * n)(*rel)
+        sizes = (C.c_uint32 * n)(*[len(t[2]) for t in tiles])
+        end = rel[-1] + len(tiles[-1][2]) if n else 0
+        return lib().gcn10_tiff_put_extent(self._level(level), buf.ctypes.data + base, end, n, txs, tys, rels, sizes)
+
+    def finish(self):
+        err = C.create_string_buffer(1024)
+        h, self._h = self._h, None
+        if lib().gcn10_tiff_finish(h, err, 1024) != 0:
+            raise HostError(err.value.decode(errors="replace"))
+
+    def abort(self):
+        if self._h:
+            lib().gcn10_tiff_abort(self._h)
+            self._h = None
 
 
 def _f(v, n):

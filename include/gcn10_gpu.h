@@ -38,7 +38,7 @@ extern "C" {
  *    streams of a strip out as one extent (option "arena_segment_align"), gcn10_gpu_deflate_arena_bound grew by
  *    the extents' pads (round 3).  A caller built against an older header must be rebuilt: check at start-up.
  *    Added within 3: the LZW encoder (gcn10_gpu_lzw_*), LZW tiles of gcn10_gpu_inflate_tiles (GCN10_TILE_LZW)
- *    and gcn10_gpu_inflate_codecs. */
+ *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*). */
 #define GCN10_GPU_ABI_VERSION 3
 
 enum {
@@ -282,6 +282,26 @@ int gcn10_gpu_inflate_tiles(gcn10_gpu_ctx *ctx, const uint8_t *comp_dev,
 #define GCN10_CODEC_RAW 2u
 #define GCN10_CODEC_LZW 4u
 int gcn10_gpu_inflate_codecs(void);
+
+/* Overviews of the Cloud Optimized GeoTIFF output (config key cog=1).  Level k of a W x H block is
+ * ceil(W / 2^k) x ceil(H / 2^k).  Added in ABI 3 without a version change; the host looks them up for cog runs only.
+ *
+ * gcn10_gpu_overview_nearest: dst (level k, row major) = src (W x H landcover, row major) sampled at
+ *   (min(2^k x + 2^(k-1), W-1), min(2^k y + 2^(k-1), H-1)), 1 <= level.  Such a level is a block of its own for
+ *   gcn10_gpu_prepare_tile and the strip encoders (its soil index maps are the block's, composed the same way).
+ * gcn10_gpu_overview_average: levels 1 .. n_levels (1..8) of every selected raster for the full-resolution rows
+ *   [y0, y0 + rows) of a block, straight from its landcover (`esa`: the block's row 0, `cj`: the block's soil rows)
+ *   and the soil gcn10_gpu_prepare_tile prepared for width W: no full-resolution CN raster is made.  Level k pixel =
+ *   the clipped 2x2 footprint in level k-1 (level 0 = the CN raster src/cn.c:114-131 defines) without the value 255,
+ *   (2 s + n) / (2 n) in integers, 255 when n = 0.  y0 and rows are multiples of 256 (rows may end at H), so a strip
+ *   gives whole rows of every level.  levels: host array of n_selected * n_levels device pointers, [q * n_levels +
+ *   k - 1] = level k of the q-th selected raster in ascending raster order, each a whole level raster (the call
+ *   writes the strip's rows of it). */
+int gcn10_gpu_overview_nearest(gcn10_gpu_ctx *ctx, const uint8_t *src, int W, int H, int level, uint8_t *dst,
+                               gcn10_stream_t stream);
+int gcn10_gpu_overview_average(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int H, int y0, int rows,
+                               const int32_t *cj, unsigned cond_mask, unsigned table_mask, int n_levels,
+                               uint8_t *const *levels, gcn10_stream_t stream);
 
 /* Launch-shape knobs of the strip kernels, for tuning runs; results never
  * depend on them.  Names: "grid_blocks_per_cu" (1..64), "ilp16" (0 = by raster count | 1 | 2),

@@ -91,7 +91,7 @@ typedef struct gcn10_config {
     /* optional extensions (absent = default) */
     int gpus;               /* "gpus": number of GPUs to use, 0 = all visible      */
     int workers_per_gpu;    /* "workers_per_gpu": block workers per GPU, 0 = default 2 */
-    int strip_rows;         /* "strip_rows": rows per staging strip, 0 = default 768 */
+    int strip_rows;         /* "strip_rows": rows per staging strip, rounded up to whole tile rows; 0 = default 2304 */
     int io_threads;         /* "io_threads": tile compression threads, 0 = auto    */
     int deflate_level;      /* "deflate_level": zlib level 1..9, 0 = zlib default 6 */
     char *esa_tile_dir;     /* "esa_tile_dir": local mirror of /vsicurl/ VRT sources */
@@ -117,9 +117,14 @@ typedef struct gcn10_config {
     int gpu_inflate_lzw;    /* "gpu_inflate_lzw": 1 (default) with gpu_inflate=1, LZW-compressed landcover tiles
                                cross PCIe compressed and are decoded on the GPU too (when the GPU library has the
                                decoder: gcn10_gpu_inflate_codecs); 0 = LZW windows through the host reader */
+    int cog;                /* "cog": 1 = Cloud Optimized GeoTIFFs with overviews (gcn10_tiff_create_cog), built on the
+                               GPU; 0 (default) = plain tiled GeoTIFFs.  No host fallback: refused with gpu_deflate=0 */
+    int overview_resampling;/* "overview_resampling": GCN10_OVERVIEW_NEAREST (default, "nearest") or
+                               GCN10_OVERVIEW_AVERAGE ("average"), any case */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
+enum { GCN10_OVERVIEW_NEAREST = 0, GCN10_OVERVIEW_AVERAGE = 1 };
 
 /* "g_ii", "p_i,f_iii", "all" -> table mask; "drained" | "undrained" | "both" | "all" -> condition mask.
  * Return 0 and set *mask, or -1 for a name that is not a lookup / condition. */
@@ -127,8 +132,12 @@ int gcn10_parse_lookups(const char *text, unsigned *mask);
 int gcn10_parse_conditions(const char *text, unsigned *mask);
 /* "deflate" | "lzw" (any case) -> GCN10_COMPRESS_*.  0, or -1 for another name. */
 int gcn10_parse_compress(const char *text, int *codec);
+/* "nearest" | "average" (any case) -> GCN10_OVERVIEW_*; "0" | "1" -> cog.  0, or -1 for another value. */
+int gcn10_parse_overview_resampling(const char *text, int *method);
+int gcn10_parse_cog(const char *text, int *cog);
 
-/* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" value; -2 a required key is missing
+/* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
+ * "overview_resampling" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -215,6 +224,26 @@ int gcn10_tiff_set_compression(gcn10_tiff_writer *w, int compression);
 /* O_DIRECT for the tile data (config key "direct_io"): extents must then be 4096-aligned in memory and
  * readable to the next multiple of 4096.  0 = on, -1 = the file system refuses (nothing changed). */
 int gcn10_tiff_set_direct(gcn10_tiff_writer *w, bool on);
+/* Cloud Optimized GeoTIFF (config key "cog"): the same raster plus n_levels overviews, in GDAL's COG layout --
+ * the 8-byte header, GDAL's ghost area at offset 8 ("GDAL_STRUCTURAL_METADATA_SIZE=nnnnnn bytes", LAYOUT=
+ * IFDS_BEFORE_DATA, BLOCK_ORDER=ROW_MAJOR, KNOWN_INCOMPATIBLE_EDITION=NO; no block leader or trailer), then
+ * every IFD with its values (full resolution first, then levels 1 .. n_levels, chained in that order), then the
+ * tile data.  Level k is ceil(xsize / 2^k) x ceil(ysize / 2^k) pixels in 256x256 tiles; its IFD has
+ * NewSubfileType = 1 and no geo tags.  The IFDs' room is reserved here (tile counts are known) and filled in by
+ * gcn10_tiff_finish.  Tile data must arrive in file order: level n_levels first, full resolution last, and within
+ * a level in row-major tile order; a put that would break that order returns -1 and writes nothing (the file
+ * stays usable).  Extents, gathered puts, direct I/O, .part + rename and Compression 5 work as for a plain file. */
+#define GCN10_COG_MAX_LEVELS 8      /* the program's limit: windows of at most 65536 px (gcn10_gpu_overview_average) */
+gcn10_tiff_writer *gcn10_tiff_create_cog(const char *path, int xsize, int ysize, const double gt[6],
+                                         const gcn10_georef *georef, int n_levels, char *err, size_t errcap);
+/* The COG rule with BLOCKSIZE = 256: the smallest k >= 0 with ceil(xsize / 2^k) <= 256 and ceil(ysize / 2^k) <= 256
+ * (-1 for a bad size). */
+int gcn10_cog_levels(int xsize, int ysize);
+/* Level `level` of a COG writer (0 = the full-resolution raster, the writer itself) as a writer for the put calls
+ * and gcn10_tiff_tiles_across / _down; owned by the file's writer (finish / abort it, not the view).  NULL for a
+ * level the file does not have. */
+gcn10_tiff_writer *gcn10_tiff_level(gcn10_tiff_writer *w, int level);
+int gcn10_tiff_n_levels(const gcn10_tiff_writer *w);   /* 0 for a plain file */
 /* Writes the directory and closes the file.  0 or -1. */
 int gcn10_tiff_finish(gcn10_tiff_writer *w, char *err, size_t errcap);
 void gcn10_tiff_abort(gcn10_tiff_writer *w);
@@ -244,6 +273,8 @@ typedef struct gcn10_run_options {
     const char *lookups;        /* --lookups g_ii[,..]: overrides the config key "lookups"       */
     const char *conditions;     /* --conditions drained|undrained|both: overrides "conditions" */
     const char *compress;       /* --compress deflate|lzw: overrides the config key "compress"   */
+    bool cog;                   /* --cog: Cloud Optimized GeoTIFFs (sets the config key "cog")   */
+    const char *overview_resampling;    /* --overview-resampling nearest|average                 */
 } gcn10_run_options;
 
 /* Runs the whole job: config, logs, block ids, lookup tables, one worker thread

@@ -1,0 +1,215 @@
+// gcn10_stats.hip -- the (landcover, soil code) pair histogram behind the band statistics of the outputs
+// (config keys stats=1 / nodata=<v>, DESIGN.md "Band statistics").
+//
+// Every raster's value at a pixel is T8[k][landcover][plane], plane = the soil plane of the pixel for the
+// condition (src/cn.c:88-131).  So one histogram per block over (landcover byte, soil code byte) pairs gives the
+// exact histogram of all 18 rasters on the host, and no CN raster has to exist for it: the kernel reads the same
+// inputs as cn_strip and the fused encoder, a landcover strip and the block's x-expanded soil codes.
+//
+// Only nine soil codes can occur (soil_code() of gcn10_gpu.hip: planes 0..4 or 5 = invalid, drained = 4 for the
+// dual classes), so the codes are mapped to a dense bin and a workgroup's private histogram is 16 x 256 dwords
+// = 16 KiB of LDS.  Contention: in patchy landcover whole waves hit one bin, and 64 lanes adding to one LDS
+// address serialise.  So every lane folds the runs of equal pairs of its 16 consecutive pixels in registers and
+// adds one count per run; a wave whose 1024 pixels are all one pair adds once.  The workgroup histogram goes to
+// the 64-bit device histogram once per workgroup, nonzero bins only.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "gcn10_gpu_internal.hpp"
+
+using namespace gcn10;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr uint32_t kPxPerLane = 16;
+constexpr uint32_t kChunk = kThreads * kPxPerLane;     // pixels of a row per workgroup step
+constexpr int kBins = GCN10_PAIR_HIST_BINS;
+constexpr int kHistWords = GCN10_PAIR_HIST_SIZE;       // [bin][landcover]
+constexpr uint32_t kRowsPerItem = 4;                   // rows of a workgroup step: 4 loads in flight per lane
+#ifndef GCN10_STATS_GRID_PER_CU
+#define GCN10_STATS_GRID_PER_CU 4     // per 36000² block, patchy: 1 -> 1.55 ms, 2 -> 0.96, 4 -> 0.78, 8 -> 0.97
+#endif
+constexpr int kGridPerCu = GCN10_STATS_GRID_PER_CU;   // workgroups per CU at most
+
+// soil code byte (drained plane | undrained plane << 4) -> dense bin: d == u -> d (0..5); a dual class
+// (d = 4, u = 1..3) -> 5 + u (6..8).  Bins 9..15 stay empty.
+__host__ __device__ inline uint32_t code_bin(uint32_t code)
+{
+    const uint32_t d = code & 15u, u = code >> 4;
+    const uint32_t b = d == u ? d : 5u + u;
+    return b < (uint32_t)kBins ? b : (uint32_t)kBins - 1u;
+}
+
+// key of pixel i of a lane: landcover in bits 0..7, soil code in bits 8..15
+__device__ __forceinline__ uint32_t pair_key(const u32x4 &e, const u32x4 &s, uint32_t i)
+{
+    const uint32_t sel = 0x0c0c0400u + (i & 3u) * 0x00000101u;  // byte 0 <- e byte i&3, byte 1 <- s byte i&3
+    return __builtin_amdgcn_perm(s[i >> 2], e[i >> 2], sel);
+}
+
+__device__ __forceinline__ void add_run(uint32_t *h, uint32_t key, uint32_t n)
+{
+    atomicAdd(&h[code_bin(key >> 8) * 256u + (key & 255u)], n);
+}
+
+__device__ __forceinline__ bool all_one_byte(const u32x4 &v)
+{
+    const uint32_t b = (v[0] & 255u) * 0x01010101u;
+    return v[0] == b && v[1] == b && v[2] == b && v[3] == b;
+}
+
+struct HistParams {
+    const uint8_t *esa;         // strip, W x rows, row major
+    const uint8_t *hx;          // x-expanded soil codes, hx_rows rows of hx_stride bytes
+    const int32_t *cj;          // soil row of every strip row
+    unsigned long long *hist;   // [kBins][256]
+    uint32_t W, rows, hx_stride, hx_rows, per_row;
+};
+
+// 16 pixels of a lane: runs of equal pairs folded in registers, one LDS add per run; a wave whose active lanes
+// all hold one single pair adds once
+__device__ __forceinline__ void count16(uint32_t *h, const u32x4 &e, const u32x4 &s)
+{
+    const uint32_t k0 = pair_key(e, s, 0);
+    const bool one = all_one_byte(e) && all_one_byte(s);
+    const uint32_t kw = __builtin_amdgcn_readfirstlane(k0);
+    if (__all(one && k0 == kw)) {
+        const uint64_t lanes = __ballot(1);
+        if (__lane_id() == (uint32_t)__ffsll((long long)lanes) - 1u)
+            add_run(h, kw, (uint32_t)__popcll(lanes) * kPxPerLane);
+    }
+    else if (one) {
+        add_run(h, k0, kPxPerLane);
+    }
+    else {
+        uint32_t cur = k0, n = 1u;
+#pragma unroll
+        for (uint32_t i = 1; i < kPxPerLane; i++) {
+            const uint32_t k = pair_key(e, s, i);
+            if (k != cur) {
+                add_run(h, cur, n);
+                cur = k;
+                n = 0u;
+            }
+            n++;
+        }
+        add_run(h, cur, n);
+    }
+}
+
+// the row's last pixels (W not a multiple of 16): byte loads, nothing past the row end
+__device__ __forceinline__ void count_tail(uint32_t *h, const uint8_t *erow, const uint8_t *srow, uint32_t m)
+{
+    uint32_t cur = (uint32_t)erow[0] | ((uint32_t)srow[0] << 8), n = 1u;
+    for (uint32_t i = 1; i < m; i++) {
+        const uint32_t k = (uint32_t)erow[i] | ((uint32_t)srow[i] << 8);
+        if (k != cur) {
+            add_run(h, cur, n);
+            cur = k;
+            n = 0u;
+        }
+        n++;
+    }
+    add_run(h, cur, n);
+}
+
+__global__ __launch_bounds__(kThreads) void pair_histogram_kernel(const HistParams p)
+{
+    __shared__ uint32_t h[kHistWords];
+    for (uint32_t i = threadIdx.x; i < (uint32_t)kHistWords; i += kThreads)
+        h[i] = 0u;
+    __syncthreads();
+
+    // a workgroup step: kChunk pixels of kRowsPerItem rows; every lane has its rows' loads in flight together
+    const uint64_t items = (uint64_t)((p.rows + kRowsPerItem - 1u) / kRowsPerItem) * p.per_row;
+    for (uint64_t t = blockIdx.x; t < items; t += gridDim.x) {
+        const uint32_t yg = (uint32_t)(t / p.per_row);
+        const uint32_t x0 = (uint32_t)(t - (uint64_t)yg * p.per_row) * kChunk + threadIdx.x * kPxPerLane;
+        const uint32_t y0 = yg * kRowsPerItem;
+        const uint32_t ny = min(kRowsPerItem, p.rows - y0);        // wave uniform
+        if (x0 >= p.W)
+            continue;
+        const uint8_t *erow[kRowsPerItem], *srow[kRowsPerItem];
+#pragma unroll
+        for (uint32_t j = 0; j < kRowsPerItem; j++) {
+            const uint32_t y = y0 + min(j, ny - 1u);
+            uint32_t r = (uint32_t)p.cj[y];
+            r = r < p.hx_rows ? r : p.hx_rows - 1u;
+            erow[j] = p.esa + (size_t)y * p.W + x0;
+            srow[j] = p.hx + (size_t)r * p.hx_stride + x0;
+        }
+        if (x0 + kPxPerLane <= p.W) {
+            // 16 pixels inside the row: one 16-byte load of each (landcover rows start anywhere, soil rows on 16)
+            typedef u32x4 u32x4_u __attribute__((aligned(1)));
+            u32x4 e[kRowsPerItem], s[kRowsPerItem];
+#pragma unroll
+            for (uint32_t j = 0; j < kRowsPerItem; j++) {
+                e[j] = *reinterpret_cast<const u32x4_u *>(erow[j]);
+                s[j] = *reinterpret_cast<const u32x4 *>(srow[j]);
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < kRowsPerItem; j++)
+                if (j < ny)
+                    count16(h, e[j], s[j]);
+        }
+        else {
+            for (uint32_t j = 0; j < ny; j++)
+                count_tail(h, erow[j], srow[j], p.W - x0);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < (uint32_t)kHistWords; i += kThreads)
+        if (h[i])
+            atomicAdd(&p.hist[i], (unsigned long long)h[i]);
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcn10_gpu_pair_histogram_codes(uint8_t codes[GCN10_PAIR_HIST_BINS])
+{
+    if (!codes)
+        return fail(GCN10_E_INVAL, "gcn10_gpu_pair_histogram_codes: null pointer");
+    for (int b = 0; b < kBins; b++)
+        codes[b] = 0x55;                            // empty bins: the invalid plane in both conditions
+    for (uint32_t d = 0; d <= 5; d++)
+        codes[code_bin(d | d << 4)] = (uint8_t)(d | d << 4);
+    for (uint32_t u = 1; u <= 3; u++)
+        codes[code_bin(4u | u << 4)] = (uint8_t)(4u | u << 4);
+    return GCN10_PAIR_HIST_BINS;
+}
+
+int gcn10_gpu_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                             unsigned long long *hist_dev, gcn10_stream_t stream)
+{
+    int rc = use_device(ctx);
+    if (rc)
+        return rc;
+    if (!ctx->d_hx || (int)ctx->hx_W != W)
+        return fail(GCN10_E_STATE, "gcn10_gpu_pair_histogram: prepare the block's tile (W=%d) first", W);
+    if (!esa || !cj || !hist_dev || W <= 0 || rows < 0)
+        return fail(GCN10_E_INVAL, "gcn10_gpu_pair_histogram: bad arguments W=%d rows=%d", W, rows);
+    if (rows == 0)
+        return GCN10_OK;
+    HistParams p = {};
+    p.esa = esa;
+    p.hx = ctx->d_hx;
+    p.cj = cj;
+    p.hist = hist_dev;
+    p.W = (uint32_t)W;
+    p.rows = (uint32_t)rows;
+    p.hx_stride = ctx->hx_stride;
+    p.hx_rows = ctx->hx_rows;
+    p.per_row = ((uint32_t)W + kChunk - 1u) / kChunk;
+    const uint64_t items = (uint64_t)((p.rows + kRowsPerItem - 1u) / kRowsPerItem) * p.per_row;
+    const uint64_t cap = (uint64_t)(ctx->n_cus > 0 ? ctx->n_cus : 256) * kGridPerCu;
+    const uint32_t grid = (uint32_t)(items < cap ? items : cap);
+    hipLaunchKernelGGL(pair_histogram_kernel, dim3(grid), dim3(kThreads), 0, as_stream(ctx, stream), p);
+    HIP_TRY(hipGetLastError());
+    return GCN10_OK;
+}
+
+}  // extern "C"

@@ -132,6 +132,32 @@ int gcn10_parse_cog(const char *text, int *cog)
     return 0;
 }
 
+int gcn10_parse_stats(const char *text, int *stats)
+{
+    return gcn10_parse_cog(text, stats);       /* the same "0" | "1" */
+}
+
+int gcn10_parse_nodata(const char *text, int *nodata)
+{
+    int v = 0;
+
+    if (!text || !*text)
+        return -1;
+    if (!strcasecmp(text, "none")) {
+        *nodata = -1;
+        return 0;
+    }
+    for (const char *c = text; *c; c++) {
+        if (*c < '0' || *c > '9' || c - text >= 3)
+            return -1;
+        v = v * 10 + (*c - '0');
+    }
+    if (v > 255)
+        return -1;
+    *nodata = v;
+    return 0;
+}
+
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap)
 {
     char line[512];                                     /* src/config.c:47 */
@@ -144,6 +170,7 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
     cfg->prefetch_blocks = 1;
     cfg->table_mask = 0x1ffu;
     cfg->cond_mask = 3u;
+    cfg->nodata = -1;
     f = fopen(path, "r");
     if (!f) {
         snprintf(err, errcap, "cannot open config '%s'", path);     /* src/config.c:52 */
@@ -222,6 +249,18 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
                  gcn10_parse_overview_resampling(val, &cfg->overview_resampling) != 0) {
             fclose(f);
             snprintf(err, errcap, "bad value for overview_resampling: '%s' (nearest or average)", val);
+            gcn10_config_free(cfg);
+            return -3;
+        }
+        else if (!strcmp(key, "stats") && gcn10_parse_stats(val, &cfg->stats) != 0) {
+            fclose(f);
+            snprintf(err, errcap, "bad value for stats: '%s' (0 or 1)", val);
+            gcn10_config_free(cfg);
+            return -3;
+        }
+        else if (!strcmp(key, "nodata") && gcn10_parse_nodata(val, &cfg->nodata) != 0) {
+            fclose(f);
+            snprintf(err, errcap, "bad value for nodata: '%s' (none or an integer 0..255)", val);
             gcn10_config_free(cfg);
             return -3;
         }

@@ -88,6 +88,9 @@ static void load_once(void)
     *(void **)(&g_api.inflate_codecs) = dlsym(h, "gcn10_gpu_inflate_codecs");
     *(void **)(&g_api.overview_nearest) = dlsym(h, "gcn10_gpu_overview_nearest");
     *(void **)(&g_api.overview_average) = dlsym(h, "gcn10_gpu_overview_average");
+    /* the pair histogram of the band statistics: needed by stats=1 runs only, which check for it */
+    *(void **)(&g_api.pair_histogram) = dlsym(h, "gcn10_gpu_pair_histogram");
+    *(void **)(&g_api.pair_histogram_codes) = dlsym(h, "gcn10_gpu_pair_histogram_codes");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -117,6 +117,10 @@ struct gcn10_gpu_api {
     int (*overview_nearest)(gcn10_gpu_ctx *, const uint8_t *, int, int, int, uint8_t *, gcn10_stream_t);
     int (*overview_average)(gcn10_gpu_ctx *, const uint8_t *, int, int, int, int, const int32_t *, unsigned, unsigned,
                             int, uint8_t *const *, gcn10_stream_t);
+    /* optional: NULL when the library has none (needed by stats=1 only) */
+    int (*pair_histogram)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, unsigned long long *,
+                          gcn10_stream_t);
+    int (*pair_histogram_codes)(uint8_t *);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

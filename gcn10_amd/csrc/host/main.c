@@ -5,7 +5,7 @@
  * plus -b as a synonym of -l (the reference's usage text advertises -b,
  * src/main.c:28, while its parser only takes -l, src/main.c:90), --gpus N, and --lookups /
  * --conditions to produce a subset of the 18 rasters (BASELINE config 3: "single lookup"), and --compress to
- * write LZW instead of DEFLATE GeoTIFFs.
+ * write LZW instead of DEFLATE GeoTIFFs, --stats / --nodata for GDAL band statistics and a NoData tag.
  * No mpirun: one process drives every GPU of the node.
  */
 #include "gcn10_host.h"
@@ -21,7 +21,7 @@ static void usage(FILE *fp)
             "usage:\n"
             "  gcn10 --config <config.txt> [--blocks <blocks.txt>] [--overwrite] [--gpus <n>]\n"
             "        [--lookups <names>] [--conditions drained|undrained|both] [--compress deflate|lzw]\n"
-            "        [--cog] [--overview-resampling nearest|average]\n"
+            "        [--cog] [--overview-resampling nearest|average] [--stats] [--nodata none|<0..255>]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -34,6 +34,8 @@ static void usage(FILE *fp)
             "  --compress <c>\tdeflate or lzw: compression of the GeoTIFFs (default: deflate)\n"
             "  --cog\t\t\tCloud Optimized GeoTIFFs with overviews built on the GPU (config key cog=1)\n"
             "  --overview-resampling <m>\tnearest or average: how the overviews are made (default: nearest)\n"
+            "  --stats\t\tGDAL band statistics in every raster, counted on the GPU (config key stats=1)\n"
+            "  --nodata <v>\t\tnone or 0..255: declare that NoData value, left out of the statistics (default: none)\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -78,6 +80,10 @@ int main(int argc, char **argv)
             opt.cog = true;
         else if (!strcmp(argv[i], "--overview-resampling") && i + 1 < argc)
             opt.overview_resampling = argv[++i];
+        else if (!strcmp(argv[i], "--stats"))
+            opt.stats = true;
+        else if (!strcmp(argv[i], "--nodata") && i + 1 < argc)
+            opt.nodata = argv[++i];
     }
     return gcn10_run(&opt);
 }

@@ -569,6 +569,14 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
         }
         if (r->lzw)
             (void)gcn10_tiff_set_compression(in->tifs[k], 5);
+        /* before any tile: a COG lays its directories out with these tags (the statistics come at finish) */
+        if ((r->nodata >= 0 && gcn10_tiff_set_nodata(in->tifs[k], r->nodata) != 0) ||
+            (r->stats && gcn10_tiff_reserve_metadata(in->tifs[k], GCN10_STATS_XML_MAX) != 0)) {
+            wlog(w, "ERROR", true, "write error: cannot place the GDAL tags of %s", path);
+            gcn10_abort_outputs(in);
+            w->t_create += now_seconds() - t_mark;
+            return 1;
+        }
         if (r->direct_io && r->gpu_deflate)
             gcn10_tiff_set_direct(in->tifs[k], true);   /* best effort: a file system that refuses writes buffered */
     }
@@ -590,10 +598,12 @@ void gcn10_abort_outputs(struct block_in *in)
 /* The strips of one raster (a block, or a level of its overviews) through the encoder and the sink.  d_block / d_cj:
  * its landcover and soil rows, for the prepared tile of width W.  premade (device, [strip][GCN10_N_RASTERS]): the
  * selected rasters are already made (average overviews), strip s's n_sel pointers at premade + s * GCN10_N_RASTERS,
- * and only the per-raster encoder runs.  Every strip has been handed to the sink, and the sink is done, on return.
- * 0, or -1 (logged) for errors the reference answers with MPI_Abort. */
+ * and only the per-raster encoder runs.  hist (device, stats=1, the block's own strips only): every strip's
+ * (landcover, soil code) pairs are added to it, behind the strip's encoder on the same stream.  Every strip has been
+ * handed to the sink, and the sink is done, on return.  0, or -1 (logged) for errors the reference answers with
+ * MPI_Abort. */
 static int run_strips(struct worker *w, int W, int H, const uint8_t *d_block, const int32_t *d_cj,
-                      const uint8_t *const *premade, gcn10_tiff_writer *tifs[GCN10_N_RASTERS])
+                      const uint8_t *const *premade, unsigned long long *hist, gcn10_tiff_writer *tifs[GCN10_N_RASTERS])
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
@@ -644,6 +654,9 @@ static int run_strips(struct worker *w, int W, int H, const uint8_t *d_block, co
         }
         if (g->event_record(w->ctx, b->ev_kernel, w->s_kernel) != 0 ||
             g->stream_wait_event(w->ctx, w->s_d2h, b->ev_kernel) != 0)
+            goto gpu_fail;
+        /* the statistics' counts after the event: the strip's copy-back does not wait for them */
+        if (hist && g->pair_histogram(w->ctx, d_esa, W, rows, d_cj + y0, hist, w->s_kernel) != 0)
             goto gpu_fail;
         /* ... and what comes back on the copy stream */
         if (r->gpu_deflate) {
@@ -743,7 +756,7 @@ static int encode_overviews(struct worker *w, struct block_in *in, gcn10_tiff_wr
             }
             for (int q = 0; q < GCN10_N_RASTERS; q++)
                 lv[q] = tifs[q] ? gcn10_tiff_level(tifs[q], k) : NULL;
-            if (run_strips(w, Wk, Hk, w->d_ov, d_cj, NULL, lv) != 0) {
+            if (run_strips(w, Wk, Hk, w->d_ov, d_cj, NULL, NULL, lv) != 0) {
                 free(idx);
                 return -1;
             }
@@ -817,7 +830,7 @@ static int encode_overviews(struct worker *w, struct block_in *in, gcn10_tiff_wr
             free(tab);
             for (int q = 0; q < GCN10_N_RASTERS; q++)
                 lv[q] = tifs[q] ? gcn10_tiff_level(tifs[q], k) : NULL;
-            if (run_strips(w, Wk, Hk, NULL, NULL, (const uint8_t *const *)w->d_ov_ptrs, lv) != 0)
+            if (run_strips(w, Wk, Hk, NULL, NULL, (const uint8_t *const *)w->d_ov_ptrs, NULL, lv) != 0)
                 return -1;
             if (g->stream_sync(w->ctx, w->s_kernel) != 0) {       /* the pointer table is rewritten next */
                 wlog(w, "ERROR", true, "gpu: %s", g->last_error());
@@ -890,10 +903,24 @@ static int encode_block(struct worker *w, struct block_in *in)
             goto out;
         }
     }
-    if (run_strips(w, W, H, in->d_block, in->d_cj, NULL, tifs) != 0) {
+    if (r->stats &&
+        (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_hist, &w->d_hist_cap,
+                             GCN10_PAIR_HIST_SIZE * sizeof *w->d_hist) != 0 ||
+         gcn10_ensure_pinned_on(w, w->ctx, (void **)&w->h_hist, &w->h_hist_cap,
+                                GCN10_PAIR_HIST_SIZE * sizeof *w->h_hist) != 0)) {
         rc = -1;
         goto out;
     }
+    if (r->stats && g->memset(w->ctx, w->d_hist, 0, GCN10_PAIR_HIST_SIZE * sizeof *w->d_hist, w->s_kernel) != 0)
+        goto gpu_fail;
+    if (run_strips(w, W, H, in->d_block, in->d_cj, NULL, r->stats ? w->d_hist : NULL, tifs) != 0) {
+        rc = -1;
+        goto out;
+    }
+    if (r->stats &&
+        (g->memcpy_d2h(w->ctx, w->h_hist, w->d_hist, GCN10_PAIR_HIST_SIZE * sizeof *w->h_hist, w->s_kernel) != 0 ||
+         g->stream_sync(w->ctx, w->s_kernel) != 0))
+        goto gpu_fail;
     ok = !atomic_load(&w->failed);
     if (in->n_inflate > 0) {
         /* every landcover chunk must have been a valid one (the statuses came back behind ev_ready) */
@@ -941,6 +968,18 @@ out:
                 gcn10_tiff_abort(tifs[k]);
                 tifs[k] = NULL;
                 continue;
+            }
+            if (r->stats) {
+                /* the raster's exact histogram from the block's pairs, its statistics as GDAL would compute them */
+                uint64_t hist[256];
+                gcn10_band_stats st;
+                char xml[GCN10_STATS_XML_MAX];
+
+                gcn10_raster_histogram((const uint64_t *)w->h_hist, r->hist_codes,
+                                       (const int (*)[5])r->tables[k % 9], k < 9, hist);
+                gcn10_band_stats_of(hist, r->nodata, &st);
+                if (gcn10_tiff_set_metadata_xml(tifs[k], gcn10_stats_xml(&st, xml, sizeof xml) ? xml : NULL) != 0)
+                    wlog(w, "ERROR", true, "write error: the statistics of block %d raster %d do not fit", block_id, k);
             }
             j = r->pool ? malloc(sizeof *j) : NULL;
             if (!j) {
@@ -1003,6 +1042,10 @@ static void worker_teardown(struct worker *w)
         if (w->d_ov) g->free(w->ctx, w->d_ov);
         if (w->d_ov_idx) g->free(w->ctx, w->d_ov_idx);
         if (w->d_ov_ptrs) g->free(w->ctx, w->d_ov_ptrs);
+        if (w->d_hist) g->free(w->ctx, w->d_hist);
+        if (w->h_hist) g->host_free(w->ctx, w->h_hist);
+        w->d_hist = w->h_hist = NULL;
+        w->d_hist_cap = w->h_hist_cap = 0;
         w->d_ov = NULL;
         w->d_ov_idx = NULL;
         w->d_ov_ptrs = NULL;
@@ -1333,6 +1376,14 @@ int gcn10_run(const gcn10_run_options *opt)
     }
     if (opt->cog)
         r->cfg.cog = 1;
+    if (opt->stats)
+        r->cfg.stats = 1;
+    if (opt->nodata && gcn10_parse_nodata(opt->nodata, &r->cfg.nodata) != 0) {
+        fprintf(stderr, "[rank 0] bad value for nodata: '%s' (none or an integer 0..255)\n", opt->nodata);
+        gcn10_config_free(&r->cfg);
+        free(r);
+        return 1;
+    }
     if (r->cfg.cog && r->cfg.gpu_deflate == 0) {
         fprintf(stderr, "[rank 0] bad value for cog: '1' with gpu_deflate=0 (overviews are built and encoded on the GPU "
                         "only; there is no host fallback)\n");
@@ -1360,6 +1411,8 @@ int gcn10_run(const gcn10_run_options *opt)
     r->lzw = r->cfg.compress == GCN10_COMPRESS_LZW;
     r->cog = r->cfg.cog != 0;
     r->ov_average = r->cfg.overview_resampling == GCN10_OVERVIEW_AVERAGE;
+    r->stats = r->cfg.stats != 0;
+    r->nodata = r->cfg.nodata;
     r->fused = r->cfg.gpu_deflate == 2 && !r->lzw;     /* the fused encoder is DEFLATE-only */
     r->gpu_inflate = r->cfg.gpu_inflate != 0;
     r->direct_io = r->cfg.direct_io != 0 || (getenv("GCN10_DIRECT_IO") && atoi(getenv("GCN10_DIRECT_IO")) != 0);
@@ -1387,6 +1440,11 @@ int gcn10_run(const gcn10_run_options *opt)
     }
     if (r->cog && (!r->gpu->overview_nearest || !r->gpu->overview_average)) {
         fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_overview_* (needed by cog=1)\n", gcn10_gpu_library_path());
+        goto done;
+    }
+    if (r->stats && (!r->gpu->pair_histogram || !r->gpu->pair_histogram_codes ||
+                     r->gpu->pair_histogram_codes(r->hist_codes) != GCN10_PAIR_HIST_BINS)) {
+        fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_pair_histogram (needed by stats=1)\n", gcn10_gpu_library_path());
         goto done;
     }
     if (r->lzw && (!r->gpu->lzw_strip || !r->gpu->lzw_arena_bound)) {
@@ -1586,6 +1644,7 @@ int gcn10_run(const gcn10_run_options *opt)
     {
         int done_blocks = 0;
         double busy = 0, rd = 0, gw = 0, sw = 0, so = 0, cr = 0, fi = 0, dv = 0, steady = 0, iw = 0, ib = 0;
+        char extras[48];                    /* the GDAL tags of the outputs */
 
         for (int i = 0; i < r->n_workers; i++) {
             done_blocks += r->workers[i].blocks_done;
@@ -1626,13 +1685,16 @@ int gcn10_run(const gcn10_run_options *opt)
                 gcn10_log_message(log0, "INFO", msg, false);
             }
         }
-        snprintf(msg, sizeof msg, "timing: %d blocks, %.3f s wall (%.3f s after start-up), %d gpu worker(s)%s%s%s; worker seconds: "
+        snprintf(extras, sizeof extras, "%s", r->stats ? ", stats" : "");
+        if (r->nodata >= 0)
+            snprintf(extras + strlen(extras), sizeof extras - strlen(extras), ", nodata %d", r->nodata);
+        snprintf(msg, sizeof msg, "timing: %d blocks, %.3f s wall (%.3f s after start-up), %d gpu worker(s)%s%s%s%s; worker seconds: "
                  "in blocks %.3f, reading landcover %.3f, waiting for gpu %.3f, waiting for sink %.3f, "
                  "soil window %.3f, creating outputs %.3f, finishing outputs %.3f, device setup %.3f, "
                  "waiting for input %.3f; input thread seconds: %.3f%s",
                  done_blocks, now_seconds() - t_start, steady, r->n_workers, r->null_sink ? ", null sink" : "",
                  r->lzw ? ", gpu lzw" : r->gpu_deflate ? (r->fused ? ", fused gpu deflate" : ", gpu deflate") : ", host zlib",
-                 r->gpu_inflate ? ", gpu inflate of deflate landcover" : "", busy, rd, gw, sw, so, cr, fi, dv, iw, ib,
+                 r->gpu_inflate ? ", gpu inflate of deflate landcover" : "", extras, busy, rd, gw, sw, so, cr, fi, dv, iw, ib,
                  r->prefetch ? " (one block ahead of the encoder)" : " (in turn with the encoder)");
         gcn10_log_message(log0, "INFO", msg, false);
         {

@@ -128,6 +128,9 @@ struct worker {
     pthread_mutex_t gate_mu;
     pthread_cond_t gate_cv;
     long gate_seq, gate_turn;
+    /* band statistics (stats=1): the block's pair histogram on the device, and its copy */
+    unsigned long long *d_hist, *h_hist;    /* GCN10_PAIR_HIST_SIZE counters; h_hist pinned */
+    size_t d_hist_cap, h_hist_cap;
     long n_win_gpu, n_win_gpu_lzw, n_win_host;  /* landcover windows through the GPU decoder (of them with LZW chunks),
                                                    through the host reader */
 };
@@ -162,6 +165,9 @@ struct run {
     bool cog;                               /* Cloud Optimized GeoTIFFs with overviews (cog=1) */
     bool ov_average;                        /* ... made by averaging (overview_resampling=average), else nearest */
     atomic_bool cog_logged;                 /* the run log has its COG line */
+    bool stats;                             /* GDAL band statistics in every written raster (stats=1) */
+    int nodata;                             /* GDAL_NODATA of every written raster, -1 = none (nodata=) */
+    uint8_t hist_codes[GCN10_PAIR_HIST_BINS];   /* soil code of each bin of the pair histogram */
     bool prefetch;                          /* input threads stage block N+1 while block N is encoded */
     int n_devices;                          /* GPUs of the run; worker i belongs to GPU i % n_devices */
     int n_physical;                         /* ... and the devices behind them: GPU d is device d % n_physical (all the

@@ -1062,6 +1062,11 @@ struct gcn10_tiff_writer {
     int cur_level;              /* root of a COG: the level tile data goes to now (starts at n_levels) */
     long long last_idx;         /* COG: highest tile index of this level written so far (-1: none) */
     uint64_t data_start;        /* root of a COG: first byte after the IFDs, where tile data begins */
+    /* GDAL tags of the root (gcn10_tiff_set_nodata, gcn10_tiff_set_metadata_xml) */
+    int nodata;                 /* -1: no GDAL_NODATA tag */
+    char nodata_s[4];           /* its ASCII value, e.g. "255" */
+    char *metadata;             /* GDAL_METADATA text of the full-resolution IFD, or NULL */
+    size_t metadata_room;       /* COG: bytes reserved for it (0: none; the tag is then written only with a text) */
 };
 
 static int write_all(int fd, const void *buf, size_t n, uint64_t off)
@@ -1149,6 +1154,7 @@ gcn10_tiff_writer *gcn10_tiff_create(const char *path, int xsize, int ysize, con
         goto oom;
     w->fd = -1;
     w->compression = 8;
+    w->nodata = -1;
     w->root = w;
     w->last_idx = -1;
     pthread_mutex_init(&w->mu, NULL);
@@ -1517,6 +1523,7 @@ struct dirent_w {
     uint32_t count;
     const void *data;       /* little-endian payload */
     size_t nbytes;
+    size_t room;            /* file bytes kept for an out-of-line payload when more than nbytes (zero filled) */
 };
 
 /* the values the entries of one IFD point at */
@@ -1552,7 +1559,7 @@ static int ifd_entries(const gcn10_tiff_writer *R, const gcn10_tiff_writer *v, s
     put16(x->s_th, TILE);
     put16(x->s_fmt, 1);             /* unsigned integer */
 #define ENT(tag_, type_, count_, data_, nbytes_) \
-    ents[ne++] = (struct dirent_w){ tag_, type_, (uint32_t)(count_), data_, nbytes_ }
+    ents[ne++] = (struct dirent_w){ tag_, type_, (uint32_t)(count_), data_, nbytes_, 0 }
     if (v != R)
         ENT(254, T_LONG, 1, x->s_sub, 4);
     ENT(256, T_LONG, 1, x->s_w, 4);
@@ -1567,8 +1574,11 @@ static int ifd_entries(const gcn10_tiff_writer *R, const gcn10_tiff_writer *v, s
     ENT(324, T_LONG, nt, v->offsets, nt * 4);      /* host is little endian (x86-64) */
     ENT(325, T_LONG, nt, v->counts, nt * 4);
     ENT(339, T_SHORT, 1, x->s_fmt, 2);
-    if (v != R)
+    if (v != R) {
+        if (R->nodata >= 0)         /* GDAL writes GDAL_NODATA on the overview IFDs too */
+            ENT(42113, T_ASCII, strlen(R->nodata_s) + 1, R->nodata_s, strlen(R->nodata_s) + 1);
         return ne;
+    }
     if (R->gt[2] == 0.0 && R->gt[4] == 0.0) {
         ENT(33550, T_DOUBLE, 3, x->scale, sizeof x->scale);
         ENT(33922, T_DOUBLE, 6, x->tie, sizeof x->tie);
@@ -1587,6 +1597,16 @@ static int ifd_entries(const gcn10_tiff_writer *R, const gcn10_tiff_writer *v, s
         ENT(34736, T_DOUBLE, R->georef.n_geodoubles, R->georef.geodoubles, (size_t)R->georef.n_geodoubles * 8);
     if (R->georef.geoascii)
         ENT(34737, T_ASCII, strlen(R->georef.geoascii) + 1, R->georef.geoascii, strlen(R->georef.geoascii) + 1);
+    if (R->metadata || R->metadata_room) {
+        /* a COG's reserved room holds at least the empty element, so the directory has the tag either way */
+        static const char empty_md[] = "<GDALMetadata>\n</GDALMetadata>\n";
+        const char *md = R->metadata ? R->metadata : empty_md;
+
+        ENT(42112, T_ASCII, strlen(md) + 1, md, strlen(md) + 1);
+        ents[ne - 1].room = R->metadata_room;
+    }
+    if (R->nodata >= 0)
+        ENT(42113, T_ASCII, strlen(R->nodata_s) + 1, R->nodata_s, strlen(R->nodata_s) + 1);
 #undef ENT
     return ne;
 }
@@ -1617,11 +1637,24 @@ static int write_ifd(int fd, const struct dirent_w *ents, int ne, uint64_t dir_p
                 memcpy(e + 8, ents[i].data, ents[i].nbytes);
             continue;
         }
-        if (pos + ents[i].nbytes > 0xffffffffull || (fd >= 0 && write_all(fd, ents[i].data, ents[i].nbytes, pos) != 0))
-            goto done;
-        if (e)
-            put32(e + 8, (uint32_t)pos);
-        pos = (pos + ents[i].nbytes + 1) & ~1ull;
+        {
+            const size_t room = ents[i].room > ents[i].nbytes ? ents[i].room : ents[i].nbytes;
+
+            if (pos + room > 0xffffffffull || (fd >= 0 && write_all(fd, ents[i].data, ents[i].nbytes, pos) != 0))
+                goto done;
+            if (fd >= 0 && room > ents[i].nbytes) {
+                unsigned char *zero = calloc(1, room - ents[i].nbytes);
+
+                if (!zero || write_all(fd, zero, room - ents[i].nbytes, pos + ents[i].nbytes) != 0) {
+                    free(zero);
+                    goto done;
+                }
+                free(zero);
+            }
+            if (e)
+                put32(e + 8, (uint32_t)pos);
+            pos = (pos + room + 1) & ~1ull;
+        }
     }
     if (dir)
         put32(dir + dirbytes - 4, next);
@@ -1755,6 +1788,82 @@ done:
     return rc;
 }
 
+/* A COG's directories were laid out at create for the tags set then; a tag that changes their size re-lays them out,
+ * which only works before the first tile went behind them.  Called with the root and its lock held. */
+static int cog_relayout(gcn10_tiff_writer *R)
+{
+    uint64_t first, end;
+
+    if (!R->cog)
+        return 0;
+    if (R->pos != R->data_start || cog_layout(R, -1, &first, &end) != 0)
+        return -1;
+    R->data_start = end;
+    R->pos = end;
+    return 0;
+}
+
+int gcn10_tiff_set_nodata(gcn10_tiff_writer *w, int v)
+{
+    int rc = 0, old;
+
+    w = w->root;
+    if (v < 0 || v > 255)
+        return -1;
+    pthread_mutex_lock(&w->mu);
+    old = w->nodata;
+    w->nodata = v;
+    snprintf(w->nodata_s, sizeof w->nodata_s, "%d", v);
+    if (old < 0 && cog_relayout(w) != 0) {
+        w->nodata = old;
+        rc = -1;
+    }
+    pthread_mutex_unlock(&w->mu);
+    return rc;
+}
+
+int gcn10_tiff_reserve_metadata(gcn10_tiff_writer *w, size_t bytes)
+{
+    int rc = 0;
+    size_t old;
+
+    w = w->root;
+    if (!w->cog)
+        return 0;
+    if (bytes > 0xffffffu)
+        return -1;
+    pthread_mutex_lock(&w->mu);
+    old = w->metadata_room;
+    w->metadata_room = bytes;
+    if ((w->metadata && strlen(w->metadata) + 1 > bytes) || cog_relayout(w) != 0) {
+        w->metadata_room = old;
+        rc = -1;
+    }
+    pthread_mutex_unlock(&w->mu);
+    return rc;
+}
+
+int gcn10_tiff_set_metadata_xml(gcn10_tiff_writer *w, const char *xml)
+{
+    char *copy = NULL;
+    int rc = 0;
+
+    w = w->root;
+    if (xml && !(copy = strdup(xml)))
+        return -1;
+    pthread_mutex_lock(&w->mu);
+    if (w->cog && copy && strlen(copy) + 1 > w->metadata_room) {
+        rc = -1;                    /* a COG's text must fit the room its directory has (reserve_metadata) */
+        free(copy);
+    }
+    else {
+        free(w->metadata);
+        w->metadata = copy;
+    }
+    pthread_mutex_unlock(&w->mu);
+    return rc;
+}
+
 static void free_level_view(gcn10_tiff_writer *v)
 {
     if (!v)
@@ -1781,6 +1890,7 @@ void gcn10_tiff_abort(gcn10_tiff_writer *w)
     free(w->offsets);
     free(w->counts);
     free(w->path);
+    free(w->metadata);
     free_georef(&w->georef);
     pthread_mutex_destroy(&w->mu);
     free(w);

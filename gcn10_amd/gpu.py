@@ -44,12 +44,24 @@ ABI_SYMBOLS = (
     "gcn10_gpu_inflate_tiles", "gcn10_gpu_stream_copy", "gcn10_gpu_tune_single_raster",
     "gcn10_gpu_soil_words_state", "gcn10_gpu_lzw_arena_bound", "gcn10_gpu_lzw_strip",
     "gcn10_gpu_inflate_codecs", "gcn10_gpu_overview_nearest", "gcn10_gpu_overview_average",
+    "gcn10_gpu_pair_histogram_codes", "gcn10_gpu_pair_histogram",
 )
+
+
+def pair_histogram_codes() -> np.ndarray:
+    """codes[b] = the soil code byte (drained plane | undrained plane << 4) counted in bin b of the pair histogram
+    (gcn10_gpu_pair_histogram_codes; no device needed)."""
+    codes = np.zeros(PAIR_HIST_BINS, np.uint8)
+    n = lib().gcn10_gpu_pair_histogram_codes(codes.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if n != PAIR_HIST_BINS:
+        raise RuntimeError("gcn10_gpu_pair_histogram_codes returned %d" % n)
+    return codes
 
 
 # struct gcn10_inflate_tile (include/gcn10_gpu.h)
 TILE_RAW, TILE_PREDICTOR2, TILE_LZW = 1, 2, 4     # gcn10_inflate_tile.flags (include/gcn10_gpu.h)
 CODEC_DEFLATE, CODEC_RAW, CODEC_LZW = 1, 2, 4       # gcn10_gpu_inflate_codecs() bits
+PAIR_HIST_BINS = 16                                 # GCN10_PAIR_HIST_BINS: pair histogram = [bin][landcover] counters
 # gcn10_inflate_tiles status words of LZW tiles (GCN10_INFLATE_E_LZW_*)
 INFLATE_E_LZW_CODE, INFLATE_E_LZW_FIRST, INFLATE_E_LZW_INPUT = 9, 10, 11
 INFLATE_TILE_DTYPE = np.dtype([("in_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("chunk_w", "<u4"),
@@ -121,6 +133,8 @@ def lib():
             "gcn10_gpu_lzw_strip": (i, [vp, vp, i, i, i, vp, sz, vp, vp, vp]),
             "gcn10_gpu_overview_nearest": (i, [vp, vp, i, i, i, vp, vp]),
             "gcn10_gpu_overview_average": (i, [vp, vp, i, i, i, i, vp, u, u, i, C.POINTER(vp), vp]),
+            "gcn10_gpu_pair_histogram_codes": (i, [C.POINTER(C.c_uint8)]),
+            "gcn10_gpu_pair_histogram": (i, [vp, vp, i, i, vp, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -385,6 +399,13 @@ class Engine:
         arr = (C.c_void_p * len(level_ptrs))(*[int(p) for p in level_ptrs])
         self._chk(lib().gcn10_gpu_overview_average(self._ctx, esa_ptr, W, H, y0, rows, cj_ptr, cond_mask, table_mask,
                                                    n_levels, arr, stream), "gcn10_gpu_overview_average")
+
+    def pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, hist_ptr: int, stream=None):
+        """Adds the (landcover, soil code) pair counts of a W x rows device strip to the device histogram hist_ptr
+        (PAIR_HIST_BINS * 256 uint64, [bin][landcover]), with the soil of the last prepare_tile
+        (gcn10_gpu_pair_histogram)."""
+        self._chk(lib().gcn10_gpu_pair_histogram(self._ctx, esa_ptr, W, rows, cj_ptr, hist_ptr, stream),
+                  "gcn10_gpu_pair_histogram")
 
     def lzw_arena_bound(self, W: int, rows: int, n_rasters: int) -> int:
         """Worst-case arena bytes of gcn10_gpu_lzw_strip for n_rasters strips of W x rows."""

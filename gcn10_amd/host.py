@@ -75,6 +75,10 @@ def lib():
         L.gcn10_tiff_create_cog.restype = vp
         L.gcn10_tiff_create.argtypes = [cp, C.c_int, C.c_int, _f64p, vp, cp, C.c_size_t]
         L.gcn10_tiff_create.restype = vp
+        # TiffWriter's own handle on it: callers that bind the shared attribute to other argtypes do not reach it
+        L.tiff_create_ = L["gcn10_tiff_create"]
+        L.tiff_create_.argtypes = [cp, C.c_int, C.c_int, _f64p, vp, cp, C.c_size_t]
+        L.tiff_create_.restype = vp
         L.gcn10_cog_levels.argtypes = [C.c_int, C.c_int]
         L.gcn10_cog_levels.restype = C.c_int
         L.gcn10_tiff_level.argtypes = [vp, C.c_int]
@@ -94,6 +98,20 @@ def lib():
         L.gcn10_tiff_set_compression.restype = C.c_int
         L.gcn10_tiff_set_direct.argtypes = [vp, C.c_bool]
         L.gcn10_tiff_set_direct.restype = C.c_int
+        L.gcn10_tiff_set_nodata.argtypes = [vp, C.c_int]
+        L.gcn10_tiff_set_nodata.restype = C.c_int
+        L.gcn10_tiff_set_metadata_xml.argtypes = [vp, cp]
+        L.gcn10_tiff_set_metadata_xml.restype = C.c_int
+        L.gcn10_tiff_reserve_metadata.argtypes = [vp, C.c_size_t]
+        L.gcn10_tiff_reserve_metadata.restype = C.c_int
+        u64p = np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")
+        L.gcn10_raster_histogram.argtypes = [u64p, np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS"),
+                                             _i32p, C.c_int, u64p]
+        L.gcn10_raster_histogram.restype = None
+        L.gcn10_band_stats_of.argtypes = [u64p, C.c_int, C.POINTER(BandStats)]
+        L.gcn10_band_stats_of.restype = None
+        L.gcn10_stats_xml.argtypes = [C.POINTER(BandStats), cp, C.c_size_t]
+        L.gcn10_stats_xml.restype = C.c_size_t
         L.gcn10_tiff_finish.argtypes = [vp, cp, C.c_size_t]
         L.gcn10_tiff_finish.restype = C.c_int
         L.gcn10_tiff_abort.argtypes = [vp]
@@ -115,7 +133,14 @@ class Config(C.Structure):
                 ("gpu_deflate", C.c_int), ("gpu_inflate", C.c_int), ("direct_io", C.c_int),
                 ("prefetch_blocks", C.c_int),
                 ("table_mask", C.c_uint), ("cond_mask", C.c_uint), ("compress", C.c_int),
-                ("gpu_inflate_lzw", C.c_int), ("cog", C.c_int), ("overview_resampling", C.c_int)]
+                ("gpu_inflate_lzw", C.c_int), ("cog", C.c_int), ("overview_resampling", C.c_int),
+                ("stats", C.c_int), ("nodata", C.c_int)]
+
+
+class BandStats(C.Structure):
+    """``gcn10_band_stats`` of include/gcn10_host.h."""
+    _fields_ = [("total", C.c_uint64), ("valid", C.c_uint64), ("min", C.c_int), ("max", C.c_int),
+                ("mean", C.c_double), ("stddev", C.c_double), ("valid_percent", C.c_double)]
 
 
 class Blocks(C.Structure):
@@ -295,7 +320,7 @@ class TiffWriter:
         err = C.create_string_buffer(1024)
         L = lib()
         if n_levels is None:
-            self._h = L.gcn10_tiff_create(os.fsencode(path), xsize, ysize, _f(gt, 6), georef_ptr, err, 1024)
+            self._h = L.tiff_create_(os.fsencode(path), xsize, ysize, _f(gt, 6), georef_ptr, err, 1024)
         else:
             self._h = L.gcn10_tiff_create_cog(os.fsencode(path), xsize, ysize, _f(gt, 6), georef_ptr, n_levels,
                                               err, 1024)
@@ -343,6 +368,15 @@ class TiffWriter:
         end = rel[-1] + len(tiles[-1][2]) if n else 0
         return lib().gcn10_tiff_put_extent(self._level(level), buf.ctypes.data + base, end, n, txs, tys, rels, sizes)
 
+    def set_nodata(self, v: int) -> int:
+        return lib().gcn10_tiff_set_nodata(self._h, v)
+
+    def set_metadata_xml(self, xml) -> int:
+        return lib().gcn10_tiff_set_metadata_xml(self._h, None if xml is None else xml.encode())
+
+    def reserve_metadata(self, nbytes: int = None) -> int:
+        return lib().gcn10_tiff_reserve_metadata(self._h, STATS_XML_MAX if nbytes is None else nbytes)
+
     def finish(self):
         err = C.create_string_buffer(1024)
         h, self._h = self._h, None
@@ -353,6 +387,35 @@ class TiffWriter:
         if self._h:
             lib().gcn10_tiff_abort(self._h)
             self._h = None
+
+
+STATS_XML_MAX = 512        # GCN10_STATS_XML_MAX
+
+
+def raster_histogram(pair_hist, codes, table, drained: bool) -> np.ndarray:
+    """One raster's histogram (256 uint64) from a block's pair histogram ([16][256] uint64, gcn10_gpu_pair_histogram),
+    the bins' soil codes (gpu.pair_histogram_codes()) and the raster's lookup table (int[256][5])
+    (gcn10_raster_histogram)."""
+    pair = np.ascontiguousarray(pair_hist, dtype=np.uint64).reshape(-1)
+    if pair.size != 16 * 256:
+        raise ValueError("pair histogram must have 16 x 256 counters")
+    out = np.zeros(256, np.uint64)
+    lib().gcn10_raster_histogram(pair, np.ascontiguousarray(codes, dtype=np.uint8).reshape(16),
+                                 np.ascontiguousarray(table, dtype=np.int32).reshape(256, 5), int(bool(drained)), out)
+    return out
+
+
+def band_stats(hist, nodata=None) -> dict:
+    """GDAL's statistics of a Byte band from its histogram (gcn10_band_stats_of): total, valid, min, max, mean,
+    stddev, valid_percent, and ``xml``, the GDAL_METADATA text gcn10_stats_xml makes of them (None: no valid pixel)."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64).reshape(256)
+    st = BandStats()
+    lib().gcn10_band_stats_of(h, -1 if nodata is None else int(nodata), C.byref(st))
+    buf = C.create_string_buffer(STATS_XML_MAX)
+    n = lib().gcn10_stats_xml(C.byref(st), buf, STATS_XML_MAX)
+    out = {name: getattr(st, name) for name, _t in BandStats._fields_}
+    out["xml"] = buf.value.decode() if n else None
+    return out
 
 
 def _f(v, n):

@@ -38,7 +38,8 @@ extern "C" {
  *    streams of a strip out as one extent (option "arena_segment_align"), gcn10_gpu_deflate_arena_bound grew by
  *    the extents' pads (round 3).  A caller built against an older header must be rebuilt: check at start-up.
  *    Added within 3: the LZW encoder (gcn10_gpu_lzw_*), LZW tiles of gcn10_gpu_inflate_tiles (GCN10_TILE_LZW)
- *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*). */
+ *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*); the pair histogram
+ *    of the band statistics (gcn10_gpu_pair_histogram*). */
 #define GCN10_GPU_ABI_VERSION 3
 
 enum {
@@ -302,6 +303,25 @@ int gcn10_gpu_overview_nearest(gcn10_gpu_ctx *ctx, const uint8_t *src, int W, in
 int gcn10_gpu_overview_average(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int H, int y0, int rows,
                                const int32_t *cj, unsigned cond_mask, unsigned table_mask, int n_levels,
                                uint8_t *const *levels, gcn10_stream_t stream);
+
+/* Band statistics of the outputs (config key stats=1).  Every raster's value at a pixel is a function of the pixel's
+ * (landcover byte, soil code byte) pair -- soil code = drained plane | undrained plane << 4, as the strip kernels
+ * derive it from the soil class (src/cn.c:88-111) --, so one histogram of those pairs per block gives the exact
+ * histogram of all 18 rasters on the host (gcn10_raster_histogram in gcn10_host.h).  The codes are kept in
+ * GCN10_PAIR_HIST_BINS dense bins: hist[bin * 256 + landcover].  Added in ABI 3 without a version change; the host
+ * looks them up for stats runs only.
+ *
+ * gcn10_gpu_pair_histogram_codes: codes[b] = the soil code counted in bin b (bins no code maps to hold 0x55, the
+ *   invalid plane in both conditions, and stay empty).  Returns GCN10_PAIR_HIST_BINS.
+ * gcn10_gpu_pair_histogram: ADDS the pair counts of one strip (`esa`: W x rows landcover, row major; `cj`: the soil
+ *   row of each of its rows, as for gcn10_gpu_cn_strip) to the device histogram hist_dev[GCN10_PAIR_HIST_SIZE], with
+ *   the soil codes gcn10_gpu_prepare_tile prepared for width W.  Only the W x rows pixels are counted (no tile
+ *   padding); 64-bit counters.  Asynchronous on `stream`; clear hist_dev once per block (gcn10_gpu_memset). */
+#define GCN10_PAIR_HIST_BINS 16
+#define GCN10_PAIR_HIST_SIZE (256 * GCN10_PAIR_HIST_BINS)
+int gcn10_gpu_pair_histogram_codes(uint8_t codes[GCN10_PAIR_HIST_BINS]);
+int gcn10_gpu_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                             unsigned long long *hist_dev, gcn10_stream_t stream);
 
 /* Launch-shape knobs of the strip kernels, for tuning runs; results never
  * depend on them.  Names: "grid_blocks_per_cu" (1..64), "ilp16" (0 = by raster count | 1 | 2),

@@ -121,6 +121,10 @@ typedef struct gcn10_config {
                                GPU; 0 (default) = plain tiled GeoTIFFs.  No host fallback: refused with gpu_deflate=0 */
     int overview_resampling;/* "overview_resampling": GCN10_OVERVIEW_NEAREST (default, "nearest") or
                                GCN10_OVERVIEW_AVERAGE ("average"), any case */
+    int stats;              /* "stats": 1 = every written raster carries GDAL band statistics (STATISTICS_* items in
+                               its GDAL_METADATA tag, 42112), counted on the GPU; 0 (default) = none */
+    int nodata;             /* "nodata": 0..255 = every written raster declares that NoData value (GDAL_NODATA tag,
+                               42113) and its statistics leave it out; -1 ("none", default) = no tag */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -135,9 +139,12 @@ int gcn10_parse_compress(const char *text, int *codec);
 /* "nearest" | "average" (any case) -> GCN10_OVERVIEW_*; "0" | "1" -> cog.  0, or -1 for another value. */
 int gcn10_parse_overview_resampling(const char *text, int *method);
 int gcn10_parse_cog(const char *text, int *cog);
+/* "0" | "1" -> stats; "none" (any case) -> -1 | an integer 0..255 -> nodata.  0, or -1 for another value. */
+int gcn10_parse_stats(const char *text, int *stats);
+int gcn10_parse_nodata(const char *text, int *nodata);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -244,6 +251,20 @@ int gcn10_cog_levels(int xsize, int ysize);
  * level the file does not have. */
 gcn10_tiff_writer *gcn10_tiff_level(gcn10_tiff_writer *w, int level);
 int gcn10_tiff_n_levels(const gcn10_tiff_writer *w);   /* 0 for a plain file */
+/* GDAL's NoData and metadata tags (config keys "nodata" and "stats"), beside the geo tags in ascending tag order.
+ * gcn10_tiff_set_nodata: GDAL_NODATA (42113, ASCII, e.g. "255") on every IFD, COG overviews included, as GDAL
+ *   writes it; v in 0..255.
+ * gcn10_tiff_set_metadata_xml: GDAL_METADATA (42112, ASCII, NUL terminated) of the full-resolution IFD only, as
+ *   GDAL's COG driver writes it; a copy is kept, NULL removes it.
+ * gcn10_tiff_reserve_metadata: a COG's directories are laid out at create, so the room of the metadata value must be
+ *   known before its text is: `bytes` (including the NUL) are kept free for it, and the tag is then always written
+ *   (an empty <GDALMetadata> element when no text is set by finish).  Nothing to do for a plain file.
+ * On a plain file all three may be called at any time before gcn10_tiff_finish.  On a COG, set_nodata and
+ * reserve_metadata change the directories' size and must come before the first tile (-1 otherwise), and a text
+ * longer than the reserved room is refused (-1).  0 or -1. */
+int gcn10_tiff_set_nodata(gcn10_tiff_writer *w, int v);
+int gcn10_tiff_set_metadata_xml(gcn10_tiff_writer *w, const char *xml);
+int gcn10_tiff_reserve_metadata(gcn10_tiff_writer *w, size_t bytes);
 /* Writes the directory and closes the file.  0 or -1. */
 int gcn10_tiff_finish(gcn10_tiff_writer *w, char *err, size_t errcap);
 void gcn10_tiff_abort(gcn10_tiff_writer *w);
@@ -262,6 +283,37 @@ int gcn10_save_raster(const uint8_t *data, int xsize, int ysize, const double gt
 
 
 /* ------------------------------------------------------------------------ */
+/* band statistics (config keys "stats", "nodata"): no counterpart in the reference                         */
+/* ------------------------------------------------------------------------ */
+
+/* The histogram of one raster from a block's (landcover, soil code) pair histogram (gcn10_gpu_pair_histogram:
+ * pair[bin * 256 + landcover], codes[bin] = the soil code of each of the 16 bins, gcn10_gpu_pair_histogram_codes).
+ * The value of a pair is the kernels' own: plane = the code's drained (low nibble) or undrained (high nibble)
+ * plane, table[landcover][plane] if plane < 5 and that value is < 255 (stored through a (uint8_t) cast), else 255
+ * (src/cn.c:114-131).  hist[v] for v in 0..255 is overwritten. */
+void gcn10_raster_histogram(const uint64_t *pair, const uint8_t codes[16], const int table[256][5], int drained,
+                            uint64_t hist[256]);
+
+/* Statistics of a histogram as GDAL's ComputeStatistics makes them for a Byte band: the valid pixels are all of
+ * them, or all but the value `nodata` (0..255; -1 = none); min and max over them, the plain mean, the population
+ * standard deviation sqrt(n * sum(v^2) - sum(v)^2) / n from exact integer sums, valid percent = 100 * valid / total. */
+typedef struct gcn10_band_stats {
+    uint64_t total, valid;
+    int min, max;
+    double mean, stddev, valid_percent;
+} gcn10_band_stats;
+void gcn10_band_stats_of(const uint64_t hist[256], int nodata, gcn10_band_stats *st);
+
+/* GDAL_METADATA text of the statistics, the way GDAL writes band statistics into a GeoTIFF:
+ *   <GDALMetadata>\n  <Item name="STATISTICS_MAXIMUM" sample="0">98</Item>\n ... </GDALMetadata>\n
+ * items in GDAL's (sorted) order MAXIMUM, MEAN, MINIMUM, STDDEV, VALID_PERCENT; min, max, mean and stddev as
+ * "%.14g", the valid percent as "%.4g" (GDALRasterBand::SetStatistics / ComputeStatistics).  Returns the length
+ * without the NUL, or 0 when the raster has no valid pixel (GDAL computes no statistics then: no items, no text)
+ * or the text does not fit cap.  GCN10_STATS_XML_MAX bytes always suffice. */
+#define GCN10_STATS_XML_MAX 512
+size_t gcn10_stats_xml(const gcn10_band_stats *st, char *buf, size_t cap);
+
+/* ------------------------------------------------------------------------ */
 /* the run: src/main.c:58-203 + process_block, src/cn.c:134-384              */
 /* ------------------------------------------------------------------------ */
 
@@ -275,6 +327,8 @@ typedef struct gcn10_run_options {
     const char *compress;       /* --compress deflate|lzw: overrides the config key "compress"   */
     bool cog;                   /* --cog: Cloud Optimized GeoTIFFs (sets the config key "cog")   */
     const char *overview_resampling;    /* --overview-resampling nearest|average                 */
+    bool stats;                 /* --stats: GDAL band statistics in every raster (sets the config key "stats") */
+    const char *nodata;         /* --nodata none|0..255: overrides the config key "nodata"                */
 } gcn10_run_options;
 
 /* Runs the whole job: config, logs, block ids, lookup tables, one worker thread

@@ -41,6 +41,8 @@ def main():
     ap.add_argument("--compress", default="deflate", help='config key "compress": deflate | lzw')
     ap.add_argument("--cog", type=int, default=0, help='config key "cog": 1 = Cloud Optimized GeoTIFFs with overviews')
     ap.add_argument("--overview-resampling", default="nearest", help='config key "overview_resampling": nearest | average')
+    ap.add_argument("--stats", type=int, default=0, help='config key "stats": 1 = GDAL band statistics in every raster')
+    ap.add_argument("--nodata", default="none", help='config key "nodata": none | 0..255')
     ap.add_argument("--workers-per-gpu", type=int, default=0)
     ap.add_argument("--gpu-inflate", type=int, default=1)
     ap.add_argument("--gpu-inflate-lzw", type=int, default=1, help='config key "gpu_inflate_lzw" (0 = LZW landcover through the host reader)')
@@ -80,10 +82,10 @@ def main():
         f.write("hysogs_data_path=%s/soil.tif\nesa_data_path=%s/esa.tif\nblocks_shp_path=%s/blocks.shp\n"
                 "lookup_table_path=%s\nlog_dir=%s/logs\nstrip_rows=%d\ndeflate_level=%d\ngpu_deflate=%d\n"
                 "workers_per_gpu=%d\ngpu_inflate=%d\ngpu_inflate_lzw=%d\nio_threads=%d\ncompress=%s\n"
-                "cog=%d\noverview_resampling=%s\n%s%s"
+                "cog=%d\noverview_resampling=%s\nstats=%d\nnodata=%s\n%s%s"
                 % (wd, wd, wd, os.path.join(ROOT, "tests", "golden", "lookups"), wd, a.strip_rows,
                    a.deflate_level, a.gpu_deflate, a.workers_per_gpu, a.gpu_inflate, a.gpu_inflate_lzw, a.io_threads,
-                   a.compress, a.cog, a.overview_resampling,
+                   a.compress, a.cog, a.overview_resampling, a.stats, a.nodata,
                    "lookups=%s\n" % a.lookups if a.lookups else "", "conditions=%s\n" % a.conditions if a.conditions else ""))
     build_s = time.time() - t0
     run_modes(a, wd, size, nb, build_s)
@@ -119,7 +121,7 @@ def run_modes(a, wd, size, nb, build_s):
     if a.lookups or a.conditions:
         n_rasters = (len([x for x in a.lookups.split(",") if x]) if a.lookups and a.lookups != "all" else 9) * \
             (1 if a.conditions in ("drained", "undrained") else 2)
-    res = {"size": size, "blocks": nb, "rasters_per_block": n_rasters, "strip_rows": a.strip_rows, "gpus": a.gpus, "pattern": a.pattern, "gpu_deflate": a.gpu_deflate, "compress": a.compress, "cog": a.cog, "overview_resampling": a.overview_resampling, "gpu_inflate": a.gpu_inflate, "gpu_inflate_lzw": a.gpu_inflate_lzw, "workers_per_gpu": a.workers_per_gpu, "esa_compression": a.esa_compression, "dual_soil_fraction": a.dual_soil_fraction,
+    res = {"size": size, "blocks": nb, "rasters_per_block": n_rasters, "strip_rows": a.strip_rows, "gpus": a.gpus, "pattern": a.pattern, "gpu_deflate": a.gpu_deflate, "compress": a.compress, "cog": a.cog, "overview_resampling": a.overview_resampling, "stats": a.stats, "nodata": a.nodata, "gpu_inflate": a.gpu_inflate, "gpu_inflate_lzw": a.gpu_inflate_lzw, "workers_per_gpu": a.workers_per_gpu, "esa_compression": a.esa_compression, "dual_soil_fraction": a.dual_soil_fraction,
            "world_build_seconds": round(build_s, 1), "modes": {}}
     for mode in a.modes.split(","):
         env = dict(os.environ)

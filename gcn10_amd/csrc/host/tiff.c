@@ -1317,6 +1317,15 @@ static void cog_order_advance(gcn10_tiff_writer *w, int n, const int *tx, const 
     w->last_idx = (long long)ty[n - 1] * w->across + tx[n - 1];
 }
 
+/* A put_tile / put_tiles write goes at the append position with the streams' own lengths, neither of them sector
+ * aligned, which ext4 and xfs refuse on an O_DIRECT descriptor (EINVAL).  So the file is written buffered from its
+ * first such put on: same offsets and append position as a file that never had direct I/O.  R->mu is held. */
+static void unaligned_put_ahead(gcn10_tiff_writer *R)
+{
+    if (R->direct)
+        gcn10_tiff_set_direct(R, false);
+}
+
 int gcn10_tiff_put_tile(gcn10_tiff_writer *w, int tx, int ty, const void *zdata, size_t nbytes)
 {
     gcn10_tiff_writer *R = w->root;
@@ -1334,15 +1343,18 @@ int gcn10_tiff_put_tile(gcn10_tiff_writer *w, int tx, int ty, const void *zdata,
         R->failed = true;           /* classic TIFF offsets are 32 bit */
         rc = -1;
     }
-    else if (write_all(R->fd, zdata, nbytes, R->pos) != 0) {
-        R->failed = true;
-        rc = -1;
-    }
     else {
-        w->offsets[idx] = (uint32_t)R->pos;
-        w->counts[idx] = (uint32_t)nbytes;
-        R->pos += nbytes;
-        cog_order_advance(w, 1, &tx, &ty);
+        unaligned_put_ahead(R);
+        if (R->direct || write_all(R->fd, zdata, nbytes, R->pos) != 0) {
+            R->failed = true;           /* (R->direct: O_DIRECT could not be cleared) */
+            rc = -1;
+        }
+        else {
+            w->offsets[idx] = (uint32_t)R->pos;
+            w->counts[idx] = (uint32_t)nbytes;
+            R->pos += nbytes;
+            cog_order_advance(w, 1, &tx, &ty);
+        }
     }
     pthread_mutex_unlock(&R->mu);
     return rc;
@@ -1362,6 +1374,9 @@ int gcn10_tiff_put_tiles(gcn10_tiff_writer *w, int n, const int *tx, const int *
         pthread_mutex_unlock(&R->mu);
         return -1;
     }
+    unaligned_put_ahead(R);
+    if (R->direct)
+        rc = -1;                        /* O_DIRECT could not be cleared */
     for (int i = 0; i < n && rc == 0;) {
         int m = 0;
         uint64_t total = 0, at = R->pos;

@@ -91,6 +91,8 @@ def lib():
         L.gcn10_tiff_tiles_down.restype = C.c_int
         L.gcn10_tiff_put_tile.argtypes = [vp, C.c_int, C.c_int, vp, C.c_size_t]
         L.gcn10_tiff_put_tile.restype = C.c_int
+        L.gcn10_tiff_put_tiles.argtypes = [vp, C.c_int, ip, ip, C.POINTER(vp), C.POINTER(C.c_uint32)]
+        L.gcn10_tiff_put_tiles.restype = C.c_int
         L.gcn10_tiff_put_extent.argtypes = [vp, vp, C.c_size_t, C.c_int, ip, ip, C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint32)]
         L.gcn10_tiff_put_extent.restype = C.c_int
@@ -347,6 +349,16 @@ class TiffWriter:
 
     def put_tile(self, tx, ty, data: bytes, level=0) -> int:
         return lib().gcn10_tiff_put_tile(self._level(level), tx, ty, data, len(data))
+
+    def put_tiles(self, tiles, level=0) -> int:
+        """tiles: [(tx, ty, bytes)] put with one gcn10_tiff_put_tiles (gathered writes from separate buffers)."""
+        n = len(tiles)
+        bufs = [C.create_string_buffer(bytes(t[2]), len(t[2])) for t in tiles]
+        txs = (C.c_int * n)(*[t[0] for t in tiles])
+        tys = (C.c_int * n)(*[t[1] for t in tiles])
+        ptrs = (C.c_void_p * n)(*[C.addressof(b) for b in bufs])
+        sizes = (C.c_uint32 * n)(*[len(t[2]) for t in tiles])
+        return lib().gcn10_tiff_put_tiles(self._level(level), n, txs, tys, ptrs, sizes)
 
     def put_extent(self, tiles, level=0) -> int:
         """tiles: [(tx, ty, bytes)] laid out back to back (16-byte slots, as the GPU encoders do) and put

@@ -229,7 +229,8 @@ int gcn10_tiff_put_extent(gcn10_tiff_writer *w, const void *data, size_t extent_
 /* TIFF Compression tag of the file: 8 (default, Adobe deflate: zlib streams) or 5 (LZW streams).  0 or -1. */
 int gcn10_tiff_set_compression(gcn10_tiff_writer *w, int compression);
 /* O_DIRECT for the tile data (config key "direct_io"): extents must then be 4096-aligned in memory and
- * readable to the next multiple of 4096.  0 = on, -1 = the file system refuses (nothing changed). */
+ * readable to the next multiple of 4096.  0 = on, -1 = the file system refuses (nothing changed).  A put_tile or
+ * put_tiles writes at unaligned positions and lengths: it turns O_DIRECT off for the rest of the file first. */
 int gcn10_tiff_set_direct(gcn10_tiff_writer *w, bool on);
 /* Cloud Optimized GeoTIFF (config key "cog"): the same raster plus n_levels overviews, in GDAL's COG layout --
  * the 8-byte header, GDAL's ghost area at offset 8 ("GDAL_STRUCTURAL_METADATA_SIZE=nnnnnn bytes", LAYOUT=

@@ -44,7 +44,7 @@ def write_cog(path, W, H, compression, direct, seed=0, extents=True):
             assert (across, down) == (math.ceil(img.shape[1] / 256), math.ceil(img.shape[0] / 256))
             for ty in range(down):
                 row = [(tx, ty, enc(tile_of(img, tx, ty))) for tx in range(across)]
-                if extents and (direct or ty % 2 == 0):     # O_DIRECT takes whole extents only
+                if extents and ty % 2 == 0:     # extents and single puts by turns, with or without O_DIRECT
                     assert wr.put_extent(row, level=k) == 0
                 else:
                     for tx, _ty, d in row:

@@ -12,6 +12,7 @@ from PIL import Image
 from gcn10_amd import host
 from oracle import cn_oracle_c as oc
 from tests import cogcheck, tiffutil
+from tests.fullblock import average_levels, nearest_level
 from tests.conftest import LOOKUPS, ROOT
 from tests.util import ESA_NASTY, HSG_NASTY, make_block, random_tables
 
@@ -31,29 +32,7 @@ IDS = "106 105 101 102\n103\n"
 GUARD = 256
 
 
-# ---- the model of the two resamplings ("Cloud Optimized GeoTIFF output") ---------------------------
-
-def nearest_level(full, k):
-    H, W = full.shape
-    ys = np.minimum((np.arange(math.ceil(H / 2 ** k)) << k) + (1 << (k - 1)), H - 1)
-    xs = np.minimum((np.arange(math.ceil(W / 2 ** k)) << k) + (1 << (k - 1)), W - 1)
-    return full[np.ix_(ys, xs)]
-
-
-def average_levels(full, L):
-    out, cur = [], full
-    for _k in range(L):
-        h, w = cur.shape
-        p = np.full((h + h % 2, w + w % 2), 255, np.int64)      # clipped footprint = padding left out like 255
-        p[:h, :w] = cur
-        q = p.reshape(p.shape[0] // 2, 2, p.shape[1] // 2, 2)
-        valid = q != 255
-        s = np.where(valid, q, 0).sum(axis=(1, 3))
-        n = valid.sum(axis=(1, 3))
-        cur = np.where(n == 0, 255, (2 * s + n) // np.maximum(2 * n, 1)).astype(np.uint8)
-        out.append(cur)
-    return out
-
+# ---- the model of the two resamplings (tests/fullblock.py) ----------------------------------------------------
 
 def test_model_rules():
     a = np.array([[10, 11, 255], [20, 255, 255]], np.uint8)

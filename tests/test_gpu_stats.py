@@ -2,7 +2,6 @@
 landcover and soil codes, and the program end to end with stats=1 / nodata=<v>: every written raster's GDAL tags
 against the statistics numpy computes from that raster's decoded pixels."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -11,7 +10,7 @@ from PIL import Image
 
 from gcn10_amd import gpu, host
 from oracle import cn_oracle_c as oc
-from tests import cogcheck, tiffutil
+from tests import cogcheck, fullblock, tiffutil
 from tests.conftest import LOOKUPS, ROOT
 from tests.util import ESA_NASTY, HSG_NASTY
 
@@ -27,7 +26,6 @@ BLOCKS = [(101, 10.0, 49.0, 11.0, 50.0),
           (105, 11.3, 49.6, 11.5, 49.85),      # 200 x 250: no overview level
           (106, 10.5, 48.2, 10.7, 48.8)]
 IDS = "106 105 101 102\n103\n"
-ITEM = re.compile(r'<Item name="STATISTICS_([A-Z_]+)" sample="0">([^<]*)</Item>')
 
 
 def soil_code(h):
@@ -139,33 +137,7 @@ def _run(tmp_path, *args, env=None):
 
 def check_tags(path, px, nodata, stats=True):
     """The file's 42112 / 42113 against numpy's statistics of its decoded pixels px."""
-    with Image.open(path) as im:
-        tags = dict(im.tag_v2)
-    if nodata is None:
-        assert 42113 not in tags
-    else:
-        assert tags[42113] == str(nodata)
-    v = px.reshape(-1)
-    counts = np.bincount(v, minlength=256)
-    if nodata is not None:
-        counts[nodata] = 0
-    n = int(counts.sum())
-    items = dict(ITEM.findall(tags.get(42112, "")))
-    if not stats:
-        assert 42112 not in tags
-        return
-    if n == 0:
-        assert not items
-        return
-    vals = np.arange(256, dtype=np.float64)
-    mean = float((counts * vals).sum() / n)
-    std = float(np.sqrt((counts * (vals - mean) ** 2).sum() / n))
-    nz = np.nonzero(counts)[0]
-    assert set(items) == {"MAXIMUM", "MEAN", "MINIMUM", "STDDEV", "VALID_PERCENT"}, path
-    assert float(items["MINIMUM"]) == nz[0] and float(items["MAXIMUM"]) == nz[-1], path
-    assert items["VALID_PERCENT"] == "%.4g" % (100.0 * n / v.size), path
-    assert float(items["MEAN"]) == pytest.approx(mean, rel=1e-12), path
-    assert float(items["STDDEV"]) == pytest.approx(std, rel=1e-12, abs=1e-12), path
+    fullblock.check_tags(path, np.bincount(px.reshape(-1), minlength=256), nodata, stats)
 
 
 def _check_outputs(tmp_path, esa, soil, tables, nodata, cog, sel=range(18), stats=True):

@@ -83,8 +83,8 @@ def packbits_encode(data: bytes) -> bytes:
 
 
 def write_tiff(path, img, gt=None, compression=1, tile=None, rows_per_strip=None, predictor=1,
-               big_endian=False, bigtiff=False, geokeys=None, pixel_is_point=False):
-    """img: uint8[H,W].  tile=(tw,th) for tiles else strips.  Returns nothing."""
+               big_endian=False, bigtiff=False, geokeys=None, pixel_is_point=False, zlevel=6):
+    """img: uint8[H,W].  tile=(tw,th) for tiles else strips; zlevel: zlib level of DEFLATE chunks.  Returns nothing."""
     img = np.ascontiguousarray(img, dtype=np.uint8)
     H, W = img.shape
     E = ">" if big_endian else "<"
@@ -111,7 +111,7 @@ def write_tiff(path, img, gt=None, compression=1, tile=None, rows_per_strip=None
         if compression == 1:
             return raw
         if compression in (8, 32946):
-            return zlib.compress(raw, 6)
+            return zlib.compress(raw, zlevel)
         if compression == 5:
             return lzw_encode(raw)
         if compression == 32773:

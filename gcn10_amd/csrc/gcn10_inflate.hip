@@ -73,7 +73,7 @@ enum {
     kErrHeader = 1,         // not a zlib stream (CM != 8, FDICT set, bad check bits)
     kErrBlockType = 2,
     kErrStored = 3,         // LEN != ~NLEN
-    kErrLengths = 4,        // bad code-length sequence or over-subscribed code
+    kErrLengths = 4,        // bad code-length sequence, over-subscribed or incomplete code, no end-of-block code
     kErrCode = 5,           // a bit pattern that is no code of the current block
     kErrDistance = 6,       // distance reaches before the start of the output
     kErrInput = 7,          // ran past the end of the compressed bytes
@@ -221,8 +221,11 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t x)
 }
 
 // Sorts the n symbols of lens[] by (length, symbol) and derives first code / offset per
-// length.  Returns false when the lengths over-subscribe the code space.
-__device__ __forceinline__ bool sort_code(const uint8_t *lens, int n, uint16_t *sorted, Code &c, int lane)
+// length.  Returns false for a set zlib refuses (inftrees.c): lengths that over-subscribe the code
+// space, or an incomplete code -- which zlib allows only for a code with no symbol at all or with a
+// single 1-bit code, and for the precode (`precode`) only with no symbol at all.
+__device__ __forceinline__ bool sort_code(const uint8_t *lens, int n, uint16_t *sorted, Code &c, int lane,
+                                          bool precode = false)
 {
     uint32_t cnt[16];
 #pragma unroll
@@ -236,7 +239,7 @@ __device__ __forceinline__ bool sort_code(const uint8_t *lens, int n, uint16_t *
             cnt[L] += (uint32_t)__builtin_popcountll(__ballot(mylen == (uint32_t)L));
     }
     uint32_t offs[16], first[16];
-    int left = 1;
+    int left = 1, longest = 0;
     bool ok = true;
     offs[0] = 0;
     first[0] = 0;
@@ -247,11 +250,15 @@ __device__ __forceinline__ bool sort_code(const uint8_t *lens, int n, uint16_t *
         left = left * 2 - (int)cnt[L];
         if (left < 0)
             ok = false;
+        if (cnt[L] != 0)
+            longest = L;
         if (L < 15) {
             offs[L + 1] = offs[L] + cnt[L];
             first[L + 1] = (first[L] + cnt[L]) << 1;
         }
     }
+    if (left > 0 && longest != 0 && (precode || longest != 1))
+        ok = false;                     // incomplete
     if (lane < 16) {
         uint32_t cv = 0, fv = 0, ov = 0;
 #pragma unroll
@@ -617,7 +624,7 @@ __device__ __forceinline__ void begin_block(Shared &sh, Decoder &d, int lane)
             if (lane == 0)
                 sh.lens[sym] = (uint8_t)v;
         }
-        if (!sort_code(sh.lens, 19, sh.lit_sorted, sh.lit, lane)) {
+        if (!sort_code(sh.lens, 19, sh.lit_sorted, sh.lit, lane, true)) {
             d.err = kErrLengths;
             d.state = kDone;
             return;
@@ -673,6 +680,11 @@ __device__ __forceinline__ void begin_block(Shared &sh, Decoder &d, int lane)
                 sh.lens[288 + lane] = dl;
             for (int i = n_lit + lane; i < 288; i += 64)
                 sh.lens[i] = 0;
+        }
+        if (uniform(sh.lens[256]) == 0u) {      // no end-of-block code: zlib refuses the block
+            d.err = kErrLengths;
+            d.state = kDone;
+            return;
         }
         n_lit = 288;
         n_dist = 32;

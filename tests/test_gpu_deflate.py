@@ -31,10 +31,94 @@ def _rasters(kind, H, W, seed):
         for k, thr in enumerate([1e-1, 3e-2, 1e-2, 3e-3, 1e-3, 3e-4, 1e-4, 5e-5, 2e-5]):
             v[idx < thr] = k
         return v
+    if kind == "deep":              # Fibonacci-skewed: values 0..15 appear 2, 2, 4, 6, 10, ... times, 16..99 evenly
+        return _deep_values(H, W, rng)  # (an unconstrained Huffman code of the tile is ~19 deep)
     if kind == "manyvals":          # > 144 live symbols but long runs: the flat-code path
         a = rng.integers(0, 256, size=((H + 7) // 8, (W + 7) // 8), dtype=np.uint8)
         return np.repeat(np.repeat(a, 8, axis=0), 8, axis=1)[:H, :W].copy()
     raise ValueError(kind)
+
+
+def _deep_values(H, W, rng, tail=16, top=100):
+    """Every 256 x 256 tile: values 0..tail-1 exactly 2, 2, 4, 6, 10, ... times (twice Fibonacci: the end of block's
+    single count does not tie with the chain), the rest even over tail..top-1 (few enough live symbols for a
+    Huffman code rather than the flat code of noise, and next to no runs or vertical repeats: no matches)."""
+    fib = [1, 1]
+    while len(fib) < tail:
+        fib.append(fib[-1] + fib[-2])
+    out = np.zeros((-(-H // 256) * 256, -(-W // 256) * 256), np.uint8)
+    for y in range(0, out.shape[0], 256):
+        for x in range(0, out.shape[1], 256):
+            v = np.concatenate([np.repeat(np.arange(tail), 2 * np.array(fib)), rng.integers(tail, top, 65536 - 2 * sum(fib))])
+            rng.shuffle(v)
+            out[y:y + 256, x:x + 256] = v.reshape(256, 256)
+    return out[:H, :W].copy()
+
+
+def _conforms(streams):
+    """Every (stream, tile bytes) parsed by the zlib model: its bytes, its size in the stream table = where the
+    stream ends, complete codes (one 1-bit code, or none for distances, as zlib allows) of at most 15 bits (7 for
+    the precode), no symbol 286/287 or distance 30/31; decoded by libdeflate at the exact tile size where it loads.
+    Returns how many dynamic blocks the length limit shaped: an unconstrained Huffman code of the block's own
+    token counts would be deeper than 15 bits (7 for the precode), and the block's code is 15 (7) deep."""
+    from tests import deflate_model as dm
+    lib = _libdeflate()
+    limited = 0
+    for st, want in streams:
+        r = dm.read(st)
+        assert r.data == want and r.end == len(st) and r.adler_ok
+        for b in r.blocks:
+            assert b.type in (0, 2)
+            if b.type == 0:
+                continue
+            for lens, limit, empty_ok in ((b.lit_lens, 15, False), (b.dist_lens, 15, True), (b.precode_lens, 7, False)):
+                used = [L for L in lens if L]
+                assert max(used, default=0) <= limit
+                kraft = sum(2.0 ** -L for L in used)
+                assert kraft == 1.0 or used == [1] or (empty_ok and not used), (lens, kraft)
+            lf, df, pf = [0] * 288, [0] * 32, [0] * 19
+            for t in b.tokens:
+                if t[0] == "lit":
+                    lf[t[1]] += 1
+                elif t[0] == "match":
+                    assert t[3] <= 285 and t[4] <= 29
+                    lf[t[3]] += 1
+                    df[t[4]] += 1
+                else:
+                    lf[256] += 1
+            for sym, _ in b.cl_items:
+                pf[sym] += 1
+            if any(max(dm.huffman_depths(f)) > lim and max(lens) == lim
+                   for f, lens, lim in ((lf, b.lit_lens, 15), (df, b.dist_lens, 15), (pf, b.precode_lens, 7))):
+                limited += 1
+        if lib is not None:
+            assert _decompress_exact(lib, st, len(want)) == want
+    return limited
+
+
+def _libdeflate():
+    import importlib.util
+    import os
+    from tests.conftest import GOLDEN
+    spec = importlib.util.spec_from_file_location("make_deflate_corpus", os.path.join(GOLDEN, "make_deflate_corpus.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    global _decompress_exact
+    _decompress_exact = mk.decompress_exact
+    return mk.load_libdeflate()
+
+
+def _streams(rasters, data, table, W, H):
+    out = []
+    for r, img in enumerate(rasters):
+        for ty in range((H + 255) // 256):
+            for tx in range((W + 255) // 256):
+                off, size = int(table[r, ty, tx, 0]), int(table[r, ty, tx, 1])
+                want = np.zeros((256, 256), np.uint8)
+                part = img[ty * 256:(ty + 1) * 256, tx * 256:(tx + 1) * 256]
+                want[:part.shape[0], :part.shape[1]] = part
+                out.append((data[off:off + size].tobytes(), want.tobytes()))
+    return out
 
 
 def _check(engine, rasters, W, H):
@@ -59,7 +143,7 @@ def _check(engine, rasters, W, H):
     return total
 
 
-@pytest.mark.parametrize("kind", ["uniform", "zeros", "patches", "noisy", "random", "rows", "skewed", "manyvals"])
+@pytest.mark.parametrize("kind", ["uniform", "zeros", "patches", "noisy", "random", "rows", "skewed", "manyvals", "deep"])
 def test_streams_inflate_to_the_tiles(engine, kind):
     H, W = 512, 768
     img = _rasters(kind, H, W, 1)
@@ -74,6 +158,25 @@ def test_streams_inflate_to_the_tiles(engine, kind):
         assert size == 6 * 65552        # stored fallback, never worse than raw + 16 B
     if kind in ("patches", "noisy", "rows", "skewed", "manyvals"):
         assert size < 2.0 * ref         # within 2x of zlib level 6 on CN-like data
+
+
+@pytest.mark.parametrize("wave_codes", [1, 0])
+def test_streams_conform_to_zlib_bit_for_bit(engine, wave_codes):
+    """Both forms of pass B (deflate_wave_codes 1 / 0): every stream parsed by the zlib model -- the table's size
+    is the stream's length, codes are complete and length-limited, no reserved symbol is used -- and the deep-tree
+    tiles prove the 15-bit limit ran."""
+    H, W = 512, 768
+    rasters = [_rasters(k, H, W, 11) for k in ("patches", "noisy", "skewed", "manyvals", "uniform", "random")]
+    rasters += [_rasters("deep", H, W, 12), _deep_values(H, W, np.random.default_rng(13), tail=20, top=110)]
+    bufs = [engine.upload(r) for r in rasters]
+    try:
+        engine.set_option("deflate_wave_codes", wave_codes)
+        data, table, used = engine.deflate_rasters([b.ptr for b in bufs], W, H)
+    finally:
+        engine.set_option("deflate_wave_codes", 1)
+        for b in bufs:
+            b.close()
+    assert _conforms(_streams(rasters, data, table, W, H)) >= 1
 
 
 @pytest.mark.parametrize("shape", [(1, 1), (256, 256), (255, 257), (300, 700), (513, 1025), (1000, 36001 // 16)])
@@ -118,7 +221,7 @@ def test_wave_and_thread_code_construction_agree(engine, kind):
 # ---- fused tile encoder: landcover + soil -> zlib streams, no CN raster in between -----------
 
 def _fused_case(engine, tables, H, W, seed, cond_mask=3, table_mask=0x1FF, nasty=True, coherent=True,
-                esa_override=None):
+                esa_override=None, streams_out=None):
     from gcn10_amd import host
     from oracle import cn_oracle_c as oc
     from tests.util import make_block
@@ -150,8 +253,20 @@ def _fused_case(engine, tables, H, W, seed, cond_mask=3, table_mask=0x1FF, nasty
                 part = want[r][ty * 256:(ty + 1) * 256, tx * 256:(tx + 1) * 256]
                 exp[:part.shape[0], :part.shape[1]] = part
                 assert zlib.decompress(data[off:off + size].tobytes()) == exp.tobytes(), (r, ty, tx)
+                if streams_out is not None:
+                    streams_out.append((data[off:off + size].tobytes(), exp.tobytes()))
                 total += size
     return total, want, sel
+
+
+def test_fused_encoder_streams_conform_to_zlib_bit_for_bit(engine, tables):
+    """The fused encoder's streams through the zlib model (see _conforms): patchy and i.i.d. CN-like blocks, one
+    raster and several.  (Its code construction is pass B's, whose length limit the per-raster test shows at work.)"""
+    streams = []
+    _fused_case(engine, tables, 300, 520, seed=31, streams_out=streams)
+    _fused_case(engine, tables, 256, 512, seed=32, coherent=False, cond_mask=1, table_mask=0x011, streams_out=streams)
+    assert len(streams) == 18 * 6 + 2 * 2
+    _conforms(streams)
 
 
 @pytest.mark.parametrize("shape", [(256, 256), (300, 700), (513, 1025), (1, 1), (700, 36001 // 40)])

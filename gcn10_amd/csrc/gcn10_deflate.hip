@@ -777,9 +777,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void deflate_codes_wave_kernel
         return;
     }
 
-    // (timing experiments, option "codes_stop" = p + 1: leave after phase p; books and sizes of the last complete
-    // launch stay in the workspace, so the passes behind this one still see valid input)
-    const uint32_t stop_after = job.codes_stop ? job.codes_stop - 1u : 99u;
     // ---- statistics: lane holds symbols lane + 64 c ----
     uint32_t h[5];
 #pragma unroll
@@ -804,8 +801,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void deflate_codes_wave_kernel
     }
     m = uni(m);
 
-    if (stop_after == 0u)
-        return;                 // phase 0: statistics loaded, live symbols compacted
     uint32_t count[17];
 #pragma unroll
     for (int i = 0; i <= 16; i++)
@@ -870,8 +865,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void deflate_codes_wave_kernel
             }
         }
         }
-        if (stop_after == 1u)
-            return;             // phase 1: + the sort
         // ---- two-queue Huffman merge; both queues live in registers ----
         if (m <= 63u) {
             // The usual case (a tile has a few dozen live symbols): one leaf and one internal node per lane, so
@@ -981,8 +974,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void deflate_codes_wave_kernel
         }
         }
         wave_sync();
-        if (stop_after == 2u)
-            return;             // phase 2: + the merge
         // ---- leaf depths: every lane walks up from its leaves to the root ----
         const uint32_t root = 2 * m - 2;
         uint32_t depth[3];
@@ -1045,8 +1036,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void deflate_codes_wave_kernel
             }
         }
     }
-    if (stop_after == 3u)
-        return;                 // phase 3: + depths, counts per length, the 15-bit cap, lengths by rank
     // distance alphabet: codes 0 (distance 1) and 15 (distance 256)
     if (lane < 32)
         w.len[288 + lane] = 0;
@@ -1106,8 +1095,6 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void deflate_codes_wave_kernel
         body_bits += __shfl_xor(body_bits, off, 64);
     body_bits += n_near * dl0 + n_far * (dl15 + 6u);
 
-    if (stop_after == 4u)
-        return;                 // phase 4: + canonical codes, body size
     // ---- block header: fixed part by lane 0, the code lengths run-length coded in parallel ----
     // hlit / hdist: trailing zero lengths are not sent
     uint32_t hlit = 257;
@@ -1546,20 +1533,6 @@ __global__ __launch_bounds__(kTile) void deflate_emit_kernel(const TileJob job)
 
 namespace gcn10 {
 
-int deflate_workspace(gcn10_gpu_ctx *ctx, size_t need)
-{
-    if (need <= ctx->deflate_ws_cap)
-        return GCN10_OK;
-    HIP_TRY(hipDeviceSynchronize());            // the old workspace may still be in use
-    if (ctx->deflate_ws)
-        HIP_TRY(hipFree(ctx->deflate_ws));
-    ctx->deflate_ws = nullptr;
-    ctx->deflate_ws_cap = 0;
-    HIP_TRY(hipMalloc(&ctx->deflate_ws, need));
-    ctx->deflate_ws_cap = need;
-    return GCN10_OK;
-}
-
 int deflate_launch_codes(gcn10_gpu_ctx *ctx, const TileJob &job, uint32_t nblocks, hipStream_t s, bool place)
 {
     static_assert(sizeof(Work) * kBuildThreads <= 160 * 1024, "code construction slices must fit LDS");
@@ -1579,11 +1552,8 @@ int deflate_launch_codes(gcn10_gpu_ctx *ctx, const TileJob &job, uint32_t nblock
         hipLaunchKernelGGL(deflate_codes_kernel, dim3((nblocks + kBuildThreads - 1) / kBuildThreads),
                            dim3(kBuildThreads), sizeof(Work) * kBuildThreads, s, job);
     }
-    if (place)
-        hipLaunchKernelGGL(deflate_place_kernel, dim3(1), dim3(kPlaceThreads), 0, s, job, job.across * job.down,
-                           (uint32_t)ctx->arena_segment_align);
     HIP_TRY(hipGetLastError());
-    return GCN10_OK;
+    return place ? deflate_launch_place(ctx, job, s) : GCN10_OK;
 }
 
 int deflate_launch_place(gcn10_gpu_ctx *ctx, const TileJob &job, hipStream_t s)
@@ -1624,7 +1594,6 @@ int gcn10_gpu_deflate_strip(gcn10_gpu_ctx *ctx, const uint8_t *const *rasters_de
     if ((reinterpret_cast<uintptr_t>(arena_dev) & 15u) != 0)
         return fail(GCN10_E_INVAL, "gcn10_gpu_deflate_strip: arena must be 16-byte aligned");
     TileJob job;
-    job.codes_stop = (uint32_t)ctx->codes_stop;
     job.rasters = rasters_dev;
     job.arena = arena_dev;
     job.table = table_dev;
@@ -1648,7 +1617,7 @@ int gcn10_gpu_deflate_strip(gcn10_gpu_ctx *ctx, const uint8_t *const *rasters_de
 
     // per-tile statistics and code books: workspace owned by the context
     const size_t need = (size_t)nblocks * ((size_t)kHistWords * 4 + (size_t)kBookBytes);
-    rc = gcn10::deflate_workspace(ctx, need);
+    rc = gcn10::grow_workspace(&ctx->deflate_ws, &ctx->deflate_ws_cap, need);
     if (rc)
         return rc;
     job.hist = reinterpret_cast<uint32_t *>(ctx->deflate_ws);

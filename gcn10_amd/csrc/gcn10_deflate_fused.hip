@@ -46,7 +46,6 @@ struct FusedJob {
     uint16_t *tok;                  // [positions][kTokStride] token stream of each tile position (F-A -> F-C)
     uint32_t *n_tok;                // [positions] its length, end-of-block token included
     uint32_t hx_stride, hx_rows;
-    uint32_t diag;                  // gcn10_gpu_set_option("fused_diag"): timing experiments
     uint32_t seg_align;             // every raster's extent of the strip starts at a multiple of this (option arena_segment_align)
     uint32_t n_sel;                 // selected rasters, ascending
     uint8_t sel[GCN10_N_RASTERS];
@@ -167,7 +166,7 @@ __device__ __forceinline__ int next_set(const unsigned long long (&m)[4], int x)
 // and bit x of `start` is set.  Every mask of the tile must have been computed before.
 // Returns the number of tokens of the row.
 __device__ __forceinline__ uint32_t tokenise_row(uint8_t *tile, int t, const RowMasks &m, uint32_t *lit_hist,
-                                                 uint32_t *dist_hist, unsigned long long (&start)[4], bool diag_no_lit)
+                                                 uint32_t *dist_hist, unsigned long long (&start)[4])
 {
     uint8_t *row = tile + t * kRowStride;
     int x = 0;
@@ -176,8 +175,6 @@ __device__ __forceinline__ uint32_t tokenise_row(uint8_t *tile, int t, const Row
     while (x < kTile) {
         const int cand = next_candidate(m, x);
         n_tokens += (uint32_t)(cand - x);
-        if (diag_no_lit)
-            x = cand;
         for (; x < cand; x++)
             atomicAdd(&lit_hist[row[x]], 1u);
         if (x >= kTile)
@@ -297,7 +294,7 @@ __global__ __launch_bounds__(kTile) void fused_stats_kernel(const FusedJob job)
         }
     }
     unsigned long long start[4];
-    const uint32_t my_tokens = tokenise_row(sh.tile, t, m, sh.a.lit_hist, sh.a.dist_hist, start, (job.diag & 8u) != 0u);
+    const uint32_t my_tokens = tokenise_row(sh.tile, t, m, sh.a.lit_hist, sh.a.dist_hist, start);
     // rows back to back: where this row's tokens go
     {
         uint32_t incl = my_tokens;
@@ -316,7 +313,7 @@ __global__ __launch_bounds__(kTile) void fused_stats_kernel(const FusedJob job)
             at += sh.a.row_base[w];
         uint16_t *out = job.tok + (size_t)tix * kTokStride;
         const uint8_t *row = sh.tile + t * kRowStride;
-        int x = (job.diag & 16u) ? kTile : 0;       // (timing experiment: no token write-out)
+        int x = 0;
         while (x < kTile) {
             const int p = next_set(start, x);
             for (; x < p; x++)
@@ -504,9 +501,6 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
     if (job.t.chunk_tot && tix == 0u)
         for (uint32_t i = (uint32_t)t; i < job.n_sel * job.t.n_chunks; i += blockDim.x)
             job.t.chunk_tot[i] = 0u;
-    // (timing experiments, option "fused_stats_stop" = p + 1: leave after phase p; the workspace keeps the results
-    // of the last complete launch, so the passes behind this one still see valid input)
-    const uint32_t stop_after = (job.diag >> 8) ? (job.diag >> 8) - 1u : 99u;
 
     for (int i = t; i < gcn10::kClassCodes * 256 / 4; i += kFA2Threads)
         reinterpret_cast<uint32_t *>(sh.class_of)[i] = reinterpret_cast<const uint32_t *>(job.class_of)[i];
@@ -551,8 +545,6 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
         }
     }
     __syncthreads();
-    if (stop_after == 0u)
-        return;                 // phase 0: class map + landcover / soil loads + class tile
     for (int i = t; i < 288; i += kFA2Threads)
         sh.a.lit_hist[i] = 0;
     if (t < 2)
@@ -585,8 +577,6 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
         if (row == 0 && seg == 0)
             near_ &= ~1ull;             // the tile's first byte has no predecessor
     }
-    if (stop_after == 1u)
-        return;                 // phase 1: + the two candidate masks
     sh.a.lead_n[row][seg] = (uint8_t)(~near_ ? __builtin_ctzll(~near_) : kSegPx);
     sh.a.lead_f[row][seg] = (uint8_t)(~far_ ? __builtin_ctzll(~far_) : kSegPx);
     __syncthreads();
@@ -608,8 +598,6 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
         }
     }
 
-    if (stop_after == 2u)
-        return;                 // phase 2: + pixels and weights per class, run by run
     // length of the run of `far ? far_ : near_` that starts at pixel p of this segment, followed into the
     // segments behind it
     auto ext_run = [&](bool far, int p) -> int {
@@ -705,8 +693,6 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
         if (sgm + 1 < kSegs)
             sh.a.exit_at[row][sgm] = (uint16_t)exit_over;
     }
-    if (stop_after == 3u)
-        return;                 // phase 3: + the parse (speculative + entry offsets)
     // statistics of the final parse
     const unsigned long long lits = ~covered;
     const uint32_t my_tokens = (uint32_t)__popcll(lits) + (uint32_t)__popcll(starts);
@@ -738,46 +724,30 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
     {
         uint32_t at = sh.a.seg_at[row * kSegs + seg];
         uint16_t *out = job.tok + (size_t)tix * kTokStride;
-        if (!(job.diag & 16u)) {
-            // Literals and matches in loops of their own (a token's place is its rank among the segment's token
-            // starts): in one loop over all tokens a wave executed both paths in every trip, as often as its busiest
-            // lane has tokens -- 18 of the kernel's 76 us on noisy tiles.  (Neither the LDS round trip per token nor
-            // the scattered 2-byte stores were what that cost: reading ahead, or writing the tokens side by side,
-            // changed nothing.)
-            const unsigned long long all = lits | starts;
-            for (unsigned long long m = lits; m; m &= m - 1ull) {
-                const int p = __builtin_ctzll(m);
-                const uint32_t c = rowp[seg * kSegPx + p];
-                if (!(job.diag & 8u))
-                    atomicAdd(&sh.a.lit_hist[c], 1u);
-                out[at + (uint32_t)__popcll(all & ((1ull << p) - 1ull))] = (uint16_t)c;
-            }
-            for (unsigned long long m = starts; m; m &= m - 1ull) {
-                const int p = __builtin_ctzll(m);
-                const bool far = ((fars >> p) & 1ull) != 0;
-                const int len = ext_run(far, p);
-                uint32_t ev;                    // (no table: a global load per match inside this divergent loop)
-                const int lc = length_code_extra(len, ev);
-                atomicAdd(&sh.a.lit_hist[257 + lc], 1u);
-                atomicAdd(&sh.a.dist_hist[far ? 1 : 0], 1u);
-                out[at + (uint32_t)__popcll(all & ((1ull << p) - 1ull))] =
-                    (uint16_t)(kTokMatch | (uint32_t)lc | ev << 5 | (far ? 1u : 0u) << 10);
-            }
-            at += my_tokens;
+        // Literals and matches in loops of their own (a token's place is its rank among the segment's token
+        // starts): in one loop over all tokens a wave executed both paths in every trip, as often as its busiest
+        // lane has tokens -- 18 of the kernel's 76 us on noisy tiles.  (Neither the LDS round trip per token nor
+        // the scattered 2-byte stores were what that cost: reading ahead, or writing the tokens side by side,
+        // changed nothing.)
+        const unsigned long long all = lits | starts;
+        for (unsigned long long m = lits; m; m &= m - 1ull) {
+            const int p = __builtin_ctzll(m);
+            const uint32_t c = rowp[seg * kSegPx + p];
+            atomicAdd(&sh.a.lit_hist[c], 1u);
+            out[at + (uint32_t)__popcll(all & ((1ull << p) - 1ull))] = (uint16_t)c;
         }
-        else {
-            // (timing: without the token write-out; the statistics all the same)
-            for (unsigned long long m = starts; m; m &= m - 1ull) {
-                const int p = __builtin_ctzll(m);
-                const bool far = ((fars >> p) & 1ull) != 0;
-                atomicAdd(&sh.a.lit_hist[257 + length_code(ext_run(far, p))], 1u);
-                atomicAdd(&sh.a.dist_hist[far ? 1 : 0], 1u);
-            }
-            if (!(job.diag & 8u))
-                for (unsigned long long m = lits; m; m &= m - 1ull)
-                    atomicAdd(&sh.a.lit_hist[rowp[seg * kSegPx + __builtin_ctzll(m)]], 1u);
-            at += my_tokens;
+        for (unsigned long long m = starts; m; m &= m - 1ull) {
+            const int p = __builtin_ctzll(m);
+            const bool far = ((fars >> p) & 1ull) != 0;
+            const int len = ext_run(far, p);
+            uint32_t ev;                    // (no table: a global load per match inside this divergent loop)
+            const int lc = length_code_extra(len, ev);
+            atomicAdd(&sh.a.lit_hist[257 + lc], 1u);
+            atomicAdd(&sh.a.dist_hist[far ? 1 : 0], 1u);
+            out[at + (uint32_t)__popcll(all & ((1ull << p) - 1ull))] =
+                (uint16_t)(kTokMatch | (uint32_t)lc | ev << 5 | (far ? 1u : 0u) << 10);
         }
+        at += my_tokens;
         if (t == kFA2Threads - 1) {
             out[at] = (uint16_t)kTokEnd;
             job.n_tok[tix] = at + 1u;
@@ -785,8 +755,6 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
     }
     __syncthreads();
 
-    if (stop_after == 4u)
-        return;                 // phase 4: + statistics, scan, token write-out
     // From here on the tile is no longer needed (its memory holds the value histograms below), and the work is
     // per (raster, class).  The row form does it with 256 threads, raster after raster (18 x 3 wave sums in a
     // row, three rounds of six value histograms); here the 16 waves split the rasters.
@@ -986,7 +954,7 @@ __global__ __launch_bounds__(kTile) void fused_emit_kernel(const FusedJob job)
     __threadfence_block();                          // the zeroed slots are in place before this workgroup ORs into them
     __syncthreads();
 
-    if (coded && !(job.diag & 2u)) {
+    if (coded) {
         const uint16_t *tok = job.tok + (size_t)tix * kTokStride;
         const uint32_t n_tok = job.n_tok[tix];
         for (uint32_t i0 = 0; i0 < n_tok; i0 += kTile) {
@@ -1341,7 +1309,7 @@ __global__ __launch_bounds__(kTile, 6) void fused_emit_wave_kernel(const FusedJo
         (&sh.c.stage[0][0])[i] = 0ull;
 
     const uint16_t *tok = job.tok + (size_t)tix * kTokStride;
-    const uint32_t n_tok = coded && !(job.diag & 2u) ? job.n_tok[tix] : 0u;
+    const uint32_t n_tok = coded ? job.n_tok[tix] : 0u;
     // this wave's quarter: whole trips of 256 tokens
     const uint32_t per_wave = ((n_tok + 4u * kTripToks - 1u) / (4u * kTripToks)) * kTripToks;
     const uint32_t c0 = (uint32_t)wave * per_wave;
@@ -1362,7 +1330,7 @@ __global__ __launch_bounds__(kTile, 6) void fused_emit_wave_kernel(const FusedJo
 #pragma unroll
         for (int k = 0; k < kGroup; k++)
             acc[k] = 0;
-        for (uint32_t i0 = (job.diag & 1u) ? c1 : c0; i0 < c1; i0 += kTripToks) {      // (diag 1: timing without phase 1)
+        for (uint32_t i0 = c0; i0 < c1; i0 += kTripToks) {
             const uint2 v = load4(i0);
 #pragma unroll
             for (int q = 0; q < kLaneToks; q++) {
@@ -1451,7 +1419,7 @@ __global__ __launch_bounds__(kTile, 6) void fused_emit_wave_kernel(const FusedJo
             // the unfinished last word of this stream's previous trip is the first word of this one
             if (lane == 0)
                 stage[0] = carry[k];
-            if (!(job.diag & 4u)) {                                     // (diag 4: timing without the LDS atomics)
+            {
                 const uint32_t rel = (first & 63u) + incl - off;
                 const uint32_t w = rel >> 6, s = rel & 63u;
                 const unsigned long long v0 = a0 << s, v1 = a1 << s | (a0 >> 1) >> (63u - s),
@@ -1473,23 +1441,20 @@ __global__ __launch_bounds__(kTile, 6) void fused_emit_wave_kernel(const FusedJo
             const bool keep_last = (end & 63u) != 0u && !last_trip;     // the last word is unfinished and this wave goes on
             const uint32_t n_out = keep_last ? n_words - 1u : n_words;
             unsigned long long kept = 0;
-            if (!(job.diag & 16u))                                      // (diag 16: timing without the write-out)
-                for (uint32_t w = (uint32_t)lane; w < n_words; w += 64u) {
-                    const unsigned long long val = stage[w];
-                    stage[w] = 0ull;
-                    if (w >= n_out) {
-                        kept = val;                 // one lane
-                        continue;
-                    }
-                    unsigned long long *dst = words[k] + (first >> 6) + w;
-                    if (job.diag & 32u)             // (diag 32: timing with the LDS half of the write-out only)
-                        continue;
-                    const bool shared = (w == 0u && i0 == c0) || (w == n_words - 1u && last_trip);
-                    if (shared && !(job.diag & 8u))     // (diag 8: timing with plain stores only)
-                        atomicOr(dst, val);
-                    else
-                        *dst = val;
+            for (uint32_t w = (uint32_t)lane; w < n_words; w += 64u) {
+                const unsigned long long val = stage[w];
+                stage[w] = 0ull;
+                if (w >= n_out) {
+                    kept = val;                 // one lane
+                    continue;
                 }
+                unsigned long long *dst = words[k] + (first >> 6) + w;
+                const bool shared = (w == 0u && i0 == c0) || (w == n_words - 1u && last_trip);
+                if (shared)
+                    atomicOr(dst, val);
+                else
+                    *dst = val;
+            }
             if (keep_last) {
                 const uint32_t src = (n_words - 1u) & 63u;
                 carry[k] = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)kept, (int)src) |
@@ -1601,7 +1566,6 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
     job.class_of = ctx->d_class_of;
     job.hx_stride = ctx->hx_stride;
     job.hx_rows = ctx->hx_rows;
-    job.diag = (uint32_t)ctx->fused_diag | (uint32_t)ctx->fused_stats_stop << 8;
     job.seg_align = (uint32_t)ctx->arena_segment_align;
     for (int r = 0; r < GCN10_N_RASTERS; r++)
         if ((cond_mask >> (r / 9)) & 1u && (table_mask >> (r % 9)) & 1u)
@@ -1618,7 +1582,6 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
         return fail(GCN10_E_INVAL, "tile encoder: an arena of %zu bytes does not fit 32-bit stream offsets "
                                    "(use fewer rows per strip)", arena_cap);
     job.t.arena_cap = arena_cap;
-    job.t.codes_stop = (uint32_t)ctx->codes_stop;
     const uint32_t positions = job.t.across * job.t.down;
     // (pass F-C adds a raster's stream sizes up in 32 bits; with the 4 GB arena limit above only a strip far beyond
     // any arena can get here)
@@ -1632,7 +1595,7 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
     const size_t tok_bytes = (size_t)positions * kTokStride * sizeof(uint16_t);
     const size_t ntok_bytes = ((size_t)positions * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t need = stats_bytes + tok_bytes + ntok_bytes + (size_t)nblocks * 8 + (size_t)job.n_sel * ((positions + 63u) / 64u) * 4;
-    rc = gcn10::deflate_workspace(ctx, need);
+    rc = gcn10::grow_workspace(&ctx->deflate_ws, &ctx->deflate_ws_cap, need);
     if (rc)
         return rc;
     job.t.hist = reinterpret_cast<uint32_t *>(ctx->deflate_ws);

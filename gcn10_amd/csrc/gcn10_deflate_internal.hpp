@@ -83,7 +83,6 @@ struct TileJob {
     uint8_t *books;                     // [n_tiles][kBookBytes]   (pass B -> C)
     uint32_t W, rows, across, down, n_tiles;
     unsigned long long arena_cap;
-    uint32_t codes_stop;                // timing experiments only (option "codes_stop"): pass B leaves after phase (value - 1)
 };
 
 // per-tile statistics written by pass A: 288 literal/length counts, 2 distance
@@ -207,8 +206,6 @@ __device__ __forceinline__ uint32_t wave_scan_dpp(uint32_t x)
 namespace gcn10 {
 using gcn10_deflate::TileJob;
 
-// Grows the context's encoder workspace (statistics, code books, token tiles) to `need` bytes.
-int deflate_workspace(gcn10_gpu_ctx *ctx, size_t need);
 // Pass B for `nblocks` (raster, tile) pairs whose statistics are in job.hist: code books to job.books,
 // sizes to job.table; with `place`, pass B' (deflate_place_kernel) behind it lays the streams out in the arena.
 int deflate_launch_codes(gcn10_gpu_ctx *ctx, const TileJob &job, uint32_t nblocks, hipStream_t s, bool place = true);

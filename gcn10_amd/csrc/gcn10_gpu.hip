@@ -281,9 +281,6 @@ __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, 
         const bool wrap = xl >= p.W;
         xl = wrap ? xl - p.W : xl;
         const uint32_t row = clamp_row(p, (int32_t)(wrap ? r1[u] : r0[u]));
-#if defined(GCN10_DIAG) && (GCN10_DIAG == 2 || GCN10_DIAG == 3)
-        tr.c16[u] = u32x4{ row, xl, 0u, 0u } & 0x11111111u;    // timing-only build: no soil load
-#else
         if (HX4) {
             // W % 16 == 0: the lane's 16 pixels are one column group; its soil codes are one dword
             tr.c16[u] = u32x4{ p.hx4[(size_t)row * p.hx4_stride + (xl >> 4)], 0u, 0u, 0u };
@@ -308,7 +305,6 @@ __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, 
             }
         }
         tr.c16[u] = a;
-#endif
     }
 }
 
@@ -373,9 +369,6 @@ __device__ __forceinline__ void finish_trip(const StripParams &p, const uint8_t 
             }
             else {
                 u32x4 v;
-#if defined(GCN10_DIAG) && (GCN10_DIAG == 1 || GCN10_DIAG == 3)
-                v = tr.e16[u] ^ c16;          // timing-only build: no table lookup
-#else
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const uint32_t e = tr.e16[u][j];
@@ -390,7 +383,6 @@ __device__ __forceinline__ void finish_trip(const StripParams &p, const uint8_t 
                     }
                     v[j] = w;
                 }
-#endif
                 if (live)
                     store16<NT>(p.out[c * 9 + p.single_k] + tr.i0[u], v);
             }
@@ -562,10 +554,9 @@ __global__ __launch_bounds__(kThreads) void cn_strip_bytes(const StripParams p,
 // word with the generation they were launched for and use the bytes for the
 // whole tile when it matches.
 // ------------------------------------------------------------------------
-#ifndef GCN10_EXPAND_ROWS
-#define GCN10_EXPAND_ROWS 4     // 2: 20.0 us, 3: 17.3, 4: 16.5, 6: 17.6 for a 36000 x 1440 window (profiles/r02/prepare_tile_rows_per_thread.txt)
-#endif
-constexpr uint32_t kExpandRows = GCN10_EXPAND_ROWS;     // coarse rows per thread of expand_x_codes
+// coarse rows per thread of expand_x_codes: 2: 20.0 us, 3: 17.3, 4: 16.5, 6: 17.6 for a 36000 x 1440 window
+// (profiles/r02/prepare_tile_rows_per_thread.txt)
+constexpr uint32_t kExpandRows = 4;
 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void expand_x_codes(const uint8_t *coarse,
@@ -865,6 +856,20 @@ int use_device(gcn10_gpu_ctx *ctx)
 hipStream_t as_stream(gcn10_gpu_ctx *ctx, gcn10_stream_t s)
 {
     return s ? reinterpret_cast<hipStream_t>(s) : ctx->main_stream;
+}
+
+int grow_workspace(void **ws, size_t *cap, size_t need)
+{
+    if (need <= *cap)
+        return GCN10_OK;
+    HIP_TRY(hipDeviceSynchronize());            // the old workspace may still be in use
+    if (*ws)
+        HIP_TRY(hipFree(*ws));
+    *ws = nullptr;
+    *cap = 0;
+    HIP_TRY(hipMalloc(ws, need));
+    *cap = need;
+    return GCN10_OK;
 }
 
 }  // namespace gcn10
@@ -1571,12 +1576,8 @@ int gcn10_gpu_set_option(gcn10_gpu_ctx *ctx, const char *name, int value)
         ctx->compact_soil = fresh.compact_soil;
         ctx->deflate_wave_codes = fresh.deflate_wave_codes;
         ctx->arena_segment_align = fresh.arena_segment_align;
-        ctx->fused_diag = fresh.fused_diag;
         ctx->fused_parse = fresh.fused_parse;
         ctx->fused_emit = fresh.fused_emit;
-        ctx->fused_stats_stop = fresh.fused_stats_stop;
-        ctx->codes_stop = fresh.codes_stop;
-        ctx->inflate_diag = fresh.inflate_diag;
         ctx->event_sync_sleep_us = fresh.event_sync_sleep_us;
         ctx->single = fresh.single;
     }
@@ -1596,20 +1597,12 @@ int gcn10_gpu_set_option(gcn10_gpu_ctx *ctx, const char *name, int value)
         ctx->deflate_wave_codes = value;
     else if (!strcmp(name, "arena_segment_align") && value >= 16 && value <= 4096 && (value & (value - 1)) == 0)
         ctx->arena_segment_align = value;
-    else if (!strcmp(name, "codes_stop") && value >= 0 && value <= 8)
-        ctx->codes_stop = value;
-    else if (!strcmp(name, "fused_stats_stop") && value >= 0 && value <= 8)
-        ctx->fused_stats_stop = value;
     else if (!strcmp(name, "fused_emit") && (value == 0 || value == 1))
         ctx->fused_emit = value;
     else if (!strcmp(name, "fused_parse") && (value == 0 || value == 1))
         ctx->fused_parse = value;
-    else if (!strcmp(name, "fused_diag") && value >= 0 && value < 64)
-        ctx->fused_diag = value;
     else if (!strcmp(name, "event_sync_sleep_us") && value >= 0 && value <= 100000)
         ctx->event_sync_sleep_us = value;
-    else if (!strcmp(name, "inflate_diag") && value >= 0 && value < 8)
-        ctx->inflate_diag = value;
     else if (!strcmp(name, "prefetch") && (value == -1 || value == 0 || value == 1))
         ctx->prefetch = value;
     else if (!strcmp(name, "compact_soil") && (value == 0 || value == 1))

@@ -23,6 +23,9 @@ int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 int use_device(gcn10_gpu_ctx *ctx);
 hipStream_t as_stream(gcn10_gpu_ctx *ctx, gcn10_stream_t s);
+// Grows one of the context's device workspaces (*ws of *cap bytes) to at least `need` bytes; the old
+// contents are not kept.
+int grow_workspace(void **ws, size_t *cap, size_t need);
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -89,12 +92,7 @@ struct gcn10_gpu_ctx {
     int deflate_wave_codes = 1;     // pass B of the tile encoder: 1 = one wave per tile, 0 = one thread
     int fused_parse = 1;            // pass F-A of the fused encoder: 1 = one lane per 64-pixel segment (round 3), 0 = one lane per row
     int fused_emit = 1;             // pass F-C of the fused encoder: 1 = every wave packs its own quarter of the tokens (round 3), 0 = lock step
-    int codes_stop = 0;             // timing experiments only: pass B leaves after phase (value - 1)
-    int fused_stats_stop = 0;       // timing experiments only: pass F-A leaves after phase (value - 1)
-    int fused_diag = 0;             // timing experiments only (streams become invalid): 2 = pass F-C
-                                    // without its token trips (set-up cost alone)
     int event_sync_sleep_us = 0;    // gcn10_gpu_event_sync: 0 = hipEventSynchronize (spins); n > 0 = query, sleep n us, query ...
-    int inflate_diag = 0;           // timing experiments only (output invalid): 1 = copier idle, 2 = empty batches
     bool fused_ready = false;
     bool codes_ready = false;       // LDS attribute of the per-thread code construction set
     bool deflate_ready = false;     // LDS attributes of the tile encoder set on this device

@@ -47,7 +47,7 @@ namespace {
 // starts further back than the ring reaches is read from the tile's slot in HBM, where every byte
 // older than kFlush + 258 already is (copy_match).  16 KiB instead of 32 lets six streams share a CU
 // (a block's ~1300-1370 tiles then decode in one round of 1536 slots instead of 1024 + a ragged rest).
-// Round 3: 8 KiB (GCN10_INFLATE_WINDOW; flush unit = half of it, sub-batches of the copier a quarter).  A
+// Round 3: 8 KiB (flush unit = half of it, sub-batches of the copier a quarter).  A
 // workgroup then needs 15.6 KB of LDS instead of 23.6: five decoder workgroups per CU (a block's 1 296 streams)
 // take 78 KB and leave room for a 77 KB tile workgroup of the encoder's pass F-A beside them -- with 16 KiB rings
 // the decoder of block N+1 and the encoder of block N, which the round-3 pipeline runs side by side, took turns
@@ -57,10 +57,7 @@ namespace {
 // 0-9 % slower with the smaller ring (more matches read back from HBM: inflate_window_ab.txt, whose 16-block
 // pipeline rows were start-up dominated and showed nothing).
 // Invariant (copy_match): kFlush + kSubCap + 258 <= kWindow.
-#ifndef GCN10_INFLATE_WINDOW
-#define GCN10_INFLATE_WINDOW 8192
-#endif
-constexpr int kWindow = GCN10_INFLATE_WINDOW;
+constexpr int kWindow = 8192;
 constexpr int kWindowMask = kWindow - 1;
 constexpr int kFlush = kWindow / 2;
 constexpr int kBatch = 64;              // token words per hand-over from the decoder to the copier
@@ -1056,7 +1053,7 @@ constexpr uint32_t kSubCap = kWindow / 4;     // (declared near kWindow: kSubCap
 constexpr uint32_t kShortMatch = 64;    // stage B takes matches up to this length (sixteen dword steps + up to three bytes)
 
 __device__ __forceinline__ uint32_t copy_batch(Shared &sh, Output &o, const uint32_t *ring, uint32_t n,
-                                               const uint8_t *stream, int lane, uint32_t diag = 0)
+                                               const uint8_t *stream, int lane)
 {
     const uint32_t tk = (uint32_t)lane < n ? ring[lane] : 0u;
     const bool valid = (uint32_t)lane < n;
@@ -1238,8 +1235,6 @@ __device__ __forceinline__ uint32_t copy_batch(Shared &sh, Output &o, const uint
         }
         // C: the other matches, in order
         unsigned long long rest = __ballot(is_match && l > 0u && !early && !early_long && !far_short);
-        if (diag == 3u)
-            rest = 0ull;                // (timing: without the matches carried out one by one)
         const uint32_t pos0 = o.pos;
         while (rest != 0ull) {
             const int i = __builtin_ctzll(rest);
@@ -1251,12 +1246,8 @@ __device__ __forceinline__ uint32_t copy_batch(Shared &sh, Output &o, const uint
         }
         o.pos = pos0 + S < o.limit ? pos0 + S : o.limit;
         done += m;
-        if (o.pos - o.flushed >= (uint32_t)kFlush) {
-            if (diag == 4u)
-                o.flushed += kFlush;    // (timing: without the flush to HBM)
-            else
-                flush_half(sh, o, lane);
-        }
+        if (o.pos - o.flushed >= (uint32_t)kFlush)
+            flush_half(sh, o, lane);
     }
     return 0;
 }
@@ -1272,12 +1263,9 @@ __device__ __forceinline__ bool tile_in_place(const TileIn &t, uint32_t slot_byt
 
 // One workgroup of two wavefronts per stream: wave 0 decodes bits into tokens, wave 1 carries
 // the tokens out; they swap halves of a small token ring at a barrier every kBatch tokens.
-// diag (gcn10_gpu_set_option "inflate_diag", timing experiments only, output invalid; 3 = the copier skips the
-// matches it carries out one by one, 4 = it skips its flushes to HBM): 1 = the copier
-// carries nothing out, 2 = the decoder hands over empty batches after decoding them
 __global__ __launch_bounds__(128) void inflate_kernel(const uint8_t *comp, const TileIn *tiles, uint32_t n_tiles,
                                                       uint8_t *scratch, uint32_t slot_bytes, uint32_t *status,
-                                                      uint32_t diag, uint8_t *dst, unsigned long long dst_stride)
+                                                      uint8_t *dst, unsigned long long dst_stride)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     Shared &sh = *reinterpret_cast<Shared *>(smem);
@@ -1349,7 +1337,7 @@ __global__ __launch_bounds__(128) void inflate_kernel(const uint8_t *comp, const
             if (!announced) {
                 const uint32_t n = decode_batch(sh, d, sh.ring[cur], lane);
                 if (lane == 0)
-                    sh.count[cur] = diag == 2u ? 0u : n;
+                    sh.count[cur] = n;
                 if (d.state == (uint32_t)kDone) {
                     if (!d.err && reader_byte_pos(d.r) > d.in_len + 4u)
                         d.err = kErrInput;
@@ -1362,8 +1350,7 @@ __global__ __launch_bounds__(128) void inflate_kernel(const uint8_t *comp, const
             }
         }
         else if (it > 0 && c_err == 0) {
-            if (diag != 1u)
-                c_err = copy_batch(sh, o, sh.ring[cur ^ 1u], uniform(sh.count[cur ^ 1u]), comp + tin.in_off, lane, diag);
+            c_err = copy_batch(sh, o, sh.ring[cur ^ 1u], uniform(sh.count[cur ^ 1u]), comp + tin.in_off, lane);
         }
         __syncthreads();
         if (it >= uniform(sh.stop))
@@ -1489,22 +1476,16 @@ int gcn10_gpu_inflate_tiles(gcn10_gpu_ctx *ctx, const uint8_t *comp_dev, const g
         return fail(GCN10_E_INVAL, "gcn10_gpu_inflate_tiles: compressed bytes must be 16-byte aligned");
     const uint32_t slot = (chunk_bytes + 255u) & ~255u;
     const size_t need = (size_t)slot * (size_t)n_tiles;
-    if (need > ctx->inflate_ws_cap) {
-        HIP_TRY(hipDeviceSynchronize());        // the old workspace may still be in use
-        if (ctx->inflate_ws)
-            HIP_TRY(hipFree(ctx->inflate_ws));
-        ctx->inflate_ws = nullptr;
-        ctx->inflate_ws_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->inflate_ws, need));
-        ctx->inflate_ws_cap = need;
-    }
+    rc = gcn10::grow_workspace(&ctx->inflate_ws, &ctx->inflate_ws_cap, need);
+    if (rc)
+        return rc;
     static_assert(kWindow / 2 + kWindow / 4 + 258 <= kWindow && (kWindow & (kWindow - 1)) == 0 && kWindow >= 4096, "window invariant");
-    static_assert(sizeof(Shared) <= (kWindow == 8192 ? 16 : 26) * 1024, "ten (8 KiB ring) or six (16 KiB) streams per CU of 160 KiB LDS");
+    static_assert(sizeof(Shared) <= 16 * 1024, "ten streams per CU of 160 KiB LDS");
     hipStream_t s = as_stream(ctx, stream);
     uint8_t *scratch = reinterpret_cast<uint8_t *>(ctx->inflate_ws);
     hipLaunchKernelGGL(inflate_kernel, dim3((uint32_t)n_tiles), dim3(128), sizeof(Shared), s, comp_dev,
                        reinterpret_cast<const TileIn *>(tiles_dev), (uint32_t)n_tiles, scratch, slot, status_dev,
-                       (uint32_t)ctx->inflate_diag, dst_dev, (unsigned long long)dst_stride);
+                       dst_dev, (unsigned long long)dst_stride);
     // LZW tiles (GCN10_TILE_LZW) into their slots; every other tile leaves at once
     gcn10::launch_lzw_decode(comp_dev, tiles_dev, (uint32_t)n_tiles, scratch, slot, status_dev, s);
     hipLaunchKernelGGL(untile_kernel, dim3((uint32_t)n_tiles, 16), dim3(256), 0, s,

@@ -27,10 +27,9 @@ constexpr int kPlane16 = 256 * 16 + 16;     // one 16-byte row of the nine table
 constexpr int kLut16Bytes = kPlanes * kPlane16;
 constexpr int kMaxLevels = 8;               // a 256 x 256 full-resolution tile holds whole pixels of levels 1..8
 constexpr int kL1Tile = 128;                // level-1 pixels per workgroup side (= 256 full-resolution pixels)
-#ifndef GCN10_OVERVIEW_L1_ROWS
-#define GCN10_OVERVIEW_L1_ROWS 4     // per 36000² block: 1 row 9.5 ms, 4 rows 9.2, 32 rows 10.5 (COG output)
-#endif
-constexpr uint32_t kL1Rows = GCN10_OVERVIEW_L1_ROWS;   // level-1 rows per workgroup of the level-1 kernel
+// level-1 rows per workgroup of the level-1 kernel; per 36000² block: 1 row 9.5 ms, 4 rows 9.2, 32 rows 10.5
+// (COG output)
+constexpr uint32_t kL1Rows = 4;
 
 __device__ __forceinline__ uint8_t avg_of(uint32_t s, uint32_t n)
 {

@@ -28,10 +28,8 @@ constexpr uint32_t kChunk = kThreads * kPxPerLane;     // pixels of a row per wo
 constexpr int kBins = GCN10_PAIR_HIST_BINS;
 constexpr int kHistWords = GCN10_PAIR_HIST_SIZE;       // [bin][landcover]
 constexpr uint32_t kRowsPerItem = 4;                   // rows of a workgroup step: 4 loads in flight per lane
-#ifndef GCN10_STATS_GRID_PER_CU
-#define GCN10_STATS_GRID_PER_CU 4     // per 36000² block, patchy: 1 -> 1.55 ms, 2 -> 0.96, 4 -> 0.78, 8 -> 0.97
-#endif
-constexpr int kGridPerCu = GCN10_STATS_GRID_PER_CU;   // workgroups per CU at most
+// workgroups per CU at most; per 36000² block, patchy: 1 -> 1.55 ms, 2 -> 0.96, 4 -> 0.78, 8 -> 0.97
+constexpr int kGridPerCu = 4;
 
 // soil code byte (drained plane | undrained plane << 4) -> dense bin: d == u -> d (0..5); a dual class
 // (d = 4, u = 1..3) -> 5 + u (6..8).  Bins 9..15 stay empty.

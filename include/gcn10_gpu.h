@@ -39,7 +39,8 @@ extern "C" {
  *    the extents' pads (round 3).  A caller built against an older header must be rebuilt: check at start-up.
  *    Added within 3: the LZW encoder (gcn10_gpu_lzw_*), LZW tiles of gcn10_gpu_inflate_tiles (GCN10_TILE_LZW)
  *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*); the pair histogram
- *    of the band statistics (gcn10_gpu_pair_histogram*). */
+ *    of the band statistics (gcn10_gpu_pair_histogram*).
+ *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
 enum {
@@ -327,13 +328,11 @@ int gcn10_gpu_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int 
  * depend on them.  Names: "grid_blocks_per_cu" (1..64), "ilp16" (0 = by raster count | 1 | 2),
  * "ilp1" (1|2|4), "nontemporal" (0|1), "xcd_slabs" (0|1), "prefetch" (software pipeline of the strip kernels: -1 = default = on | 0 | 1), "compact_soil" (0|1: gcn10_gpu_prepare_tile writes,
  * and strips of 16-byte aligned rows read, the compact soil words; default 1), "deflate_wave_codes" (0|1: code
- * construction of the tile encoder by one thread or one wave per tile), "fused_diag" (timing
- * experiments on the fused encoder; nonzero values produce invalid streams), "defaults" (value
+ * construction of the tile encoder by one thread or one wave per tile), "defaults" (value
  * ignored: every knob back to its built-in default).
  * Round 3: "arena_segment_align" (16..4096, a power of two; default 4096: every raster's extent of a strip starts at a
  * multiple of it in the arena), "fused_parse" / "fused_emit" (0 = the round-2 forms of the fused encoder's first and
- * last pass, kept as cross-checks; 1 = default; the streams are the same bytes), "fused_stats_stop", "codes_stop",
- * "inflate_diag" (timing experiments, like "fused_diag"), "event_sync_sleep_us" (0 = default: gcn10_gpu_event_sync
+ * last pass, kept as cross-checks; 1 = default; the streams are the same bytes), "event_sync_sleep_us" (0 = default: gcn10_gpu_event_sync
  * is hipEventSynchronize, which spins; n > 0: it queries the event and sleeps n microseconds in between -- what a
  * host pipeline's waiting threads want). */
 int gcn10_gpu_set_option(gcn10_gpu_ctx *ctx, const char *name, int value);

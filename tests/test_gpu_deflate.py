@@ -199,6 +199,10 @@ def test_argument_errors(engine):
     assert gpu.lib().gcn10_gpu_deflate_arena_bound(256, 256, 1) == 65552 + 4096      # + the pad that brings a raster's extent to a multiple of 4096 (round 3)
     assert gpu.lib().gcn10_gpu_deflate_arena_bound(257, 256, 2) == 4 * 65552 + 2 * 4096
     assert gpu.lib().gcn10_gpu_deflate_arena_bound(0, 256, 1) == 0
+    # the timing-experiment switches of round 3 are gone: their names are unknown options now
+    for name in ("fused_diag", "fused_stats_stop", "codes_stop", "inflate_diag"):
+        with pytest.raises(gpu.Gcn10GpuError):
+            engine.set_option(name, 0)
 
 
 @pytest.mark.parametrize("kind", ["patches", "noisy", "skewed", "manyvals", "rows", "uniform"])

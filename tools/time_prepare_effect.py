@@ -34,18 +34,6 @@ variants = [("flat ilp2 pf bpc8", dict(ilp1=2, prefetch=1, grid_blocks_per_cu=8)
             ("flat ilp4 bpc16", dict(ilp1=4, prefetch=0, grid_blocks_per_cu=16)),
             ("flat ilp4 bpc16, prepare_tile before every launch", dict(ilp1=4, prefetch=0, grid_blocks_per_cu=16, PREP=1)),
             ("copy", None)]
-_unused = [("flat ilp2 pf bpc8", dict(tile_rows=0, ilp1=2, prefetch=1, grid_blocks_per_cu=8)),
-            ("flat ilp4 bpc16", dict(tile_rows=0, ilp1=4, prefetch=0, grid_blocks_per_cu=16)),
-            ("tile8 bpc8", dict(tile_rows=8, grid_blocks_per_cu=8)),
-            ("tile8 bpc12", dict(tile_rows=8, grid_blocks_per_cu=12)),
-            ("tile8 bpc16", dict(tile_rows=8, grid_blocks_per_cu=16)),
-            ("tile4 bpc8", dict(tile_rows=4, grid_blocks_per_cu=8)),
-            ("tile4 bpc16", dict(tile_rows=4, grid_blocks_per_cu=16)),
-            ("tile8 bpc16 no slabs", dict(tile_rows=8, grid_blocks_per_cu=16, xcd_slabs=0)),
-            ("tile4 bpc32", dict(tile_rows=4, grid_blocks_per_cu=32)),
-            ("tile8 bpc16 NO SOIL LOADS", dict(tile_rows=8, grid_blocks_per_cu=16, fused_diag=1)),
-            ("tile4 bpc16 NO SOIL LOADS", dict(tile_rows=4, grid_blocks_per_cu=16, fused_diag=1)),
-            ("copy", None)]
 res = {}
 for rnd in range(4):
     for where, buf in outs.items():

@@ -56,6 +56,7 @@ constexpr int kInvalidPlane = 5;
 // that equal landcover classes in different planes fall in different banks.
 constexpr int kPlane16 = 256 * 16 + 16;
 constexpr int kLut16Bytes = kPlanes * kPlane16;
+static_assert(kPlane16 == gcn10::kLut16Plane && kLut16Bytes == gcn10::kLut16Bytes, "gcn10_verify.hip reads this image");
 // LDS plane stride for the single-table byte LUT (+4 B pad: next bank).
 constexpr int kPlane1 = 256 + 4;
 constexpr int kLut1Bytes = kPlanes * kPlane1;

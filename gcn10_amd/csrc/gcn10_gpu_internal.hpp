@@ -49,6 +49,12 @@ void launch_lzw_decode(const uint8_t *comp_dev, const gcn10_inflate_tile *tiles_
 // compact index = drained * 6 + undrained
 constexpr int kClassCodes = 36;
 
+// device image of the all-tables lookup (gcn10_gpu_ctx::d_lut16, written by gcn10_gpu_set_tables): six soil planes
+// (0..4 and "invalid") of 256 rows of 16 bytes -- byte k = table k's value for (plane, landcover), 255 where there is
+// none -- and one row of padding per plane, so that equal classes of different planes fall in different LDS banks
+constexpr int kLut16Plane = 256 * 16 + 16;
+constexpr int kLut16Bytes = 6 * kLut16Plane;
+
 }  // namespace gcn10
 
 struct gcn10_gpu_ctx {

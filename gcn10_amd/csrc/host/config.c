@@ -137,6 +137,11 @@ int gcn10_parse_stats(const char *text, int *stats)
     return gcn10_parse_cog(text, stats);       /* the same "0" | "1" */
 }
 
+int gcn10_parse_verify(const char *text, int *verify)
+{
+    return gcn10_parse_cog(text, verify);      /* the same "0" | "1" */
+}
+
 int gcn10_parse_nodata(const char *text, int *nodata)
 {
     int v = 0;
@@ -261,6 +266,12 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
         else if (!strcmp(key, "nodata") && gcn10_parse_nodata(val, &cfg->nodata) != 0) {
             fclose(f);
             snprintf(err, errcap, "bad value for nodata: '%s' (none or an integer 0..255)", val);
+            gcn10_config_free(cfg);
+            return -3;
+        }
+        else if (!strcmp(key, "verify") && gcn10_parse_verify(val, &cfg->verify) != 0) {
+            fclose(f);
+            snprintf(err, errcap, "bad value for verify: '%s' (0 or 1)", val);
             gcn10_config_free(cfg);
             return -3;
         }

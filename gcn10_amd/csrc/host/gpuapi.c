@@ -91,6 +91,9 @@ static void load_once(void)
     /* the pair histogram of the band statistics: needed by stats=1 runs only, which check for it */
     *(void **)(&g_api.pair_histogram) = dlsym(h, "gcn10_gpu_pair_histogram");
     *(void **)(&g_api.pair_histogram_codes) = dlsym(h, "gcn10_gpu_pair_histogram_codes");
+    /* the raster verifier: needed by verify=1 runs only, which check for it */
+    *(void **)(&g_api.verify_strip) = dlsym(h, "gcn10_gpu_verify_strip");
+    *(void **)(&g_api.verify_buffers) = dlsym(h, "gcn10_gpu_verify_buffers");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -7,6 +7,12 @@
 
 struct gcn10_tiff;      /* tiff.c: one open TIFF file */
 struct gcn10_tiff *gcn10_tiff_open_reader(const char *path, char *err, size_t errcap);
+/* directory `level` of the file (0 = the raster, k = overview k of a COG); *why (optional): GCN10_TIFF_E_* of a NULL */
+enum { GCN10_TIFF_E_STRUCTURE = 1, GCN10_TIFF_E_MISSING = 2, GCN10_TIFF_E_NOT_BYTE = 3, GCN10_TIFF_E_NO_IFD = 4 };
+struct gcn10_tiff *gcn10_tiff_open_reader_ifd(const char *path, int level, int *why, char *err, size_t errcap);
+int gcn10_tiff_reader_samples(const struct gcn10_tiff *t);      /* SamplesPerPixel of the file */
+bool gcn10_tiff_reader_has_next(const struct gcn10_tiff *t);    /* another directory follows this one */
+int gcn10_tiff_check_chunks(const struct gcn10_tiff *t, uint64_t *index, uint64_t *off, uint64_t *count);
 void gcn10_tiff_close_reader(struct gcn10_tiff *t);
 void gcn10_tiff_reader_info(const struct gcn10_tiff *t, int *xsize, int *ysize, double gt[6]);
 const gcn10_georef *gcn10_tiff_reader_georef(const struct gcn10_tiff *t);
@@ -121,6 +127,12 @@ struct gcn10_gpu_api {
     int (*pair_histogram)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, unsigned long long *,
                           gcn10_stream_t);
     int (*pair_histogram_codes)(uint8_t *);
+    /* optional: NULL when the library has none (needed by verify=1 only) */
+    int (*verify_strip)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, unsigned, unsigned,
+                        const uint8_t *const[GCN10_N_RASTERS], size_t, int, gcn10_verify_count *, gcn10_stream_t);
+    int (*verify_buffers)(gcn10_gpu_ctx *, const uint8_t *const[GCN10_N_RASTERS], size_t,
+                          const uint8_t *const[GCN10_N_RASTERS], size_t, int, int, int, unsigned, gcn10_verify_count *,
+                          gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -5,7 +5,8 @@
  * plus -b as a synonym of -l (the reference's usage text advertises -b,
  * src/main.c:28, while its parser only takes -l, src/main.c:90), --gpus N, and --lookups /
  * --conditions to produce a subset of the 18 rasters (BASELINE config 3: "single lookup"), and --compress to
- * write LZW instead of DEFLATE GeoTIFFs, --stats / --nodata for GDAL band statistics and a NoData tag.
+ * write LZW instead of DEFLATE GeoTIFFs, --stats / --nodata for GDAL band statistics and a NoData tag, and --verify
+ * to check the rasters a run has written instead of writing them.
  * No mpirun: one process drives every GPU of the node.
  */
 #include "gcn10_host.h"
@@ -22,6 +23,7 @@ static void usage(FILE *fp)
             "  gcn10 --config <config.txt> [--blocks <blocks.txt>] [--overwrite] [--gpus <n>]\n"
             "        [--lookups <names>] [--conditions drained|undrained|both] [--compress deflate|lzw]\n"
             "        [--cog] [--overview-resampling nearest|average] [--stats] [--nodata none|<0..255>]\n"
+            "        [--verify]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -36,6 +38,9 @@ static void usage(FILE *fp)
             "  --overview-resampling <m>\tnearest or average: how the overviews are made (default: nearest)\n"
             "  --stats\t\tGDAL band statistics in every raster, counted on the GPU (config key stats=1)\n"
             "  --nodata <v>\t\tnone or 0..255: declare that NoData value, left out of the statistics (default: none)\n"
+            "  --verify\t\twrite nothing: decode the rasters that exist on the GPU and compare every pixel with\n"
+            "\t\t\tthe value computed now (config key verify=1); exit code 2 = a bad or missing raster,\n"
+            "\t\t\ttheir blocks listed in <log_dir>/verify_failed_blocks.txt; not with --overwrite\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -84,6 +89,8 @@ int main(int argc, char **argv)
             opt.stats = true;
         else if (!strcmp(argv[i], "--nodata") && i + 1 < argc)
             opt.nodata = argv[++i];
+        else if (!strcmp(argv[i], "--verify"))
+            opt.verify = true;
     }
     return gcn10_run(&opt);
 }

@@ -1030,6 +1030,7 @@ static void worker_teardown(struct worker *w)
     gcn10_input_teardown(w);
     if (w->ctx) {
         g->device_sync(w->ctx);
+        gcn10_verify_teardown(w);
         free_strip_buffers(w);
         for (int i = 0; i < w->run->nbuf; i++) {
             struct strip_buf *b = &w->buf[i];
@@ -1200,7 +1201,10 @@ static void *worker_main(void *arg)
         if (!in)
             break;
         t0 = now_seconds();
-        if (in->outcome == 0 && !atomic_load(&r->fatal) && encode_block(w, in) != 0)
+        if (r->verify && in->outcome == 1)
+            gcn10_verify_block_unreadable(w, in->block_id);
+        if (in->outcome == 0 && !atomic_load(&r->fatal) &&
+            (r->verify ? gcn10_verify_block(w, in) : encode_block(w, in)) != 0)
             atomic_store(&r->fatal, 1);     /* where the reference calls MPI_Abort */
         gcn10_abort_outputs(in);            /* files of a block that was not encoded after all (a no-op otherwise) */
         w->busy_seconds += now_seconds() - t0;
@@ -1249,22 +1253,29 @@ static void outer_from_env(int *rank, int *size)
  * library: every process leaves "<log_dir>/.done_<job>_<rank>" with its counts when its workers have
  * joined, and launcher rank 0 waits for all of them (GCN10_BARRIER_SECONDS, default 600) and logs the totals.
  * <job> tells launches apart (the launcher's job id from the environment, else the parent process id). */
-static void closing_barrier(struct run *r, gcn10_log *log0)
+static void job_tag(char job[96])
 {
     static const char *const job_vars[] = { "SLURM_JOB_ID", "OMPI_MCA_ess_base_jobid", "PMIX_NAMESPACE", "PMI_JOBID",
                                             "GCN10_JOB_ID" };
+
+    job[0] = '\0';
+    for (size_t i = 0; i < sizeof job_vars / sizeof job_vars[0] && !job[0]; i++)
+        if (getenv(job_vars[i]) && *getenv(job_vars[i]))
+            snprintf(job, 96, "%s", getenv(job_vars[i]));
+    if (!job[0])
+        snprintf(job, 96, "p%ld", (long)getppid());     /* the ranks of one mpirun share their parent */
+    for (char *c = job; *c; c++)
+        if (!((*c >= '0' && *c <= '9') || (*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z')))
+            *c = '_';
+}
+
+static void closing_barrier(struct run *r, gcn10_log *log0)
+{
     char job[96] = "", path[PATH_MAX], msg[512];
     const double limit = getenv("GCN10_BARRIER_SECONDS") ? atof(getenv("GCN10_BARRIER_SECONDS")) : 600.0;
     FILE *f;
 
-    for (size_t i = 0; i < sizeof job_vars / sizeof job_vars[0] && !job[0]; i++)
-        if (getenv(job_vars[i]) && *getenv(job_vars[i]))
-            snprintf(job, sizeof job, "%s", getenv(job_vars[i]));
-    if (!job[0])
-        snprintf(job, sizeof job, "p%ld", (long)getppid());     /* the ranks of one mpirun share their parent */
-    for (char *c = job; *c; c++)
-        if (!((*c >= '0' && *c <= '9') || (*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z')))
-            *c = '_';
+    job_tag(job);
     snprintf(path, sizeof path, "%s/.done_%s_%d", r->cfg.log_dir, job, r->outer_rank);
     f = fopen(path, "w");
     if (f) {
@@ -1306,6 +1317,100 @@ static void closing_barrier(struct run *r, gcn10_log *log0)
     }
 }
 
+static int by_int(const void *a, const void *b)
+{
+    const int x = *(const int *)a, y = *(const int *)b;
+
+    return x < y ? -1 : (x > y ? 1 : 0);
+}
+
+/* The end of a verify run: the closing console line and <log_dir>/verify_failed_blocks.txt, the ids of the blocks
+ * with a bad or missing file, ascending, one per line (what -l reads).  Under an MPI launcher every process leaves
+ * its counts and ids in "<log_dir>/.verify_<job>_<rank>" BEFORE the closing barrier, and launcher rank 0 merges
+ * them behind it, the way it prints the run's totals.  Returns the number of bad + missing files it knows of. */
+static void verify_leave_part(struct run *r)
+{
+    char job[96], path[PATH_MAX];
+    FILE *f;
+
+    job_tag(job);
+    snprintf(path, sizeof path, "%s/.verify_%s_%d", r->cfg.log_dir, job, r->outer_rank);
+    f = fopen(path, "w");
+    if (!f)
+        return;
+    fprintf(f, "%d %d %d %d %d %d\n", r->n_blocks, atomic_load(&r->verify_n_ok), atomic_load(&r->verify_n_bad),
+            atomic_load(&r->verify_n_missing), atomic_load(&r->verify_n_unchecked), r->verify_n_failed);
+    for (int i = 0; i < r->verify_n_failed; i++)
+        fprintf(f, "%d\n", r->verify_failed[i]);
+    fclose(f);
+}
+
+static int verify_summary(struct run *r, gcn10_log *log0)
+{
+    int blocks = r->n_blocks, ok = atomic_load(&r->verify_n_ok), bad = atomic_load(&r->verify_n_bad);
+    int missing = atomic_load(&r->verify_n_missing), unchecked = atomic_load(&r->verify_n_unchecked);
+    int *ids = r->verify_failed, n_ids = r->verify_n_failed;
+    const int mine = bad + missing;
+    char path[PATH_MAX], msg[PATH_MAX + 64];
+    FILE *f;
+
+    if (r->outer_size > 1) {
+        char job[96];
+
+        if (r->outer_rank != 0)
+            return mine;
+        job_tag(job);
+        for (int p = 1; p < r->outer_size; p++) {
+            int b, o, x, m, u, n;
+
+            snprintf(path, sizeof path, "%s/.verify_%s_%d", r->cfg.log_dir, job, p);
+            f = fopen(path, "r");
+            if (!f)
+                continue;               /* (the barrier has said so: "some processes did not report in time") */
+            if (fscanf(f, "%d %d %d %d %d %d", &b, &o, &x, &m, &u, &n) == 6 && n >= 0) {
+                int *g = realloc(ids == r->verify_failed ? NULL : ids, (size_t)(n_ids + n + 1) * sizeof *g);
+
+                if (g) {
+                    if (ids == r->verify_failed && n_ids > 0)
+                        memcpy(g, r->verify_failed, (size_t)n_ids * sizeof *g);
+                    ids = g;
+                    for (int i = 0; i < n && fscanf(f, "%d", &ids[n_ids]) == 1; i++)
+                        n_ids++;
+                }
+                blocks += b;
+                ok += o;
+                bad += x;
+                missing += m;
+                unchecked += u;
+            }
+            fclose(f);
+            unlink(path);
+        }
+        snprintf(path, sizeof path, "%s/.verify_%s_0", r->cfg.log_dir, job);
+        unlink(path);
+    }
+    if (n_ids > 0)
+        qsort(ids, (size_t)n_ids, sizeof *ids, by_int);
+    snprintf(path, sizeof path, "%s/verify_failed_blocks.txt", r->cfg.log_dir);
+    f = fopen(path, "w");
+    if (f) {
+        for (int i = 0; i < n_ids; i++)
+            if (i == 0 || ids[i] != ids[i - 1])
+                fprintf(f, "%d\n", ids[i]);
+        fclose(f);
+    }
+    else {
+        snprintf(msg, sizeof msg, "cannot write %s", path);
+        gcn10_log_message(log0, "ERROR", msg, true);
+    }
+    snprintf(msg, sizeof msg, "verify: %d blocks, %d files verified, %d bad, %d missing, %d overview levels not checked",
+             blocks, ok, bad, missing, unchecked);
+    gcn10_log_message(log0, bad + missing ? "ERROR" : "INFO", msg, true);
+    if (ids != r->verify_failed)
+        free(ids);
+    return bad + missing > mine ? bad + missing : mine;
+}
+
 struct row_error_ctx {
     gcn10_log *log;
 };
@@ -1323,7 +1428,7 @@ int gcn10_run(const gcn10_run_options *opt)
     char err[2048] = "";
     char msg[8192];
     gcn10_log *log0 = NULL;
-    int exit_code = 1, n_dev, failed_k = -1, rc;
+    int exit_code = 1, n_dev, failed_k = -1, rc, verify_found = 0;
     const char *sink = getenv("GCN10_SINK");
     double t_start = now_seconds();
 
@@ -1380,6 +1485,15 @@ int gcn10_run(const gcn10_run_options *opt)
         r->cfg.stats = 1;
     if (opt->nodata && gcn10_parse_nodata(opt->nodata, &r->cfg.nodata) != 0) {
         fprintf(stderr, "[rank 0] bad value for nodata: '%s' (none or an integer 0..255)\n", opt->nodata);
+        gcn10_config_free(&r->cfg);
+        free(r);
+        return 1;
+    }
+    if (opt->verify)
+        r->cfg.verify = 1;
+    r->verify = r->cfg.verify != 0;
+    if (r->verify && opt->overwrite) {
+        fprintf(stderr, "[rank 0] --verify writes nothing and cannot be combined with --overwrite\n");
         gcn10_config_free(&r->cfg);
         free(r);
         return 1;
@@ -1445,6 +1559,10 @@ int gcn10_run(const gcn10_run_options *opt)
     if (r->stats && (!r->gpu->pair_histogram || !r->gpu->pair_histogram_codes ||
                      r->gpu->pair_histogram_codes(r->hist_codes) != GCN10_PAIR_HIST_BINS)) {
         fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_pair_histogram (needed by stats=1)\n", gcn10_gpu_library_path());
+        goto done;
+    }
+    if (r->verify && (!r->gpu->verify_strip || !r->gpu->verify_buffers)) {
+        fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_verify_strip (needed by verify=1)\n", gcn10_gpu_library_path());
         goto done;
     }
     if (r->lzw && (!r->gpu->lzw_strip || !r->gpu->lzw_arena_bound)) {
@@ -1625,6 +1743,13 @@ int gcn10_run(const gcn10_run_options *opt)
         }
     }
 
+    if (r->verify) {
+        pthread_mutex_init(&r->verify_mu, NULL);
+        r->verify_failed = malloc((size_t)(r->n_blocks > 0 ? r->n_blocks : 1) * sizeof *r->verify_failed);
+        r->verify_failed_cap = r->verify_failed ? r->n_blocks : 0;
+        gcn10_log_message(log0, "INFO", "verify: nothing is written; the rasters that exist are compared with the "
+                          "values computed now", true);
+    }
     atomic_store(&r->next_block, 0);
     atomic_store(&r->fatal, 0);
     for (int i = 0; i < r->n_workers; i++)
@@ -1639,8 +1764,12 @@ int gcn10_run(const gcn10_run_options *opt)
 
     snprintf(msg, sizeof msg, "processed %d blocks on %d ranks", r->n_blocks, r->n_workers);  /* src/main.c:191 */
     gcn10_log_message(log0, "INFO", msg, true);
+    if (r->verify && r->outer_size > 1)
+        verify_leave_part(r);
     if (r->outer_size > 1)
         closing_barrier(r, log0);           /* MPI_Barrier + rank 0's summary, src/main.c:187-194 */
+    if (r->verify)
+        verify_found = verify_summary(r, log0);
     {
         int done_blocks = 0;
         double busy = 0, rd = 0, gw = 0, sw = 0, so = 0, cr = 0, fi = 0, dv = 0, steady = 0, iw = 0, ib = 0;
@@ -1795,7 +1924,7 @@ int gcn10_run(const gcn10_run_options *opt)
             gcn10_log_message(log0, "INFO", msg, false);
         }
     }
-    exit_code = atomic_load(&r->fatal) ? 1 : 0;
+    exit_code = atomic_load(&r->fatal) ? 1 : (verify_found > 0 ? 2 : 0);
 
 done:
     gcn10_pool_destroy(r->pool);
@@ -1805,6 +1934,7 @@ done:
     }
     gcn10_log_close(log0);                              /* finalize_logging, src/main.c:197 */
     free(r->workers);
+    free(r->verify_failed);
     free(r->block_ids);
     gcn10_blocks_free(&r->blocks);
     gcn10_config_free(&r->cfg);

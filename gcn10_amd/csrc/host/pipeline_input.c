@@ -442,6 +442,11 @@ static int fill_block(struct worker *w, struct block_in *in, int block_id)
     /* the block's 18 files, while the copies and the decoder run (the reference creates each raster's file
      * inside save_raster, after computing it: src/raster.c:204; an existing raster of that name is untouched
      * until this one is complete either way: files are written as <name>.part) */
+    if (r->verify) {
+        memset(in->tifs, 0, sizeof in->tifs);       /* a verify run writes nothing */
+        in->tifs_ok = false;
+        return 0;
+    }
     rc = gcn10_create_outputs(w, in);
     if (rc < 0)
         return -1;

@@ -15,6 +15,7 @@
 enum { TILE = 256, MAX_NBUF = 8, DEFAULT_NBUF = 4, DEFAULT_STRIP_ROWS = 2304, MAX_STRIP_ROWS = 4096 };
 
 struct run;
+struct gcn10_verify_state;
 
 /* one rotating set of strip buffers */
 struct strip_buf {
@@ -131,6 +132,7 @@ struct worker {
     /* band statistics (stats=1): the block's pair histogram on the device, and its copy */
     unsigned long long *d_hist, *h_hist;    /* GCN10_PAIR_HIST_SIZE counters; h_hist pinned */
     size_t d_hist_cap, h_hist_cap;
+    struct gcn10_verify_state *verify;      /* verify=1: the worker's decode buffers and counters (verify.c) */
     long n_win_gpu, n_win_gpu_lzw, n_win_host;  /* landcover windows through the GPU decoder (of them with LZW chunks),
                                                    through the host reader */
 };
@@ -176,6 +178,12 @@ struct run {
     unsigned cond_mask, table_mask;         /* the rasters this run produces ("conditions" / "lookups") */
     int n_sel;                              /* how many: popcount(cond_mask) * popcount(table_mask) */
     int sel[GCN10_N_RASTERS];               /* their raster indices cond*9 + hc*3 + arc, ascending */
+    /* verify=1: nothing is written; what the workers found */
+    bool verify;
+    atomic_int verify_n_ok, verify_n_bad, verify_n_missing, verify_n_unchecked;    /* files; overview levels */
+    pthread_mutex_t verify_mu;
+    int *verify_failed;                     /* ids of the blocks with a bad or missing file, in the order found */
+    int verify_n_failed, verify_failed_cap;
 };
 
 double gcn10_now_seconds(void);
@@ -196,6 +204,11 @@ int gcn10_ensure_pinned_on(struct worker *w, gcn10_gpu_ctx *ctx, void **p, size_
  * (logged like save_raster logs, the block is given up), -1 = an output directory cannot be made (fatal, src/cn.c:250) */
 int gcn10_create_outputs(struct worker *w, struct block_in *in);
 void gcn10_abort_outputs(struct block_in *in);
+/* verify.c: a staged block's files against the values computed now (0, or -1 for errors that end the run); a block
+ * whose inputs could not be staged; the worker's verify buffers */
+int gcn10_verify_block(struct worker *w, struct block_in *in);
+void gcn10_verify_block_unreadable(struct worker *w, int block_id);
+void gcn10_verify_teardown(struct worker *w);
 int gcn10_input_setup(struct worker *w);
 void gcn10_input_teardown(struct worker *w);
 int gcn10_input_start(struct worker *w);

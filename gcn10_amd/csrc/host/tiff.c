@@ -48,6 +48,8 @@ struct gcn10_tiff {
     uint64_t n_chunks;
     uint64_t file_size;
     uint64_t id_dev, id_ino;    /* which file (the chunk cache is shared by every open handle of it) */
+    uint64_t next_ifd;          /* offset of the directory behind the one that was read, 0 = none */
+    uint16_t spp_file;          /* SamplesPerPixel as the file says (spp is 1 for band-sequential files) */
     double gt[6];
     gcn10_georef georef;
 };
@@ -178,6 +180,13 @@ void gcn10_tiff_close_reader(struct gcn10_tiff *t)
 
 struct gcn10_tiff *gcn10_tiff_open_reader(const char *path, char *err, size_t errcap)
 {
+    return gcn10_tiff_open_reader_ifd(path, 0, NULL, err, errcap);
+}
+
+/* directory `level` of the file's chain (0 = the first: the raster itself; k = the k-th one behind it: overview k
+ * of a Cloud Optimized GeoTIFF).  *why (optional) says what kind of failure a NULL is: GCN10_TIFF_E_* */
+struct gcn10_tiff *gcn10_tiff_open_reader_ifd(const char *path, int level, int *why, char *err, size_t errcap)
+{
     struct gcn10_tiff *t = calloc(1, sizeof *t);
     unsigned char hdr[16], *dir = NULL;
     uint64_t ifd, nent;
@@ -191,8 +200,12 @@ struct gcn10_tiff *gcn10_tiff_open_reader(const char *path, char *err, size_t er
         snprintf(err, errcap, "out of memory for raster %s", path);
         return NULL;
     }
+    if (why)
+        *why = GCN10_TIFF_E_STRUCTURE;
     t->fd = open(path, O_RDONLY);
     if (t->fd < 0 || pread_all(t->fd, hdr, 8, 0) != 0) {
+        if (why && t->fd < 0 && errno == ENOENT)
+            *why = GCN10_TIFF_E_MISSING;
         snprintf(err, errcap, "gdal open failed: %s", path);        /* src/raster.c:121 */
         goto fail;
     }
@@ -229,8 +242,8 @@ struct gcn10_tiff *gcn10_tiff_open_reader(const char *path, char *err, size_t er
             goto badfile;
         }
     }
-    {
-        unsigned char cnt[8];
+    for (int k = 0;; k++) {
+        unsigned char cnt[8], next[8];
         int cn = t->big ? 8 : 2;
 
         if (pread_all(t->fd, cnt, (size_t)cn, ifd) != 0)
@@ -239,9 +252,23 @@ struct gcn10_tiff *gcn10_tiff_open_reader(const char *path, char *err, size_t er
         esz = t->big ? 20 : 12;
         if (nent == 0 || nent > 4096)
             goto badfile;
+        /* the chain's next directory (0: this is the last one); a file that ends right behind its entries has none */
+        t->next_ifd = pread_all(t->fd, next, t->big ? 8 : 4, ifd + (uint64_t)cn + nent * esz) == 0
+                          ? rd(next, t->big ? 8 : 4, t->swap) : 0;
+        if (k < level) {
+            if (t->next_ifd == 0 || k >= 64) {
+                if (why)
+                    *why = GCN10_TIFF_E_NO_IFD;
+                snprintf(err, errcap, "gdal open failed: %s has no directory %d", path, level);
+                goto fail;
+            }
+            ifd = t->next_ifd;
+            continue;
+        }
         dir = malloc((size_t)nent * esz);
         if (!dir || pread_all(t->fd, dir, (size_t)nent * esz, ifd + (uint64_t)cn) != 0)
             goto badfile;
+        break;
     }
     t->bps = 1;
     t->spp = 1;
@@ -339,7 +366,10 @@ struct gcn10_tiff *gcn10_tiff_open_reader(const char *path, char *err, size_t er
 
     if (!t->width || !t->height || !have_off || !have_cnt)
         goto badfile;
+    t->spp_file = t->spp;
     if (t->bps != 8) {
+        if (why)
+            *why = GCN10_TIFF_E_NOT_BYTE;
         snprintf(err, errcap, "gdal open failed: %s (%u bits per sample; only Byte rasters are supported)",
                  path, t->bps);
         goto fail;
@@ -427,6 +457,31 @@ void gcn10_tiff_reader_info(const struct gcn10_tiff *t, int *xsize, int *ysize, 
 const gcn10_georef *gcn10_tiff_reader_georef(const struct gcn10_tiff *t)
 {
     return &t->georef;
+}
+
+int gcn10_tiff_reader_samples(const struct gcn10_tiff *t)
+{
+    return t->spp_file;
+}
+
+bool gcn10_tiff_reader_has_next(const struct gcn10_tiff *t)
+{
+    return t->next_ifd != 0;
+}
+
+/* The first chunk of the raster that cannot hold pixels: no bytes at all (a sparse chunk, which reads as zeros), or
+ * bytes that reach beyond the end of the file.  0 = every chunk is in the file; 1 = *index / *off / *count name one. */
+int gcn10_tiff_check_chunks(const struct gcn10_tiff *t, uint64_t *index, uint64_t *off, uint64_t *count)
+{
+    for (uint64_t i = 0; i < (uint64_t)t->across * t->down; i++) {
+        if (t->counts[i] != 0 && t->offsets[i] <= t->file_size && t->counts[i] <= t->file_size - t->offsets[i])
+            continue;
+        *index = i;
+        *off = t->offsets[i];
+        *count = t->counts[i];
+        return 1;
+    }
+    return 0;
 }
 
 /* TIFF LZW (TIFF 6.0 section 13): MSB-first codes of 9..12 bits, ClearCode 256,

@@ -1,0 +1,856 @@
+/* verify.c -- the verification mode of the run (config key verify=1, --verify; DESIGN.md "Verification").
+ *
+ * Nothing is written into the output directories.  For a block whose landcover and soil the input side has staged
+ * exactly as for a write run, every selected raster file cn_rasters_<cond>/cn_<hc>_<arc>_<id>.tif is
+ *   1. checked for its structure on the host (gcn10_verify_structure: the file, the TIFF, one band of Byte, the
+ *      window's size and geotransform, every chunk inside the file, the overview directories' sizes),
+ *   2. read strip by strip AS IT LIES IN THE FILE: the chunks that cover the strip are planned (gcn10_tiff_plan_window
+ *      with DEFLATE | RAW | LZW), read into pinned memory by the I/O pool, copied to the device and decoded there by
+ *      gcn10_gpu_inflate_tiles -- the chunks of all 18 files in one call -- into 18 strip buffers,
+ *   3. compared there with what the program computes now: gcn10_gpu_verify_strip over the strip's landcover and the
+ *      prepared soil (the expected rasters are never made); overview levels the same way, a nearest level as a block
+ *      of its own, an average level against gcn10_gpu_overview_average's buffers (gcn10_gpu_verify_buffers).
+ * A window the planner leaves to the host reader (PackBits, very wide raw strips) is decoded by it and uploaded.
+ * The per-chunk status words of the decoder are findings: a stream that does not decode makes its file unreadable,
+ * it never faults the device.
+ */
+#include "pipeline_internal.h"
+
+#include <errno.h>
+#include <limits.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+
+#define wlog gcn10_wlog
+
+enum { V_LEVELS = GCN10_COG_MAX_LEVELS + 1, V_STAGE = 2 };
+enum { V_STAGE_BYTES = 64 << 20 };
+/* device memory of the 18 decode buffers of a strip: bounds the strip height together with strip_rows */
+#define V_GOT_BYTES ((size_t)1 << 30)
+
+static const char *const finding_names[] = { "ok", "missing", "not a TIFF", "not 1 band Byte", "size", "geotransform",
+                                             "chunk", "overview size", "decode", "pixels" };
+
+/* ------------------------------------------------------------------------ */
+/* structure of one file                                                     */
+/* ------------------------------------------------------------------------ */
+
+static int level_dim(int n, int k)
+{
+    return (int)(((int64_t)n + ((int64_t)1 << k) - 1) >> k);
+}
+
+/* The checks of gcn10_verify_structure; the readers of the raster and of its overview directories stay open in
+ * lv[0 .. *n_levels] when the finding is GCN10_VERIFY_OK (closed otherwise). */
+static int open_checked(const char *path, int W, int H, const double gt[6], struct gcn10_tiff *lv[V_LEVELS],
+                        int *n_levels, int *n_beyond, char *reason, size_t cap)
+{
+    char err[1024] = "";
+    int why = 0, finding = GCN10_VERIFY_OK, fw, fh, n = 0;
+    double fgt[6];
+    uint64_t idx, off, cnt;
+
+    memset(lv, 0, V_LEVELS * sizeof lv[0]);
+    *n_levels = 0;
+    *n_beyond = 0;
+    lv[0] = gcn10_tiff_open_reader_ifd(path, 0, &why, err, sizeof err);
+    if (!lv[0]) {
+        if (why == GCN10_TIFF_E_MISSING) {
+            snprintf(reason, cap, "no such file");
+            return GCN10_VERIFY_MISSING;
+        }
+        snprintf(reason, cap, "%s", err);
+        return why == GCN10_TIFF_E_NOT_BYTE ? GCN10_VERIFY_NOT_BYTE : GCN10_VERIFY_NOT_TIFF;
+    }
+    gcn10_tiff_reader_info(lv[0], &fw, &fh, fgt);
+    if (gcn10_tiff_reader_samples(lv[0]) != 1) {
+        snprintf(reason, cap, "%d samples per pixel, not 1 band of Byte", gcn10_tiff_reader_samples(lv[0]));
+        finding = GCN10_VERIFY_NOT_BYTE;
+    }
+    else if (fw != W || fh != H) {
+        snprintf(reason, cap, "size %dx%d, the block's window is %dx%d", fw, fh, W, H);
+        finding = GCN10_VERIFY_SIZE;
+    }
+    else if (memcmp(fgt, gt, sizeof fgt) != 0) {
+        /* the six doubles the writer stores come back from the reader bit for bit (origin = tiepoint, pixel
+         * size = scale), so anything but equality is another georeference */
+        snprintf(reason, cap, "geotransform {%.17g, %.17g, %.17g, %.17g, %.17g, %.17g}, the window's is "
+                 "{%.17g, %.17g, %.17g, %.17g, %.17g, %.17g}", fgt[0], fgt[1], fgt[2], fgt[3], fgt[4], fgt[5],
+                 gt[0], gt[1], gt[2], gt[3], gt[4], gt[5]);
+        finding = GCN10_VERIFY_GEOTRANSFORM;
+    }
+    else if (gcn10_tiff_check_chunks(lv[0], &idx, &off, &cnt) != 0) {
+        snprintf(reason, cap, "chunk %llu: offset %llu + %llu bytes %s", (unsigned long long)idx,
+                 (unsigned long long)off, (unsigned long long)cnt,
+                 cnt == 0 ? "(no bytes where pixels are expected)" : "lies beyond the end of the file");
+        finding = GCN10_VERIFY_CHUNK;
+    }
+    /* the overview directories behind it: each must be the halving rule's size and lie inside the file */
+    while (finding == GCN10_VERIFY_OK && gcn10_tiff_reader_has_next(lv[n])) {
+        struct gcn10_tiff *t;
+
+        if (n + 1 >= V_LEVELS) {
+            (*n_beyond)++;              /* more levels than the program makes: counted as not checked */
+            break;
+        }
+        t = gcn10_tiff_open_reader_ifd(path, n + 1, &why, err, sizeof err);
+        if (!t) {
+            snprintf(reason, cap, "overview %d: %s", n + 1, err);
+            finding = why == GCN10_TIFF_E_NOT_BYTE ? GCN10_VERIFY_NOT_BYTE : GCN10_VERIFY_NOT_TIFF;
+            break;
+        }
+        lv[++n] = t;
+        gcn10_tiff_reader_info(t, &fw, &fh, fgt);
+        if (gcn10_tiff_reader_samples(t) != 1) {
+            snprintf(reason, cap, "overview %d: %d samples per pixel, not 1 band of Byte", n, gcn10_tiff_reader_samples(t));
+            finding = GCN10_VERIFY_NOT_BYTE;
+        }
+        else if (fw != level_dim(W, n) || fh != level_dim(H, n)) {
+            snprintf(reason, cap, "overview %d: size %dx%d, level %d of %dx%d is %dx%d", n, fw, fh, n, W, H,
+                     level_dim(W, n), level_dim(H, n));
+            finding = GCN10_VERIFY_OVERVIEW;
+        }
+        else if (gcn10_tiff_check_chunks(t, &idx, &off, &cnt) != 0) {
+            snprintf(reason, cap, "overview %d, chunk %llu: offset %llu + %llu bytes %s", n, (unsigned long long)idx,
+                     (unsigned long long)off, (unsigned long long)cnt,
+                     cnt == 0 ? "(no bytes where pixels are expected)" : "lies beyond the end of the file");
+            finding = GCN10_VERIFY_CHUNK;
+        }
+    }
+    if (finding != GCN10_VERIFY_OK) {
+        for (int k = 0; k < V_LEVELS; k++) {
+            gcn10_tiff_close_reader(lv[k]);
+            lv[k] = NULL;
+        }
+        return finding;
+    }
+    *n_levels = n;
+    return GCN10_VERIFY_OK;
+}
+
+int gcn10_verify_structure(const char *path, int xsize, int ysize, const double gt[6], int *n_levels, char *reason,
+                           size_t reason_cap)
+{
+    struct gcn10_tiff *lv[V_LEVELS];
+    char text[1024] = "";
+    int n = 0, beyond = 0;
+    const int finding = open_checked(path, xsize, ysize, gt, lv, &n, &beyond, text, sizeof text);
+
+    for (int k = 0; k < V_LEVELS; k++)
+        gcn10_tiff_close_reader(lv[k]);
+    if (n_levels)
+        *n_levels = n + beyond;
+    if (reason && reason_cap)
+        snprintf(reason, reason_cap, "%s", text);
+    return finding;
+}
+
+/* ------------------------------------------------------------------------ */
+/* the worker's verify state                                                 */
+/* ------------------------------------------------------------------------ */
+
+struct vfile {
+    int k;                                  /* raster index cond*9 + hc*3 + arc */
+    struct gcn10_tiff *lv[V_LEVELS];
+    int n_levels;
+    int finding;                            /* GCN10_VERIFY_* */
+    char reason[1200];
+};
+
+struct gcn10_verify_state {
+    uint8_t *d_got;                         /* n_sel strip buffers */
+    size_t got_cap;
+    uint8_t *d_comp;
+    size_t comp_cap;
+    uint8_t *h_stage[V_STAGE];              /* pinned */
+    gcn10_event_t ev_stage[V_STAGE];
+    bool stage_busy[V_STAGE];
+    gcn10_inflate_tile *h_jobs, *d_jobs;    /* h_jobs pinned */
+    uint32_t *h_status, *d_status;          /* h_status pinned */
+    struct gcn10_chunk_ref *chunks;         /* the strip's chunks of all files, and whose they are */
+    int *owner;
+    size_t jobs_cap;
+    gcn10_verify_count *d_counts, *h_counts;    /* [V_LEVELS][GCN10_N_RASTERS]; h_counts pinned */
+    uint8_t *h_rows;                        /* a host-decoded strip on its way up */
+    size_t h_rows_cap;
+};
+
+#define GPU_V(w, call)                                                         \
+    do {                                                                       \
+        if ((call) != 0) {                                                     \
+            wlog((w), "ERROR", true, "gpu: %s", (w)->run->gpu->last_error());  \
+            return -1;                                                         \
+        }                                                                      \
+    } while (0)
+
+static int state_setup(struct worker *w)
+{
+    const struct gcn10_gpu_api *g = w->run->gpu;
+    struct gcn10_verify_state *v;
+    const size_t n_counts = (size_t)V_LEVELS * GCN10_N_RASTERS;
+
+    if (w->verify)
+        return 0;
+    v = calloc(1, sizeof *v);
+    if (!v) {
+        wlog(w, "ERROR", true, "malloc failed for the verifier");
+        return -1;
+    }
+    w->verify = v;
+    for (int i = 0; i < V_STAGE; i++) {
+        GPU_V(w, g->host_alloc(w->ctx, V_STAGE_BYTES, (void **)&v->h_stage[i]));
+        GPU_V(w, g->event_create(w->ctx, &v->ev_stage[i]));
+        atomic_fetch_add(&w->run->pinned_bytes, (long long)V_STAGE_BYTES);
+    }
+    GPU_V(w, g->malloc(w->ctx, n_counts * sizeof *v->d_counts, (void **)&v->d_counts));
+    GPU_V(w, g->host_alloc(w->ctx, n_counts * sizeof *v->h_counts, (void **)&v->h_counts));
+    return 0;
+}
+
+void gcn10_verify_teardown(struct worker *w)
+{
+    const struct gcn10_gpu_api *g = w->run->gpu;
+    struct gcn10_verify_state *v = w->verify;
+
+    if (!v)
+        return;
+    if (v->d_got) g->free(w->ctx, v->d_got);
+    if (v->d_comp) g->free(w->ctx, v->d_comp);
+    for (int i = 0; i < V_STAGE; i++) {
+        if (v->h_stage[i]) g->host_free(w->ctx, v->h_stage[i]);
+        if (v->ev_stage[i]) g->event_destroy(w->ctx, v->ev_stage[i]);
+    }
+    if (v->h_jobs) g->host_free(w->ctx, v->h_jobs);
+    if (v->d_jobs) g->free(w->ctx, v->d_jobs);
+    if (v->h_status) g->host_free(w->ctx, v->h_status);
+    if (v->d_status) g->free(w->ctx, v->d_status);
+    if (v->d_counts) g->free(w->ctx, v->d_counts);
+    if (v->h_counts) g->host_free(w->ctx, v->h_counts);
+    free(v->chunks);
+    free(v->owner);
+    free(v->h_rows);
+    free(v);
+    w->verify = NULL;
+}
+
+/* room for n chunks in the strip's lists; the first `keep` entries (the files planned so far) stay */
+static int jobs_ensure(struct worker *w, size_t n, size_t keep)
+{
+    const struct gcn10_gpu_api *g = w->run->gpu;
+    struct gcn10_verify_state *v = w->verify;
+    struct gcn10_chunk_ref *c;
+    gcn10_inflate_tile *h_jobs = NULL;
+    uint32_t *h_status = NULL;
+    int *o;
+
+    if (n <= v->jobs_cap)
+        return 0;
+    n = n * 2 > 4096 ? n * 2 : 4096;
+    /* the caller appends while it plans: the host lists are kept, the device-side arrays are rewritten per strip */
+    c = realloc(v->chunks, n * sizeof *c);
+    if (c)
+        v->chunks = c;
+    o = realloc(v->owner, n * sizeof *o);
+    if (o)
+        v->owner = o;
+    if (!c || !o) {
+        wlog(w, "ERROR", true, "malloc failed for the verifier's read plan");
+        return -1;
+    }
+    GPU_V(w, g->stream_sync(w->ctx, w->s_kernel));
+    GPU_V(w, g->host_alloc(w->ctx, n * sizeof *h_jobs, (void **)&h_jobs));
+    if (g->host_alloc(w->ctx, n * 4, (void **)&h_status) != 0) {
+        wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+        g->host_free(w->ctx, h_jobs);
+        return -1;
+    }
+    if (keep > 0) {
+        memcpy(h_jobs, v->h_jobs, keep * sizeof *h_jobs);
+        memcpy(h_status, v->h_status, keep * 4);
+    }
+    if (v->h_jobs) g->host_free(w->ctx, v->h_jobs);
+    if (v->h_status) g->host_free(w->ctx, v->h_status);
+    if (v->d_jobs) g->free(w->ctx, v->d_jobs);
+    if (v->d_status) g->free(w->ctx, v->d_status);
+    v->h_jobs = h_jobs;
+    v->h_status = h_status;
+    v->d_jobs = NULL;
+    v->d_status = NULL;
+    v->jobs_cap = 0;
+    GPU_V(w, g->malloc(w->ctx, n * sizeof *v->d_jobs, (void **)&v->d_jobs));
+    GPU_V(w, g->malloc(w->ctx, n * 4, (void **)&v->d_status));
+    v->jobs_cap = n;
+    return 0;
+}
+
+/* ------------------------------------------------------------------------ */
+/* chunks -> pinned staging -> device                                        */
+/* ------------------------------------------------------------------------ */
+
+struct read_job {
+    const struct gcn10_chunk_ref *chunks;
+    const gcn10_inflate_tile *jobs;
+    size_t n;
+    uint8_t *dst;
+    uint64_t base;
+    pthread_mutex_t *mu;
+    pthread_cond_t *cv;
+    int *pending;
+    int *bad;                               /* per chunk: the bytes could not be read */
+};
+
+static void read_job_run(void *arg)
+{
+    struct read_job *j = arg;
+
+    for (size_t i = 0; i < j->n; i++) {
+        uint8_t *p = j->dst + (j->jobs[i].in_off - j->base);
+        size_t left = j->chunks[i].nbytes;
+        uint64_t off = j->chunks[i].file_off;
+
+        while (left > 0) {
+            ssize_t got = pread(j->chunks[i].fd, p, left, (off_t)off);
+
+            if (got <= 0) {
+                j->bad[i] = 1;
+                memset(p, 0, left);
+                p += left;
+                break;
+            }
+            p += got;
+            off += (uint64_t)got;
+            left -= (size_t)got;
+        }
+        memset(p, 0, 16);               /* the decoder's bit reader may look a few bytes ahead */
+    }
+    pthread_mutex_lock(j->mu);
+    if (--*j->pending == 0)
+        pthread_cond_broadcast(j->cv);
+    pthread_mutex_unlock(j->mu);
+    free(j);
+}
+
+static size_t comp_slot(uint32_t nbytes)
+{
+    return (((size_t)nbytes + 15) & ~(size_t)15) + 16;
+}
+
+/* the n chunks of the strip into d_comp at their in_off, batch by batch through the pinned buffers; bad[i] is set
+ * for a chunk whose bytes could not be read */
+static int stage_chunks(struct worker *w, size_t n, int *bad)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    struct gcn10_verify_state *v = w->verify;
+    pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
+    pthread_cond_t cv = PTHREAD_COND_INITIALIZER;
+    int k = 0;
+
+    for (size_t i0 = 0; i0 < n;) {
+        const uint64_t base = v->h_jobs[i0].in_off;
+        uint64_t end = base;
+        size_t i1 = i0;
+        int pending = 0;
+
+        while (i1 < n) {
+            const uint64_t e = v->h_jobs[i1].in_off + comp_slot(v->h_jobs[i1].in_len);
+
+            if (e - base > (uint64_t)V_STAGE_BYTES)
+                break;
+            end = e;
+            i1++;
+        }
+        if (i1 == i0) {
+            /* one chunk larger than a staging buffer: the planner's limit is 2^31 bytes, a tile of ours is 64 KiB;
+             * such a file goes the slow way */
+            bad[i0] = 2;
+            i0++;
+            continue;
+        }
+        if (v->stage_busy[k]) {
+            GPU_V(w, g->event_sync(w->ctx, v->ev_stage[k]));
+            v->stage_busy[k] = false;
+        }
+        for (size_t i = i0; i < i1; i += 64) {
+            struct read_job job = { v->chunks + i, v->h_jobs + i, i1 - i < 64 ? i1 - i : 64, v->h_stage[k], base,
+                                    &mu, &cv, &pending, bad + i };
+            struct read_job *j = malloc(sizeof *j);
+
+            if (!j) {
+                wlog(w, "ERROR", true, "malloc failed for the verifier's read jobs");
+                pthread_mutex_lock(&mu);
+                while (pending > 0)
+                    pthread_cond_wait(&cv, &mu);
+                pthread_mutex_unlock(&mu);
+                return -1;
+            }
+            *j = job;
+            pthread_mutex_lock(&mu);
+            pending++;
+            pthread_mutex_unlock(&mu);
+            if (r->pool)
+                gcn10_pool_submit(r->pool, read_job_run, j);
+            else
+                read_job_run(j);
+        }
+        pthread_mutex_lock(&mu);
+        while (pending > 0)
+            pthread_cond_wait(&cv, &mu);
+        pthread_mutex_unlock(&mu);
+        GPU_V(w, g->memcpy_h2d(w->ctx, v->d_comp + base, v->h_stage[k], (size_t)(end - base), w->s_kernel));
+        GPU_V(w, g->event_record(w->ctx, v->ev_stage[k], w->s_kernel));
+        v->stage_busy[k] = true;
+        k = (k + 1) % V_STAGE;
+        i0 = i1;
+    }
+    return 0;
+}
+
+/* ------------------------------------------------------------------------ */
+/* one level of a block                                                      */
+/* ------------------------------------------------------------------------ */
+
+static void set_finding(struct vfile *f, int finding, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+static void set_finding(struct vfile *f, int finding, const char *fmt, ...)
+{
+    va_list ap;
+
+    if (f->finding != GCN10_VERIFY_OK)
+        return;                             /* the first finding of a file is the one reported */
+    f->finding = finding;
+    va_start(ap, fmt);
+    vsnprintf(f->reason, sizeof f->reason, fmt, ap);
+    va_end(ap);
+}
+
+/* Rows per strip of a level Wk pixels wide: what strip_rows says, as far as the n_sel decode buffers fit
+ * V_GOT_BYTES; whole tile rows, at least one. */
+static int rows_per_strip(const struct run *r, size_t stride)
+{
+    size_t rows = V_GOT_BYTES / ((size_t)r->n_sel * stride);
+
+    rows = rows / TILE * TILE;
+    if (rows > (size_t)r->strip_rows)
+        rows = (size_t)r->strip_rows;
+    return rows < TILE ? TILE : (int)rows;
+}
+
+/* Level `level` (Wk x Hk) of the block's files against d_esa / d_cj (the level's landcover and soil rows, the tile of
+ * width Wk prepared) or, with `want` (per selected raster q: the level's expected raster, rows Wk apart), against
+ * those buffers.  Files with a finding are left out.  0, or -1 for a device error (logged). */
+static int verify_level(struct worker *w, struct vfile *files, int level, int Wk, int Hk, const uint8_t *d_esa,
+                        const int32_t *d_cj, uint8_t *const *want)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    struct gcn10_verify_state *v = w->verify;
+    const size_t stride = ((size_t)Wk + 15) & ~(size_t)15;
+    const int strip = rows_per_strip(r, stride);
+    const size_t slot = stride * (size_t)(strip < Hk ? strip : Hk);
+    gcn10_verify_count *counts = v->d_counts + (size_t)level * GCN10_N_RASTERS;
+    const unsigned codecs = r->inflate_codecs | GCN10_CODEC_DEFLATE | GCN10_CODEC_RAW;
+    int *bad = NULL;
+    size_t bad_cap = 0;
+    int rc = -1;
+
+    if (gcn10_ensure_dev_on(w, w->ctx, (void **)&v->d_got, &v->got_cap, slot * (size_t)r->n_sel + 16) != 0)
+        return -1;
+    for (int y0 = 0; y0 < Hk; y0 += strip) {
+        const int rows = Hk - y0 < strip ? Hk - y0 : strip;
+        const uint8_t *got[GCN10_N_RASTERS] = { 0 }, *exp[GCN10_N_RASTERS] = { 0 };
+        unsigned mask = 0;
+        size_t n = 0, comp_bytes = 0;
+        uint32_t chunk_bytes = 16;
+        bool sparse = false;
+
+        /* plan: the chunks of every file that cover the strip */
+        for (int q = 0; q < r->n_sel; q++) {
+            struct vfile *f = &files[q];
+            struct gcn10_read_plan plan;
+            char err[1024] = "";
+            int prc;
+
+            got[f->k] = v->d_got + (size_t)q * slot;
+            if (want)
+                exp[f->k] = want[q] + (size_t)y0 * (size_t)Wk;
+            if (f->finding != GCN10_VERIFY_OK || level > f->n_levels)
+                continue;
+            memset(&plan, 0, sizeof plan);
+            prc = gcn10_tiff_plan_window(f->lv[level], 0, y0, Wk, rows, 0, 0, codecs, &plan, err, sizeof err);
+            if (prc < 0) {
+                set_finding(f, GCN10_VERIFY_CHUNK, "level %d, rows %d..%d: %s", level, y0, y0 + rows - 1, err);
+                gcn10_read_plan_free(&plan);
+                continue;
+            }
+            if (prc > 0) {
+                /* the host reader's codecs and shapes: decoded here, uploaded; slower, the same answer */
+                gcn10_read_plan_free(&plan);
+                if (v->h_rows_cap < stride * (size_t)rows) {
+                    free(v->h_rows);
+                    v->h_rows = malloc(stride * (size_t)rows);
+                    v->h_rows_cap = v->h_rows ? stride * (size_t)rows : 0;
+                }
+                if (!v->h_rows) {
+                    wlog(w, "ERROR", true, "malloc failed for a host-decoded strip");
+                    goto out;
+                }
+                if (gcn10_tiff_read_window(f->lv[level], 0, y0, Wk, rows, v->h_rows, stride, err, sizeof err) != 0) {
+                    set_finding(f, GCN10_VERIFY_DECODE, "level %d, rows %d..%d: %s", level, y0, y0 + rows - 1, err);
+                    continue;
+                }
+                /* pageable memory: the copy is done with the buffer when the call returns */
+                if (g->memcpy_h2d(w->ctx, v->d_got + (size_t)q * slot, v->h_rows, stride * (size_t)rows, w->s_kernel) != 0 ||
+                    g->stream_sync(w->ctx, w->s_kernel) != 0)
+                    goto gpu_fail;
+                mask |= 1u << f->k;
+                continue;
+            }
+            if (jobs_ensure(w, n + plan.n, n) != 0) {
+                gcn10_read_plan_free(&plan);
+                goto out;
+            }
+            for (size_t i = 0; i < plan.n; i++) {
+                const struct gcn10_chunk_ref *c = &plan.chunks[i];
+                gcn10_inflate_tile *j = &v->h_jobs[n];
+
+                v->chunks[n] = *c;
+                v->owner[n] = q;
+                j->in_off = comp_bytes;
+                j->in_len = c->nbytes;
+                j->out_len = c->out_len;
+                j->chunk_w = c->chunk_w;
+                j->src_x = c->src_x;
+                j->src_y = c->src_y;
+                j->copy_w = c->copy_w;
+                j->copy_h = c->copy_h;
+                j->flags = c->flags;
+                j->dst_off = (uint64_t)q * slot + (uint64_t)c->dst_y * stride + c->dst_x;
+                v->h_status[n] = 0xffffffffu;
+                comp_bytes += comp_slot(c->nbytes);
+                n++;
+            }
+            if (plan.max_chunk_bytes > chunk_bytes)
+                chunk_bytes = plan.max_chunk_bytes;
+            if (plan.covered < (uint64_t)Wk * (uint64_t)rows)
+                sparse = true;
+            /* (the readers of this block stay open until it is done: the chunks' descriptors stay valid) */
+            gcn10_read_plan_free(&plan);
+            mask |= 1u << f->k;
+        }
+        if (mask == 0)
+            continue;
+        if (n > 0) {
+            if (n > bad_cap) {
+                free(bad);
+                bad = malloc(n * sizeof *bad);
+                bad_cap = bad ? n : 0;
+                if (!bad) {
+                    wlog(w, "ERROR", true, "malloc failed for the verifier's read plan");
+                    goto out;
+                }
+            }
+            memset(bad, 0, n * sizeof *bad);
+            if (gcn10_ensure_dev_on(w, w->ctx, (void **)&v->d_comp, &v->comp_cap, comp_bytes + 16) != 0)
+                goto out;
+            if (sparse && g->memset(w->ctx, v->d_got, 0, slot * (size_t)r->n_sel, w->s_kernel) != 0)
+                goto gpu_fail;
+            if (stage_chunks(w, n, bad) != 0)
+                goto out;
+            for (size_t i = 0; i < n; i++)
+                if (bad[i]) {
+                    /* a chunk that cannot be read is not handed to the decoder: an empty window */
+                    v->h_jobs[i].copy_w = v->h_jobs[i].copy_h = 0;
+                    v->h_jobs[i].in_len = 0;
+                    v->h_jobs[i].flags = GCN10_TILE_RAW;
+                    v->h_jobs[i].out_len = 0;
+                }
+            if (g->memcpy_h2d(w->ctx, v->d_jobs, v->h_jobs, n * sizeof *v->h_jobs, w->s_kernel) != 0 ||
+                g->memcpy_h2d(w->ctx, v->d_status, v->h_status, n * 4, w->s_kernel) != 0 ||
+                g->inflate_tiles(w->ctx, v->d_comp, v->d_jobs, (int)n, chunk_bytes, v->d_got, stride, v->d_status,
+                                 w->s_kernel) != 0 ||
+                g->memcpy_d2h(w->ctx, v->h_status, v->d_status, n * 4, w->s_kernel) != 0)
+                goto gpu_fail;
+        }
+        if (want) {
+            if (g->verify_buffers(w->ctx, exp, (size_t)Wk, got, stride, Wk, rows, y0, mask, counts, w->s_kernel) != 0)
+                goto gpu_fail;
+        }
+        else if (g->verify_strip(w->ctx, d_esa + (size_t)y0 * (size_t)Wk, Wk, rows, d_cj + y0, r->cond_mask,
+                                 r->table_mask, got, stride, y0, counts, w->s_kernel) != 0) {
+            goto gpu_fail;
+        }
+        /* the strip's buffers, job lists and staging are reused by the next one */
+        if (g->stream_sync(w->ctx, w->s_kernel) != 0)
+            goto gpu_fail;
+        for (int i = 0; i < V_STAGE; i++)
+            v->stage_busy[i] = false;
+        for (size_t i = 0; i < n; i++) {
+            struct vfile *f = &files[v->owner[i]];
+            const struct gcn10_chunk_ref *c = &v->chunks[i];
+
+            if (bad[i])
+                set_finding(f, GCN10_VERIFY_CHUNK, "level %d: the %u bytes of the chunk at x=%u y=%d cannot be read%s",
+                            level, c->nbytes, c->dst_x, y0 + (int)c->dst_y, bad[i] == 2 ? " (too large to stage)" : "");
+            else if (v->h_status[i] != 0)
+                set_finding(f, GCN10_VERIFY_DECODE, "level %d: the chunk at x=%u y=%d (%u bytes at offset %llu) does "
+                            "not decode, status %u", level, c->dst_x, y0 + (int)c->dst_y, c->nbytes,
+                            (unsigned long long)c->file_off, v->h_status[i]);
+        }
+    }
+    rc = 0;
+    goto out;
+
+gpu_fail:
+    wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+out:
+    free(bad);
+    return rc;
+}
+
+/* ------------------------------------------------------------------------ */
+/* one block                                                                 */
+/* ------------------------------------------------------------------------ */
+
+/* the overview levels of the files against nearest-neighbour levels: each a block of its own (pipeline.c walks the
+ * same path when it writes them) */
+static int verify_nearest_levels(struct worker *w, struct block_in *in, struct vfile *files, int L)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    const int W = in->W, H = in->H;
+    const int W1 = (W + 1) / 2, H1 = (H + 1) / 2;
+    const size_t n_idx = (size_t)W1 + 4 + (size_t)H1;
+    int32_t *idx = malloc(n_idx * sizeof *idx);
+    int rc = -1;
+
+    if (!idx) {
+        wlog(w, "ERROR", true, "malloc failed for overview index maps");
+        return -1;
+    }
+    if (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov, &w->ov_cap, (size_t)W1 * (size_t)H1 + 16) != 0 ||
+        gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov_idx, &w->ov_idx_cap, n_idx * sizeof *idx) != 0)
+        goto out;
+    for (int k = L; k >= 1; k--) {
+        const int Wk = level_dim(W, k), Hk = level_dim(H, k), half = 1 << (k - 1);
+        const size_t cj_at = ((size_t)Wk + 3) & ~(size_t)3;
+
+        for (int x = 0; x < Wk; x++)
+            idx[x] = in->h_ci[(int64_t)x * (1 << k) + half < W ? (int64_t)x * (1 << k) + half : W - 1];
+        for (int y = 0; y < Hk; y++)
+            idx[cj_at + y] = in->h_cj[(int64_t)y * (1 << k) + half < H ? (int64_t)y * (1 << k) + half : H - 1];
+        if (g->overview_nearest(w->ctx, in->d_block, W, H, k, w->d_ov, w->s_kernel) != 0 ||
+            g->memcpy_h2d(w->ctx, w->d_ov_idx, idx, (cj_at + (size_t)Hk) * sizeof *idx, w->s_kernel) != 0 ||
+            g->stream_sync(w->ctx, w->s_kernel) != 0 ||
+            g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, w->d_ov_idx, Wk, w->s_kernel) != 0) {
+            wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+            goto out;
+        }
+        if (verify_level(w, files, k, Wk, Hk, w->d_ov, w->d_ov_idx + cj_at, NULL) != 0)
+            goto out;
+    }
+    rc = 0;
+out:
+    free(idx);
+    return rc;
+}
+
+/* ... against averaged levels: the pyramid of every selected raster from gcn10_gpu_overview_average (the block's
+ * tile is prepared), then level by level against those buffers */
+static int verify_average_levels(struct worker *w, struct block_in *in, struct vfile *files, int L)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    const int W = in->W, H = in->H;
+    size_t lvl_off[V_LEVELS], total = 0;
+    uint8_t *levels[GCN10_N_RASTERS * GCN10_COG_MAX_LEVELS];
+
+    for (int k = 1; k <= L; k++) {
+        lvl_off[k] = total;
+        total += ((size_t)level_dim(W, k) * (size_t)level_dim(H, k) + 255) & ~(size_t)255;
+    }
+    if (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov, &w->ov_cap, total * (size_t)r->n_sel + 16) != 0)
+        return -1;
+    for (int q = 0; q < r->n_sel; q++)
+        for (int k = 1; k <= L; k++)
+            levels[q * L + k - 1] = w->d_ov + (size_t)q * total + lvl_off[k];
+    for (int y0 = 0; y0 < H; y0 += r->strip_rows) {
+        const int rows = H - y0 < r->strip_rows ? H - y0 : r->strip_rows;
+
+        GPU_V(w, g->overview_average(w->ctx, in->d_block, W, H, y0, rows, in->d_cj, r->cond_mask, r->table_mask, L,
+                                     levels, w->s_kernel));
+    }
+    for (int k = L; k >= 1; k--) {
+        uint8_t *want[GCN10_N_RASTERS];
+
+        for (int q = 0; q < r->n_sel; q++)
+            want[q] = levels[q * L + k - 1];
+        if (verify_level(w, files, k, level_dim(W, k), level_dim(H, k), NULL, NULL, want) != 0)
+            return -1;
+    }
+    return 0;
+}
+
+static void raster_name(char *out, size_t cap, int k)
+{
+    snprintf(out, cap, "%s/%s/%s", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3]);
+}
+
+static void block_failed(struct run *r, int block_id)
+{
+    pthread_mutex_lock(&r->verify_mu);
+    if (r->verify_n_failed < r->verify_failed_cap)
+        r->verify_failed[r->verify_n_failed++] = block_id;
+    pthread_mutex_unlock(&r->verify_mu);
+}
+
+void gcn10_verify_block_unreadable(struct worker *w, int block_id)
+{
+    struct run *r = w->run;
+
+    wlog(w, "ERROR", true, "UNREADABLE block %d: its landcover or soil window could not be read, %d rasters not verified",
+         block_id, r->n_sel);
+    atomic_fetch_add(&r->verify_n_bad, r->n_sel);
+    block_failed(r, block_id);
+}
+
+int gcn10_verify_block(struct worker *w, struct block_in *in)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    const int W = in->W, H = in->H, block_id = in->block_id;
+    struct vfile files[GCN10_N_RASTERS];
+    struct gcn10_verify_state *v;
+    int L = 0, rc = -1, n_beyond_total = 0;
+    bool any_failed = false, inputs_ok = true;
+
+    memset(files, 0, sizeof files);
+    if (state_setup(w) != 0)
+        return -1;
+    v = w->verify;
+
+    /* 1. the files' structure, on the host, before any pixel work */
+    for (int q = 0; q < r->n_sel; q++) {
+        struct vfile *f = &files[q];
+        char path[PATH_MAX];
+        int beyond = 0;
+
+        f->k = r->sel[q];
+        snprintf(path, sizeof path, "cn_rasters_%s/cn_%s_%s_%d.tif", gcn10_conds[f->k / 9], gcn10_hcs[(f->k % 9) / 3],
+                 gcn10_arcs[f->k % 3], block_id);                           /* src/cn.c:308 */
+        f->finding = open_checked(path, W, H, in->gt, f->lv, &f->n_levels, &beyond, f->reason, sizeof f->reason);
+        n_beyond_total += beyond;
+        if (beyond) {
+            char name[64];
+
+            raster_name(name, sizeof name, f->k);
+            wlog(w, "ERROR", true, "block %d: %s: overview levels beyond %d not checked", block_id, name,
+                 GCN10_COG_MAX_LEVELS);
+        }
+        if (f->finding == GCN10_VERIFY_OK && f->n_levels > L)
+            L = f->n_levels;
+    }
+
+    /* 2. the block on the device, as for a write run */
+    if (g->stream_wait_event(w->ctx, w->s_kernel, in->ev_ready) != 0)
+        goto gpu_fail;
+    if (in->n_inflate > 0) {
+        if (g->event_sync(w->ctx, in->ev_ready) != 0)
+            goto gpu_fail;
+        for (size_t i = 0; i < in->n_inflate && inputs_ok; i++)
+            if (in->h_status[i] != 0) {
+                wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
+                                       "(stream %zu, reason %u)", in->xoff, in->yoff, W, H, i, in->h_status[i]);
+                wlog(w, "ERROR", true, "esa load failed for block %d", block_id);
+                inputs_ok = false;
+            }
+    }
+    if (!inputs_ok) {
+        gcn10_verify_block_unreadable(w, block_id);
+        rc = 0;
+        goto out;
+    }
+    for (size_t i = 0; i < (size_t)V_LEVELS * GCN10_N_RASTERS; i++)
+        v->h_counts[i] = (gcn10_verify_count){ 0, UINT64_MAX, 0, 0 };
+    if (g->memcpy_h2d(w->ctx, v->d_counts, v->h_counts, (size_t)V_LEVELS * GCN10_N_RASTERS * sizeof *v->h_counts,
+                      w->s_kernel) != 0)
+        goto gpu_fail;
+
+    /* 3. overview levels (nearest ones prepare their own tiles, so they come first), then the raster itself */
+    if (L > 0 && !r->ov_average) {
+        if (verify_nearest_levels(w, in, files, L) != 0)
+            goto out;
+    }
+    if (g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, W, w->s_kernel) != 0)
+        goto gpu_fail;
+    if (L > 0 && r->ov_average) {
+        if (verify_average_levels(w, in, files, L) != 0)
+            goto out;
+    }
+    if (verify_level(w, files, 0, W, H, in->d_block, in->d_cj, NULL) != 0)
+        goto out;
+    if (g->memcpy_d2h(w->ctx, v->h_counts, v->d_counts, (size_t)V_LEVELS * GCN10_N_RASTERS * sizeof *v->h_counts,
+                      w->s_kernel) != 0 ||
+        g->stream_sync(w->ctx, w->s_kernel) != 0)
+        goto gpu_fail;
+
+    /* 4. one line per file */
+    for (int q = 0; q < r->n_sel; q++) {
+        struct vfile *f = &files[q];
+        char name[64];
+        uint64_t n_diff = 0;
+        int first_level = -1;
+
+        raster_name(name, sizeof name, f->k);
+        if (f->finding == GCN10_VERIFY_MISSING) {
+            wlog(w, "ERROR", true, "MISSING block %d: %s", block_id, name);
+            atomic_fetch_add(&r->verify_n_missing, 1);
+            any_failed = true;
+            continue;
+        }
+        if (f->finding != GCN10_VERIFY_OK) {
+            wlog(w, "ERROR", true, "UNREADABLE block %d: %s: %s: %s", block_id, name, finding_names[f->finding], f->reason);
+            atomic_fetch_add(&r->verify_n_bad, 1);
+            any_failed = true;
+            continue;
+        }
+        for (int k = 0; k <= f->n_levels; k++) {
+            const gcn10_verify_count *c = &v->h_counts[(size_t)k * GCN10_N_RASTERS + f->k];
+
+            n_diff += c->mismatches;
+            if (c->mismatches && first_level < 0)
+                first_level = k;
+        }
+        if (n_diff) {
+            const gcn10_verify_count *c = &v->h_counts[(size_t)first_level * GCN10_N_RASTERS + f->k];
+
+            wlog(w, "ERROR", true, "MISMATCH block %d: %s: %llu pixels differ, first at x=%u y=%u (level %d): file %u, "
+                 "expected %u", block_id, name, (unsigned long long)n_diff, (unsigned)(c->first & 0xffffffffu),
+                 (unsigned)(c->first >> 32), first_level, c->got, c->want);
+            atomic_fetch_add(&r->verify_n_bad, 1);
+            any_failed = true;
+            continue;
+        }
+        wlog(w, "INFO", false, "verified block %d: %s", block_id, name);
+        atomic_fetch_add(&r->verify_n_ok, 1);
+    }
+    atomic_fetch_add(&r->verify_n_unchecked, n_beyond_total);
+    if (any_failed)
+        block_failed(r, block_id);
+    rc = 0;
+    goto out;
+
+gpu_fail:
+    wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+out:
+    if (w->ctx)
+        g->stream_sync(w->ctx, w->s_kernel);
+    for (int i = 0; i < V_STAGE; i++)
+        v->stage_busy[i] = false;
+    for (int q = 0; q < r->n_sel; q++)
+        for (int k = 0; k < V_LEVELS; k++)
+            gcn10_tiff_close_reader(files[q].lv[k]);
+    return rc;
+}

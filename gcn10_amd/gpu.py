@@ -45,6 +45,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_soil_words_state", "gcn10_gpu_lzw_arena_bound", "gcn10_gpu_lzw_strip",
     "gcn10_gpu_inflate_codecs", "gcn10_gpu_overview_nearest", "gcn10_gpu_overview_average",
     "gcn10_gpu_pair_histogram_codes", "gcn10_gpu_pair_histogram",
+    "gcn10_gpu_verify_strip", "gcn10_gpu_verify_buffers",
 )
 
 
@@ -64,6 +65,9 @@ CODEC_DEFLATE, CODEC_RAW, CODEC_LZW = 1, 2, 4       # gcn10_gpu_inflate_codecs()
 PAIR_HIST_BINS = 16                                 # GCN10_PAIR_HIST_BINS: pair histogram = [bin][landcover] counters
 # gcn10_inflate_tiles status words of LZW tiles (GCN10_INFLATE_E_LZW_*)
 INFLATE_E_LZW_CODE, INFLATE_E_LZW_FIRST, INFLATE_E_LZW_INPUT = 9, 10, 11
+# struct gcn10_verify_count (include/gcn10_gpu.h); first == VERIFY_NONE: nothing differs
+VERIFY_COUNT_DTYPE = np.dtype([("mismatches", "<u8"), ("first", "<u8"), ("want", "<u4"), ("got", "<u4")])
+VERIFY_NONE = 0xFFFFFFFFFFFFFFFF
 INFLATE_TILE_DTYPE = np.dtype([("in_off", "<u8"), ("in_len", "<u4"), ("out_len", "<u4"), ("chunk_w", "<u4"),
                                ("src_x", "<u4"), ("src_y", "<u4"), ("copy_w", "<u4"), ("copy_h", "<u4"),
                                ("flags", "<u4"), ("dst_off", "<u8")])
@@ -135,6 +139,8 @@ def lib():
             "gcn10_gpu_overview_average": (i, [vp, vp, i, i, i, i, vp, u, u, i, C.POINTER(vp), vp]),
             "gcn10_gpu_pair_histogram_codes": (i, [C.POINTER(C.c_uint8)]),
             "gcn10_gpu_pair_histogram": (i, [vp, vp, i, i, vp, vp, vp]),
+            "gcn10_gpu_verify_strip": (i, [vp, vp, i, i, vp, C.c_uint, C.c_uint, vp, sz, i, vp, vp]),
+            "gcn10_gpu_verify_buffers": (i, [vp, vp, sz, vp, sz, i, i, i, C.c_uint, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -406,6 +412,40 @@ class Engine:
         (gcn10_gpu_pair_histogram)."""
         self._chk(lib().gcn10_gpu_pair_histogram(self._ctx, esa_ptr, W, rows, cj_ptr, hist_ptr, stream),
                   "gcn10_gpu_pair_histogram")
+
+    def verify_counts_alloc(self, stream=None) -> DevBuf:
+        """A cleared gcn10_verify_count[N_RASTERS] on the device: no mismatches, first = UINT64_MAX."""
+        buf = self.alloc(N_RASTERS * VERIFY_COUNT_DTYPE.itemsize)
+        clear = np.zeros(N_RASTERS, VERIFY_COUNT_DTYPE)
+        clear["first"] = VERIFY_NONE
+        self.h2d(buf.ptr, clear, stream)
+        self.sync(stream)
+        return buf
+
+    def verify_counts(self, counts_ptr: int, stream=None) -> np.ndarray:
+        """The device counters as a VERIFY_COUNT_DTYPE array of N_RASTERS records."""
+        return self.download(counts_ptr, (N_RASTERS,), dtype=VERIFY_COUNT_DTYPE, stream=stream)
+
+    def verify_strip(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, cond_mask: int, table_mask: int,
+                     got: Sequence[Optional[int]], got_stride: int, y0: int, counts_ptr: int, stream=None):
+        """Compares the decoded strips got[r] (device pointers, rows got_stride bytes apart) of rows [y0, y0 + rows)
+        with the values computed from the landcover strip and the prepared soil, and adds what differs to the device
+        counters (gcn10_gpu_verify_strip)."""
+        arr = (C.c_void_p * N_RASTERS)()
+        for r in range(N_RASTERS):
+            arr[r] = got[r] if r < len(got) and got[r] else None
+        self._chk(lib().gcn10_gpu_verify_strip(self._ctx, esa_ptr, W, rows, cj_ptr, cond_mask, table_mask, arr,
+                                               got_stride, y0, counts_ptr, stream), "gcn10_gpu_verify_strip")
+
+    def verify_buffers(self, want: Sequence[Optional[int]], want_stride: int, got: Sequence[Optional[int]],
+                       got_stride: int, W: int, rows: int, y0: int, raster_mask: int, counts_ptr: int, stream=None):
+        """The same counting for expected rasters that exist in device memory (gcn10_gpu_verify_buffers)."""
+        wa, ga = (C.c_void_p * N_RASTERS)(), (C.c_void_p * N_RASTERS)()
+        for r in range(N_RASTERS):
+            wa[r] = want[r] if r < len(want) and want[r] else None
+            ga[r] = got[r] if r < len(got) and got[r] else None
+        self._chk(lib().gcn10_gpu_verify_buffers(self._ctx, wa, want_stride, ga, got_stride, W, rows, y0,
+                                                 raster_mask, counts_ptr, stream), "gcn10_gpu_verify_buffers")
 
     def lzw_arena_bound(self, W: int, rows: int, n_rasters: int) -> int:
         """Worst-case arena bytes of gcn10_gpu_lzw_strip for n_rasters strips of W x rows."""

@@ -139,6 +139,16 @@ class Config(C.Structure):
                 ("stats", C.c_int), ("nodata", C.c_int)]
 
 
+class ConfigFull(Config):
+    """The whole ``gcn10_config``: ``Config`` is the struct as it stood when the statistics keys were added (its
+    field list is pinned by the tests of that change); fields appended to the C struct since then are appended here.
+    ``Config`` ends on a multiple of 8 bytes, so the fields below lie where the C compiler puts them."""
+    _fields_ = [("verify", C.c_int)]
+
+
+assert C.sizeof(Config) % 8 == 0
+
+
 class BandStats(C.Structure):
     """``gcn10_band_stats`` of include/gcn10_host.h."""
     _fields_ = [("total", C.c_uint64), ("valid", C.c_uint64), ("min", C.c_int), ("max", C.c_int),
@@ -155,16 +165,16 @@ class HostError(RuntimeError):
 
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = Config()
+    cfg = ConfigFull()
     err = C.create_string_buffer(1024)
-    rc = lib().gcn10_config_parse(os.fsencode(path), C.byref(cfg), err, 1024)
+    rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
     out = {}
-    for name, _t in Config._fields_:
+    for name, _t in Config._fields_ + ConfigFull._fields_:
         v = getattr(cfg, name)
         out[name] = v.decode() if isinstance(v, bytes) else v
-    lib().gcn10_config_free(C.byref(cfg))
+    lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))
     return out
 
 
@@ -415,6 +425,27 @@ def raster_histogram(pair_hist, codes, table, drained: bool) -> np.ndarray:
     lib().gcn10_raster_histogram(pair, np.ascontiguousarray(codes, dtype=np.uint8).reshape(16),
                                  np.ascontiguousarray(table, dtype=np.int32).reshape(256, 5), int(bool(drained)), out)
     return out
+
+
+#: findings of verify_structure (GCN10_VERIFY_* of include/gcn10_host.h), by code
+VERIFY_FINDINGS = ("ok", "missing", "not a TIFF", "not 1 band Byte", "size", "geotransform", "chunk", "overview size",
+                   "decode", "pixels")
+
+
+def verify_structure(path: str, xsize: int, ysize: int, gt) -> dict:
+    """The structure checks a verify run makes on one output raster before any pixel work (gcn10_verify_structure):
+    ``finding`` (a VERIFY_FINDINGS name, "ok" = none), ``code``, ``reason`` and ``n_levels``, the overview directories
+    behind the raster."""
+    L = lib()
+    L.gcn10_verify_structure.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int),
+                                         C.c_char_p, C.c_size_t]
+    L.gcn10_verify_structure.restype = C.c_int
+    g = (C.c_double * 6)(*[float(v) for v in gt])
+    n = C.c_int(0)
+    reason = C.create_string_buffer(1024)
+    code = L.gcn10_verify_structure(os.fsencode(path), int(xsize), int(ysize), g, C.byref(n), reason, 1024)
+    return {"code": code, "finding": VERIFY_FINDINGS[code], "reason": reason.value.decode(errors="replace"),
+            "n_levels": n.value}
 
 
 def band_stats(hist, nodata=None) -> dict:

@@ -39,7 +39,7 @@ extern "C" {
  *    the extents' pads (round 3).  A caller built against an older header must be rebuilt: check at start-up.
  *    Added within 3: the LZW encoder (gcn10_gpu_lzw_*), LZW tiles of gcn10_gpu_inflate_tiles (GCN10_TILE_LZW)
  *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*); the pair histogram
- *    of the band statistics (gcn10_gpu_pair_histogram*).
+ *    of the band statistics (gcn10_gpu_pair_histogram*); the raster verifier (gcn10_gpu_verify_*).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -323,6 +323,34 @@ int gcn10_gpu_overview_average(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, in
 int gcn10_gpu_pair_histogram_codes(uint8_t codes[GCN10_PAIR_HIST_BINS]);
 int gcn10_gpu_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
                              unsigned long long *hist_dev, gcn10_stream_t stream);
+
+/* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
+ * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.
+ *
+ * gcn10_gpu_verify_strip: same contract for `esa`, `cj`, the masks and the soil prepared by gcn10_gpu_prepare_tile
+ *   as gcn10_gpu_cn_strip, for rows [y0, y0 + rows) of the block.  got[r] (host array of device pointers; entries of
+ *   unselected rasters are ignored) is the decoded strip of raster r, rows got_stride >= W bytes apart; bytes
+ *   beyond column W are never read and nothing is written to got.  The call ADDS to counts_dev[GCN10_N_RASTERS]:
+ *   clear it once per block -- mismatches = 0, first = UINT64_MAX (gcn10_gpu_memset with 0xff, then the counters
+ *   with 0, or a copy of such an array).  Entries of unselected rasters are left alone.  `first` is the minimum over
+ *   everything added so far in row-major order, so it does not depend on strip size or launch shape; want / got
+ *   are those of the pixel `first` names, written by a second small launch when that pixel lies in this call's
+ *   rows.  The calls that add to one counts_dev must therefore be ordered (one stream, or events).
+ * gcn10_gpu_verify_buffers: the same counting for rasters whose expected pixels exist in device memory (the
+ *   average overviews): want[r] against got[r], W x rows pixels each with their own row strides, for the rasters
+ *   of raster_mask (bit r). */
+typedef struct gcn10_verify_count {
+    uint64_t mismatches;        /* pixels of this raster whose file value differs from the computed one */
+    uint64_t first;             /* smallest (y << 32 | x) among them, block coordinates; UINT64_MAX if none */
+    uint32_t want, got;         /* computed value and file value at `first` */
+} gcn10_verify_count;
+int gcn10_gpu_verify_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                           unsigned cond_mask, unsigned table_mask,
+                           const uint8_t *const got[GCN10_N_RASTERS], size_t got_stride, int y0,
+                           gcn10_verify_count *counts_dev, gcn10_stream_t stream);
+int gcn10_gpu_verify_buffers(gcn10_gpu_ctx *ctx, const uint8_t *const want[GCN10_N_RASTERS], size_t want_stride,
+                             const uint8_t *const got[GCN10_N_RASTERS], size_t got_stride, int W, int rows, int y0,
+                             unsigned raster_mask, gcn10_verify_count *counts_dev, gcn10_stream_t stream);
 
 /* Launch-shape knobs of the strip kernels, for tuning runs; results never
  * depend on them.  Names: "grid_blocks_per_cu" (1..64), "ilp16" (0 = by raster count | 1 | 2),

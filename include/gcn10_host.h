@@ -125,6 +125,8 @@ typedef struct gcn10_config {
                                its GDAL_METADATA tag, 42112), counted on the GPU; 0 (default) = none */
     int nodata;             /* "nodata": 0..255 = every written raster declares that NoData value (GDAL_NODATA tag,
                                42113) and its statistics leave it out; -1 ("none", default) = no tag */
+    int verify;             /* "verify": 1 = nothing is written: the rasters that exist are decoded on the GPU and every
+                               pixel is compared with the value computed now (gcn10_verify_*); 0 (default) = a write run */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -142,9 +144,10 @@ int gcn10_parse_cog(const char *text, int *cog);
 /* "0" | "1" -> stats; "none" (any case) -> -1 | an integer 0..255 -> nodata.  0, or -1 for another value. */
 int gcn10_parse_stats(const char *text, int *stats);
 int gcn10_parse_nodata(const char *text, int *nodata);
+int gcn10_parse_verify(const char *text, int *verify);      /* "0" | "1".  0, or -1 for another value. */
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -330,14 +333,39 @@ typedef struct gcn10_run_options {
     const char *overview_resampling;    /* --overview-resampling nearest|average                 */
     bool stats;                 /* --stats: GDAL band statistics in every raster (sets the config key "stats") */
     const char *nodata;         /* --nodata none|0..255: overrides the config key "nodata"                */
+    bool verify;                /* --verify: check the rasters that exist instead of writing (sets the config key "verify") */
 } gcn10_run_options;
+
+/* ------------------------------------------------------------------------ */
+/* verification (config key "verify", --verify): no counterpart in the reference                            */
+/* ------------------------------------------------------------------------ */
+
+/* What a raster file can have wrong before any pixel is looked at, in the order it is checked. */
+enum {
+    GCN10_VERIFY_OK = 0,
+    GCN10_VERIFY_MISSING = 1,       /* no such file */
+    GCN10_VERIFY_NOT_TIFF = 2,      /* not a TIFF the reader opens */
+    GCN10_VERIFY_NOT_BYTE = 3,      /* not one band of Byte samples */
+    GCN10_VERIFY_SIZE = 4,          /* another size than the block's window */
+    GCN10_VERIFY_GEOTRANSFORM = 5,  /* another geotransform than the clipped window's (the six doubles, exactly) */
+    GCN10_VERIFY_CHUNK = 6,         /* a tile or strip without bytes, or with bytes beyond the end of the file */
+    GCN10_VERIFY_OVERVIEW = 7,      /* an overview directory whose size is not the halving rule's */
+    GCN10_VERIFY_DECODE = 8,        /* a tile or strip that does not decode (found with the pixels, not by the check below) */
+    GCN10_VERIFY_PIXELS = 9         /* pixels differ (likewise) */
+};
+/* The structure of one output raster: the checks 1..7 above against the window (xsize x ysize, geotransform gt) of
+ * its block.  Returns the first finding (GCN10_VERIFY_OK: none) and its text in `reason`; *n_levels (optional)
+ * receives the number of overview directories behind the raster. */
+int gcn10_verify_structure(const char *path, int xsize, int ysize, const double gt[6], int *n_levels,
+                           char *reason, size_t reason_cap);
 
 /* Runs the whole job: config, logs, block ids, lookup tables, one worker thread
  * per GPU pulling block ids from a shared atomic counter (replaces the static
  * round-robin over MPI ranks, src/main.c:171), per block: windows, index maps,
  * pinned-host strips double-buffered against the fused kernel, 18 tiled DEFLATE
  * GeoTIFFs named as src/cn.c:308, 341.  Returns the process exit code: 0, or 1
- * where the reference calls MPI_Abort(.., 1). */
+ * where the reference calls MPI_Abort(.., 1).  A verify run (opt->verify / "verify=1") writes no raster: 0 = every
+ * selected raster of every block verified, 2 = it ran to its end and found a bad or missing file, 1 as above. */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

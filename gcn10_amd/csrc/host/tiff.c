@@ -528,6 +528,8 @@ static int lzw_decode(const unsigned char *src, size_t n, unsigned char *dst, si
                 return op >= cap ? 0 : -1;
             dst[op++] = (unsigned char)code;
             prev = code;
+            if (op >= cap)
+                return 0;               /* chunk complete; trailing codes are padding */
             continue;
         }
         {

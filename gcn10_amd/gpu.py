@@ -502,12 +502,13 @@ class Engine:
         """CODEC_* bits of the chunk codecs inflate_tiles decodes (gcn10_gpu_inflate_codecs)."""
         return int(lib().gcn10_gpu_inflate_codecs())
 
-    def inflate_tiles(self, streams: Sequence[bytes], chunk_w: int, chunk_rows: Sequence[int],
+    def inflate_tiles(self, streams: Sequence[bytes], chunk_w, chunk_rows: Sequence[int],
                       windows: Sequence[tuple], dst_shape: tuple, stream=None, flags: Optional[Sequence[int]] = None,
                       out_lens: Optional[Sequence[int]] = None):
         """Decodes zlib and TIFF LZW streams on the GPU (gcn10_gpu_inflate_tiles).
 
-        streams[i] decodes to a chunk of chunk_rows[i] x chunk_w pixels; windows[i] =
+        streams[i] decodes to a chunk of chunk_rows[i] x chunk_w pixels (chunk_w: one width, or one per
+        stream); windows[i] =
         (src_x, src_y, copy_w, copy_h, dst_x, dst_y) places part of it in a zero-filled uint8
         raster of dst_shape.  flags[i]: TILE_RAW (streams[i] is the chunk's pixels as they are) or
         TILE_LZW (a TIFF LZW stream; 0 = a zlib stream), either with
@@ -515,12 +516,13 @@ class Engine:
         (a raw chunk staged from its first wanted row on).  Returns (raster, status uint32[n])."""
         n = len(streams)
         H, W = dst_shape
+        widths = [int(chunk_w)] * n if np.isscalar(chunk_w) else [int(w) for w in chunk_w]
         tiles = np.zeros(n, dtype=INFLATE_TILE_DTYPE)
         parts, off = [], 0
         for k, st in enumerate(streams):
             sx, sy, cw, ch, dx, dy = windows[k]
-            tiles[k] = (off, len(st), out_lens[k] if out_lens else chunk_w * chunk_rows[k], chunk_w, sx, sy, cw, ch,
-                        flags[k] if flags else 0, dy * W + dx)
+            tiles[k] = (off, len(st), out_lens[k] if out_lens else widths[k] * chunk_rows[k], widths[k], sx, sy, cw,
+                        ch, flags[k] if flags else 0, dy * W + dx)
             pad = (-len(st)) % 16 + 16
             parts.append(st)
             parts.append(bytes(pad))
@@ -532,7 +534,8 @@ class Engine:
             self.memset(bufs[2].ptr, 0, max(H * W, 1), stream)
             self.memset(bufs[3].ptr, 0xFF, 4 * max(n, 1), stream)
             self._chk(lib().gcn10_gpu_inflate_tiles(self._ctx, bufs[0].ptr, bufs[1].ptr, n,
-                                                    max(chunk_w * max(chunk_rows, default=1), 1), bufs[2].ptr, W,
+                                                    max([w * r for w, r in zip(widths, chunk_rows)] + [1]),
+                                                    bufs[2].ptr, W,
                                                     bufs[3].ptr, stream), "gcn10_gpu_inflate_tiles")
             out = self.download(bufs[2].ptr, (H, W), stream=stream)
             status = self.download(bufs[3].ptr, (n,), dtype=np.uint32, stream=stream)

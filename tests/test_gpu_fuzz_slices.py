@@ -1,6 +1,6 @@
-"""Short seeded slices of the two randomised codec checks, so that every round's GPU run covers them
-(the long runs are `python tests/fuzz_fused_encoder.py --cases N` and `python tools/fuzz_inflate.py
---streams N`; their latest results are under profiles/)."""
+"""Short seeded slices of the randomised codec checks, so that every round's GPU run covers them
+(the long runs are `python tests/fuzz_fused_encoder.py --cases N`, `python tools/fuzz_inflate.py
+--streams N` and `python tests/fuzz_lzw_decode.py --streams N`; their latest results are under profiles/)."""
 import importlib.util
 import os
 
@@ -36,3 +36,15 @@ def test_inflate_random_streams(seed):
     n, ok, refused, bad = fz.run(seed=seed, streams_budget=512, batch=256, verbose=False)
     assert not bad, bad[:5]
     assert n == 512 and ok + refused == 512 and refused >= 1        # a few of the ~75 corrupted streams are refused
+
+
+@pytest.mark.parametrize("seed", [5, 3])
+def test_lzw_decode_random_code_streams(engine, seed):
+    """Random code streams (literals, live entries, the newest entries, KwKwK, Clears; some with an invalid code
+    or truncated; out_len below, at and above the decoded size): bytes and status as the reference decoder
+    gives them.  The slice must hold what it is there for: refused streams, cut codes, 11-bit codes."""
+    fz = _load(os.path.join(ROOT, "tests", "fuzz_lzw_decode.py"), "fuzz_lzw_decode")
+    res = fz.run(seed=seed, streams=512, engine=engine, verbose=False)
+    assert not res["bad"], res["bad"][:5]
+    assert res["n"] == 512 and 0.05 * 512 <= res["refused"] <= 0.25 * 512
+    assert res["cut"] >= 50 and res["wide"] >= 50

@@ -1,6 +1,6 @@
 """GPU decoding of LZW landcover tiles (GCN10_TILE_LZW tiles of gcn10_gpu_inflate_tiles, gcn10_lzw_decode.hip),
 through the C ABI and the status words, against the host reader (tiff.c lzw_decode), PIL's libtiff and the
-reference decoder of tests/test_lzw_input_plan.py; and the gcn10 program end to end on LZW landcover."""
+reference decoder of tests/lzw_model.py; and the gcn10 program end to end on LZW landcover."""
 import os
 import zlib
 
@@ -11,7 +11,7 @@ from PIL import Image
 from gcn10_amd import gpu, host
 from tests import tiffutil
 from tests.test_cli import BLOCKS, ESA_GT, _check_block, _run, _world
-from tests.test_lzw_input_plan import lzw_decode_ref
+from tests.lzw_model import lzw_decode_ref, pack, width_of as _width
 
 pytestmark = pytest.mark.gpu
 GUARD = 16              # zero columns / rows around every tile's window in the destination
@@ -21,28 +21,6 @@ GUARD = 16              # zero columns / rows around every tile's window in the 
 def engine():
     with gpu.Engine(0) as e:
         yield e
-
-
-def _width(n):
-    return 9 if n < 254 else 10 if n < 766 else 11 if n < 1790 else 12
-
-
-def pack(codes):
-    """MSB-first bit packing of a code sequence at the widths the decoder reads them (early change)."""
-    acc, nbits, out, n = 0, 0, bytearray(), 0
-    for c in codes:
-        w = _width(n)
-        assert c < (1 << w)
-        acc = (acc << w) | c
-        nbits += w
-        while nbits >= 8:
-            out.append((acc >> (nbits - 8)) & 0xFF)
-            nbits -= 8
-        acc &= (1 << nbits) - 1
-        n = 0 if c == 256 else n + 1
-    if nbits:
-        out.append((acc << (8 - nbits)) & 0xFF)
-    return bytes(out)
 
 
 def codes_of(data, clear_every=None, clear=True):
@@ -145,9 +123,12 @@ def test_early_eoi_missing_eoi_and_trailing_codes(engine):
     streams = [pack(codes_of(data[:3000]) + [257]),            # early EOI: zeros after 3000 bytes
                pack(codes_of(data[:3000])),                     # no EOI, short: an error
                pack(full),                                      # no EOI, exactly full: fine
-               pack(codes_of(np.concatenate([data, data[:500]])) + [257]),    # codes past out_len: ignored
+               pack(codes_of(np.concatenate([data, np.full(500, data[-1], np.uint8)])) + [257]),   # the last code
+                                                                # is cut by out_len, codes past it: ignored
                pack(full + [bad, bad, 300]),                    # invalid codes past out_len: ignored
                pack(full + [256, 1, 2, 3, 257])]                # a Clear and codes past out_len: ignored
+    last = lzw_decode_ref(streams[3], 8192, trace=True)[1].codes[-1]
+    assert last.cut and last.pos + last.length > 8192 + 8
     chunks, status = run_tiles(engine, streams, [8192] * 6, chunk_w=256)
     assert list(status) == [0, gpu.INFLATE_E_LZW_INPUT, 0, 0, 0, 0]
     assert np.array_equal(chunks[0][:3000], data[:3000]) and not chunks[0][3000:].any()

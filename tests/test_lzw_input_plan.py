@@ -6,55 +6,10 @@ import pytest
 
 from gcn10_amd import host
 from tests import tiffutil
+from tests.lzw_model import lzw_decode_ref  # noqa: F401  (its old home: other tests import it from here)
 
 TILE_RAW, TILE_PREDICTOR2, TILE_LZW = 1, 2, 4
 GT = [-111.0, 0.01, 0.0, 39.0, 0.0, -0.02]
-
-
-def lzw_decode_ref(src: bytes, cap: int) -> bytes:
-    """TIFF LZW as tiff.c lzw_decode reads it: cap bytes out (zeros after an early EOI), codes after cap
-    bytes ignored; ValueError where it fails (a code beyond the dictionary, a first code that is not a
-    literal, input that ends without EOI before cap bytes)."""
-    out = bytearray()
-    table = [bytes([i]) for i in range(256)] + [b"", b""]
-    width, prev = 9, None
-    bits = nbits = ip = 0
-    while True:
-        while nbits < width:
-            if ip >= len(src):
-                if len(out) >= cap:
-                    return bytes(out[:cap])
-                raise ValueError("input ended without EOI")
-            bits = (bits << 8) | src[ip]
-            ip += 1
-            nbits += 8
-        code = (bits >> (nbits - width)) & ((1 << width) - 1)
-        nbits -= width
-        if code == 257:
-            break
-        if code == 256:
-            table = table[:258]
-            width, prev = 9, None
-            continue
-        if prev is None:
-            if code >= 256:
-                raise ValueError("first code is not a literal")
-            out += table[code]
-            prev = code
-        else:
-            nxt = len(table)
-            if code > nxt:
-                raise ValueError("code beyond the dictionary")
-            s = table[prev] + table[prev][:1] if code == nxt else table[code]
-            out += s
-            if nxt < 4096:
-                table.append(table[prev] + s[:1])
-                if len(table) + 1 >= (1 << width) and width < 12:
-                    width += 1
-            prev = code
-        if len(out) >= cap:
-            return bytes(out[:cap])
-    return bytes(out[:cap]) + bytes(max(0, cap - len(out)))
 
 
 def _img(seed, H, W):

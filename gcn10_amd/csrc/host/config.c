@@ -142,6 +142,11 @@ int gcn10_parse_verify(const char *text, int *verify)
     return gcn10_parse_cog(text, verify);      /* the same "0" | "1" */
 }
 
+int gcn10_parse_zonal(const char *text, int *zonal)
+{
+    return gcn10_parse_cog(text, zonal);       /* the same "0" | "1" */
+}
+
 int gcn10_parse_nodata(const char *text, int *nodata)
 {
     int v = 0;
@@ -275,6 +280,25 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             gcn10_config_free(cfg);
             return -3;
         }
+        else if (!strcmp(key, "zonal") && gcn10_parse_zonal(val, &cfg->zonal) != 0) {
+            fclose(f);
+            snprintf(err, errcap, "bad value for zonal: '%s' (0 or 1)", val);
+            gcn10_config_free(cfg);
+            return -3;
+        }
+        else if (!strcmp(key, "zones_shp_path"))
+            rc = set_str(&cfg->zones_shp_path, val);
+        else if (!strcmp(key, "zonal_output"))
+            rc = set_str(&cfg->zonal_output, val);
+        else if (!strcmp(key, "zones_id_field")) {
+            if (!*val || strlen(val) > 10) {        /* a dBASE field name has at most 10 characters */
+                fclose(f);
+                snprintf(err, errcap, "bad value for zones_id_field: '%s' (a .dbf field name, 1..10 characters)", val);
+                gcn10_config_free(cfg);
+                return -3;
+            }
+            rc = set_str(&cfg->zones_id_field, val);
+        }
         if (rc != 0) {
             fclose(f);
             snprintf(err, errcap, "malloc failed for %s", key);     /* src/config.c:71 */
@@ -315,5 +339,8 @@ void gcn10_config_free(gcn10_config *cfg)
     free(cfg->lookup_table_path);
     free(cfg->log_dir);
     free(cfg->esa_tile_dir);
+    free(cfg->zones_shp_path);
+    free(cfg->zones_id_field);
+    free(cfg->zonal_output);
     memset(cfg, 0, sizeof *cfg);
 }

@@ -94,6 +94,8 @@ static void load_once(void)
     /* the raster verifier: needed by verify=1 runs only, which check for it */
     *(void **)(&g_api.verify_strip) = dlsym(h, "gcn10_gpu_verify_strip");
     *(void **)(&g_api.verify_buffers) = dlsym(h, "gcn10_gpu_verify_buffers");
+    /* the pair histogram per zone: needed by zonal=1 runs only, which check for it */
+    *(void **)(&g_api.zonal_pair_histogram) = dlsym(h, "gcn10_gpu_zonal_pair_histogram");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

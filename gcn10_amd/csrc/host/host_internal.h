@@ -74,6 +74,11 @@ int gcn10_tiff_plan_window(struct gcn10_tiff *t, int xoff, int yoff, int xcount,
                            int dst_y, unsigned codecs, struct gcn10_read_plan *plan, char *err, size_t errcap);
 void gcn10_read_plan_free(struct gcn10_read_plan *plan);
 
+/* stats.c: gcn10_raster_histogram over the m nonzero counters of a pair histogram alone -- counter i is n[i] at index
+ * at[i] = bin * 256 + landcover -- for callers that turn one pair histogram into many rasters' (zonal.c) */
+void gcn10_raster_histogram_sparse(const uint16_t *at, const uint64_t *n, size_t m, const uint8_t codes[16],
+                                   const int table[256][5], int drained, uint64_t hist[256]);
+
 /* gpuapi.c: include/gcn10_gpu.h bound with dlopen */
 struct gcn10_gpu_api {
     bool loaded;
@@ -133,6 +138,9 @@ struct gcn10_gpu_api {
     int (*verify_buffers)(gcn10_gpu_ctx *, const uint8_t *const[GCN10_N_RASTERS], size_t,
                           const uint8_t *const[GCN10_N_RASTERS], size_t, int, int, int, unsigned, gcn10_verify_count *,
                           gcn10_stream_t);
+    /* optional: NULL when the library has none (needed by zonal=1 only) */
+    int (*zonal_pair_histogram)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const gcn10_zone_span *,
+                                const gcn10_zone_item *, size_t, int, unsigned long long *, gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

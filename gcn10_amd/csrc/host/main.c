@@ -6,7 +6,8 @@
  * src/main.c:28, while its parser only takes -l, src/main.c:90), --gpus N, and --lookups /
  * --conditions to produce a subset of the 18 rasters (BASELINE config 3: "single lookup"), and --compress to
  * write LZW instead of DEFLATE GeoTIFFs, --stats / --nodata for GDAL band statistics and a NoData tag, and --verify
- * to check the rasters a run has written instead of writing them.
+ * to check the rasters a run has written instead of writing them, and --zonal / --zones for the composite curve
+ * numbers of the polygons of a shapefile instead of rasters.
  * No mpirun: one process drives every GPU of the node.
  */
 #include "gcn10_host.h"
@@ -23,7 +24,7 @@ static void usage(FILE *fp)
             "  gcn10 --config <config.txt> [--blocks <blocks.txt>] [--overwrite] [--gpus <n>]\n"
             "        [--lookups <names>] [--conditions drained|undrained|both] [--compress deflate|lzw]\n"
             "        [--cog] [--overview-resampling nearest|average] [--stats] [--nodata none|<0..255>]\n"
-            "        [--verify]\n"
+            "        [--verify] [--zonal] [--zones <zones.shp>]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -41,6 +42,11 @@ static void usage(FILE *fp)
             "  --verify\t\twrite nothing: decode the rasters that exist on the GPU and compare every pixel with\n"
             "\t\t\tthe value computed now (config key verify=1); exit code 2 = a bad or missing raster,\n"
             "\t\t\ttheir blocks listed in <log_dir>/verify_failed_blocks.txt; not with --overwrite\n"
+            "  --zonal\t\twrite no raster but one table, zonal_cn.csv (config key zonal_output): the composite\n"
+            "\t\t\t(pixel-weighted mean) curve number of every polygon of zones_shp_path and every selected\n"
+            "\t\t\traster, counted on the GPU (config key zonal=1); not with --overwrite or --verify\n"
+            "  --zones <file.shp>\tthe zone polygons, in the landcover's CRS (config key zones_shp_path; the zone id\n"
+            "\t\t\tis the numeric field zones_id_field, default ID); implies --zonal\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -91,6 +97,12 @@ int main(int argc, char **argv)
             opt.nodata = argv[++i];
         else if (!strcmp(argv[i], "--verify"))
             opt.verify = true;
+        else if (!strcmp(argv[i], "--zonal"))
+            opt.zonal = true;
+        else if (!strcmp(argv[i], "--zones") && i + 1 < argc) {
+            opt.zones = argv[++i];
+            opt.zonal = true;
+        }
     }
     return gcn10_run(&opt);
 }

@@ -1031,6 +1031,7 @@ static void worker_teardown(struct worker *w)
     if (w->ctx) {
         g->device_sync(w->ctx);
         gcn10_verify_teardown(w);
+        gcn10_zonal_teardown(w);
         free_strip_buffers(w);
         for (int i = 0; i < w->run->nbuf; i++) {
             struct strip_buf *b = &w->buf[i];
@@ -1203,8 +1204,10 @@ static void *worker_main(void *arg)
         t0 = now_seconds();
         if (r->verify && in->outcome == 1)
             gcn10_verify_block_unreadable(w, in->block_id);
+        if (r->zonal && in->outcome == 1)
+            gcn10_zonal_block_unreadable(w, in->block_id);
         if (in->outcome == 0 && !atomic_load(&r->fatal) &&
-            (r->verify ? gcn10_verify_block(w, in) : encode_block(w, in)) != 0)
+            (r->verify ? gcn10_verify_block(w, in) : r->zonal ? gcn10_zonal_block(w, in) : encode_block(w, in)) != 0)
             atomic_store(&r->fatal, 1);     /* where the reference calls MPI_Abort */
         gcn10_abort_outputs(in);            /* files of a block that was not encoded after all (a no-op otherwise) */
         w->busy_seconds += now_seconds() - t0;
@@ -1508,6 +1511,34 @@ int gcn10_run(const gcn10_run_options *opt)
     for (int k = 0; k < GCN10_N_RASTERS; k++)
         if ((r->cond_mask >> (k / 9)) & 1u && (r->table_mask >> (k % 9)) & 1u)
             r->sel[r->n_sel++] = k;
+    /* a zonal run: refused combinations and the zone file, before any GPU is opened */
+    if (opt->zones) {
+        free(r->cfg.zones_shp_path);
+        r->cfg.zones_shp_path = strdup(opt->zones);
+    }
+    if (opt->zonal)
+        r->cfg.zonal = 1;
+    r->zonal = r->cfg.zonal != 0;
+    if (r->zonal) {
+        const char *why = NULL;
+
+        outer_from_env(&r->outer_rank, &r->outer_size);
+        if (!r->cfg.zones_shp_path || !*r->cfg.zones_shp_path)
+            why = "zonal=1 needs the zone polygons: zones_shp_path=<file.shp> or --zones <file.shp>";
+        else if (opt->overwrite)
+            why = "--zonal writes no raster and cannot be combined with --overwrite";
+        else if (r->verify)
+            why = "--zonal cannot be combined with --verify";
+        else if (r->outer_size > 1)
+            why = "--zonal runs as one process: merging tables across launcher ranks is not supported";
+        if (why)
+            fprintf(stderr, "[rank 0] %s\n", why);
+        if (why || gcn10_zonal_start(r) != 0) {
+            gcn10_config_free(&r->cfg);
+            free(r);
+            return 1;
+        }
+    }
     r->null_sink = sink && strcmp(sink, "null") == 0;
     /* Rows per strip.  Rounds 2 and 3 ran 768 rows (three tile rows of a 36000-px block = 423 tile positions, one round
      * of the fused statistics pass's 512 workgroup slots); larger strips lost end to end to the coarser hand-over between
@@ -1559,6 +1590,11 @@ int gcn10_run(const gcn10_run_options *opt)
     if (r->stats && (!r->gpu->pair_histogram || !r->gpu->pair_histogram_codes ||
                      r->gpu->pair_histogram_codes(r->hist_codes) != GCN10_PAIR_HIST_BINS)) {
         fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_pair_histogram (needed by stats=1)\n", gcn10_gpu_library_path());
+        goto done;
+    }
+    if (r->zonal && (!r->gpu->zonal_pair_histogram || !r->gpu->pair_histogram_codes ||
+                     r->gpu->pair_histogram_codes(r->hist_codes) != GCN10_PAIR_HIST_BINS)) {
+        fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_zonal_pair_histogram (needed by zonal=1)\n", gcn10_gpu_library_path());
         goto done;
     }
     if (r->verify && (!r->gpu->verify_strip || !r->gpu->verify_buffers)) {
@@ -1770,6 +1806,21 @@ int gcn10_run(const gcn10_run_options *opt)
         closing_barrier(r, log0);           /* MPI_Barrier + rank 0's summary, src/main.c:187-194 */
     if (r->verify)
         verify_found = verify_summary(r, log0);
+    if (r->zonal) {
+        double plan = 0, accum = 0;
+        int done_blocks = 0;
+
+        if (gcn10_zonal_finish(r, log0) != 0)
+            atomic_store(&r->fatal, 1);
+        for (int i = 0; i < r->n_workers; i++) {
+            plan += r->workers[i].t_zone_plan;
+            accum += r->workers[i].t_zone_accum;
+            done_blocks += r->workers[i].blocks_done;
+        }
+        snprintf(msg, sizeof msg, "timing: zonal: host seconds building spans %.3f (%.4f per block, on the input side), "
+                 "adding histograms up %.3f", plan, done_blocks > 0 ? plan / done_blocks : 0.0, accum);
+        gcn10_log_message(log0, "INFO", msg, false);
+    }
     {
         int done_blocks = 0;
         double busy = 0, rd = 0, gw = 0, sw = 0, so = 0, cr = 0, fi = 0, dv = 0, steady = 0, iw = 0, ib = 0;
@@ -1924,7 +1975,7 @@ int gcn10_run(const gcn10_run_options *opt)
             gcn10_log_message(log0, "INFO", msg, false);
         }
     }
-    exit_code = atomic_load(&r->fatal) ? 1 : (verify_found > 0 ? 2 : 0);
+    exit_code = atomic_load(&r->fatal) || atomic_load(&r->zonal_incomplete) ? 1 : (verify_found > 0 ? 2 : 0);
 
 done:
     gcn10_pool_destroy(r->pool);
@@ -1935,6 +1986,7 @@ done:
     gcn10_log_close(log0);                              /* finalize_logging, src/main.c:197 */
     free(r->workers);
     free(r->verify_failed);
+    gcn10_zonal_end(r);
     free(r->block_ids);
     gcn10_blocks_free(&r->blocks);
     gcn10_config_free(&r->cfg);

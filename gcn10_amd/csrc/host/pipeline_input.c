@@ -442,9 +442,16 @@ static int fill_block(struct worker *w, struct block_in *in, int block_id)
     /* the block's 18 files, while the copies and the decoder run (the reference creates each raster's file
      * inside save_raster, after computing it: src/raster.c:204; an existing raster of that name is untouched
      * until this one is complete either way: files are written as <name>.part) */
-    if (r->verify) {
-        memset(in->tifs, 0, sizeof in->tifs);       /* a verify run writes nothing */
+    if (r->verify || r->zonal) {
+        memset(in->tifs, 0, sizeof in->tifs);       /* a verify run and a zonal run write no raster */
         in->tifs_ok = false;
+        /* the zones over this block, here on the input side: it overlaps the block before */
+        if (r->zonal && gcn10_zonal_plan_block(w, in, r->blocks.bbox[bi]) != 0) {
+            g->stream_sync(w->in_ctx, w->s_in);
+            for (int k = 0; k < N_RING; k++)
+                w->ring_busy[k] = false;
+            return -1;
+        }
         return 0;
     }
     rc = gcn10_create_outputs(w, in);
@@ -590,6 +597,7 @@ void gcn10_input_teardown(struct worker *w)
             struct block_in *in = &w->in[k];
 
             gcn10_abort_outputs(in);        /* a staged block the worker never took */
+            gcn10_zone_plan_free(&in->zplan);
             if (in->h_coarse) g->host_free(w->in_ctx, in->h_coarse);
             if (in->h_ci) g->host_free(w->in_ctx, in->h_ci);
             if (in->h_cj) g->host_free(w->in_ctx, in->h_cj);

@@ -16,6 +16,8 @@ enum { TILE = 256, MAX_NBUF = 8, DEFAULT_NBUF = 4, DEFAULT_STRIP_ROWS = 2304, MA
 
 struct run;
 struct gcn10_verify_state;
+struct gcn10_zonal_state;
+struct gcn10_zonal_table;
 
 /* one rotating set of strip buffers */
 struct strip_buf {
@@ -75,6 +77,7 @@ struct block_in {
      * the input side while the block before is encoded: 18 open + truncate calls are 5-10 ms per block */
     gcn10_tiff_writer *tifs[GCN10_N_RASTERS];
     bool tifs_ok;                           /* all of the run's rasters have their file */
+    gcn10_zone_plan zplan;                  /* zonal=1: the zones' spans and items over this block (zones.c) */
 };
 
 struct worker {
@@ -133,6 +136,8 @@ struct worker {
     unsigned long long *d_hist, *h_hist;    /* GCN10_PAIR_HIST_SIZE counters; h_hist pinned */
     size_t d_hist_cap, h_hist_cap;
     struct gcn10_verify_state *verify;      /* verify=1: the worker's decode buffers and counters (verify.c) */
+    struct gcn10_zonal_state *zonal;        /* zonal=1: the worker's span, item and histogram buffers (zonal.c) */
+    double t_zone_plan, t_zone_accum;       /* ... seconds of the input side building spans, of the worker adding up */
     long n_win_gpu, n_win_gpu_lzw, n_win_host;  /* landcover windows through the GPU decoder (of them with LZW chunks),
                                                    through the host reader */
 };
@@ -184,6 +189,11 @@ struct run {
     pthread_mutex_t verify_mu;
     int *verify_failed;                     /* ids of the blocks with a bad or missing file, in the order found */
     int verify_n_failed, verify_failed_cap;
+    /* zonal=1: nothing is written but the table of composite curve numbers per zone (zonal.c) */
+    bool zonal;
+    gcn10_zones zones;
+    struct gcn10_zonal_table *zonal_table;
+    atomic_int zonal_incomplete;            /* a block's inputs could not be read: the table lacks it, exit code 1 */
 };
 
 double gcn10_now_seconds(void);
@@ -209,6 +219,16 @@ void gcn10_abort_outputs(struct block_in *in);
 int gcn10_verify_block(struct worker *w, struct block_in *in);
 void gcn10_verify_block_unreadable(struct worker *w, int block_id);
 void gcn10_verify_teardown(struct worker *w);
+/* zonal.c: the zones and the table of the run (start: before any GPU is opened; finish: the table and the closing
+ * line; end: frees both); the spans of a staged block, made by the input side; a staged block counted (0, or -1 for
+ * errors that end the run); a block whose inputs could not be staged; the worker's zonal buffers */
+int gcn10_zonal_start(struct run *r);
+int gcn10_zonal_finish(struct run *r, gcn10_log *log0);
+void gcn10_zonal_end(struct run *r);
+int gcn10_zonal_plan_block(struct worker *w, struct block_in *in, const double own[4]);
+int gcn10_zonal_block(struct worker *w, struct block_in *in);
+void gcn10_zonal_block_unreadable(struct worker *w, int block_id);
+void gcn10_zonal_teardown(struct worker *w);
 int gcn10_input_setup(struct worker *w);
 void gcn10_input_teardown(struct worker *w);
 int gcn10_input_start(struct worker *w);

@@ -9,10 +9,18 @@
  * percent "%.4g").  GDAL is not used here, so this formatting is pinned by tests/test_stats_host.py.
  */
 #include "gcn10_host.h"
+#include "host_internal.h"
 
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+
+/* the value of a (landcover, soil plane) pair: src/cn.c:114-131 with the 255 pre-fill of src/cn.c:289: only values
+ * < 255 are stored, as (uint8_t) */
+static inline int pair_value(const int table[256][5], int lc, int plane)
+{
+    return plane < 5 && table[lc][plane] < 255 ? (uint8_t)table[lc][plane] : 255;
+}
 
 void gcn10_raster_histogram(const uint64_t *pair, const uint8_t codes[16], const int table[256][5], int drained,
                             uint64_t hist[256])
@@ -23,15 +31,21 @@ void gcn10_raster_histogram(const uint64_t *pair, const uint8_t codes[16], const
 
         for (int lc = 0; lc < 256; lc++) {
             const uint64_t n = pair[b * 256 + lc];
-            int v = 255;
 
-            if (!n)
-                continue;
-            /* src/cn.c:114-131 with the 255 pre-fill of src/cn.c:289: only values < 255 are stored, as (uint8_t) */
-            if (plane < 5 && table[lc][plane] < 255)
-                v = (uint8_t)table[lc][plane];
-            hist[v] += n;
+            if (n)
+                hist[pair_value(table, lc, plane)] += n;
         }
+    }
+}
+
+void gcn10_raster_histogram_sparse(const uint16_t *at, const uint64_t *n, size_t m, const uint8_t codes[16],
+                                   const int table[256][5], int drained, uint64_t hist[256])
+{
+    memset(hist, 0, 256 * sizeof *hist);
+    for (size_t i = 0; i < m; i++) {
+        const int b = at[i] >> 8, plane = drained ? (codes[b] & 15) : (codes[b] >> 4);
+
+        hist[pair_value(table, at[i] & 255, plane)] += n[i];
     }
 }
 

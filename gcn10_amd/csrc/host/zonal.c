@@ -1,0 +1,350 @@
+/* zonal.c -- composite curve numbers per zone (config key "zonal", --zonal / --zones): no counterpart in the reference.
+ *
+ * A zonal run writes no raster.  Every block is staged as for a write run (input thread, GPU inflate, prepare_tile);
+ * the input side also scan-converts the zones over the block (zones.c), so that this overlaps the block before.  The
+ * worker uploads the spans and items from pinned memory, runs gcn10_gpu_zonal_pair_histogram over the decoded
+ * landcover block, and takes the local zones' pair histograms back -- in batches, so that device and pinned memory
+ * stay bounded whatever the shapefile holds.  The host turns a zone's pair histogram into the selected rasters'
+ * histograms (gcn10_raster_histogram) and adds pixels, valid pixels (value != 255, whatever "nodata" says: 255 is
+ * never a curve number), sum, sum of squares, min and max into one table of the whole process.  All of it is
+ * integers, so the table does not depend on the order in which the workers of all GPUs add to it.
+ */
+#include "pipeline_internal.h"
+
+#include <limits.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+
+#define wlog gcn10_wlog
+
+/* Zones and spans of one kernel call.  1024 zones are 32 MiB of pair histograms on the device and as much pinned
+ * memory per worker, 2^20 spans another 16 MiB; a block with more is done in several calls (a zone may be cut between
+ * two of them: everything the table keeps adds up).  The batch is sized by memory, not by time: a call over 1 000
+ * zones takes 0.06 ms and one over 100 000 zones 0.5 ms (profiles/zonal/kernel_bounds.json, "small_zones"), 5 us per
+ * 1 000 zones either way, so a larger batch would save microseconds per block.  What a block costs on the host is
+ * not measured yet (DESIGN.md "Zonal composites"). */
+enum { ZONE_BATCH = 1024, SPAN_BATCH = 1 << 20 };
+
+struct zcell {
+    uint64_t pixels, valid, sum, sum2;
+    int min, max;
+};
+
+struct gcn10_zonal_table {
+    pthread_mutex_t mu;
+    struct zcell *cell;         /* [zones.n][n_sel] */
+    int blocks;                 /* blocks counted */
+};
+
+struct gcn10_zonal_state {
+    gcn10_zone_span *h_spans, *d_spans;     /* h_* pinned */
+    gcn10_zone_item *h_items, *d_items;
+    unsigned long long *h_hist, *d_hist;
+    size_t h_spans_cap, d_spans_cap, h_items_cap, d_items_cap, h_hist_cap, d_hist_cap;
+    struct zcell *part;                     /* [ZONE_BATCH][n_sel]: a batch, before it goes into the table */
+};
+
+int gcn10_zonal_start(struct run *r)
+{
+    char err[1024] = "";
+    struct gcn10_zonal_table *t;
+
+    if (gcn10_zones_open(r->cfg.zones_shp_path, r->cfg.zones_id_field, &r->zones, err, sizeof err) != 0) {
+        fprintf(stderr, "[rank 0] %s\n", err);
+        return -1;
+    }
+    t = calloc(1, sizeof *t);
+    if (t)
+        t->cell = calloc((size_t)(r->zones.n > 0 ? r->zones.n : 1) * (size_t)(r->n_sel > 0 ? r->n_sel : 1), sizeof *t->cell);
+    if (!t || !t->cell) {
+        fprintf(stderr, "[rank 0] out of memory for the table of %d zones\n", r->zones.n);
+        free(t);
+        gcn10_zones_free(&r->zones);
+        return -1;
+    }
+    for (size_t i = 0; i < (size_t)r->zones.n * (size_t)r->n_sel; i++) {
+        t->cell[i].min = 255;
+        t->cell[i].max = 0;
+    }
+    pthread_mutex_init(&t->mu, NULL);
+    r->zonal_table = t;
+    return 0;
+}
+
+void gcn10_zonal_teardown(struct worker *w)
+{
+    const struct gcn10_gpu_api *g = w->run->gpu;
+    struct gcn10_zonal_state *z = w->zonal;
+
+    if (!z)
+        return;
+    if (w->ctx) {
+        if (z->h_spans) g->host_free(w->ctx, z->h_spans);
+        if (z->h_items) g->host_free(w->ctx, z->h_items);
+        if (z->h_hist) g->host_free(w->ctx, z->h_hist);
+        if (z->d_spans) g->free(w->ctx, z->d_spans);
+        if (z->d_items) g->free(w->ctx, z->d_items);
+        if (z->d_hist) g->free(w->ctx, z->d_hist);
+    }
+    free(z->part);
+    free(z);
+    w->zonal = NULL;
+}
+
+void gcn10_zonal_block_unreadable(struct worker *w, int block_id)
+{
+    wlog(w, "ERROR", true, "zonal block %d: its landcover or soil window could not be read; the table lacks this block",
+         block_id);
+    atomic_store(&w->run->zonal_incomplete, 1);
+}
+
+/* the input side: the zones over the staged block, while the block before is counted */
+int gcn10_zonal_plan_block(struct worker *w, struct block_in *in, const double own[4])
+{
+    struct run *r = w->run;
+    char err[1024] = "";
+    const double t0 = gcn10_now_seconds();
+
+    gcn10_zone_plan_free(&in->zplan);
+    if (gcn10_zones_build_plan(&r->zones, in->gt, in->W, in->H, own, 0, 0, &in->zplan, err, sizeof err) != 0) {
+        wlog(w, "ERROR", true, "zonal block %d: %s", in->block_id, err);
+        return -1;
+    }
+    w->t_zone_plan += gcn10_now_seconds() - t0;
+    return 0;
+}
+
+/* one zone's pair histogram into the cells of the selected rasters: gcn10_raster_histogram, over the nonzero counters
+ * only (a zone holds a few dozen of the 4096 pairs, and there are up to 18 rasters per zone) */
+static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *cell)
+{
+    uint16_t at[GCN10_PAIR_HIST_SIZE];
+    uint64_t n[GCN10_PAIR_HIST_SIZE];
+    size_t m = 0;
+
+    for (int i = 0; i < GCN10_PAIR_HIST_SIZE; i++)
+        if (pair[i]) {
+            at[m] = (uint16_t)i;
+            n[m++] = pair[i];
+        }
+    for (int q = 0; q < r->n_sel; q++) {
+        const int k = r->sel[q];
+        struct zcell *c = &cell[q];
+        uint64_t hist[256];
+
+        gcn10_raster_histogram_sparse(at, n, m, r->hist_codes, r->tables[k % 9], k / 9 == 0, hist);
+        c->pixels = c->valid = c->sum = c->sum2 = 0;
+        c->min = 255;
+        c->max = 0;
+        for (int v = 0; v < 256; v++) {
+            if (!hist[v])
+                continue;
+            c->pixels += hist[v];
+            if (v == GCN10_NODATA)
+                continue;
+            c->valid += hist[v];
+            c->sum += hist[v] * (uint64_t)v;
+            c->sum2 += hist[v] * (uint64_t)(v * v);
+            if (v < c->min)
+                c->min = v;
+            if (v > c->max)
+                c->max = v;
+        }
+    }
+}
+
+int gcn10_zonal_block(struct worker *w, struct block_in *in)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    const gcn10_zone_plan *p = &in->zplan;
+    struct gcn10_zonal_table *t = r->zonal_table;
+    struct gcn10_zonal_state *z;
+    const size_t row = (size_t)GCN10_PAIR_HIST_SIZE;
+    bool prepared = false;
+
+    if (!w->zonal) {
+        w->zonal = calloc(1, sizeof *w->zonal);
+        if (w->zonal)
+            w->zonal->part = calloc((size_t)ZONE_BATCH * (size_t)(r->n_sel > 0 ? r->n_sel : 1), sizeof *w->zonal->part);
+        if (!w->zonal || !w->zonal->part) {
+            wlog(w, "ERROR", true, "out of memory for the zonal buffers");
+            return -1;
+        }
+    }
+    z = w->zonal;
+
+    /* the block on the device, as for a write run */
+    if (g->stream_wait_event(w->ctx, w->s_kernel, in->ev_ready) != 0)
+        goto gpu_fail;
+    if (in->n_inflate > 0) {
+        if (g->event_sync(w->ctx, in->ev_ready) != 0)
+            goto gpu_fail;
+        for (size_t i = 0; i < in->n_inflate; i++)
+            if (in->h_status[i] != 0) {
+                wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
+                                       "(stream %zu, reason %u)", in->xoff, in->yoff, in->W, in->H, i, in->h_status[i]);
+                wlog(w, "ERROR", true, "esa load failed for block %d", in->block_id);
+                gcn10_zonal_block_unreadable(w, in->block_id);
+                return 0;
+            }
+    }
+    wlog(w, "INFO", false, "zonal block %d: %d zones, %zu spans", in->block_id, p->n_local, p->n_spans);
+
+    /* batches of items: at most ZONE_BATCH zones and SPAN_BATCH spans each (one item at least) */
+    for (size_t i0 = 0; i0 < p->n_items;) {
+        const size_t s0 = p->items[i0].first_span;
+        const int zone0 = p->spans[s0].zone;
+        size_t i1 = i0, s1 = s0;
+        int nz;
+
+        while (i1 < p->n_items) {
+            const gcn10_zone_item *it = &p->items[i1];
+
+            if (i1 > i0 && (p->spans[it->first_span].zone - zone0 >= ZONE_BATCH ||
+                            it->first_span + it->n_spans - s0 > SPAN_BATCH))
+                break;
+            s1 = (size_t)it->first_span + it->n_spans;
+            i1++;
+        }
+        nz = p->spans[s1 - 1].zone - zone0 + 1;
+
+        if (gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_spans, &z->h_spans_cap, (s1 - s0) * sizeof *z->h_spans) != 0 ||
+            gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_items, &z->h_items_cap, (i1 - i0) * sizeof *z->h_items) != 0 ||
+            gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_hist, &z->h_hist_cap, (size_t)nz * row * sizeof *z->h_hist) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_spans, &z->d_spans_cap, (s1 - s0) * sizeof *z->d_spans) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_items, &z->d_items_cap, (i1 - i0) * sizeof *z->d_items) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_hist, &z->d_hist_cap, (size_t)nz * row * sizeof *z->d_hist) != 0)
+            return -1;
+        for (size_t s = s0; s < s1; s++) {
+            z->h_spans[s - s0] = p->spans[s];
+            z->h_spans[s - s0].zone -= zone0;
+        }
+        for (size_t i = i0; i < i1; i++) {
+            z->h_items[i - i0] = p->items[i];
+            z->h_items[i - i0].first_span -= (uint32_t)s0;
+        }
+        if (!prepared) {
+            if (g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, in->W, w->s_kernel) != 0)
+                goto gpu_fail;
+            prepared = true;
+        }
+        if (g->memcpy_h2d(w->ctx, z->d_spans, z->h_spans, (s1 - s0) * sizeof *z->h_spans, w->s_kernel) != 0 ||
+            g->memcpy_h2d(w->ctx, z->d_items, z->h_items, (i1 - i0) * sizeof *z->h_items, w->s_kernel) != 0 ||
+            g->memset(w->ctx, z->d_hist, 0, (size_t)nz * row * sizeof *z->d_hist, w->s_kernel) != 0 ||
+            g->zonal_pair_histogram(w->ctx, in->d_block, in->W, in->H, in->d_cj, z->d_spans, z->d_items, i1 - i0, nz,
+                                    z->d_hist, w->s_kernel) != 0 ||
+            g->memcpy_d2h(w->ctx, z->h_hist, z->d_hist, (size_t)nz * row * sizeof *z->h_hist, w->s_kernel) != 0)
+            goto gpu_fail;
+        {
+            const double t0 = gcn10_now_seconds();
+
+            if (g->stream_sync(w->ctx, w->s_kernel) != 0)
+                goto gpu_fail;
+            w->t_gpu_wait += gcn10_now_seconds() - t0;
+        }
+        {
+            const double t0 = gcn10_now_seconds();
+
+            for (int k = 0; k < nz; k++)
+                cells_of(r, (const uint64_t *)z->h_hist + (size_t)k * row, &z->part[(size_t)k * (size_t)r->n_sel]);
+            pthread_mutex_lock(&t->mu);
+            for (int k = 0; k < nz; k++) {
+                struct zcell *dst = &t->cell[(size_t)p->local_zone[zone0 + k] * (size_t)r->n_sel];
+                const struct zcell *src = &z->part[(size_t)k * (size_t)r->n_sel];
+
+                for (int q = 0; q < r->n_sel; q++) {
+                    dst[q].pixels += src[q].pixels;
+                    dst[q].valid += src[q].valid;
+                    dst[q].sum += src[q].sum;
+                    dst[q].sum2 += src[q].sum2;
+                    if (src[q].valid && src[q].min < dst[q].min)
+                        dst[q].min = src[q].min;
+                    if (src[q].valid && src[q].max > dst[q].max)
+                        dst[q].max = src[q].max;
+                }
+            }
+            pthread_mutex_unlock(&t->mu);
+            w->t_zone_accum += gcn10_now_seconds() - t0;
+        }
+        i0 = i1;
+    }
+    pthread_mutex_lock(&t->mu);
+    t->blocks++;
+    pthread_mutex_unlock(&t->mu);
+    return 0;
+
+gpu_fail:
+    wlog(w, "ERROR", true, "gpu: %s", g->last_error());
+    if (w->ctx)
+        g->stream_sync(w->ctx, w->s_kernel);
+    return -1;
+}
+
+/* The table, through a temporary name and rename, and the closing console line.  0, or -1 when it could not be written. */
+int gcn10_zonal_finish(struct run *r, gcn10_log *log0)
+{
+    struct gcn10_zonal_table *t = r->zonal_table;
+    const char *path = r->cfg.zonal_output && *r->cfg.zonal_output ? r->cfg.zonal_output : "zonal_cn.csv";
+    char tmp[PATH_MAX], msg[PATH_MAX + 256];
+    int without = 0, rc = -1;
+    FILE *f;
+
+    snprintf(tmp, sizeof tmp, "%s.part.%ld", path, (long)getpid());
+    f = fopen(tmp, "w");
+    if (f) {
+        fprintf(f, "zone_id,condition,hc,arc,pixels,valid,sum,mean,min,max,stddev\n");
+        for (int i = 0; i < r->zones.n; i++) {
+            if (r->n_sel > 0 && t->cell[(size_t)i * (size_t)r->n_sel].pixels == 0)
+                without++;
+            for (int q = 0; q < r->n_sel; q++) {
+                const struct zcell *c = &t->cell[(size_t)i * (size_t)r->n_sel + (size_t)q];
+                const int k = r->sel[q];
+
+                fprintf(f, "%lld,%s,%s,%s,%llu,%llu,%llu,", (long long)r->zones.id[i], gcn10_conds[k / 9],
+                        gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3], (unsigned long long)c->pixels,
+                        (unsigned long long)c->valid, (unsigned long long)c->sum);
+                if (c->valid) {
+                    /* the mean and the population standard deviation as gcn10_band_stats_of forms them */
+                    const unsigned __int128 var = (unsigned __int128)c->sum2 * c->valid - (unsigned __int128)c->sum * c->sum;
+
+                    fprintf(f, "%.14g,%d,%d,%.14g\n", (double)c->sum / (double)c->valid, c->min, c->max,
+                            sqrt((double)var) / (double)c->valid);
+                }
+                else {
+                    fprintf(f, ",,,\n");
+                }
+            }
+        }
+        {
+            const bool bad = fflush(f) != 0 || ferror(f);
+
+            if (fclose(f) == 0 && !bad && rename(tmp, path) == 0)
+                rc = 0;
+            else
+                unlink(tmp);
+        }
+    }
+    if (rc != 0) {
+        snprintf(msg, sizeof msg, "zonal: cannot write the table %s", path);
+        gcn10_log_message(log0, "ERROR", msg, true);
+        return -1;
+    }
+    snprintf(msg, sizeof msg, "zonal: %d blocks, %d zones, %d without pixels, table %s", t->blocks, r->zones.n, without, path);
+    gcn10_log_message(log0, "INFO", msg, true);
+    return 0;
+}
+
+void gcn10_zonal_end(struct run *r)
+{
+    if (r->zonal_table) {
+        pthread_mutex_destroy(&r->zonal_table->mu);
+        free(r->zonal_table->cell);
+        free(r->zonal_table);
+        r->zonal_table = NULL;
+    }
+    gcn10_zones_free(&r->zones);
+}

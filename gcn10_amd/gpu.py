@@ -45,7 +45,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_soil_words_state", "gcn10_gpu_lzw_arena_bound", "gcn10_gpu_lzw_strip",
     "gcn10_gpu_inflate_codecs", "gcn10_gpu_overview_nearest", "gcn10_gpu_overview_average",
     "gcn10_gpu_pair_histogram_codes", "gcn10_gpu_pair_histogram",
-    "gcn10_gpu_verify_strip", "gcn10_gpu_verify_buffers",
+    "gcn10_gpu_verify_strip", "gcn10_gpu_verify_buffers", "gcn10_gpu_zonal_pair_histogram",
 )
 
 
@@ -141,6 +141,7 @@ def lib():
             "gcn10_gpu_pair_histogram": (i, [vp, vp, i, i, vp, vp, vp]),
             "gcn10_gpu_verify_strip": (i, [vp, vp, i, i, vp, C.c_uint, C.c_uint, vp, sz, i, vp, vp]),
             "gcn10_gpu_verify_buffers": (i, [vp, vp, sz, vp, sz, i, i, i, C.c_uint, vp, vp]),
+            "gcn10_gpu_zonal_pair_histogram": (i, [vp, vp, i, i, vp, vp, vp, sz, i, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -405,6 +406,41 @@ class Engine:
         arr = (C.c_void_p * len(level_ptrs))(*[int(p) for p in level_ptrs])
         self._chk(lib().gcn10_gpu_overview_average(self._ctx, esa_ptr, W, H, y0, rows, cj_ptr, cond_mask, table_mask,
                                                    n_levels, arr, stream), "gcn10_gpu_overview_average")
+
+    def zonal_pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans, items, n_zones: int,
+                             hist_ptr: int, stream=None):
+        """ADDS the pair counts of the pixels of every span to hist[zone] ([n_zones][16][256] uint64 on the device) with
+        the soil codes prepare_tile prepared for width W (gcn10_gpu_zonal_pair_histogram).  spans (host.ZONE_SPAN_DTYPE,
+        sorted by zone) and items (host.ZONE_ITEM_DTYPE), as host.Zones.build_plan / host.zone_items make them, are
+        checked here -- the kernel trusts them --, uploaded, and freed when the call has run."""
+        sp = np.ascontiguousarray(spans, dtype=_host.ZONE_SPAN_DTYPE)
+        it = np.ascontiguousarray(items, dtype=_host.ZONE_ITEM_DTYPE)
+        if sp.size and not ((sp["y"] >= 0).all() and (sp["y"] < rows).all() and (sp["x0"] >= 0).all() and
+                            (sp["x0"] < sp["x1"]).all() and (sp["x1"] <= W).all() and (sp["zone"] >= 0).all() and
+                            (sp["zone"] < n_zones).all()):
+            raise ValueError("a span lies outside the %d x %d strip or its zone outside 0..%d" % (W, rows, n_zones - 1))
+        first, n = it["first_span"].astype(np.int64), it["n_spans"].astype(np.int64)
+        if it.size and not ((n > 0).all() and first[0] == 0 and (first[1:] == (first + n)[:-1]).all() and
+                            int(first[-1] + n[-1]) == sp.size and
+                            all(len(set(sp["zone"][a:a + m].tolist())) == 1 for a, m in zip(first, n))):
+            raise ValueError("the items must name every span once, in order, each item the spans of one zone")
+        if it.size == 0 and sp.size:
+            raise ValueError("spans without items")
+        bufs = [self.upload(sp), self.upload(it)] if it.size else []
+        try:
+            self.zonal_pair_histogram_device(esa_ptr, W, rows, cj_ptr, bufs[0].ptr if bufs else None,
+                                             bufs[1].ptr if bufs else None, it.size, n_zones, hist_ptr, stream)
+            self.sync(stream)
+        finally:
+            for b in bufs:
+                b.close()
+
+    def zonal_pair_histogram_device(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans_ptr, items_ptr,
+                                    n_items: int, n_zones: int, hist_ptr: int, stream=None):
+        """gcn10_gpu_zonal_pair_histogram over spans and items that are on the device already: asynchronous on `stream`
+        and UNCHECKED -- for spans and items that zonal_pair_histogram has taken once, launched again (timing)."""
+        self._chk(lib().gcn10_gpu_zonal_pair_histogram(self._ctx, esa_ptr, W, rows, cj_ptr, spans_ptr, items_ptr, n_items,
+                                                       n_zones, hist_ptr, stream), "gcn10_gpu_zonal_pair_histogram")
 
     def pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, hist_ptr: int, stream=None):
         """Adds the (landcover, soil code) pair counts of a W x rows device strip to the device histogram hist_ptr

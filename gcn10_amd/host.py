@@ -116,6 +116,17 @@ def lib():
         L.gcn10_stats_xml.restype = C.c_size_t
         L.gcn10_tiff_finish.argtypes = [vp, cp, C.c_size_t]
         L.gcn10_tiff_finish.restype = C.c_int
+        L.gcn10_zones_open.argtypes = [cp, cp, C.POINTER(ZonesStruct), cp, C.c_size_t]
+        L.gcn10_zones_open.restype = C.c_int
+        L.gcn10_zones_free.argtypes = [C.POINTER(ZonesStruct)]
+        L.gcn10_zones_free.restype = None
+        L.gcn10_zones_build_plan.argtypes = [C.POINTER(ZonesStruct), _f64p, C.c_int, C.c_int, vp, C.c_uint32,
+                                             C.c_uint32, C.POINTER(ZonePlan), cp, C.c_size_t]
+        L.gcn10_zones_build_plan.restype = C.c_int
+        L.gcn10_zone_plan_free.argtypes = [C.POINTER(ZonePlan)]
+        L.gcn10_zone_plan_free.restype = None
+        L.gcn10_zone_items_build.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(ZonePlan)]
+        L.gcn10_zone_items_build.restype = C.c_int
         L.gcn10_tiff_abort.argtypes = [vp]
         L.gcn10_tiff_abort.restype = None
         L.free_ = C.CDLL(None).free
@@ -143,7 +154,8 @@ class ConfigFull(Config):
     """The whole ``gcn10_config``: ``Config`` is the struct as it stood when the statistics keys were added (its
     field list is pinned by the tests of that change); fields appended to the C struct since then are appended here.
     ``Config`` ends on a multiple of 8 bytes, so the fields below lie where the C compiler puts them."""
-    _fields_ = [("verify", C.c_int)]
+    _fields_ = [("verify", C.c_int), ("zonal", C.c_int), ("zones_shp_path", C.c_char_p),
+                ("zones_id_field", C.c_char_p), ("zonal_output", C.c_char_p)]
 
 
 assert C.sizeof(Config) % 8 == 0
@@ -159,8 +171,110 @@ class Blocks(C.Structure):
     _fields_ = [("n", C.c_int), ("id", C.POINTER(C.c_int)), ("bbox", C.POINTER(C.c_double * 4))]
 
 
+class ZonesStruct(C.Structure):
+    """``gcn10_zones`` of include/gcn10_host.h."""
+    _fields_ = [("n", C.c_int), ("id", C.POINTER(C.c_int64)), ("bbox", C.POINTER(C.c_double * 4)),
+                ("ring_first", C.POINTER(C.c_uint64)), ("ring_pt", C.POINTER(C.c_uint64)),
+                ("xy", C.POINTER(C.c_double)), ("n_rings", C.c_uint64), ("n_points", C.c_uint64)]
+
+
+class ZonePlan(C.Structure):
+    """``gcn10_zone_plan`` of include/gcn10_host.h."""
+    _fields_ = [("n_local", C.c_int), ("local_zone", C.POINTER(C.c_int32)), ("local_pixels", C.POINTER(C.c_uint64)),
+                ("n_spans", C.c_size_t), ("n_items", C.c_size_t), ("spans", C.c_void_p), ("items", C.c_void_p)]
+
+
+# struct gcn10_zone_span / gcn10_zone_item (include/gcn10_host.h, include/gcn10_gpu.h)
+ZONE_SPAN_DTYPE = np.dtype([("y", "<i4"), ("x0", "<i4"), ("x1", "<i4"), ("zone", "<i4")])
+ZONE_ITEM_DTYPE = np.dtype([("first_span", "<u4"), ("n_spans", "<u4")])
+
+
 class HostError(RuntimeError):
     pass
+
+
+def _copy(ptr, n, dtype):
+    """n elements of dtype at a ctypes pointer / address, copied."""
+    n = int(n)
+    if n == 0 or not ptr:
+        return np.zeros(0, dtype)
+    addr = ptr if isinstance(ptr, int) else C.cast(ptr, C.c_void_p).value
+    nbytes = n * np.dtype(dtype).itemsize
+    return np.frombuffer(C.string_at(addr, nbytes), dtype=dtype).copy()
+
+
+def _plan_out(plan: ZonePlan) -> dict:
+    out = {"local_zone": _copy(plan.local_zone, plan.n_local, np.int32),
+           "local_pixels": _copy(plan.local_pixels, plan.n_local, np.uint64),
+           "spans": _copy(plan.spans, plan.n_spans, ZONE_SPAN_DTYPE),
+           "items": _copy(plan.items, plan.n_items, ZONE_ITEM_DTYPE)}
+    lib().gcn10_zone_plan_free(C.byref(plan))
+    return out
+
+
+class Zones:
+    """A polygon shapefile of zones (``gcn10_zones_open``): ``ids`` (int64), ``bbox`` (float64[n,4]), ``ring_first``
+    (rings of record i: ring_first[i] .. ring_first[i+1]), ``ring_pt`` (points of ring k: ring_pt[k] .. ring_pt[k+1])
+    and ``xy`` (float64[n_points,2])."""
+
+    def __init__(self, path: str, id_field: str | None = None):
+        self._z = ZonesStruct()
+        err = C.create_string_buffer(1024)
+        if lib().gcn10_zones_open(os.fsencode(path), id_field.encode() if id_field else None, C.byref(self._z),
+                                  err, 1024) != 0:
+            self._z = None
+            raise HostError(err.value.decode(errors="replace"))
+        z = self._z
+        self.n = z.n
+        self.ids = _copy(z.id, z.n, np.int64)
+        self.bbox = _copy(z.bbox, z.n * 4, np.float64).reshape(z.n, 4)
+        self.ring_first = _copy(z.ring_first, z.n + 1, np.uint64)
+        self.ring_pt = _copy(z.ring_pt, z.n_rings + 1, np.uint64)
+        self.xy = _copy(z.xy, z.n_points * 2, np.float64).reshape(-1, 2)
+
+    def n_rings(self, i: int) -> int:
+        return int(self.ring_first[i + 1] - self.ring_first[i])
+
+    def rings(self, i: int):
+        """The rings of record i, float64[m,2] each."""
+        return [self.xy[int(self.ring_pt[k]):int(self.ring_pt[k + 1])]
+                for k in range(int(self.ring_first[i]), int(self.ring_first[i + 1]))]
+
+    def build_plan(self, gt, W: int, H: int, own=None, max_span_px: int = 0, max_item_px: int = 0) -> dict:
+        """Spans and work items of the zones over a block (``gcn10_zones_build_plan``): ``local_zone``, ``local_pixels``,
+        ``spans`` (ZONE_SPAN_DTYPE) and ``items`` (ZONE_ITEM_DTYPE)."""
+        plan = ZonePlan()
+        err = C.create_string_buffer(1024)
+        o = None if own is None else _f(own, 4)
+        rc = lib().gcn10_zones_build_plan(C.byref(self._z), _f(gt, 6), int(W), int(H),
+                                          None if o is None else o.ctypes.data, int(max_span_px), int(max_item_px),
+                                          C.byref(plan), err, 1024)
+        if rc != 0:
+            raise HostError(err.value.decode(errors="replace"))
+        return _plan_out(plan)
+
+    def close(self):
+        if self._z is not None:
+            lib().gcn10_zones_free(C.byref(self._z))
+            self._z = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def zone_items(spans, max_span_px: int = 0, max_item_px: int = 0):
+    """Spans sorted by (zone, y, x0) -> (spans split at max_span_px, items of at most max_item_px pixels)
+    (``gcn10_zone_items_build``; 0 = the built-in bounds)."""
+    a = np.ascontiguousarray(spans, dtype=ZONE_SPAN_DTYPE)
+    plan = ZonePlan()
+    if lib().gcn10_zone_items_build(a.ctypes.data if a.size else None, a.size, int(max_span_px), int(max_item_px),
+                                    C.byref(plan)) != 0:
+        raise HostError("gcn10_zone_items_build: an empty span, or out of memory")
+    out = _plan_out(plan)
+    return out["spans"], out["items"]
 
 
 def parse_config(path: str) -> dict:

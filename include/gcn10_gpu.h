@@ -39,7 +39,8 @@ extern "C" {
  *    the extents' pads (round 3).  A caller built against an older header must be rebuilt: check at start-up.
  *    Added within 3: the LZW encoder (gcn10_gpu_lzw_*), LZW tiles of gcn10_gpu_inflate_tiles (GCN10_TILE_LZW)
  *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*); the pair histogram
- *    of the band statistics (gcn10_gpu_pair_histogram*); the raster verifier (gcn10_gpu_verify_*).
+ *    of the band statistics (gcn10_gpu_pair_histogram*); the raster verifier (gcn10_gpu_verify_*); the pair histogram
+ *    per zone of the zonal composites (gcn10_gpu_zonal_pair_histogram).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -323,6 +324,29 @@ int gcn10_gpu_overview_average(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, in
 int gcn10_gpu_pair_histogram_codes(uint8_t codes[GCN10_PAIR_HIST_BINS]);
 int gcn10_gpu_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
                              unsigned long long *hist_dev, gcn10_stream_t stream);
+
+/* Composite curve numbers per zone (config key zonal=1): the same pair counts restricted to the pixels of zones.  Added
+ * in ABI 3 without a version change; the host looks it up for zonal runs only.
+ *
+ * gcn10_gpu_zonal_pair_histogram: ADDS to hist_dev[zone * GCN10_PAIR_HIST_SIZE + bin * 256 + landcover] the pair counts
+ *   of the pixels of every span -- columns [x0, x1) of row y, y relative to esa's first row.  esa, W, rows, cj, the
+ *   soil prepared by gcn10_gpu_prepare_tile, the bin layout and the 64-bit counters are exactly those of
+ *   gcn10_gpu_pair_histogram.  spans_dev is sorted by zone; items_dev[i] names n_spans consecutive spans of ONE zone
+ *   from first_span on, and together the items name every span once (gcn10_zones_build_plan / gcn10_zone_items_build
+ *   of gcn10_host.h make both; a workgroup takes a contiguous run of items).  The caller guarantees 0 <= y < rows,
+ *   0 <= x0 < x1 <= W and 0 <= zone < n_zones: the kernel does not check them.  n_items == 0 is a successful no-op.
+ *   Asynchronous on `stream`; clear hist_dev once (gcn10_gpu_memset).  Pixels named by two spans count twice.  A workgroup
+ *   counts a zone in 32-bit words until the zone changes, so the spans of one zone in one call name fewer than 2^32
+ *   pixels in all (a block has at most 2^31, and the builder names each once). */
+#ifndef GCN10_ZONE_SPAN_DEFINED
+#define GCN10_ZONE_SPAN_DEFINED
+typedef struct gcn10_zone_span { int32_t y, x0, x1, zone; } gcn10_zone_span;       /* columns [x0, x1) of row y */
+typedef struct gcn10_zone_item { uint32_t first_span, n_spans; } gcn10_zone_item;
+#endif
+int gcn10_gpu_zonal_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                                   const gcn10_zone_span *spans_dev, const gcn10_zone_item *items_dev, size_t n_items,
+                                   int n_zones, unsigned long long *hist_dev /* [n_zones][GCN10_PAIR_HIST_SIZE] */,
+                                   gcn10_stream_t stream);
 
 /* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
  * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.

@@ -127,6 +127,11 @@ typedef struct gcn10_config {
                                42113) and its statistics leave it out; -1 ("none", default) = no tag */
     int verify;             /* "verify": 1 = nothing is written: the rasters that exist are decoded on the GPU and every
                                pixel is compared with the value computed now (gcn10_verify_*); 0 (default) = a write run */
+    int zonal;              /* "zonal": 1 = nothing is written but one table: the composite (mean) curve number of every
+                               zone of zones_shp_path and every selected raster, counted on the GPU (zonal.c); 0 (default) */
+    char *zones_shp_path;   /* "zones_shp_path": polygon shapefile of the zones, in the landcover's CRS (needed by zonal=1) */
+    char *zones_id_field;   /* "zones_id_field": numeric .dbf field that names a zone (absent = "ID") */
+    char *zonal_output;     /* "zonal_output": the table's path, relative to the CWD as the rasters are (absent = zonal_cn.csv) */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -145,9 +150,10 @@ int gcn10_parse_cog(const char *text, int *cog);
 int gcn10_parse_stats(const char *text, int *stats);
 int gcn10_parse_nodata(const char *text, int *nodata);
 int gcn10_parse_verify(const char *text, int *verify);      /* "0" | "1".  0, or -1 for another value. */
+int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or -1 for another value. */
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -318,6 +324,67 @@ void gcn10_band_stats_of(const uint64_t hist[256], int nodata, gcn10_band_stats 
 size_t gcn10_stats_xml(const gcn10_band_stats *st, char *buf, size_t cap);
 
 /* ------------------------------------------------------------------------ */
+/* zones (config keys "zonal", "zones_shp_path"): no counterpart in the reference                           */
+/* ------------------------------------------------------------------------ */
+
+/* A polygon shapefile of zones (watersheds, counties, ...), read without OGR: shape types 5, 15 and 25 (Z and M are
+ * ignored) with any number of parts; a null shape (type 0) is a zone without pixels; any other type is an error that
+ * names the record.  id[i] is the numeric .dbf field `id_field` (NULL = "ID", matched without case) of record i;
+ * duplicates are allowed.  The files are untrusted: every length, count and offset is checked against the file size,
+ * part offsets must start at 0 and ascend inside the point array, and coordinates must be finite.
+ * Ring k (over all records) is the points ring_pt[k] .. ring_pt[k + 1]; record i has the rings ring_first[i] ..
+ * ring_first[i + 1].  A ring whose last point is not its first is closed by the reader's users. */
+typedef struct gcn10_zones {
+    int n;                  /* records = zones, file order */
+    int64_t *id;
+    double (*bbox)[4];      /* {minx, miny, maxx, maxy} of the record's points (the header's box is not believed); all zero for a null shape */
+    uint64_t *ring_first;   /* [n + 1] */
+    uint64_t *ring_pt;      /* [n_rings + 1] */
+    double *xy;             /* [n_points][2] */
+    uint64_t n_rings, n_points;
+} gcn10_zones;
+int gcn10_zones_open(const char *shp_path, const char *id_field, gcn10_zones *out, char *err, size_t errcap);
+void gcn10_zones_free(gcn10_zones *z);
+
+/* Spans of zone pixels and the work items of gcn10_gpu_zonal_pair_histogram (the same structs as in gcn10_gpu.h). */
+#ifndef GCN10_ZONE_SPAN_DEFINED
+#define GCN10_ZONE_SPAN_DEFINED
+typedef struct gcn10_zone_span { int32_t y, x0, x1, zone; } gcn10_zone_span;       /* columns [x0, x1) of row y */
+typedef struct gcn10_zone_item { uint32_t first_span, n_spans; } gcn10_zone_item;
+#endif
+
+/* Scan conversion of the zones over one block.  The block has the clipped geotransform gt (gcn10_raster_window;
+ * north up: gt[1] > 0, gt[5] < 0, no rotation) and W x H pixels; pixel (x, y) has the centre
+ *   px = gt[0] + (x + 0.5) * gt[1],  py = gt[3] + (y + 0.5) * gt[5]     (IEEE double, this order, no FMA).
+ * Membership: an edge (x1,y1)-(x2,y2) of any ring of the zone crosses row y iff (y1 <= py) != (y2 <= py), at
+ * xc = x1 + (py - y1) * (x2 - x1) / (y2 - y1); with the row's crossings sorted c0 <= c1 <= ..., the pixel is in the
+ * zone iff c[2i] <= px < c[2i+1] for some i (even-odd: holes and nested parts need no special case).
+ * Ownership: only pixels with own[0] <= px < own[2] and own[1] < py <= own[3] are counted (own = the block's
+ * shapefile bounding box {minx, miny, maxx, maxy}; NULL = every pixel of the window), so that blocks whose windows
+ * overlap count every pixel once.
+ * Result: the local zones (records whose bounding box meets the block and that own at least one pixel there), their
+ * spans sorted by (zone = local index, y, x0), never empty and never longer than max_span_px, and items of
+ * consecutive spans of one zone covering at most max_item_px pixels each (0 = the built-in bounds; results never
+ * depend on them).  Cost: O(edges + rows touched + crossings) per zone.  0, or -1 with a message. */
+typedef struct gcn10_zone_plan {
+    int n_local;
+    int32_t *local_zone;        /* [n_local] record index of each local zone, ascending */
+    uint64_t *local_pixels;     /* [n_local] pixels of its spans */
+    size_t n_spans, n_items;
+    gcn10_zone_span *spans;
+    gcn10_zone_item *items;
+} gcn10_zone_plan;
+int gcn10_zones_build_plan(const gcn10_zones *z, const double gt[6], int W, int H, const double own[4],
+                           uint32_t max_span_px, uint32_t max_item_px, gcn10_zone_plan *out, char *err,
+                           size_t errcap);
+void gcn10_zone_plan_free(gcn10_zone_plan *p);
+/* The item rule alone, over spans already sorted by (zone, y, x0): splits spans longer than max_span_px, then groups
+ * them.  out->spans and out->items are filled (the local_* arrays stay empty).  0 or -1 (out of memory, or a span
+ * with x0 >= x1). */
+int gcn10_zone_items_build(const gcn10_zone_span *spans, size_t n_spans, uint32_t max_span_px, uint32_t max_item_px,
+                           gcn10_zone_plan *out);
+
+/* ------------------------------------------------------------------------ */
 /* the run: src/main.c:58-203 + process_block, src/cn.c:134-384              */
 /* ------------------------------------------------------------------------ */
 
@@ -334,6 +401,8 @@ typedef struct gcn10_run_options {
     bool stats;                 /* --stats: GDAL band statistics in every raster (sets the config key "stats") */
     const char *nodata;         /* --nodata none|0..255: overrides the config key "nodata"                */
     bool verify;                /* --verify: check the rasters that exist instead of writing (sets the config key "verify") */
+    bool zonal;                 /* --zonal: composite curve numbers per zone instead of rasters (sets the config key "zonal") */
+    const char *zones;          /* --zones <file.shp>: overrides the config key "zones_shp_path" and implies --zonal */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -365,7 +434,9 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * pinned-host strips double-buffered against the fused kernel, 18 tiled DEFLATE
  * GeoTIFFs named as src/cn.c:308, 341.  Returns the process exit code: 0, or 1
  * where the reference calls MPI_Abort(.., 1).  A verify run (opt->verify / "verify=1") writes no raster: 0 = every
- * selected raster of every block verified, 2 = it ran to its end and found a bad or missing file, 1 as above. */
+ * selected raster of every block verified, 2 = it ran to its end and found a bad or missing file, 1 as above.  A zonal
+ * run (opt->zonal / "zonal=1") writes no raster either, only its table: exit codes as for a write run, and 1 as well
+ * when a block's inputs could not be read (the table is written, but lacks that block). */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

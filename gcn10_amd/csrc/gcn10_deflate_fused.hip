@@ -1561,7 +1561,8 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
     FusedJob job;
     memset(&job, 0, sizeof job);
     job.esa = esa;
-    job.hx = ctx->d_hx;
+    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &job.hx)) != GCN10_OK)     // made on first use
+        return rc;
     job.cj = cj;
     job.class_of = ctx->d_class_of;
     job.hx_stride = ctx->hx_stride;

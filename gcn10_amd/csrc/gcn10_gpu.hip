@@ -12,10 +12,15 @@
 // malloc'd buffers, src/raster.c:169-178):
 //   esa      [rows*W]            landcover strip, read once, 16 B / lane
 //   out[r]   [rows*W]  r < 18    CN rasters, written once, 16 B / lane, nontemporal
-//   hx       [hsy][hx_stride]    soil window expanded along x only, one byte per
-//                                fine column holding both remapped soil groups;
-//                                52 MB for a 36000-wide block, re-read ~25x per
-//                                row from L2 / Infinity Cache, once from HBM
+//   hx4      [hsy][hx_stride/16] compact soil words, one dword per 16-px column group and
+//                                coarse row (13 MB for a 36000-wide block), read by the
+//                                strips of 16-byte aligned rows
+//   codes    [hsy][codes_stride] one byte per coarse soil cell holding both remapped
+//                                soil groups, and cx[W'], the coarse column of every fine
+//                                column (2.1 MB + 144 KB): the snapshot hx is made from
+//   hx       [hsy][hx_stride]    the same codes expanded along x, one byte per fine
+//                                column (52 MB for a 36000-wide block); made on demand
+//                                for the kernels that read soil per pixel (soil_bytes)
 //   lut16    [6][256] x 16 B     row (s, lc): bytes 0..8 = CN of tables 0..8,
 //                                plane s=5 is all 255 (soil group not in 0..4)
 //   lut1[k]  [6][256] x 1 B      the same for a single table k
@@ -64,7 +69,7 @@ constexpr int kLut1Bytes = kPlanes * kPlane1;
 
 struct StripParams {
     const uint8_t *esa;
-    const uint8_t *hx;      // x-expanded soil codes
+    const uint8_t *hx;      // x-expanded soil codes (null when the strip reads the soil tables)
     const int32_t *cj;      // coarse row of every strip row
     const uint8_t *lut;     // device image of the LDS table (lut16 or lut1[k])
     uint8_t *out[GCN10_N_RASTERS];
@@ -78,11 +83,14 @@ struct StripParams {
     uint32_t table_mask;
     uint32_t single_k;      // table index for the single-table variant
     uint32_t xcd_slabs;     // 1: each XCD streams a contiguous eighth of the strip
-    // compact soil words (one dword per 16-px column group, see expand_x_codes); hx4 = null: not in use
-    const uint32_t *hx4;
-    const uint32_t *hx4_complex;    // device word: == hx4_gen when some group of the tile has no compact form
-    uint32_t hx4_stride;            // dwords per soil row
-    uint32_t hx4_gen;               // generation number of the prepared tile (never 0)
+    // soil tables of the prepared tile (see soil_tables_kernel); hx4 = null: not in use, hx holds the bytes
+    const uint32_t *hx4;            // compact soil words, one per 16-px column group and coarse row
+    uint32_t hx4_stride;            // dwords per coarse row
+    const uint32_t *cx;             // coarse column of every fine column
+    const uint8_t *codes;           // soil code of every coarse cell, codes_stride bytes per coarse row
+    uint32_t codes_stride;
+    const uint32_t *soil_complex;    // device word: == soil_gen when some group of the tile has no compact form
+    uint32_t soil_gen;               // generation number of the prepared tile (never 0)
 };
 
 // soil code byte: low nibble = plane for "drained", high nibble = "undrained".
@@ -247,6 +255,13 @@ enum { kLut16 = 0, kLut1 = 1 };
 constexpr uint32_t kWavePx = 64u * kPxPerLane;      // 1024 px per wave chunk
 constexpr uint32_t kMinVectorW = kWavePx + 16u;
 
+// Where a strip kernel takes the soil codes of a lane's 16 pixels from.
+//   kSoilBytes:  the code bytes of the hx workspace (any W)
+//   kSoilWords:  W % 16 == 0, so the 16 pixels are one column group: one compact word {code a, code b, split}
+//   kSoilPixels: the codes table through the column map, pixel by pixel, for a tile with a group that has no
+//                compact word
+enum { kSoilBytes = 0, kSoilWords = 1, kSoilPixels = 2 };
+
 // What a lane holds of one trip between issuing its loads and using them.
 template <int ILP>
 struct Trip {
@@ -254,7 +269,7 @@ struct Trip {
     uint32_t i0[ILP];
 };
 
-template <int ILP, bool NT, bool HX4>
+template <int ILP, bool NT, int SOIL>
 __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, uint32_t lane_off,
                                            uint32_t wave_off, Trip<ILP> &tr)
 {
@@ -282,9 +297,27 @@ __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, 
         const bool wrap = xl >= p.W;
         xl = wrap ? xl - p.W : xl;
         const uint32_t row = clamp_row(p, (int32_t)(wrap ? r1[u] : r0[u]));
-        if (HX4) {
-            // W % 16 == 0: the lane's 16 pixels are one column group; its soil codes are one dword
+        if (SOIL == kSoilWords) {
             tr.c16[u] = u32x4{ p.hx4[(size_t)row * p.hx4_stride + (xl >> 4)], 0u, 0u, 0u };
+            continue;
+        }
+        if (SOIL == kSoilPixels) {
+            // rare (a tile with fewer than 8 columns per soil cell, a map that is not monotone): asked to be right,
+            // not fast -- a rolled loop, so that it adds nothing to the registers of the kernel
+            const uint8_t *cr = p.codes + (size_t)row * p.codes_stride;
+            const u32x4 *pc = reinterpret_cast<const u32x4 *>(p.cx + xl);   // W % 16 == 0: xl is a multiple of 16
+            u32x4 a = { 0u, 0u, 0u, 0u };
+#pragma unroll 1
+            for (int j = 0; j < 4; j++) {
+                const u32x4 c4 = pc[j];
+                const uint32_t w = (uint32_t)cr[c4[0]] | (uint32_t)cr[c4[1]] << 8 | (uint32_t)cr[c4[2]] << 16 |
+                                   (uint32_t)cr[c4[3]] << 24;
+                a[0] = j == 0 ? w : a[0];
+                a[1] = j == 1 ? w : a[1];
+                a[2] = j == 2 ? w : a[2];
+                a[3] = j == 3 ? w : a[3];
+            }
+            tr.c16[u] = a;
             continue;
         }
         const uint8_t *pa = p.hx + (size_t)row * p.hx_stride + xl;
@@ -326,14 +359,14 @@ __device__ __forceinline__ u32x4 expand_soil_word(uint32_t w)
     return cd;
 }
 
-template <int KIND, int COND_MASK, int ILP, bool NT, bool HX4>
+template <int KIND, int COND_MASK, int ILP, bool NT, int SOIL>
 __device__ __forceinline__ void finish_trip(const StripParams &p, const uint8_t *lut, uint32_t tmask,
                                             const Trip<ILP> &tr)
 {
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
         const bool live = tr.i0[u] < p.nvec16;
-        const u32x4 c16 = HX4 ? expand_soil_word(tr.c16[u][0]) : tr.c16[u];
+        const u32x4 c16 = SOIL == kSoilWords ? expand_soil_word(tr.c16[u][0]) : tr.c16[u];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if (!(COND_MASK & (1 << c)))
@@ -391,39 +424,41 @@ __device__ __forceinline__ void finish_trip(const StripParams &p, const uint8_t 
     }
 }
 
-// The trip loop of cn_strip_kernel (HX4: soil codes from the compact words).
-template <int KIND, int COND_MASK, int ILP, bool NT, bool PF, bool HX4>
+// The trip loop of cn_strip_kernel.
+template <int KIND, int COND_MASK, int ILP, bool NT, bool PF, int SOIL>
 __device__ __forceinline__ void strip_loop(const StripParams &p, const uint8_t *lut, uint32_t tmask,
                                            uint32_t lane_off, uint32_t wave_off)
 {
     // p.nchunks counts trips (groups of ILP chunks of 4096 px) here
     uint32_t step, end;
     uint32_t trip = first_chunk(p.nchunks, step, end, p.xcd_slabs != 0);
+    if (trip >= end)
+        return;
     if (!PF) {
         for (; trip < end; trip += step) {
             Trip<ILP> tr;
-            issue_trip<ILP, NT, HX4>(p, trip, lane_off, wave_off, tr);
-            finish_trip<KIND, COND_MASK, ILP, NT, HX4>(p, lut, tmask, tr);
+            issue_trip<ILP, NT, SOIL>(p, trip, lane_off, wave_off, tr);
+            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tr);
         }
     }
-    else if (trip < end) {
+    else {
         Trip<ILP> ta, tb;       // used alternately: a copy would wait for the loads it copies
-        issue_trip<ILP, NT, HX4>(p, trip, lane_off, wave_off, ta);
+        issue_trip<ILP, NT, SOIL>(p, trip, lane_off, wave_off, ta);
         for (;;) {
             trip += step;
             if (trip >= end) {
-                finish_trip<KIND, COND_MASK, ILP, NT, HX4>(p, lut, tmask, ta);
+                finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, ta);
                 break;
             }
-            issue_trip<ILP, NT, HX4>(p, trip, lane_off, wave_off, tb);
-            finish_trip<KIND, COND_MASK, ILP, NT, HX4>(p, lut, tmask, ta);
+            issue_trip<ILP, NT, SOIL>(p, trip, lane_off, wave_off, tb);
+            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, ta);
             trip += step;
             if (trip >= end) {
-                finish_trip<KIND, COND_MASK, ILP, NT, HX4>(p, lut, tmask, tb);
+                finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tb);
                 break;
             }
-            issue_trip<ILP, NT, HX4>(p, trip, lane_off, wave_off, ta);
-            finish_trip<KIND, COND_MASK, ILP, NT, HX4>(p, lut, tmask, tb);
+            issue_trip<ILP, NT, SOIL>(p, trip, lane_off, wave_off, ta);
+            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tb);
         }
     }
 }
@@ -452,12 +487,14 @@ __global__ __launch_bounds__(kThreads) void cn_strip_kernel(const StripParams p)
     const uint32_t wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kWavePx;
     const uint32_t tmask = ALL_TABLES ? 0x1ffu : p.table_mask;
 
-    // compact soil words when the host offers them and no column group of this tile is complex
-    // (wave-uniform: the flag comes through the scalar cache)
-    if (p.hx4 && (uint32_t)scalar_load_i32(reinterpret_cast<const int32_t *>(p.hx4_complex), 0u) != p.hx4_gen)
-        strip_loop<KIND, COND_MASK, ILP, NT, PF, true>(p, lut, tmask, lane_off, wave_off);
+    // the soil tables when the host offers them: compact words, or the codes table pixel by pixel when some group
+    // of this tile is complex (wave-uniform: the flag comes through the scalar cache); else the code bytes
+    if (!p.hx4)
+        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilBytes>(p, lut, tmask, lane_off, wave_off);
+    else if ((uint32_t)scalar_load_i32(reinterpret_cast<const int32_t *>(p.soil_complex), 0u) != p.soil_gen)
+        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilWords>(p, lut, tmask, lane_off, wave_off);
     else
-        strip_loop<KIND, COND_MASK, ILP, NT, PF, false>(p, lut, tmask, lane_off, wave_off);
+        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilPixels>(p, lut, tmask, lane_off, wave_off);
 
     // the last npix % 16 pixels, one per thread
     if (blockIdx.x == 0 && threadIdx.x < p.npix - p.nvec16) {
@@ -465,6 +502,7 @@ __global__ __launch_bounds__(kThreads) void cn_strip_kernel(const StripParams p)
         const uint32_t y = i / p.W;
         const uint32_t x = i - y * p.W;
         const uint32_t lc = p.esa[i];
+        // (a strip that reads the soil tables has W % 16 == 0, so no tail: p.hx is set whenever this runs)
         const uint32_t cd = p.hx[(size_t)soil_row(p, y) * p.hx_stride + x];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
@@ -540,40 +578,70 @@ __global__ __launch_bounds__(kThreads) void cn_strip_bytes(const StripParams p,
 }
 
 // ------------------------------------------------------------------------
-// x-expansion of the coarse soil window (the x half of src/cn.c:218-232):
-// hx[r][x] = soil_code(coarse[r][ci[x]]) for every coarse row r.
-//
-// Next to the bytes, one COMPACT WORD per 16-px column group and coarse row:
-// hx4[r][g] = code a | code b << 8 | split << 16, meaning pixels [0, split)
-// of the group have code a and the rest code b.  At the usual ratio (25 fine
-// columns per coarse cell) every group has that form, and the strip kernels
-// then load one dword per lane instead of 16 bytes (the soil stream costs the
-// single-raster kernel 5 % with bytes, 1-2 % with words: DESIGN.md section 5).
-// A group that has no such form (three cells under 16 columns, a map that is
-// not monotone) gets split = 0xff and stores this tile's generation number in
-// *complex (no reset between tiles needed); the strip kernels compare that
-// word with the generation they were launched for and use the bytes for the
-// whole tile when it matches.
+// The soil of a prepared tile (the x half of src/cn.c:218-232).  The fine soil code of column x in coarse row r is
+// soil_code(coarse[r][ci[x]]).  gcn10_gpu_prepare_tile writes, into memory the context owns:
+//   codes[r][c]  = soil_code(coarse[r][c]) for c < hsx, the "invalid" code for hsx <= c < codes_stride
+//   cx[x]        = ci[x] clamped to the window, whatever its value; hsx (a column of padding codes) for the
+//                  columns [W, hx_stride) right of the raster
+//   hx4[r][g]    = one COMPACT WORD per 16-px column group g and coarse row r: code a | code b << 8 | split << 16,
+//                  meaning pixels [0, split) of the group have code a and the rest code b.  At the usual ratio
+//                  (25 fine columns per coarse cell) every group has that form, and the strip kernels of 16-byte
+//                  aligned rows load one dword per lane.
+// A group that has no such form (three cells under 16 columns, a map that is not monotone) gets split = 0xff and
+// stores this tile's generation number in *complex (no reset between tiles needed); the strip kernels compare that
+// word with the generation they were launched for and go through codes and cx pixel by pixel for the whole tile
+// when it matches.
+// codes and cx are a snapshot: the code bytes of the tile (expand_code_bytes) are made from them on demand, and the
+// caller's coarse and ci are not read after this kernel.
 // ------------------------------------------------------------------------
-// coarse rows per thread of expand_x_codes: 2: 20.0 us, 3: 17.3, 4: 16.5, 6: 17.6 for a 36000 x 1440 window
-// (profiles/r02/prepare_tile_rows_per_thread.txt)
-constexpr uint32_t kExpandRows = 4;
+constexpr uint32_t kWordRows = 8;       // coarse rows per thread of the words part
 
 template <bool VEC>
-__global__ __launch_bounds__(kThreads) void expand_x_codes(const uint8_t *coarse,
-                                                           uint32_t hsx, uint32_t hsy,
-                                                           const int32_t *ci, uint32_t W,
-                                                           uint8_t *hx, uint32_t hx_stride,
-                                                           uint32_t *hx4, uint32_t *complex, uint32_t gen)
+__global__ __launch_bounds__(kThreads) void soil_tables_kernel(const uint8_t *coarse, uint32_t hsx, uint32_t hsy,
+                                                               const int32_t *ci, uint32_t W, uint32_t hx_stride,
+                                                               uint32_t word_chunks, uint8_t *codes,
+                                                               uint32_t codes_stride, uint32_t *cx_out, uint32_t *hx4,
+                                                               uint32_t *complex, uint32_t gen)
 {
-    // one thread = 16 consecutive fine columns of kExpandRows coarse rows: the 16 column indices are
-    // loaded once (dwordx4 when ci is 16-byte aligned) and clamped once, then per row 16 byte gathers
-    // that hit L1/L2 (a coarse row is ~1.4 KB) and one 16-byte store
+    const uint32_t pad = (uint32_t)(kInvalidPlane | (kInvalidPlane << 4));
+    if (blockIdx.y >= word_chunks) {
+        // ---- codes: one thread = 16 consecutive cells of one coarse row ----
+        const uint32_t per_row = codes_stride / 16u;
+        const uint32_t t = ((blockIdx.y - word_chunks) * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+        const uint32_t r = t / per_row;
+        if (r >= hsy)
+            return;
+        const uint32_t c0 = (t - r * per_row) * 16u;
+        const uint8_t *row = coarse + (size_t)r * hsx;
+        u32x4 in = { 0u, 0u, 0u, 0u };
+        if (c0 + 16u <= hsx) {
+            in = load16_any(row + c0);
+        }
+        else {
+#pragma unroll
+            for (int q = 0; q < 16; q++)
+                if (c0 + q < hsx)
+                    in[q >> 2] |= (uint32_t)row[c0 + q] << (8 * (q & 3));
+        }
+        u32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            uint32_t w = 0;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint32_t code = c0 + 4 * j + q < hsx ? soil_code((uint8_t)(in[j] >> (8 * q))) : pad;
+                w |= code << (8 * q);
+            }
+            o[j] = w;
+        }
+        *reinterpret_cast<u32x4 *>(codes + (size_t)r * codes_stride + c0) = o;
+        return;
+    }
+    // ---- column map and compact words: one thread = 16 consecutive fine columns of kWordRows coarse rows ----
     const uint32_t x = (blockIdx.x * blockDim.x + threadIdx.x) * 16u;
-    const uint32_t r0 = blockIdx.y * kExpandRows;
+    const uint32_t r0 = blockIdx.y * kWordRows;
     if (x >= hx_stride || r0 >= hsy)
         return;
-    const uint8_t pad = (uint8_t)(kInvalidPlane | (kInvalidPlane << 4));
     uint32_t cx[16];
     if (VEC && x + 16u <= W) {
         const u32x4 *civ = reinterpret_cast<const u32x4 *>(ci + x);
@@ -588,37 +656,81 @@ __global__ __launch_bounds__(kThreads) void expand_x_codes(const uint8_t *coarse
     else {
 #pragma unroll
         for (int q = 0; q < 16; q++) {
-            // columns past W are padding: marked here, given the "invalid" code below
-            const uint32_t xx = x + q;
             // (an index of the raster is clamped exactly as in the vector path, whatever its value;
             // only columns past W get the padding mark)
+            const uint32_t xx = x + q;
             const uint32_t c = xx < W ? (uint32_t)ci[xx] : 0u;
-            cx[q] = xx < W ? (c < hsx ? c : hsx - 1u) : 0xffffffffu;
+            cx[q] = xx < W ? (c < hsx ? c : hsx - 1u) : hsx;
         }
+    }
+    // compact form: a run of c_lo followed by a run of c_hi (also: padding only, right of the raster)
+    const uint32_t c_lo = cx[0], c_hi = cx[15];
+    uint32_t split = 0;
+    bool compact = true;
+#pragma unroll
+    for (int q = 0; q < 16; q++) {
+        const bool lo = cx[q] == c_lo;
+        compact = compact && (lo ? split == (uint32_t)q : cx[q] == c_hi);
+        split += lo && split == (uint32_t)q ? 1u : 0u;
+    }
+    if (blockIdx.y == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            *reinterpret_cast<u32x4 *>(cx_out + x + 4 * j) =
+                u32x4{ cx[4 * j], cx[4 * j + 1], cx[4 * j + 2], cx[4 * j + 3] };
+        if (x < W && !compact && *reinterpret_cast<volatile uint32_t *>(complex) != gen)
+            *reinterpret_cast<volatile uint32_t *>(complex) = gen;      // every writer stores the same value
+    }
+    const uint32_t r1 = r0 + kWordRows < hsy ? r0 + kWordRows : hsy;
+    for (uint32_t r = r0; r < r1; r++) {
+        const uint8_t *row = coarse + (size_t)r * hsx;
+        // (hsx names the padding right of the raster: not a cell of the window)
+        const uint32_t a = c_lo < hsx ? soil_code(row[c_lo]) : pad, b = c_hi < hsx ? soil_code(row[c_hi]) : pad;
+        __builtin_nontemporal_store(compact ? a | (b << 8) | (split << 16) : 0x00ff0000u,
+                                    hx4 + (size_t)r * (hx_stride / 16u) + x / 16u);
+    }
+}
+
+// ------------------------------------------------------------------------
+// The code bytes of the prepared tile, for the kernels that read soil per pixel (gcn10::soil_bytes launches it
+// when the first of them asks): hx[r][x] = codes[r][cx[x]].
+// ------------------------------------------------------------------------
+// coarse rows per thread: 2: 20.0 us, 3: 17.3, 4: 16.5, 6: 17.6 for a 36000 x 1440 window
+// (profiles/r02/prepare_tile_rows_per_thread.txt, measured when this loop was part of prepare_tile)
+constexpr uint32_t kExpandRows = 4;
+
+__global__ __launch_bounds__(kThreads) void expand_code_bytes(const uint8_t *codes, uint32_t codes_stride,
+                                                              uint32_t hsy, const uint32_t *cx_in, uint8_t *hx,
+                                                              uint32_t hx_stride)
+{
+    // one thread = 16 consecutive fine columns of kExpandRows coarse rows: the 16 column indices are
+    // loaded once, then per row byte gathers that hit L1/L2 (a row of codes is ~1.4 KB) and one 16-byte store
+    const uint32_t x = (blockIdx.x * blockDim.x + threadIdx.x) * 16u;
+    const uint32_t r0 = blockIdx.y * kExpandRows;
+    if (x >= hx_stride || r0 >= hsy)
+        return;
+    uint32_t cx[16];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const u32x4 c4 = *reinterpret_cast<const u32x4 *>(cx_in + x + 4 * j);
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            cx[4 * j + q] = c4[q];
     }
     // at the usual ratio (25 fine columns per coarse cell) 16 consecutive columns see at most two coarse
     // cells, the first column's and the last one's: two byte loads and 16 selects instead of 16 byte
     // gathers (the kernel is bound by the number of load instructions, not by bytes)
     const uint32_t c_lo = cx[0], c_hi = cx[15];
-    const uint32_t r1 = r0 + kExpandRows < hsy ? r0 + kExpandRows : hsy;
-    // compact form: a run of c_lo followed by a run of c_hi (also: padding only, right of the raster)
-    uint32_t split = 0;
-    bool compact = true, in_set = true;
+    bool two = true;
 #pragma unroll
-    for (int q = 0; q < 16; q++) {
-        const bool lo = cx[q] == c_lo;
-        in_set = in_set && (lo || cx[q] == c_hi);
-        compact = compact && (lo ? split == (uint32_t)q : cx[q] == c_hi);
-        split += lo && split == (uint32_t)q ? 1u : 0u;
-    }
-    const bool two = c_lo != 0xffffffffu && c_hi != 0xffffffffu && in_set;
-    if (hx4 && x < W && !compact && *reinterpret_cast<volatile uint32_t *>(complex) != gen)
-        *reinterpret_cast<volatile uint32_t *>(complex) = gen;      // every writer stores the same value
+    for (int q = 0; q < 16; q++)
+        two = two && (cx[q] == c_lo || cx[q] == c_hi);
+    const uint32_t r1 = r0 + kExpandRows < hsy ? r0 + kExpandRows : hsy;
     for (uint32_t r = r0; r < r1; r++) {
-        const uint8_t *row = coarse + (size_t)r * hsx;
+        const uint8_t *row = codes + (size_t)r * codes_stride;
         u32x4 o;
         if (two) {
-            const uint32_t code_lo = soil_code(row[c_lo]), code_hi = soil_code(row[c_hi]);
+            const uint32_t code_lo = row[c_lo], code_hi = row[c_hi];
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 uint32_t w = 0;
@@ -633,18 +745,12 @@ __global__ __launch_bounds__(kThreads) void expand_x_codes(const uint8_t *coarse
             for (int j = 0; j < 4; j++) {
                 uint32_t w = 0;
 #pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t c = cx[4 * j + q];
-                    const uint8_t code = c == 0xffffffffu ? pad : soil_code(row[c]);
-                    w |= (uint32_t)code << (8 * q);
-                }
+                for (int q = 0; q < 4; q++)
+                    w |= (uint32_t)row[cx[4 * j + q]] << (8 * q);
                 o[j] = w;
             }
         }
         __builtin_nontemporal_store(o, reinterpret_cast<u32x4 *>(hx + (size_t)r * hx_stride + x));
-        if (hx4)
-            __builtin_nontemporal_store(compact ? (o[0] & 0xffu) | ((o[3] >> 24) << 8) | (split << 16) : 0x00ff0000u,
-                                        hx4 + (size_t)r * (hx_stride / 16u) + x / 16u);
     }
 }
 
@@ -873,6 +979,28 @@ int grow_workspace(void **ws, size_t *cap, size_t need)
     return GCN10_OK;
 }
 
+int soil_bytes(gcn10_gpu_ctx *ctx, hipStream_t stream, const uint8_t **hx)
+{
+    *hx = nullptr;
+    if (!ctx->d_hx || ctx->hx_W == 0)
+        return fail(GCN10_E_STATE, "no prepared tile: call gcn10_gpu_prepare_tile first");
+    if (!ctx->hx_made) {
+        // the header's rule is all this relies on: `stream` is ordered after the prepare_tile that wrote the tables
+        dim3 grid((ctx->hx_stride / 16 + kThreads - 1) / kThreads, (ctx->hx_rows + kExpandRows - 1) / kExpandRows);
+        hipLaunchKernelGGL(expand_code_bytes, grid, dim3(kThreads), 0, stream, ctx->d_codes, ctx->codes_stride,
+                           ctx->hx_rows, ctx->d_cx, ctx->d_hx, ctx->hx_stride);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(ctx->hx_made_ev, stream));
+        ctx->hx_made = true;
+    }
+    else {
+        // whatever the stream: a handle compared with the expanding stream's could be a new stream's by now
+        HIP_TRY(hipStreamWaitEvent(stream, ctx->hx_made_ev, 0));
+    }
+    *hx = ctx->d_hx;
+    return GCN10_OK;
+}
+
 }  // namespace gcn10
 
 namespace {
@@ -943,6 +1071,13 @@ int gcn10_gpu_init(int device, gcn10_gpu_ctx **out)
         e2 = hipMalloc(reinterpret_cast<void **>(&ctx->d_lut16), kLut16Bytes);
     if (e2 == hipSuccess)
         e2 = hipMalloc(reinterpret_cast<void **>(&ctx->d_lut1), GCN10_N_TABLES * kLut1Bytes);
+    // the "complex tile" word lives as long as the context: generation numbers never repeat within its life
+    if (e2 == hipSuccess)
+        e2 = hipMalloc(reinterpret_cast<void **>(&ctx->d_soil_complex), 16);
+    if (e2 == hipSuccess)
+        e2 = hipMemset(ctx->d_soil_complex, 0, 16);
+    if (e2 == hipSuccess)
+        e2 = hipEventCreateWithFlags(&ctx->hx_made_ev, hipEventDisableTiming);
     if (e2 != hipSuccess) {
         int rc = fail(GCN10_E_HIP, "context setup: %s", hipGetErrorString(e2));
         gcn10_gpu_destroy(ctx);
@@ -967,6 +1102,10 @@ void gcn10_gpu_destroy(gcn10_gpu_ctx *ctx)
         (void)hipFree(ctx->d_lut1);
     if (ctx->d_hx_alloc)
         (void)hipFree(ctx->d_hx_alloc);
+    if (ctx->d_soil_complex)
+        (void)hipFree(ctx->d_soil_complex);
+    if (ctx->hx_made_ev)
+        (void)hipEventDestroy(ctx->hx_made_ev);
     if (ctx->deflate_ws)
         (void)hipFree(ctx->deflate_ws);
     if (ctx->inflate_ws)
@@ -1383,47 +1522,55 @@ int gcn10_gpu_prepare_tile(gcn10_gpu_ctx *ctx, const uint8_t *coarse, int hsx, i
     // rows padded to a multiple of 16 plus one extra group so that any 16-byte
     // read starting below W stays inside the row
     const uint32_t stride = (((uint32_t)W + 15u) & ~15u) + 16u;
-    const size_t need = (size_t)stride * (size_t)hsy;
+    const size_t need_hx = ((size_t)stride * (size_t)hsy + 63) & ~(size_t)63;
+    // behind the code bytes: compact words, cx, codes (a row of codes ends with at least one padding code, which is
+    // what cx names for the columns right of the raster)
+    const uint32_t codes_stride = (((uint32_t)hsx + 1u) + 15u) & ~15u;
+    const size_t off_words = need_hx;
+    const size_t off_cx = (off_words + (size_t)(stride / 16u) * 4u * (size_t)hsy + 15) & ~(size_t)15;
+    const size_t off_codes = (off_cx + (size_t)stride * 4u + 15) & ~(size_t)15;
+    const size_t need = off_codes + (size_t)codes_stride * (size_t)hsy;
     if (need > ctx->hx_capacity) {
         // growing the workspace is the one allocation on this path; it happens
         // once per run for equally sized blocks (sync: the old buffer may be in use).
+        // The byte part is allocated here although it is filled only on demand: a reader never allocates.
         // 16 bytes in front of row 0: the strip kernel's second soil load of a lane that
         // straddles a row end starts up to 15 bytes before a soil row.
         HIP_TRY(hipDeviceSynchronize());
         if (ctx->d_hx_alloc)
             HIP_TRY(hipFree(ctx->d_hx_alloc));
         ctx->d_hx_alloc = ctx->d_hx = nullptr;
-        ctx->d_hx4 = ctx->d_hx4_complex = nullptr;
-        ctx->hx4_ready = false;
         ctx->hx_capacity = 0;
-        // behind the code bytes: the compact words (a quarter of the bytes) and their "complex" flag
-        const size_t need16 = (need + 15) & ~(size_t)15;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_hx_alloc), 16 + need16 + need16 / 4 + 16));
+        ctx->hx_W = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_hx_alloc), 16 + need));
         ctx->d_hx = ctx->d_hx_alloc + 16;
-        ctx->d_hx4 = reinterpret_cast<uint32_t *>(ctx->d_hx + need16);
-        ctx->d_hx4_complex = reinterpret_cast<uint32_t *>(ctx->d_hx + need16 + need16 / 4);
-        // on the launch's own stream: ordered before expand_x_codes whatever the blocking mode of the stream
-        HIP_TRY(hipMemsetAsync(ctx->d_hx4_complex, 0, 4, as_stream(ctx, stream)));
-        ctx->hx4_gen = 0;
         ctx->hx_capacity = need;
     }
-    uint32_t *hx4 = ctx->compact_soil ? ctx->d_hx4 : nullptr;
-    ctx->hx4_ready = hx4 != nullptr;
-    if (hx4 && ++ctx->hx4_gen == 0u)
-        ctx->hx4_gen = 1u;      // 0 is what the word holds before the first complex tile
+    ctx->d_hx4 = reinterpret_cast<uint32_t *>(ctx->d_hx + off_words);
+    ctx->d_cx = reinterpret_cast<uint32_t *>(ctx->d_hx + off_cx);
+    ctx->d_codes = ctx->d_hx + off_codes;
+    ctx->codes_stride = codes_stride;
+    if (++ctx->soil_gen == 0u)
+        ctx->soil_gen = 1u;      // 0 is what the word holds before the first complex tile
+    ctx->hx_made = false;
     ctx->hx_stride = stride;
     ctx->hx_W = (uint32_t)W;
     ctx->hx_rows = (uint32_t)hsy;
-    dim3 grid((stride / 16 + kThreads - 1) / kThreads, ((uint32_t)hsy + kExpandRows - 1) / kExpandRows);
-    if (aligned16(ci))
-        hipLaunchKernelGGL(expand_x_codes<true>, grid, dim3(kThreads), 0, as_stream(ctx, stream),
-                           coarse, (uint32_t)hsx, (uint32_t)hsy, ci, (uint32_t)W, ctx->d_hx, stride, hx4,
-                           ctx->d_hx4_complex, ctx->hx4_gen);
-    else
-        hipLaunchKernelGGL(expand_x_codes<false>, grid, dim3(kThreads), 0, as_stream(ctx, stream),
-                           coarse, (uint32_t)hsx, (uint32_t)hsy, ci, (uint32_t)W, ctx->d_hx, stride, hx4,
-                           ctx->d_hx4_complex, ctx->hx4_gen);
+    hipStream_t s = as_stream(ctx, stream);
+    const uint32_t group_blocks = (stride / 16u + kThreads - 1) / kThreads;
+    const uint32_t word_chunks = ((uint32_t)hsy + kWordRows - 1) / kWordRows;
+    const size_t code_threads = (size_t)(codes_stride / 16u) * (size_t)hsy;
+    const uint32_t code_chunks = (uint32_t)((code_threads + (size_t)group_blocks * kThreads - 1) / ((size_t)group_blocks * kThreads));
+    auto fn = aligned16(ci) ? soil_tables_kernel<true> : soil_tables_kernel<false>;
+    hipLaunchKernelGGL(fn, dim3(group_blocks, word_chunks + code_chunks), dim3(kThreads), 0, s, coarse, (uint32_t)hsx,
+                       (uint32_t)hsy, ci, (uint32_t)W, stride, word_chunks, ctx->d_codes, codes_stride, ctx->d_cx,
+                       ctx->d_hx4, ctx->d_soil_complex, ctx->soil_gen);
     HIP_TRY(hipGetLastError());
+    // a tile whose strips are certain to read the bytes gets them now, behind the tables on the same stream
+    if (!ctx->compact_soil || (W & 15)) {
+        const uint8_t *hx;
+        return gcn10::soil_bytes(ctx, s, &hx);
+    }
     return GCN10_OK;
 }
 
@@ -1468,7 +1615,6 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
         }
     }
     p.esa = esa;
-    p.hx = ctx->d_hx;
     p.cj = cj;
     p.W = (uint32_t)W;
     p.rows = (uint32_t)rows;
@@ -1481,16 +1627,24 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
 
     p.xcd_slabs = (uint32_t)ctx->xcd_slabs;
     p.nvec16 = p.npix & ~15u;
-    if (ctx->hx4_ready && ctx->compact_soil && (p.W & 15u) == 0u) {
-        // rows are 16-byte aligned: a lane's 16 pixels are one column group of the compact soil words
-        p.hx4 = ctx->d_hx4;
-        p.hx4_complex = ctx->d_hx4_complex;
-        p.hx4_stride = ctx->hx_stride / 16u;
-        p.hx4_gen = ctx->hx4_gen;
-    }
     // the vector kernel wants a wave's 1024-px span to cross at most one row end
     if (p.npix < 16u || p.W < kMinVectorW)
         all_aligned = false;
+    if (all_aligned && ctx->compact_soil && (p.W & 15u) == 0u) {
+        // rows are 16-byte aligned: a lane's 16 pixels are one column group of the compact soil words
+        p.hx4 = ctx->d_hx4;
+        p.hx4_stride = ctx->hx_stride / 16u;
+        p.cx = ctx->d_cx;
+        p.codes = ctx->d_codes;
+        p.codes_stride = ctx->codes_stride;
+        p.soil_complex = ctx->d_soil_complex;
+        p.soil_gen = ctx->soil_gen;
+    }
+    else {
+        rc = gcn10::soil_bytes(ctx, s, &p.hx);
+        if (rc)
+            return rc;
+    }
     if (!all_aligned) {
         p.lut = ctx->d_lut16;
         const uint32_t g = stream_grid(ctx, ((uint64_t)p.npix + kThreads - 1) / kThreads);
@@ -1607,7 +1761,7 @@ int gcn10_gpu_set_option(gcn10_gpu_ctx *ctx, const char *name, int value)
     else if (!strcmp(name, "prefetch") && (value == -1 || value == 0 || value == 1))
         ctx->prefetch = value;
     else if (!strcmp(name, "compact_soil") && (value == 0 || value == 1))
-        ctx->compact_soil = value;      // strips launched from now on; 1 needs a gcn10_gpu_prepare_tile made with it on
+        ctx->compact_soil = value;      // strips launched from now on (every prepared tile has the tables)
     else
         return fail(GCN10_E_INVAL, "gcn10_gpu_set_option: unknown option or bad value: %s=%d", name, value);
     return GCN10_OK;
@@ -1755,13 +1909,13 @@ int gcn10_gpu_soil_words_state(gcn10_gpu_ctx *ctx, gcn10_stream_t stream)
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    if (!ctx->hx4_ready || !ctx->d_hx4_complex)
+    if (!ctx->compact_soil || !ctx->d_hx || ctx->hx_W == 0)
         return 0;
     uint32_t flag = 0;
     hipStream_t s = as_stream(ctx, stream);
-    HIP_TRY(hipMemcpyAsync(&flag, ctx->d_hx4_complex, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&flag, ctx->d_soil_complex, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    return flag == ctx->hx4_gen ? 2 : 1;
+    return flag == ctx->soil_gen ? 2 : 1;
 }
 
 const char *gcn10_gpu_last_kernel_name(gcn10_gpu_ctx *ctx)

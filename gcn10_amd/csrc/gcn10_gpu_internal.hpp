@@ -26,6 +26,10 @@ hipStream_t as_stream(gcn10_gpu_ctx *ctx, gcn10_stream_t s);
 // Grows one of the context's device workspaces (*ws of *cap bytes) to at least `need` bytes; the old
 // contents are not kept.
 int grow_workspace(void **ws, size_t *cap, size_t need);
+// The soil code bytes of the prepared tile (gcn10_gpu_ctx::d_hx), valid for work that `stream` runs after this call:
+// the first caller after a gcn10_gpu_prepare_tile expands them from the tile's tables on its own stream, every later
+// caller's stream is made to wait for that expansion (no cost on the stream that ran it).  Every kernel that reads the bytes gets them here.
+int soil_bytes(gcn10_gpu_ctx *ctx, hipStream_t stream, const uint8_t **hx);
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -64,13 +68,24 @@ struct gcn10_gpu_ctx {
     uint8_t *d_lut16 = nullptr;     // kLut16Bytes
     uint8_t *d_lut1 = nullptr;      // 9 * kLut1Bytes
     int n_tables = 0;
-    uint8_t *d_hx = nullptr;        // row 0 of the soil-code workspace (= d_hx_alloc + 16)
+    // Soil workspace of the prepared tile (one allocation, grown by gcn10_gpu_prepare_tile):
+    //   d_hx      [hx_rows][hx_stride]      soil code bytes, one per fine column.  Allocated with the tile, FILLED ON
+    //                                        DEMAND: every reader gets the pointer from gcn10::soil_bytes()
+    //   d_hx4     [hx_rows][hx_stride / 16] compact soil words, one per 16-px column group and coarse row
+    //   d_cx      [hx_stride]               clamped coarse column of every fine column; hsx = padding
+    //   d_codes   [hx_rows][codes_stride]   soil code of every coarse cell; columns >= hsx hold the padding code
+    // d_cx and d_codes are a snapshot of the caller's `coarse` and `ci`: nothing reads those after prepare_tile.
+    uint8_t *d_hx = nullptr;        // row 0 of the soil-code bytes (= d_hx_alloc + 16)
     uint8_t *d_hx_alloc = nullptr;
-    uint32_t *d_hx4 = nullptr;          // compact soil words, one per 16-px column group and coarse row
-    uint32_t *d_hx4_complex = nullptr;  // device word: == hx4_gen when some group of the prepared tile has no compact form
-    uint32_t hx4_gen = 0;               // generation number of the prepared tile
-    bool hx4_ready = false;             // the last gcn10_gpu_prepare_tile wrote the words
-    int compact_soil = 1;               // option: write and use the compact words
+    uint32_t *d_hx4 = nullptr;
+    uint32_t *d_cx = nullptr;
+    uint8_t *d_codes = nullptr;
+    uint32_t codes_stride = 0;
+    uint32_t *d_soil_complex = nullptr;  // device word: == soil_gen when some group of the prepared tile has no compact form
+    uint32_t soil_gen = 0;               // generation number of the prepared tile (never 0 once a tile is prepared)
+    int compact_soil = 1;               // option: aligned strips read the tables, not the bytes
+    bool hx_made = false;               // the bytes of the prepared tile have been launched ...
+    hipEvent_t hx_made_ev = nullptr;    // ... and this event follows them
     size_t hx_capacity = 0;
     uint32_t hx_stride = 0;
     uint32_t hx_W = 0;

@@ -239,7 +239,8 @@ int gcn10_gpu_overview_average(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, in
     p.esa = esa;
     p.cj = cj;
     p.lut16 = ctx->d_lut16;
-    p.hx = ctx->d_hx;
+    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &p.hx)) != GCN10_OK)     // made on first use
+        return rc;
     p.hx_stride = ctx->hx_stride;
     p.hx_rows = ctx->hx_rows;
     p.W = (uint32_t)W;

@@ -118,7 +118,8 @@ int gcn10_gpu_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int 
         return GCN10_OK;
     HistParams p = {};
     p.esa = esa;
-    p.hx = ctx->d_hx;
+    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &p.hx)) != GCN10_OK)     // made on first use
+        return rc;
     p.cj = cj;
     p.hist = hist_dev;
     p.W = (uint32_t)W;

@@ -389,7 +389,8 @@ int gcn10_gpu_verify_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int ro
         }
     }
     p.esa = esa;
-    p.hx = ctx->d_hx;
+    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &p.hx)) != GCN10_OK)     // made on first use
+        return rc;
     p.cj = cj;
     p.lut = ctx->d_lut16;
     p.counts = counts_dev;

@@ -185,7 +185,8 @@ int gcn10_gpu_zonal_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W
                     rows, n_zones, n_items);
     ZonalParams p = {};
     p.esa = esa;
-    p.hx = ctx->d_hx;
+    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &p.hx)) != GCN10_OK)     // made on first use
+        return rc;
     p.cj = cj;
     p.spans = spans_dev;
     p.items = items_dev;

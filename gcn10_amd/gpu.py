@@ -322,8 +322,9 @@ class Engine:
         self._chk(lib().gcn10_gpu_stream_copy(self._ctx, src, dst, int(nbytes), stream), "gcn10_gpu_stream_copy")
 
     def soil_words_state(self, stream=None) -> int:
-        """0 = code bytes (option off), 1 = compact words, 2 = code bytes (a column group of the prepared tile
-        spans more than two soil cells); see include/gcn10_gpu.h."""
+        """What aligned strips of the prepared tile read: 0 = code bytes (option off), 1 = compact words,
+        2 = the cell codes through the column map, pixel by pixel (a column group of the tile spans more than two soil cells); see
+        include/gcn10_gpu.h."""
         rc = lib().gcn10_gpu_soil_words_state(self._ctx, stream)
         if rc < 0:
             self._chk(rc, "gcn10_gpu_soil_words_state")

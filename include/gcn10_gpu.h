@@ -154,13 +154,27 @@ int gcn10_gpu_calculate_cn(gcn10_gpu_ctx *ctx, const uint8_t *esa,
  * (src/cn.c:205-290): resample + memcpy + modify_hysogs_data + memset +
  * calculate_cn for every (cond, hc, arc), in one pass over the landcover.
  *
- * gcn10_gpu_prepare_tile: once per block.  Expands the coarse soil window
- * along x only (one row of W bytes per coarse row, kept in a device workspace
- * that stays L2 / Infinity-Cache resident) -- the x half of src/cn.c:218-232.
- * Next to the bytes it writes one compact word per 16-pixel column group and
- * coarse row (two codes and the position where the second begins); strips
- * whose width is a multiple of 16 read those instead of the bytes when every
- * group of the tile has that form (gcn10_gpu_soil_words_state).
+ * gcn10_gpu_prepare_tile: once per block.  Takes a snapshot of the soil of
+ * the block into memory owned by the context -- the x half of
+ * src/cn.c:218-232: the soil code of every coarse cell (hsx * hsy bytes),
+ * the clamped coarse column of every fine column (ci[x] < 0 or >= hsx names
+ * column hsx - 1), and one compact word per 16-pixel column group and coarse
+ * row (two codes and the position where the second begins).  `coarse` and
+ * `ci` are not read after the kernel this call launches: the caller may
+ * reuse them once `stream` has passed it.
+ * Strips whose width is a multiple of 16 read the compact words when every
+ * group of the tile has that form, and otherwise the code of every pixel
+ * from the cell codes through the column map
+ * (gcn10_gpu_soil_words_state).  Everything else that needs soil -- strips of
+ * other widths or of unaligned rasters, strips with "compact_soil" off, the
+ * fused encoder, verify, the pair histograms, the average overviews -- reads
+ * one code byte per fine column and coarse row from a workspace (hsy rows of
+ * W bytes) that is allocated here and filled from the tables by the first
+ * such call after prepare_tile, on that call's stream; a later reader on
+ * another stream waits for that through an event of the context.  The order
+ * the caller has to provide is the one below and no other: every reader's
+ * stream is ordered after prepare_tile's, and the next prepare_tile after the
+ * readers of this one.
  *
  * gcn10_gpu_cn_strip: any number of times per block, one row strip each
  * (rows y0 .. y0+rows of the block; `esa` and every out[] pointer address the
@@ -378,8 +392,9 @@ int gcn10_gpu_verify_buffers(gcn10_gpu_ctx *ctx, const uint8_t *const want[GCN10
 
 /* Launch-shape knobs of the strip kernels, for tuning runs; results never
  * depend on them.  Names: "grid_blocks_per_cu" (1..64), "ilp16" (0 = by raster count | 1 | 2),
- * "ilp1" (1|2|4), "nontemporal" (0|1), "xcd_slabs" (0|1), "prefetch" (software pipeline of the strip kernels: -1 = default = on | 0 | 1), "compact_soil" (0|1: gcn10_gpu_prepare_tile writes,
- * and strips of 16-byte aligned rows read, the compact soil words; default 1), "deflate_wave_codes" (0|1: code
+ * "ilp1" (1|2|4), "nontemporal" (0|1), "xcd_slabs" (0|1), "prefetch" (software pipeline of the strip kernels: -1 = default = on | 0 | 1), "compact_soil" (0|1: strips of
+ * 16-byte aligned rows read the compact soil words of the prepared tile, not its code bytes; takes effect with the next
+ * strip, no new gcn10_gpu_prepare_tile needed; default 1), "deflate_wave_codes" (0|1: code
  * construction of the tile encoder by one thread or one wave per tile), "defaults" (value
  * ignored: every knob back to its built-in default).
  * Round 3: "arena_segment_align" (16..4096, a power of two; default 4096: every raster's extent of a strip starts at a
@@ -423,10 +438,10 @@ int gcn10_gpu_tune_single_raster(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, 
                                  gcn10_stream_t stream);
 
 /* What the strips of the tile last prepared on this context read their soil codes from (synchronises
- * `stream`, on which gcn10_gpu_prepare_tile ran): 0 = code bytes (compact words switched off with
- * gcn10_gpu_set_option("compact_soil", 0)), 1 = compact words -- one dword per 16-pixel column group, used by
- * strips whose width is a multiple of 16 --, 2 = code bytes because some column group of this tile spans
- * more than two soil cells.  <0 on error.  A diagnostic: nothing needs to call it. */
+ * `stream`, on which gcn10_gpu_prepare_tile ran): 0 = code bytes (tables switched off with
+ * gcn10_gpu_set_option("compact_soil", 0)), 1 = compact words -- one dword per 16-pixel column group, used by strips
+ * whose width is a multiple of 16 --, 2 = the cell codes through the column map, pixel by pixel, because some column
+ * group of this tile spans more than two soil cells.  <0 on error.  A diagnostic: nothing needs to call it. */
 int gcn10_gpu_soil_words_state(gcn10_gpu_ctx *ctx, gcn10_stream_t stream);
 
 /* Name of the variant of the strip kernel the last cn_strip call launched

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times gcn10_gpu_prepare_tile (expand_x_codes) on a 36000-wide block: 50 calls between two events."""
+"""Times gcn10_gpu_prepare_tile (soil_tables_kernel) on a 36000-wide block: 50 calls between two events."""
 import os, sys, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

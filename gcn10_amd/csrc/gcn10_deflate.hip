@@ -1446,8 +1446,12 @@ __global__ __launch_bounds__(kTile) void deflate_emit_kernel(const TileJob job)
 
     if (!uniform)
         load_tile(job, job.rasters[raster], tx, ty, sh.tile, t);
-    // the output image: block header from pass B, zeros up to the stream's end
-    for (uint32_t i = t; i < n_words + 1; i += kTile)
+    // the output image: block header from pass B, zeros up to the end of the stream's 16-byte slot (whole vectors
+    // are stored below: the slot's tail goes into the raster's extent and from there into the file)
+    const uint32_t nvec = (stream_bytes + 15) / 16;
+    static_assert(SharedC<true>::kWords >= (kSmallStream + 15) / 16 * 4 + 1 && SharedC<false>::kWords >= (kMaxStream + 15) / 16 * 4 + 1,
+                  "the output image holds the whole slot and the word the emitters may touch behind the stream");
+    for (uint32_t i = t; i < (4 * nvec > n_words + 1 ? 4 * nvec : n_words + 1); i += kTile)
         sh.out[i] = (i < 64 && !stored) ? book->header[i] : 0u;
     for (int i = t; i < 288; i += kTile) {
         sh.lit_len[i] = book->lit_len[i];
@@ -1521,7 +1525,6 @@ __global__ __launch_bounds__(kTile) void deflate_emit_kernel(const TileJob job)
     }
     __syncthreads();
     {
-        const uint32_t nvec = (stream_bytes + 15) / 16;
         u32x4 *dst = reinterpret_cast<u32x4 *>(job.arena + slot);
         const u32x4 *srcv = reinterpret_cast<const u32x4 *>(sh.out);
         for (uint32_t i = t; i < nvec; i += kTile)

@@ -32,7 +32,8 @@
 //             what does not fit the arena.
 //   pass L-C  one workgroup per tile: every thread assembles whole 32-bit words of the stream from the
 //             segments' bit strings (the segment bit offsets are a 4-entry prefix sum) and stores them into
-//             the stream's slot.  No word is written past the stream's 16-byte slot.
+//             the stream's slot.  The whole 16-byte slot is written: zero words behind the stream's last word,
+//             nothing past the slot.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -237,7 +238,9 @@ __global__ __launch_bounds__(256) void lzw_pack_kernel(const LzwJob job)
         base[s + 1] = base[s] + job.seg_bits[(size_t)tile * kSegs + s];
     const uint32_t *segw = job.seg_words + (size_t)tile * kSegs * kSegWords;
     uint32_t *dst = reinterpret_cast<uint32_t *>(job.arena + off);     // 16-byte aligned slot
-    const uint32_t n_words = (bytes + 3u) / 4u;     // <= the slot: stream bytes rounded up to 16
+    // the whole 16-byte slot: the words behind the stream's last one take bits of no segment and are stored as
+    // zeros (the slot's tail goes into the raster's extent and from there into the file)
+    const uint32_t n_words = (bytes + 15u) / 16u * 4u;
     for (uint32_t j = threadIdx.x; j < n_words; j += 256u) {
         const uint32_t p0 = j * 32u, p1 = p0 + 32u;
         uint32_t v = 0;

@@ -372,28 +372,47 @@ class Engine:
                                            arr, stream), "gcn10_gpu_cn_strip")
 
     # -- output encode (src/raster.c:204-219 on the GPU) ----------------------
-    def deflate_rasters(self, raster_ptrs: Sequence[int], W: int, rows: int, stream=None):
-        """zlib-encodes every 256x256 tile of the given device rasters.
-
-        Returns (arena bytes as uint8 array, table uint32[n, down, across, 2])."""
-        n = len(raster_ptrs)
+    def _encode_into_arena(self, launch, where: str, n: int, W: int, rows: int, cap: int, stream, poison: Optional[int],
+                           guard: int, held=()):
+        """The arena / table / cursor contract the three tile encoders share: launch(arena, cap, table, cursor) runs
+        one of them.  Returns (arena bytes, table uint32[n, down, across, 2], used).  poison = a byte value (tests):
+        the arena and `guard` bytes behind arena_cap are filled with it before the launch and the whole image of
+        cap + guard bytes is returned instead of the bytes used."""
         across, down = (W + 255) // 256, (rows + 255) // 256
-        cap = int(lib().gcn10_gpu_deflate_arena_bound(W, rows, n))
-        ptrs = self.upload(np.array(raster_ptrs, dtype=np.uint64))
-        arena = self.alloc(cap)
-        table = self.alloc(n * across * down * 8)
-        cursor = self.alloc(8)
+        image = cap + int(guard) if poison is not None else cap
+        bufs = list(held)
         try:
-            self._chk(lib().gcn10_gpu_deflate_strip(self._ctx, ptrs.ptr, n, W, rows, arena.ptr, cap,
-                                                    table.ptr, cursor.ptr, stream),
-                      "gcn10_gpu_deflate_strip")
+            arena = self.alloc(max(image, 16))
+            bufs.append(arena)
+            table = self.alloc(n * across * down * 8)
+            bufs.append(table)
+            cursor = self.alloc(8)
+            bufs.append(cursor)
+            if poison is not None:
+                self.memset(arena.ptr, int(poison), max(image, 16), stream)
+            self._chk(launch(arena.ptr, cap, table.ptr, cursor.ptr), where)
             used = int(self.download(cursor.ptr, (1,), dtype=np.uint64, stream=stream)[0])
             tab = self.download(table.ptr, (n, down, across, 2), dtype=np.uint32, stream=stream)
-            data = self.download(arena.ptr, (min(used, cap),), stream=stream)
+            data = self.download(arena.ptr, (image if poison is not None else min(used, cap),), stream=stream)
         finally:
-            for b in (ptrs, arena, table, cursor):
+            for b in bufs:
                 b.close()
         return data, tab, used
+
+    def deflate_rasters(self, raster_ptrs: Sequence[int], W: int, rows: int, stream=None, arena_cap: Optional[int] = None,
+                        poison: Optional[int] = None, guard: int = 0):
+        """zlib-encodes every 256x256 tile of the given device rasters.
+
+        Returns (arena bytes as uint8 array, table uint32[n, down, across, 2], used).
+        arena_cap: an arena smaller than gcn10_gpu_deflate_arena_bound (tests: streams that do not fit);
+        poison, guard: see _encode_into_arena."""
+        n = len(raster_ptrs)
+        cap = int(lib().gcn10_gpu_deflate_arena_bound(W, rows, n)) if arena_cap is None else int(arena_cap)
+        ptrs = self.upload(np.array(raster_ptrs, dtype=np.uint64))
+        return self._encode_into_arena(
+            lambda arena, c, table, cursor: lib().gcn10_gpu_deflate_strip(self._ctx, ptrs.ptr, n, W, rows, arena, c, table,
+                                                                          cursor, stream),
+            "gcn10_gpu_deflate_strip", n, W, rows, cap, stream, poison, guard, held=(ptrs,))
 
     def overview_nearest(self, src_ptr: int, W: int, H: int, level: int, dst_ptr: int, stream=None):
         """Level `level` of a W x H device landcover, nearest sampling, into dst (gcn10_gpu_overview_nearest)."""
@@ -488,51 +507,35 @@ class Engine:
         """Worst-case arena bytes of gcn10_gpu_lzw_strip for n_rasters strips of W x rows."""
         return int(lib().gcn10_gpu_lzw_arena_bound(W, rows, n_rasters))
 
-    def lzw_strip(self, raster_ptrs: Sequence[int], W: int, rows: int, stream=None, arena_cap: Optional[int] = None):
+    def lzw_strip(self, raster_ptrs: Sequence[int], W: int, rows: int, stream=None, arena_cap: Optional[int] = None,
+                  poison: Optional[int] = None, guard: int = 0):
         """TIFF-LZW-encodes every 256x256 tile of the given device rasters (gcn10_gpu_lzw_strip).
 
         Returns (arena bytes as uint8 array, table uint32[n, down, across, 2], used).
-        arena_cap: an arena smaller than lzw_arena_bound (tests: streams that do not fit)."""
+        arena_cap: an arena smaller than lzw_arena_bound (tests: streams that do not fit);
+        poison, guard: see _encode_into_arena."""
         n = len(raster_ptrs)
-        across, down = (W + 255) // 256, (rows + 255) // 256
         cap = self.lzw_arena_bound(W, rows, n) if arena_cap is None else int(arena_cap)
         ptrs = self.upload(np.array(raster_ptrs, dtype=np.uint64))
-        arena = self.alloc(max(cap, 16))
-        table = self.alloc(n * across * down * 8)
-        cursor = self.alloc(8)
-        try:
-            self._chk(lib().gcn10_gpu_lzw_strip(self._ctx, ptrs.ptr, n, W, rows, arena.ptr, cap, table.ptr,
-                                                cursor.ptr, stream), "gcn10_gpu_lzw_strip")
-            used = int(self.download(cursor.ptr, (1,), dtype=np.uint64, stream=stream)[0])
-            tab = self.download(table.ptr, (n, down, across, 2), dtype=np.uint32, stream=stream)
-            data = self.download(arena.ptr, (min(used, cap),), stream=stream)
-        finally:
-            for b in (ptrs, arena, table, cursor):
-                b.close()
-        return data, tab, used
+        return self._encode_into_arena(
+            lambda arena, c, table, cursor: lib().gcn10_gpu_lzw_strip(self._ctx, ptrs.ptr, n, W, rows, arena, c, table,
+                                                                      cursor, stream),
+            "gcn10_gpu_lzw_strip", n, W, rows, cap, stream, poison, guard, held=(ptrs,))
 
     def deflate_fused(self, esa_d: int, W: int, rows: int, cj_d: int, cond_mask: int = 3,
-                      table_mask: int = ALL_TABLES, stream=None, arena_cap: Optional[int] = None):
+                      table_mask: int = ALL_TABLES, stream=None, arena_cap: Optional[int] = None,
+                      poison: Optional[int] = None, guard: int = 0):
         """Encoded tiles of the selected rasters straight from landcover + prepared soil
         (gcn10_gpu_deflate_fused_strip).  Returns (arena bytes, table uint32[n, down, across, 2], used).
-        arena_cap: an arena smaller than gcn10_gpu_deflate_arena_bound (tests: streams that do not fit)."""
+        arena_cap: an arena smaller than gcn10_gpu_deflate_arena_bound (tests: streams that do not fit);
+        poison, guard: see _encode_into_arena."""
         n = bin(cond_mask & 3).count("1") * bin(table_mask & ALL_TABLES).count("1")
-        across, down = (W + 255) // 256, (rows + 255) // 256
         cap = int(lib().gcn10_gpu_deflate_arena_bound(W, rows, n)) if arena_cap is None else int(arena_cap)
-        arena = self.alloc(cap)
-        table = self.alloc(n * across * down * 8)
-        cursor = self.alloc(8)
-        try:
-            self._chk(lib().gcn10_gpu_deflate_fused_strip(self._ctx, esa_d, W, rows, cj_d, cond_mask,
-                                                          table_mask, arena.ptr, cap, table.ptr, cursor.ptr,
-                                                          stream), "gcn10_gpu_deflate_fused_strip")
-            used = int(self.download(cursor.ptr, (1,), dtype=np.uint64, stream=stream)[0])
-            tab = self.download(table.ptr, (n, down, across, 2), dtype=np.uint32, stream=stream)
-            data = self.download(arena.ptr, (min(used, cap),), stream=stream)
-        finally:
-            for b in (arena, table, cursor):
-                b.close()
-        return data, tab, used
+        return self._encode_into_arena(
+            lambda arena, c, table, cursor: lib().gcn10_gpu_deflate_fused_strip(self._ctx, esa_d, W, rows, cj_d, cond_mask,
+                                                                                table_mask, arena, c, table, cursor,
+                                                                                stream),
+            "gcn10_gpu_deflate_fused_strip", n, W, rows, cap, stream, poison, guard)
 
     @staticmethod
     def inflate_codecs() -> int:

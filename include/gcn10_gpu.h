@@ -214,6 +214,16 @@ size_t gcn10_gpu_strip_algorithmic_bytes(int W, int rows, int hsx, int hsy,
  * dynamic Huffman) in `arena_dev`; table_dev[(r*tiles + ty*across + tx)*2 + {0,1}]
  * receives the stream's byte offset in the arena and its size (offset 0xffffffff:
  * the arena was too small); *cursor_dev receives the number of arena bytes used.
+ * The arena: streams lie in index order (raster-major, tiles row-major), each in a slot of
+ * its size rounded up to 16 bytes; raster 0's extent starts at 0, every later raster's at
+ * the next multiple of "arena_segment_align" (gcn10_gpu_set_option) behind the previous
+ * raster's last slot; the cursor is the end of the last raster's last slot, not aligned.
+ * A stream fits iff offset + slot <= arena_cap.  Inside [0, ceil_align(cursor)) every byte
+ * is part of a stream or ZERO -- slot tails, the pads between extents and the pad behind
+ * the last one are written as zeros, in whole 16-byte units that end at or before
+ * arena_cap -- because the host writes whole extents into the files; no other byte of the
+ * arena, and none at or behind arena_cap, is touched (tests/arena_model.py states the
+ * rule in Python; tests/test_gpu_arena.py holds all three encoders to it).
  * rasters_dev is a DEVICE array of n_rasters device pointers.  Asynchronous on
  * `stream`.  The raw rasters never have to cross PCIe. */
 size_t gcn10_gpu_deflate_arena_bound(int W, int rows, int n_rasters);

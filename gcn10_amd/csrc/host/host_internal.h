@@ -20,6 +20,12 @@ int gcn10_tiff_read_window(struct gcn10_tiff *t, int xoff, int yoff, int xcount,
                            uint8_t *dst, size_t dst_stride, char *err, size_t errcap);
 
 
+/* size of overview level k of a raster n pixels wide or high: ceil(n / 2^k) */
+static inline int gcn10_level_dim(int n, int k)
+{
+    return (int)(((int64_t)n + ((int64_t)1 << k) - 1) >> k);
+}
+
 /* pool.c: fixed thread pool (tile compression, tile decode) */
 typedef struct gcn10_pool gcn10_pool;
 typedef void (*gcn10_job_fn)(void *arg);

@@ -365,14 +365,6 @@ gpu_error:
 /* worker resources                                                          */
 /* ------------------------------------------------------------------------ */
 
-#define GPU_TRY(w, call)                                                       \
-    do {                                                                       \
-        if ((call) != 0) {                                                     \
-            wlog((w), "ERROR", true, "gpu: %s", (w)->run->gpu->last_error());  \
-            return -1;                                                         \
-        }                                                                      \
-    } while (0)
-
 static void free_strip_buffers(struct worker *w)
 {
     const struct gcn10_gpu_api *g = w->run->gpu;
@@ -421,18 +413,18 @@ static int ensure_strip_buffers(struct worker *w, int W)
 
             if (!w->run->gpu_deflate)
             {
-                GPU_TRY(w, g->host_alloc(w->ctx, px, (void **)&b->h_out[k]));
+                GPU_OR_RETURN(w, -1, g->host_alloc(w->ctx, px, (void **)&b->h_out[k]));
                 atomic_fetch_add(&w->run->pinned_bytes, (long long)px);
             }
             if (!w->fused)
-                GPU_TRY(w, g->malloc(w->ctx, px, (void **)&b->d_out[k]));
+                GPU_OR_RETURN(w, -1, g->malloc(w->ctx, px, (void **)&b->d_out[k]));
         }
         if (w->run->gpu_deflate) {
             size_t tiles = n_tiles;
 
             b->arena_cap = w->run->lzw ? g->lzw_arena_bound(W, w->strip_rows, GCN10_N_RASTERS)
                                        : g->deflate_arena_bound(W, w->strip_rows, GCN10_N_RASTERS);
-            GPU_TRY(w, g->malloc(w->ctx, b->arena_cap + 4096, (void **)&b->d_arena));
+            GPU_OR_RETURN(w, -1, g->malloc(w->ctx, b->arena_cap + 4096, (void **)&b->d_arena));
             b->h_arena_cap = b->arena_cap / 8 > ((size_t)32 << 20) ? b->arena_cap / 8 : ((size_t)32 << 20);
             if (getenv("GCN10_PINNED_ARENA_BYTES"))        /* tests: force the spill path */
                 b->h_arena_cap = (size_t)strtoull(getenv("GCN10_PINNED_ARENA_BYTES"), NULL, 10);
@@ -441,22 +433,22 @@ static int ensure_strip_buffers(struct worker *w, int W)
             if (b->h_arena_cap > b->arena_cap)
                 b->h_arena_cap = b->arena_cap;
             b->h_arena_cap &= ~(size_t)4095;
-            GPU_TRY(w, g->host_alloc(w->ctx, b->h_arena_cap + 4096, (void **)&b->h_arena));
+            GPU_OR_RETURN(w, -1, g->host_alloc(w->ctx, b->h_arena_cap + 4096, (void **)&b->h_arena));
             atomic_fetch_add(&w->run->pinned_bytes, (long long)(b->h_arena_cap + 4096 + tiles * GCN10_N_RASTERS * 8));
-            GPU_TRY(w, g->malloc(w->ctx, tiles * GCN10_N_RASTERS * 8, (void **)&b->d_table));
-            GPU_TRY(w, g->host_alloc(w->ctx, tiles * GCN10_N_RASTERS * 8, (void **)&b->h_table));
-            GPU_TRY(w, g->malloc(w->ctx, 8, (void **)&b->d_cursor));
-            GPU_TRY(w, g->host_alloc(w->ctx, 8, (void **)&b->h_cursor));
+            GPU_OR_RETURN(w, -1, g->malloc(w->ctx, tiles * GCN10_N_RASTERS * 8, (void **)&b->d_table));
+            GPU_OR_RETURN(w, -1, g->host_alloc(w->ctx, tiles * GCN10_N_RASTERS * 8, (void **)&b->h_table));
+            GPU_OR_RETURN(w, -1, g->malloc(w->ctx, 8, (void **)&b->d_cursor));
+            GPU_OR_RETURN(w, -1, g->host_alloc(w->ctx, 8, (void **)&b->h_cursor));
             if (!w->fused) {
                 /* the per-raster encoder takes the selected strips, packed in raster order */
                 uint8_t *packed[GCN10_N_RASTERS] = { 0 };
 
                 for (int q = 0; q < w->run->n_sel; q++)
                     packed[q] = b->d_out[w->run->sel[q]];
-                GPU_TRY(w, g->malloc(w->ctx, GCN10_N_RASTERS * sizeof(void *), (void **)&b->d_ptrs));
-                GPU_TRY(w, g->memcpy_h2d(w->ctx, (void *)b->d_ptrs, packed, GCN10_N_RASTERS * sizeof(void *),
+                GPU_OR_RETURN(w, -1, g->malloc(w->ctx, GCN10_N_RASTERS * sizeof(void *), (void **)&b->d_ptrs));
+                GPU_OR_RETURN(w, -1, g->memcpy_h2d(w->ctx, (void *)b->d_ptrs, packed, GCN10_N_RASTERS * sizeof(void *),
                                          w->s_kernel));
-                GPU_TRY(w, g->stream_sync(w->ctx, w->s_kernel));
+                GPU_OR_RETURN(w, -1, g->stream_sync(w->ctx, w->s_kernel));
             }
         }
     }
@@ -476,7 +468,7 @@ int gcn10_ensure_pinned_on(struct worker *w, gcn10_gpu_ctx *ctx, void **p, size_
     *p = NULL;
     *cap = 0;
     need += need / 8 + 4096;
-    GPU_TRY(w, g->host_alloc(ctx, need, p));
+    GPU_OR_RETURN(w, -1, g->host_alloc(ctx, need, p));
     atomic_fetch_add(&w->run->pinned_bytes, (long long)need);
     *cap = need;
     return 0;
@@ -489,10 +481,10 @@ int gcn10_ensure_dev_on(struct worker *w, gcn10_gpu_ctx *ctx, void **p, size_t *
     if (need <= *cap)
         return 0;
     if (*p)
-        GPU_TRY(w, g->free(ctx, *p));
+        GPU_OR_RETURN(w, -1, g->free(ctx, *p));
     *p = NULL;
     *cap = 0;
-    GPU_TRY(w, g->malloc(ctx, need, p));
+    GPU_OR_RETURN(w, -1, g->malloc(ctx, need, p));
     *cap = need;
     return 0;
 }
@@ -720,95 +712,34 @@ static int encode_overviews(struct worker *w, struct block_in *in, gcn10_tiff_wr
     gcn10_tiff_writer *lv[GCN10_N_RASTERS];
 
     if (!r->ov_average) {
-        const int W1 = (W + 1) / 2, H1 = (H + 1) / 2;
-        /* a level's ci, padded to a multiple of 4 entries, then its cj: at most W1 + 3 + H1 entries */
-        const size_t n_idx = (size_t)W1 + 4 + (size_t)H1;
-        int32_t *idx = malloc(n_idx * sizeof *idx);
-
-        if (!idx) {
-            wlog(w, "ERROR", true, "malloc failed for overview index maps");
-            return -1;
-        }
-        if (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov, &w->ov_cap, (size_t)W1 * (size_t)H1 + 16) != 0 ||
-            gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov_idx, &w->ov_idx_cap, n_idx * sizeof *idx) != 0) {
-            free(idx);
-            return -1;
-        }
         for (int k = L; k >= 1; k--) {
-            const int Wk = (int)(((int64_t)W + ((int64_t)1 << k) - 1) >> k);
-            const int Hk = (int)(((int64_t)H + ((int64_t)1 << k) - 1) >> k);
-            const int half = 1 << (k - 1);
-            /* cj of the level right after its ci, 16-byte aligned */
-            const size_t cj_at = ((size_t)Wk + 3) & ~(size_t)3;
-            int32_t *d_ci = w->d_ov_idx, *d_cj = w->d_ov_idx + cj_at;
+            const int32_t *d_cj;
+            int Wk, Hk;
 
-            for (int x = 0; x < Wk; x++)
-                idx[x] = in->h_ci[(int64_t)x * (1 << k) + half < W ? (int64_t)x * (1 << k) + half : W - 1];
-            for (int y = 0; y < Hk; y++)
-                idx[cj_at + y] = in->h_cj[(int64_t)y * (1 << k) + half < H ? (int64_t)y * (1 << k) + half : H - 1];
-            if (g->overview_nearest(w->ctx, in->d_block, W, H, k, w->d_ov, w->s_kernel) != 0 ||
-                g->memcpy_h2d(w->ctx, w->d_ov_idx, idx, (cj_at + (size_t)Hk) * sizeof *idx, w->s_kernel) != 0 ||
-                g->stream_sync(w->ctx, w->s_kernel) != 0 ||
-                g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, d_ci, Wk, w->s_kernel) != 0) {
-                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
-                free(idx);
+            if (gcn10_level_nearest(w, in, k, &Wk, &Hk, &d_cj) != 0)
                 return -1;
-            }
             for (int q = 0; q < GCN10_N_RASTERS; q++)
                 lv[q] = tifs[q] ? gcn10_tiff_level(tifs[q], k) : NULL;
-            if (run_strips(w, Wk, Hk, w->d_ov, d_cj, NULL, NULL, lv) != 0) {
-                free(idx);
+            if (run_strips(w, Wk, Hk, w->d_ov, d_cj, NULL, NULL, lv) != 0)
                 return -1;
-            }
             /* the next level overwrites the index maps and the level's landcover: this one's kernels are done */
-            if (g->stream_sync(w->ctx, w->s_kernel) != 0) {
-                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
-                free(idx);
-                return -1;
-            }
+            GPU_OR_RETURN(w, -1, g->stream_sync(w->ctx, w->s_kernel));
         }
-        free(idx);
-        if (g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, W, w->s_kernel) != 0) {
-            wlog(w, "ERROR", true, "gpu: %s", g->last_error());
-            return -1;
-        }
+        GPU_OR_RETURN(w, -1, g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, W, w->s_kernel));
         return 0;
     }
 
     /* average: the pyramid of the selected rasters, level by level, raster by raster */
     {
-        size_t lvl_off[GCN10_COG_MAX_LEVELS + 1], total = 0;
         uint8_t *levels[GCN10_N_RASTERS * GCN10_COG_MAX_LEVELS];
-        size_t n_ptrs = 0;
+        /* level 1 has the most strips */
+        const size_t n_ptrs = ((size_t)gcn10_level_dim(H, 1) + (size_t)w->strip_rows - 1) / (size_t)w->strip_rows;
 
-        for (int k = 1; k <= L; k++) {
-            const size_t Wk = (size_t)(((int64_t)W + ((int64_t)1 << k) - 1) >> k);
-            const size_t Hk = (size_t)(((int64_t)H + ((int64_t)1 << k) - 1) >> k);
-            const int n_strips = (int)((Hk + (size_t)w->strip_rows - 1) / (size_t)w->strip_rows);
-
-            lvl_off[k] = total;
-            total += (Wk * Hk + 255) & ~(size_t)255;
-            n_ptrs = (size_t)n_strips > n_ptrs ? (size_t)n_strips : n_ptrs;
-        }
-        if (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov, &w->ov_cap, total * (size_t)r->n_sel + 16) != 0 ||
-            gcn10_ensure_dev_on(w, w->ctx, &w->d_ov_ptrs, &w->ov_ptrs_cap,
-                                n_ptrs * GCN10_N_RASTERS * sizeof(void *)) != 0)
+        if (gcn10_ensure_dev_on(w, w->ctx, &w->d_ov_ptrs, &w->ov_ptrs_cap, n_ptrs * GCN10_N_RASTERS * sizeof(void *)) != 0 ||
+            gcn10_levels_average(w, in, L, w->strip_rows, levels) != 0)
             return -1;
-        for (int q = 0; q < r->n_sel; q++)
-            for (int k = 1; k <= L; k++)
-                levels[q * L + k - 1] = w->d_ov + (size_t)q * total + lvl_off[k];
-        for (int y0 = 0; y0 < H; y0 += w->strip_rows) {
-            const int rows = H - y0 < w->strip_rows ? H - y0 : w->strip_rows;
-
-            if (g->overview_average(w->ctx, in->d_block, W, H, y0, rows, in->d_cj, r->cond_mask, r->table_mask, L,
-                                    levels, w->s_kernel) != 0) {
-                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
-                return -1;
-            }
-        }
         for (int k = L; k >= 1; k--) {
-            const int Wk = (int)(((int64_t)W + ((int64_t)1 << k) - 1) >> k);
-            const int Hk = (int)(((int64_t)H + ((int64_t)1 << k) - 1) >> k);
+            const int Wk = gcn10_level_dim(W, k), Hk = gcn10_level_dim(H, k);
             const int n_strips = (Hk + w->strip_rows - 1) / w->strip_rows;
             const uint8_t **tab = calloc((size_t)n_strips * GCN10_N_RASTERS, sizeof *tab);
 
@@ -832,10 +763,7 @@ static int encode_overviews(struct worker *w, struct block_in *in, gcn10_tiff_wr
                 lv[q] = tifs[q] ? gcn10_tiff_level(tifs[q], k) : NULL;
             if (run_strips(w, Wk, Hk, NULL, NULL, (const uint8_t *const *)w->d_ov_ptrs, NULL, lv) != 0)
                 return -1;
-            if (g->stream_sync(w->ctx, w->s_kernel) != 0) {       /* the pointer table is rewritten next */
-                wlog(w, "ERROR", true, "gpu: %s", g->last_error());
-                return -1;
-            }
+            GPU_OR_RETURN(w, -1, g->stream_sync(w->ctx, w->s_kernel));    /* the pointer table is rewritten next */
         }
     }
     return 0;
@@ -927,9 +855,9 @@ static int encode_block(struct worker *w, struct block_in *in)
         if (g->event_sync(w->ctx, in->ev_ready) != 0)
             goto gpu_fail;
         for (size_t i = 0; i < in->n_inflate; i++)
-            if (in->h_status[i] != 0) {
+            if (in->jl.h_status[i] != 0) {
                 wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
-                                       "(stream %zu, reason %u)", in->xoff, in->yoff, W, H, i, in->h_status[i]);
+                                       "(stream %zu, reason %u)", in->xoff, in->yoff, W, H, i, in->jl.h_status[i]);
                 wlog(w, "ERROR", true, "esa load failed for block %d", block_id);
                 ok = false;
                 break;
@@ -1156,18 +1084,18 @@ static int worker_setup(struct worker *w)
      * it waits for a strip's table, would otherwise spin in user mode for the whole wait (GCN10_EVENT_SLEEP_US=0: spin) */
     if (r->event_sleep_us > 0 && g->set_option)
         (void)g->set_option(w->ctx, "event_sync_sleep_us", r->event_sleep_us);
-    GPU_TRY(w, g->set_tables(w->ctx, &r->tables[0][0][0], 9));
+    GPU_OR_RETURN(w, -1, g->set_tables(w->ctx, &r->tables[0][0][0], 9));
     w->fused = r->fused && g->deflate_fused_available(w->ctx) == 1;
     if (r->fused && !w->fused)
         wlog(w, "INFO", false, "the lookup tables define more than 256 pixel classes: "
                                "per-raster GPU encoding instead of the fused encoder");
-    GPU_TRY(w, g->stream_create(w->ctx, &w->s_kernel));
-    GPU_TRY(w, g->stream_create(w->ctx, &w->s_d2h));
+    GPU_OR_RETURN(w, -1, g->stream_create(w->ctx, &w->s_kernel));
+    GPU_OR_RETURN(w, -1, g->stream_create(w->ctx, &w->s_d2h));
     for (int i = 0; i < w->run->nbuf; i++) {
-        GPU_TRY(w, g->event_create(w->ctx, &w->buf[i].ev_h2d));
-        GPU_TRY(w, g->event_create(w->ctx, &w->buf[i].ev_kernel));
-        GPU_TRY(w, g->event_create(w->ctx, &w->buf[i].ev_d2h));
-        GPU_TRY(w, g->event_create(w->ctx, &w->buf[i].ev_meta));
+        GPU_OR_RETURN(w, -1, g->event_create(w->ctx, &w->buf[i].ev_h2d));
+        GPU_OR_RETURN(w, -1, g->event_create(w->ctx, &w->buf[i].ev_kernel));
+        GPU_OR_RETURN(w, -1, g->event_create(w->ctx, &w->buf[i].ev_d2h));
+        GPU_OR_RETURN(w, -1, g->event_create(w->ctx, &w->buf[i].ev_meta));
     }
     /* the reference reopens both rasters for every block (src/raster.c:119);
      * here each worker keeps its own handles */

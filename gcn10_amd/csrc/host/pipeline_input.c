@@ -32,52 +32,6 @@
 #define now_seconds gcn10_now_seconds
 #define wlog gcn10_wlog
 
-enum { RING_BYTES = 64 << 20 };     /* one pinned staging buffer; a block of DEFLATE landcover is 2-3 of them */
-
-/* chunks of a read plan -> pinned staging, a slice per pool job */
-struct comp_job {
-    const struct gcn10_chunk_ref *chunks;
-    const gcn10_inflate_tile *jobs;
-    size_t n;
-    uint8_t *dst;                   /* staging buffer; chunk i goes to dst + (jobs[i].in_off - base) */
-    uint64_t base;
-    pthread_mutex_t *mu;
-    pthread_cond_t *cv;
-    int *pending, *failed;
-};
-
-static void comp_job_run(void *arg)
-{
-    struct comp_job *j = arg;
-    int bad = 0;
-
-    for (size_t i = 0; i < j->n && !bad; i++) {
-        uint8_t *p = j->dst + (j->jobs[i].in_off - j->base);
-        size_t left = j->chunks[i].nbytes;
-        uint64_t off = j->chunks[i].file_off;
-
-        while (left > 0) {
-            ssize_t got = pread(j->chunks[i].fd, p, left, (off_t)off);
-
-            if (got <= 0) {
-                bad = 1;
-                break;
-            }
-            p += got;
-            off += (uint64_t)got;
-            left -= (size_t)got;
-        }
-        memset(p, 0, 16);               /* the decoder's bit reader may look a few bytes ahead */
-    }
-    pthread_mutex_lock(j->mu);
-    if (bad)
-        *j->failed = 1;
-    if (--*j->pending == 0)
-        pthread_cond_broadcast(j->cv);
-    pthread_mutex_unlock(j->mu);
-    free(j);
-}
-
 /* longest stream first among the compressed ones (one workgroup decodes one stream and the GPU hands
  * workgroups out in index order: the stragglers start first); raw chunks keep their file order behind them */
 static int by_size_desc(const void *a, const void *b)
@@ -92,57 +46,6 @@ static int by_size_desc(const void *a, const void *b)
     return x->nbytes < y->nbytes ? 1 : (x->nbytes > y->nbytes ? -1 : 0);
 }
 
-#define GPU_IN(w, call)                                                        \
-    do {                                                                       \
-        if ((call) != 0) {                                                     \
-            wlog((w), "ERROR", true, "gpu: %s", (w)->run->gpu->last_error());  \
-            return -2;                                                         \
-        }                                                                      \
-    } while (0)
-
-/* a staging buffer of the ring, free to be written: its last copy to the device has finished */
-static int ring_take(struct worker *w, int k)
-{
-    const struct gcn10_gpu_api *g = w->run->gpu;
-
-    if (w->ring_busy[k]) {
-        GPU_IN(w, g->event_sync(w->in_ctx, w->ev_ring[k]));
-        w->ring_busy[k] = false;
-    }
-    return 0;
-}
-
-static int ring_sent(struct worker *w, int k)
-{
-    GPU_IN(w, w->run->gpu->event_record(w->in_ctx, w->ev_ring[k], w->s_in));
-    w->ring_busy[k] = true;
-    return 0;
-}
-
-static int ring_ensure(struct worker *w, size_t need)
-{
-    const struct gcn10_gpu_api *g = w->run->gpu;
-
-    if (need <= w->ring_cap)
-        return 0;
-    for (int k = 0; k < N_RING; k++) {
-        if (ring_take(w, k) != 0)
-            return -2;
-        if (w->h_ring[k])
-            g->host_free(w->in_ctx, w->h_ring[k]);
-        w->h_ring[k] = NULL;
-    }
-    w->ring_cap = 0;
-    need = (need + 4095) & ~(size_t)4095;
-    for (int k = 0; k < N_RING; k++)
-    {
-        GPU_IN(w, g->host_alloc(w->in_ctx, need, (void **)&w->h_ring[k]));
-        atomic_fetch_add(&w->run->pinned_bytes, (long long)need);
-    }
-    w->ring_cap = need;
-    return 0;
-}
-
 /* The landcover window through the GPU side.  0 = issued on s_in; 1 = this window needs the host reader;
  * -1 = the window cannot be read (logged; the block is skipped as after a failed load_raster,
  * src/cn.c:188-192); -2 = device error (logged; fatal for the run). */
@@ -150,12 +53,11 @@ static int stage_planned(struct worker *w, struct block_in *in)
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
+    struct gcn10_job_list *jl = &in->jl;
     struct gcn10_read_plan plan;
     char err[1024] = "";
-    pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
-    pthread_cond_t cv = PTHREAD_COND_INITIALIZER;
-    int rc, k = 0;
-    size_t comp_bytes = 0, largest = 0;
+    int rc;
+    size_t comp_bytes = 0, largest = RING_BYTES, n_bad = 0;
     const int W = in->W, H = in->H;
     double t0 = now_seconds();
 
@@ -170,119 +72,42 @@ static int stage_planned(struct worker *w, struct block_in *in)
     if (!getenv("GCN10_INFLATE_FILE_ORDER"))      /* (A/B switch for tools/) */
         qsort(plan.chunks, plan.n, sizeof *plan.chunks, by_size_desc);
     rc = -2;
-    if (plan.n > in->jobs_cap) {
-        if (in->h_jobs) g->host_free(w->in_ctx, in->h_jobs);
-        if (in->d_jobs) g->free(w->in_ctx, in->d_jobs);
-        if (in->h_status) g->host_free(w->in_ctx, in->h_status);
-        if (in->d_status) g->free(w->in_ctx, in->d_status);
-        in->h_jobs = NULL;
-        in->d_jobs = NULL;
-        in->h_status = NULL;
-        in->d_status = NULL;
-        in->jobs_cap = 0;
-        if (g->host_alloc(w->in_ctx, plan.n * sizeof *in->h_jobs, (void **)&in->h_jobs) != 0 ||
-            g->malloc(w->in_ctx, plan.n * sizeof *in->d_jobs, (void **)&in->d_jobs) != 0 ||
-            g->host_alloc(w->in_ctx, plan.n * 4, (void **)&in->h_status) != 0 ||
-            g->malloc(w->in_ctx, plan.n * 4, (void **)&in->d_status) != 0)
-            goto gpu_fail;
-        in->jobs_cap = plan.n;
-    }
+    if (gcn10_job_list_ensure(g, w->in_ctx, jl, plan.n, 0) != 0)
+        goto gpu_fail;
     for (size_t i = 0; i < plan.n; i++) {
         const struct gcn10_chunk_ref *c = &plan.chunks[i];
-        gcn10_inflate_tile *j = &in->h_jobs[i];
-        const size_t slot = (((size_t)c->nbytes + 15) & ~(size_t)15) + 16;
+        const size_t slot = gcn10_chunk_slot(c->nbytes);
 
-        j->in_off = comp_bytes;
-        j->in_len = c->nbytes;
-        j->out_len = c->out_len;
-        j->chunk_w = c->chunk_w;
-        j->src_x = c->src_x;
-        j->src_y = c->src_y;
-        j->copy_w = c->copy_w;
-        j->copy_h = c->copy_h;
-        j->flags = c->flags;
-        j->dst_off = (uint64_t)c->dst_y * (uint64_t)W + c->dst_x;
+        gcn10_inflate_job_from_chunk(&jl->h_jobs[i], c, comp_bytes, (uint64_t)c->dst_y * (uint64_t)W + c->dst_x);
         comp_bytes += slot;
         if (slot > largest)
             largest = slot;
-        in->h_status[i] = 0xffffffffu;
+        jl->h_status[i] = 0xffffffffu;
     }
-    if (gcn10_ensure_dev_on(w, w->in_ctx, (void **)&in->d_comp, &in->d_comp_cap, comp_bytes + 16) != 0 ||
-        ring_ensure(w, largest > (size_t)RING_BYTES ? largest : (size_t)RING_BYTES) != 0)
+    if (gcn10_ensure_dev_on(w, w->in_ctx, (void **)&in->d_comp, &in->d_comp_cap, comp_bytes + 16) != 0)
         goto out;               /* logged */
-    if (plan.covered < (uint64_t)W * (uint64_t)H &&
-        g->memset(w->in_ctx, in->d_block, 0, (size_t)W * (size_t)H, w->s_in) != 0)
+    /* the ring takes the largest chunk: none is too large to stage */
+    if (gcn10_stager_ensure(&w->ring, largest) != 0 ||
+        (plan.covered < (uint64_t)W * (uint64_t)H &&
+         g->memset(w->in_ctx, in->d_block, 0, (size_t)W * (size_t)H, w->s_in) != 0) ||
+        gcn10_stager_stage(&w->ring, plan.chunks, jl->h_jobs, plan.n, in->d_comp, w->s_in, jl->bad) != 0)
         goto gpu_fail;
-
-    /* batches of chunks: the pool preads batch b into staging buffer b % N_RING while the copy of batch
-     * b - 1 to the device is in flight */
-    for (size_t i0 = 0; i0 < plan.n;) {
-        const uint64_t base = in->h_jobs[i0].in_off;
-        size_t i1 = i0;
-        uint64_t end = base;
-        int pending = 0, failed = 0;
-
-        while (i1 < plan.n) {
-            const uint64_t e = in->h_jobs[i1].in_off + ((((uint64_t)in->h_jobs[i1].in_len + 15) & ~(uint64_t)15) + 16);
-
-            if (e - base > w->ring_cap)
-                break;
-            end = e;
-            i1++;
-        }
-        if (ring_take(w, k) != 0)
-            goto out;
-        for (size_t i = i0; i < i1; i += 32) {
-            struct comp_job *j = malloc(sizeof *j);
-            struct comp_job job = { plan.chunks + i, in->h_jobs + i, i1 - i < 32 ? i1 - i : 32, w->h_ring[k], base,
-                                    &mu, &cv, &pending, &failed };
-
-            pthread_mutex_lock(&mu);
-            pending++;
-            pthread_mutex_unlock(&mu);
-            if (!j || !r->pool) {
-                struct comp_job *tmp = j ? j : malloc(sizeof *tmp);
-
-                if (!tmp) {
-                    pthread_mutex_lock(&mu);
-                    pending--;
-                    failed = 1;
-                    pthread_mutex_unlock(&mu);
-                    break;
-                }
-                *tmp = job;
-                comp_job_run(tmp);
-                continue;
-            }
-            *j = job;
-            gcn10_pool_submit(r->pool, comp_job_run, j);
-        }
-        pthread_mutex_lock(&mu);
-        while (pending > 0)
-            pthread_cond_wait(&cv, &mu);
-        pthread_mutex_unlock(&mu);
-        if (failed) {
-            w->t_read += now_seconds() - t0;
-            wlog(w, "ERROR", true, "gdalrasterio error: cannot read the landcover tiles of the window %d,%d %dx%d",
-                 in->xoff, in->yoff, W, H);
-            wlog(w, "ERROR", true, "esa load failed for block %d", in->block_id);
-            rc = -1;
-            goto out;
-        }
-        if (g->memcpy_h2d(w->in_ctx, in->d_comp + base, w->h_ring[k], (size_t)(end - base), w->s_in) != 0)
-            goto gpu_fail;
-        if (ring_sent(w, k) != 0)
-            goto out;
-        k = (k + 1) % N_RING;
-        i0 = i1;
-    }
     w->t_read += now_seconds() - t0;
+    for (size_t i = 0; i < plan.n; i++)
+        n_bad += jl->bad[i] != 0;
+    if (n_bad) {
+        wlog(w, "ERROR", true, "gdalrasterio error: cannot read the landcover tiles of the window %d,%d %dx%d",
+             in->xoff, in->yoff, W, H);
+        wlog(w, "ERROR", true, "esa load failed for block %d", in->block_id);
+        rc = -1;
+        goto out;
+    }
     if (plan.n > 0 &&
-        (g->memcpy_h2d(w->in_ctx, in->d_jobs, in->h_jobs, plan.n * sizeof *in->h_jobs, w->s_in) != 0 ||
-         g->memcpy_h2d(w->in_ctx, in->d_status, in->h_status, plan.n * 4, w->s_in) != 0 ||
-         g->inflate_tiles(w->in_ctx, in->d_comp, in->d_jobs, (int)plan.n, plan.max_chunk_bytes ? plan.max_chunk_bytes : 16,
-                          in->d_block, (size_t)W, in->d_status, w->s_in) != 0 ||
-         g->memcpy_d2h(w->in_ctx, in->h_status, in->d_status, plan.n * 4, w->s_in) != 0))
+        (g->memcpy_h2d(w->in_ctx, jl->d_jobs, jl->h_jobs, plan.n * sizeof *jl->h_jobs, w->s_in) != 0 ||
+         g->memcpy_h2d(w->in_ctx, jl->d_status, jl->h_status, plan.n * 4, w->s_in) != 0 ||
+         g->inflate_tiles(w->in_ctx, in->d_comp, jl->d_jobs, (int)plan.n, plan.max_chunk_bytes ? plan.max_chunk_bytes : 16,
+                          in->d_block, (size_t)W, jl->d_status, w->s_in) != 0 ||
+         g->memcpy_d2h(w->in_ctx, jl->h_status, jl->d_status, plan.n * 4, w->s_in) != 0))
         goto gpu_fail;
     in->n_inflate = plan.n;
     w->n_win_gpu++;
@@ -316,9 +141,9 @@ static int stage_host(struct worker *w, struct block_in *in)
     char err[1024] = "";
     int band, k = 0;
 
-    if (ring_ensure(w, (size_t)W * 256 > (size_t)RING_BYTES ? (size_t)W * 256 : (size_t)RING_BYTES) != 0)
-        return -2;
-    band = (int)(w->ring_cap / (size_t)W);
+    GPU_OR_RETURN(w, -2, gcn10_stager_ensure(&w->ring, (size_t)W * 256 > (size_t)RING_BYTES ? (size_t)W * 256
+                                                                                              : (size_t)RING_BYTES));
+    band = (int)(w->ring.cap / (size_t)W);
     if (band > r->strip_rows)
         band = r->strip_rows;           /* the granularity of round 1-2's per-strip reads */
     for (int y0 = 0; y0 < H; y0 += band) {
@@ -326,19 +151,17 @@ static int stage_host(struct worker *w, struct block_in *in)
         double t0 = now_seconds();
         int rc;
 
-        if (ring_take(w, k) != 0)
-            return -2;
-        rc = gcn10_raster_read_mt(w->esa, in->xoff, in->yoff + y0, W, rows, w->h_ring[k], r->pool, err, sizeof err);
+        GPU_OR_RETURN(w, -2, gcn10_stager_take(&w->ring, k));
+        rc = gcn10_raster_read_mt(w->esa, in->xoff, in->yoff + y0, W, rows, w->ring.h[k], r->pool, err, sizeof err);
         w->t_read += now_seconds() - t0;
         if (rc != 0) {
             wlog(w, "ERROR", true, "%s", err);
             wlog(w, "ERROR", true, "esa load failed for block %d", in->block_id);
             return -1;
         }
-        GPU_IN(w, g->memcpy_h2d(w->in_ctx, in->d_block + (size_t)y0 * (size_t)W, w->h_ring[k],
-                                (size_t)W * (size_t)rows, w->s_in));
-        if (ring_sent(w, k) != 0)
-            return -2;
+        GPU_OR_RETURN(w, -2, g->memcpy_h2d(w->in_ctx, in->d_block + (size_t)y0 * (size_t)W, w->ring.h[k],
+                                           (size_t)W * (size_t)rows, w->s_in));
+        GPU_OR_RETURN(w, -2, gcn10_stager_sent(&w->ring, k, w->s_in));
         k = (k + 1) % N_RING;
     }
     return 0;
@@ -435,8 +258,7 @@ static int fill_block(struct worker *w, struct block_in *in, int block_id)
     if (rc != 0) {
         /* nothing of a block that is not going to be encoded may still be in flight when its slot is reused */
         g->stream_sync(w->in_ctx, w->s_in);
-        for (int k = 0; k < N_RING; k++)
-            w->ring_busy[k] = false;
+        gcn10_stager_idle(&w->ring);
         return rc == -2 ? -1 : 1;
     }
     /* the block's 18 files, while the copies and the decoder run (the reference creates each raster's file
@@ -448,8 +270,7 @@ static int fill_block(struct worker *w, struct block_in *in, int block_id)
         /* the zones over this block, here on the input side: it overlaps the block before */
         if (r->zonal && gcn10_zonal_plan_block(w, in, r->blocks.bbox[bi]) != 0) {
             g->stream_sync(w->in_ctx, w->s_in);
-            for (int k = 0; k < N_RING; k++)
-                w->ring_busy[k] = false;
+            gcn10_stager_idle(&w->ring);
             return -1;
         }
         return 0;
@@ -518,14 +339,15 @@ int gcn10_input_setup(struct worker *w)
     /* a context of its own: the input side calls the GPU library concurrently with the worker, and a
      * context is not shared between threads (include/gcn10_gpu.h); device memory and events are valid
      * in both, they belong to the device */
-    GPU_IN(w, g->init(w->device, &w->in_ctx));
+    GPU_OR_RETURN(w, -2, g->init(w->device, &w->in_ctx));
     if (w->run->event_sleep_us > 0 && g->set_option)
         (void)g->set_option(w->in_ctx, "event_sync_sleep_us", w->run->event_sleep_us);
-    GPU_IN(w, g->stream_create(w->in_ctx, &w->s_in));
-    for (int k = 0; k < N_RING; k++)
-        GPU_IN(w, g->event_create(w->in_ctx, &w->ev_ring[k]));
+    GPU_OR_RETURN(w, -2, g->stream_create(w->in_ctx, &w->s_in));
+    /* (its buffers come with the first block) */
+    GPU_OR_RETURN(w, -2, gcn10_stager_setup(&w->ring, g, w->in_ctx, w->run->pool, &w->run->pinned_bytes, N_RING,
+                                            0));
     for (int k = 0; k < N_IN; k++)
-        GPU_IN(w, g->event_create(w->in_ctx, &w->in[k].ev_ready));
+        GPU_OR_RETURN(w, -2, g->event_create(w->in_ctx, &w->in[k].ev_ready));
     return 0;
 }
 
@@ -606,19 +428,11 @@ void gcn10_input_teardown(struct worker *w)
             if (in->d_cj) g->free(w->in_ctx, in->d_cj);
             if (in->d_block) g->free(w->in_ctx, in->d_block);
             if (in->d_comp) g->free(w->in_ctx, in->d_comp);
-            if (in->h_jobs) g->host_free(w->in_ctx, in->h_jobs);
-            if (in->d_jobs) g->free(w->in_ctx, in->d_jobs);
-            if (in->h_status) g->host_free(w->in_ctx, in->h_status);
-            if (in->d_status) g->free(w->in_ctx, in->d_status);
+            gcn10_job_list_free(g, w->in_ctx, &in->jl);
             if (in->ev_ready) g->event_destroy(w->in_ctx, in->ev_ready);
             memset(in, 0, sizeof *in);
         }
-        for (int k = 0; k < N_RING; k++) {
-            if (w->h_ring[k]) g->host_free(w->in_ctx, w->h_ring[k]);
-            if (w->ev_ring[k]) g->event_destroy(w->in_ctx, w->ev_ring[k]);
-            w->h_ring[k] = NULL;
-            w->ev_ring[k] = NULL;
-        }
+        gcn10_stager_teardown(&w->ring);
         if (w->s_in) g->stream_destroy(w->in_ctx, w->s_in);
         g->destroy(w->in_ctx);
         w->in_ctx = NULL;

@@ -1,5 +1,6 @@
 /* pipeline_internal.h -- the worker and run state shared by pipeline.c (block queue, strips,
- * sink) and pipeline_input.c (landcover input through the GPU decoder). */
+ * sink), pipeline_input.c (landcover input through the GPU decoder), verify.c and zonal.c, and what the
+ * writer and the verifier have in common: the chunk stager (stage.c) and the overview levels (levels.c). */
 #ifndef GCN10_PIPELINE_INTERNAL_H
 #define GCN10_PIPELINE_INTERNAL_H
 
@@ -15,9 +16,73 @@
 enum { TILE = 256, MAX_NBUF = 8, DEFAULT_NBUF = 4, DEFAULT_STRIP_ROWS = 2304, MAX_STRIP_ROWS = 4096 };
 
 struct run;
+struct worker;
 struct gcn10_verify_state;
 struct gcn10_zonal_state;
 struct gcn10_zonal_table;
+
+/* ---- stage.c: chunks as they lie in the files -> pinned ring -> device, for gcn10_gpu_inflate_tiles ---- */
+
+/* bytes a chunk of nbytes takes in the staging buffers and on the device: 16-byte aligned, and 16 zero bytes behind
+ * it (the decoder's bit reader may look a few bytes ahead) */
+size_t gcn10_chunk_slot(uint32_t nbytes);
+/* the decoder's job for chunk c: its bytes at in_off of the compressed buffer, its pixels to dst_off of the output */
+void gcn10_inflate_job_from_chunk(gcn10_inflate_tile *j, const struct gcn10_chunk_ref *c, uint64_t in_off,
+                                  uint64_t dst_off);
+
+/* the jobs of one gcn10_gpu_inflate_tiles call and their status words, host (pinned) and device, and the stager's
+ * word on each job's chunk (gcn10_stager_stage's bad[]; pinned like the rest, so there is one way to fail) */
+struct gcn10_job_list {
+    gcn10_inflate_tile *h_jobs, *d_jobs;
+    uint32_t *h_status, *d_status;
+    int *bad;
+    size_t cap;
+};
+/* room for n jobs; the first `keep` host entries stay.  Nothing may be in flight on the lists.  0, or a device error */
+int gcn10_job_list_ensure(const struct gcn10_gpu_api *g, gcn10_gpu_ctx *ctx, struct gcn10_job_list *l, size_t n,
+                          size_t keep);
+void gcn10_job_list_free(const struct gcn10_gpu_api *g, gcn10_gpu_ctx *ctx, struct gcn10_job_list *l);
+
+/* A ring of pinned buffers of one size on one context: buffer k is filled while the copy of buffer k - 1 to the device
+ * is in flight.  One thread uses a stager.  Every call returns 0 or a device error (gpu->last_error() has the text). */
+enum { GCN10_STAGER_MAX = 3 };
+struct gcn10_stager {
+    const struct gcn10_gpu_api *gpu;
+    gcn10_gpu_ctx *ctx;
+    gcn10_pool *pool;                       /* reads the chunks; NULL: the calling thread does */
+    atomic_llong *pinned_bytes;             /* the run's count of pinned memory asked for */
+    int n;
+    size_t cap;                             /* bytes of one buffer */
+    uint8_t *h[GCN10_STAGER_MAX];
+    gcn10_event_t ev[GCN10_STAGER_MAX];
+    bool busy[GCN10_STAGER_MAX];            /* a copy out of the buffer was issued and not yet waited for */
+    /* the batch being read: pool jobs take slices of [next, end) in turn */
+    pthread_mutex_t mu;
+    pthread_cond_t cv;
+    const struct gcn10_chunk_ref *chunks;
+    const gcn10_inflate_tile *jobs;
+    int *bad;
+    uint8_t *dst;
+    uint64_t base;
+    size_t next, end;
+    int pending;
+};
+/* n_buffers events, and buffers of `bytes` (0: none before the first gcn10_stager_ensure) */
+int gcn10_stager_setup(struct gcn10_stager *s, const struct gcn10_gpu_api *g, gcn10_gpu_ctx *ctx, gcn10_pool *pool,
+                       atomic_llong *pinned_bytes, int n_buffers, size_t bytes);
+void gcn10_stager_teardown(struct gcn10_stager *s);
+/* buffers of at least `bytes`: waits for the copies in flight, then reallocates */
+int gcn10_stager_ensure(struct gcn10_stager *s, size_t bytes);
+/* buffer k free to be written (its last copy has finished); a copy out of buffer k has been issued on `stream` */
+int gcn10_stager_take(struct gcn10_stager *s, int k);
+int gcn10_stager_sent(struct gcn10_stager *s, int k, gcn10_stream_t stream);
+/* the caller has waited for the stream of the copies: every buffer is free */
+void gcn10_stager_idle(struct gcn10_stager *s);
+/* The n chunks to d_comp + jobs[i].in_off (in_off ascending, a gcn10_chunk_slot apart), as many per buffer as fit,
+ * copied on `stream`.  bad[i] = 0: staged; 1: its bytes cannot be read (zeros are staged); 2: larger than a buffer
+ * (nothing is staged).  The other chunks go on either way. */
+int gcn10_stager_stage(struct gcn10_stager *s, const struct gcn10_chunk_ref *chunks, const gcn10_inflate_tile *jobs,
+                       size_t n, uint8_t *d_comp, gcn10_stream_t stream, int *bad);
 
 /* one rotating set of strip buffers */
 struct strip_buf {
@@ -50,6 +115,7 @@ struct strip_buf {
 enum { IN_FREE = 0, IN_FILLING = 1, IN_READY = 2, IN_END = 3 };
 enum { N_IN = 2 };                          /* the block being encoded + the one being staged */
 enum { N_RING = 3 };                        /* pinned staging buffers of the input thread */
+enum { RING_BYTES = 64 << 20 };             /* ... each; a block of DEFLATE landcover is 2-3 of them (the verifier's too) */
 
 struct block_in {
     int state;                              /* IN_*; guarded by worker.in_mu */
@@ -68,9 +134,7 @@ struct block_in {
     size_t block_cap;
     uint8_t *d_comp;                        /* the window's chunks as they lie in the files (compressed or raw) */
     size_t d_comp_cap;
-    gcn10_inflate_tile *h_jobs, *d_jobs;    /* h_jobs pinned */
-    uint32_t *h_status, *d_status;          /* h_status pinned */
-    size_t jobs_cap;
+    struct gcn10_job_list jl;               /* the decoder's jobs and their status words */
     size_t n_inflate;                       /* chunks whose status must be looked at (0: host reader) */
     gcn10_event_t ev_ready;                 /* recorded behind everything the block needs on the device */
     /* the block's output files (src/cn.c:236-360: directories, names, the trailing-underscore rule), created by
@@ -105,10 +169,7 @@ struct worker {
     pthread_mutex_t in_mu;
     pthread_cond_t in_cv;
     bool in_stop;                           /* the worker is going away: the input thread must not wait for it */
-    uint8_t *h_ring[N_RING];                /* pinned: chunks (or host-decoded rows) on their way to the device */
-    size_t ring_cap;
-    gcn10_event_t ev_ring[N_RING];
-    bool ring_busy[N_RING];
+    struct gcn10_stager ring;               /* pinned: chunks (or host-decoded rows) on their way to the device */
     int blocks_done;
     int in_seq;                             /* blocks taken from the input side so far: slot = in_seq % N_IN */
     int device;                             /* the GPU this worker drives */
@@ -200,9 +261,30 @@ double gcn10_now_seconds(void);
 void gcn10_wlog(struct worker *w, const char *level, bool console, const char *fmt, ...)
     __attribute__((format(printf, 4, 5)));
 
+/* a GPU library call that failed: one log line with its message, and the caller returns `ret` */
+#define GPU_OR_RETURN(w, ret, call)                                                    \
+    do {                                                                               \
+        if ((call) != 0) {                                                             \
+            gcn10_wlog((w), "ERROR", true, "gpu: %s", (w)->run->gpu->last_error());    \
+            return (ret);                                                              \
+        }                                                                              \
+    } while (0)
+
 /* device / pinned buffer of at least `need` bytes on context `ctx` (grown by reallocation); -1 and a log line on failure */
 int gcn10_ensure_dev_on(struct worker *w, gcn10_gpu_ctx *ctx, void **p, size_t *cap, size_t need);
 int gcn10_ensure_pinned_on(struct worker *w, gcn10_gpu_ctx *ctx, void **p, size_t *cap, size_t need);
+
+/* levels.c: the overview levels of a staged block, for the writer and the verifier alike.
+ * gcn10_level_nearest: level k by nearest-neighbour sampling, ready as a block of its own -- its landcover in w->d_ov,
+ *   its index maps on the device, the tile of its width *Wk prepared (the block's own is gone) -- on s_kernel; *d_cj:
+ *   its soil rows (the three are set on failure too, and mean nothing then).  The level's kernels must be done before
+ *   the next call.
+ * gcn10_levels_average: the pyramid of the selected rasters, levels 1 .. L, from the block's prepared tile, strip_rows
+ *   rows at a time; levels[q * L + k - 1]: level k of selected raster q, rows gcn10_level_dim(W, k) apart, in w->d_ov.
+ * 0, or -1 (logged). */
+int gcn10_level_nearest(struct worker *w, const struct block_in *in, int k, int *Wk, int *Hk, const int32_t **d_cj);
+int gcn10_levels_average(struct worker *w, const struct block_in *in, int L, int strip_rows,
+                         uint8_t *levels[GCN10_N_RASTERS * GCN10_COG_MAX_LEVELS]);
 
 /* pipeline_input.c: the input side of a worker.
  * gcn10_input_setup / _teardown: context, stream, events, pinned ring of the input side.

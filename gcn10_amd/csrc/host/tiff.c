@@ -1302,8 +1302,8 @@ gcn10_tiff_writer *gcn10_tiff_create_cog(const char *path, int xsize, int ysize,
         v->level = k;
         v->last_idx = -1;
         v->fd = -1;
-        v->xsize = (int)(((int64_t)xsize + ((int64_t)1 << k) - 1) >> k);
-        v->ysize = (int)(((int64_t)ysize + ((int64_t)1 << k) - 1) >> k);
+        v->xsize = gcn10_level_dim(xsize, k);
+        v->ysize = gcn10_level_dim(ysize, k);
         v->across = (v->xsize + TILE - 1) / TILE;
         v->down = (v->ysize + TILE - 1) / TILE;
         nt = (size_t)v->across * (size_t)v->down;

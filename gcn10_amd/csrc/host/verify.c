@@ -27,7 +27,6 @@
 #define wlog gcn10_wlog
 
 enum { V_LEVELS = GCN10_COG_MAX_LEVELS + 1, V_STAGE = 2 };
-enum { V_STAGE_BYTES = 64 << 20 };
 /* device memory of the 18 decode buffers of a strip: bounds the strip height together with strip_rows */
 #define V_GOT_BYTES ((size_t)1 << 30)
 
@@ -37,11 +36,6 @@ static const char *const finding_names[] = { "ok", "missing", "not a TIFF", "not
 /* ------------------------------------------------------------------------ */
 /* structure of one file                                                     */
 /* ------------------------------------------------------------------------ */
-
-static int level_dim(int n, int k)
-{
-    return (int)(((int64_t)n + ((int64_t)1 << k) - 1) >> k);
-}
 
 /* The checks of gcn10_verify_structure; the readers of the raster and of its overview directories stay open in
  * lv[0 .. *n_levels] when the finding is GCN10_VERIFY_OK (closed otherwise). */
@@ -108,9 +102,9 @@ static int open_checked(const char *path, int W, int H, const double gt[6], stru
             snprintf(reason, cap, "overview %d: %d samples per pixel, not 1 band of Byte", n, gcn10_tiff_reader_samples(t));
             finding = GCN10_VERIFY_NOT_BYTE;
         }
-        else if (fw != level_dim(W, n) || fh != level_dim(H, n)) {
+        else if (fw != gcn10_level_dim(W, n) || fh != gcn10_level_dim(H, n)) {
             snprintf(reason, cap, "overview %d: size %dx%d, level %d of %dx%d is %dx%d", n, fw, fh, n, W, H,
-                     level_dim(W, n), level_dim(H, n));
+                     gcn10_level_dim(W, n), gcn10_level_dim(H, n));
             finding = GCN10_VERIFY_OVERVIEW;
         }
         else if (gcn10_tiff_check_chunks(t, &idx, &off, &cnt) != 0) {
@@ -165,26 +159,14 @@ struct gcn10_verify_state {
     size_t got_cap;
     uint8_t *d_comp;
     size_t comp_cap;
-    uint8_t *h_stage[V_STAGE];              /* pinned */
-    gcn10_event_t ev_stage[V_STAGE];
-    bool stage_busy[V_STAGE];
-    gcn10_inflate_tile *h_jobs, *d_jobs;    /* h_jobs pinned */
-    uint32_t *h_status, *d_status;          /* h_status pinned */
-    struct gcn10_chunk_ref *chunks;         /* the strip's chunks of all files, and whose they are */
+    struct gcn10_stager stage;              /* V_STAGE pinned buffers of RING_BYTES, copies on s_kernel */
+    struct gcn10_job_list jl;               /* the strip's chunks of all files: the decoder's jobs, */
+    struct gcn10_chunk_ref *chunks;         /* ... where they lie and whose they are */
     int *owner;
-    size_t jobs_cap;
     gcn10_verify_count *d_counts, *h_counts;    /* [V_LEVELS][GCN10_N_RASTERS]; h_counts pinned */
     uint8_t *h_rows;                        /* a host-decoded strip on its way up */
     size_t h_rows_cap;
 };
-
-#define GPU_V(w, call)                                                         \
-    do {                                                                       \
-        if ((call) != 0) {                                                     \
-            wlog((w), "ERROR", true, "gpu: %s", (w)->run->gpu->last_error());  \
-            return -1;                                                         \
-        }                                                                      \
-    } while (0)
 
 static int state_setup(struct worker *w)
 {
@@ -200,13 +182,10 @@ static int state_setup(struct worker *w)
         return -1;
     }
     w->verify = v;
-    for (int i = 0; i < V_STAGE; i++) {
-        GPU_V(w, g->host_alloc(w->ctx, V_STAGE_BYTES, (void **)&v->h_stage[i]));
-        GPU_V(w, g->event_create(w->ctx, &v->ev_stage[i]));
-        atomic_fetch_add(&w->run->pinned_bytes, (long long)V_STAGE_BYTES);
-    }
-    GPU_V(w, g->malloc(w->ctx, n_counts * sizeof *v->d_counts, (void **)&v->d_counts));
-    GPU_V(w, g->host_alloc(w->ctx, n_counts * sizeof *v->h_counts, (void **)&v->h_counts));
+    GPU_OR_RETURN(w, -1, gcn10_stager_setup(&v->stage, g, w->ctx, w->run->pool, &w->run->pinned_bytes, V_STAGE,
+                                            RING_BYTES));
+    GPU_OR_RETURN(w, -1, g->malloc(w->ctx, n_counts * sizeof *v->d_counts, (void **)&v->d_counts));
+    GPU_OR_RETURN(w, -1, g->host_alloc(w->ctx, n_counts * sizeof *v->h_counts, (void **)&v->h_counts));
     return 0;
 }
 
@@ -219,14 +198,8 @@ void gcn10_verify_teardown(struct worker *w)
         return;
     if (v->d_got) g->free(w->ctx, v->d_got);
     if (v->d_comp) g->free(w->ctx, v->d_comp);
-    for (int i = 0; i < V_STAGE; i++) {
-        if (v->h_stage[i]) g->host_free(w->ctx, v->h_stage[i]);
-        if (v->ev_stage[i]) g->event_destroy(w->ctx, v->ev_stage[i]);
-    }
-    if (v->h_jobs) g->host_free(w->ctx, v->h_jobs);
-    if (v->d_jobs) g->free(w->ctx, v->d_jobs);
-    if (v->h_status) g->host_free(w->ctx, v->h_status);
-    if (v->d_status) g->free(w->ctx, v->d_status);
+    gcn10_stager_teardown(&v->stage);
+    gcn10_job_list_free(g, w->ctx, &v->jl);
     if (v->d_counts) g->free(w->ctx, v->d_counts);
     if (v->h_counts) g->host_free(w->ctx, v->h_counts);
     free(v->chunks);
@@ -242,11 +215,9 @@ static int jobs_ensure(struct worker *w, size_t n, size_t keep)
     const struct gcn10_gpu_api *g = w->run->gpu;
     struct gcn10_verify_state *v = w->verify;
     struct gcn10_chunk_ref *c;
-    gcn10_inflate_tile *h_jobs = NULL;
-    uint32_t *h_status = NULL;
     int *o;
 
-    if (n <= v->jobs_cap)
+    if (n <= v->jl.cap)
         return 0;
     n = n * 2 > 4096 ? n * 2 : 4096;
     /* the caller appends while it plans: the host lists are kept, the device-side arrays are rewritten per strip */
@@ -260,152 +231,8 @@ static int jobs_ensure(struct worker *w, size_t n, size_t keep)
         wlog(w, "ERROR", true, "malloc failed for the verifier's read plan");
         return -1;
     }
-    GPU_V(w, g->stream_sync(w->ctx, w->s_kernel));
-    GPU_V(w, g->host_alloc(w->ctx, n * sizeof *h_jobs, (void **)&h_jobs));
-    if (g->host_alloc(w->ctx, n * 4, (void **)&h_status) != 0) {
-        wlog(w, "ERROR", true, "gpu: %s", g->last_error());
-        g->host_free(w->ctx, h_jobs);
-        return -1;
-    }
-    if (keep > 0) {
-        memcpy(h_jobs, v->h_jobs, keep * sizeof *h_jobs);
-        memcpy(h_status, v->h_status, keep * 4);
-    }
-    if (v->h_jobs) g->host_free(w->ctx, v->h_jobs);
-    if (v->h_status) g->host_free(w->ctx, v->h_status);
-    if (v->d_jobs) g->free(w->ctx, v->d_jobs);
-    if (v->d_status) g->free(w->ctx, v->d_status);
-    v->h_jobs = h_jobs;
-    v->h_status = h_status;
-    v->d_jobs = NULL;
-    v->d_status = NULL;
-    v->jobs_cap = 0;
-    GPU_V(w, g->malloc(w->ctx, n * sizeof *v->d_jobs, (void **)&v->d_jobs));
-    GPU_V(w, g->malloc(w->ctx, n * 4, (void **)&v->d_status));
-    v->jobs_cap = n;
-    return 0;
-}
-
-/* ------------------------------------------------------------------------ */
-/* chunks -> pinned staging -> device                                        */
-/* ------------------------------------------------------------------------ */
-
-struct read_job {
-    const struct gcn10_chunk_ref *chunks;
-    const gcn10_inflate_tile *jobs;
-    size_t n;
-    uint8_t *dst;
-    uint64_t base;
-    pthread_mutex_t *mu;
-    pthread_cond_t *cv;
-    int *pending;
-    int *bad;                               /* per chunk: the bytes could not be read */
-};
-
-static void read_job_run(void *arg)
-{
-    struct read_job *j = arg;
-
-    for (size_t i = 0; i < j->n; i++) {
-        uint8_t *p = j->dst + (j->jobs[i].in_off - j->base);
-        size_t left = j->chunks[i].nbytes;
-        uint64_t off = j->chunks[i].file_off;
-
-        while (left > 0) {
-            ssize_t got = pread(j->chunks[i].fd, p, left, (off_t)off);
-
-            if (got <= 0) {
-                j->bad[i] = 1;
-                memset(p, 0, left);
-                p += left;
-                break;
-            }
-            p += got;
-            off += (uint64_t)got;
-            left -= (size_t)got;
-        }
-        memset(p, 0, 16);               /* the decoder's bit reader may look a few bytes ahead */
-    }
-    pthread_mutex_lock(j->mu);
-    if (--*j->pending == 0)
-        pthread_cond_broadcast(j->cv);
-    pthread_mutex_unlock(j->mu);
-    free(j);
-}
-
-static size_t comp_slot(uint32_t nbytes)
-{
-    return (((size_t)nbytes + 15) & ~(size_t)15) + 16;
-}
-
-/* the n chunks of the strip into d_comp at their in_off, batch by batch through the pinned buffers; bad[i] is set
- * for a chunk whose bytes could not be read */
-static int stage_chunks(struct worker *w, size_t n, int *bad)
-{
-    struct run *r = w->run;
-    const struct gcn10_gpu_api *g = r->gpu;
-    struct gcn10_verify_state *v = w->verify;
-    pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
-    pthread_cond_t cv = PTHREAD_COND_INITIALIZER;
-    int k = 0;
-
-    for (size_t i0 = 0; i0 < n;) {
-        const uint64_t base = v->h_jobs[i0].in_off;
-        uint64_t end = base;
-        size_t i1 = i0;
-        int pending = 0;
-
-        while (i1 < n) {
-            const uint64_t e = v->h_jobs[i1].in_off + comp_slot(v->h_jobs[i1].in_len);
-
-            if (e - base > (uint64_t)V_STAGE_BYTES)
-                break;
-            end = e;
-            i1++;
-        }
-        if (i1 == i0) {
-            /* one chunk larger than a staging buffer: the planner's limit is 2^31 bytes, a tile of ours is 64 KiB;
-             * such a file goes the slow way */
-            bad[i0] = 2;
-            i0++;
-            continue;
-        }
-        if (v->stage_busy[k]) {
-            GPU_V(w, g->event_sync(w->ctx, v->ev_stage[k]));
-            v->stage_busy[k] = false;
-        }
-        for (size_t i = i0; i < i1; i += 64) {
-            struct read_job job = { v->chunks + i, v->h_jobs + i, i1 - i < 64 ? i1 - i : 64, v->h_stage[k], base,
-                                    &mu, &cv, &pending, bad + i };
-            struct read_job *j = malloc(sizeof *j);
-
-            if (!j) {
-                wlog(w, "ERROR", true, "malloc failed for the verifier's read jobs");
-                pthread_mutex_lock(&mu);
-                while (pending > 0)
-                    pthread_cond_wait(&cv, &mu);
-                pthread_mutex_unlock(&mu);
-                return -1;
-            }
-            *j = job;
-            pthread_mutex_lock(&mu);
-            pending++;
-            pthread_mutex_unlock(&mu);
-            if (r->pool)
-                gcn10_pool_submit(r->pool, read_job_run, j);
-            else
-                read_job_run(j);
-        }
-        pthread_mutex_lock(&mu);
-        while (pending > 0)
-            pthread_cond_wait(&cv, &mu);
-        pthread_mutex_unlock(&mu);
-        GPU_V(w, g->memcpy_h2d(w->ctx, v->d_comp + base, v->h_stage[k], (size_t)(end - base), w->s_kernel));
-        GPU_V(w, g->event_record(w->ctx, v->ev_stage[k], w->s_kernel));
-        v->stage_busy[k] = true;
-        k = (k + 1) % V_STAGE;
-        i0 = i1;
-    }
+    GPU_OR_RETURN(w, -1, g->stream_sync(w->ctx, w->s_kernel));
+    GPU_OR_RETURN(w, -1, gcn10_job_list_ensure(g, w->ctx, &v->jl, n, keep));
     return 0;
 }
 
@@ -452,8 +279,6 @@ static int verify_level(struct worker *w, struct vfile *files, int level, int Wk
     const size_t slot = stride * (size_t)(strip < Hk ? strip : Hk);
     gcn10_verify_count *counts = v->d_counts + (size_t)level * GCN10_N_RASTERS;
     const unsigned codecs = r->inflate_codecs | GCN10_CODEC_DEFLATE | GCN10_CODEC_RAW;
-    int *bad = NULL;
-    size_t bad_cap = 0;
     int rc = -1;
 
     if (gcn10_ensure_dev_on(w, w->ctx, (void **)&v->d_got, &v->got_cap, slot * (size_t)r->n_sel + 16) != 0)
@@ -514,22 +339,13 @@ static int verify_level(struct worker *w, struct vfile *files, int level, int Wk
             }
             for (size_t i = 0; i < plan.n; i++) {
                 const struct gcn10_chunk_ref *c = &plan.chunks[i];
-                gcn10_inflate_tile *j = &v->h_jobs[n];
 
                 v->chunks[n] = *c;
                 v->owner[n] = q;
-                j->in_off = comp_bytes;
-                j->in_len = c->nbytes;
-                j->out_len = c->out_len;
-                j->chunk_w = c->chunk_w;
-                j->src_x = c->src_x;
-                j->src_y = c->src_y;
-                j->copy_w = c->copy_w;
-                j->copy_h = c->copy_h;
-                j->flags = c->flags;
-                j->dst_off = (uint64_t)q * slot + (uint64_t)c->dst_y * stride + c->dst_x;
-                v->h_status[n] = 0xffffffffu;
-                comp_bytes += comp_slot(c->nbytes);
+                gcn10_inflate_job_from_chunk(&v->jl.h_jobs[n], c, comp_bytes,
+                                             (uint64_t)q * slot + (uint64_t)c->dst_y * stride + c->dst_x);
+                v->jl.h_status[n] = 0xffffffffu;
+                comp_bytes += gcn10_chunk_slot(c->nbytes);
                 n++;
             }
             if (plan.max_chunk_bytes > chunk_bytes)
@@ -543,35 +359,25 @@ static int verify_level(struct worker *w, struct vfile *files, int level, int Wk
         if (mask == 0)
             continue;
         if (n > 0) {
-            if (n > bad_cap) {
-                free(bad);
-                bad = malloc(n * sizeof *bad);
-                bad_cap = bad ? n : 0;
-                if (!bad) {
-                    wlog(w, "ERROR", true, "malloc failed for the verifier's read plan");
-                    goto out;
-                }
-            }
-            memset(bad, 0, n * sizeof *bad);
             if (gcn10_ensure_dev_on(w, w->ctx, (void **)&v->d_comp, &v->comp_cap, comp_bytes + 16) != 0)
                 goto out;
             if (sparse && g->memset(w->ctx, v->d_got, 0, slot * (size_t)r->n_sel, w->s_kernel) != 0)
                 goto gpu_fail;
-            if (stage_chunks(w, n, bad) != 0)
-                goto out;
+            if (gcn10_stager_stage(&v->stage, v->chunks, v->jl.h_jobs, n, v->d_comp, w->s_kernel, v->jl.bad) != 0)
+                goto gpu_fail;
             for (size_t i = 0; i < n; i++)
-                if (bad[i]) {
+                if (v->jl.bad[i]) {
                     /* a chunk that cannot be read is not handed to the decoder: an empty window */
-                    v->h_jobs[i].copy_w = v->h_jobs[i].copy_h = 0;
-                    v->h_jobs[i].in_len = 0;
-                    v->h_jobs[i].flags = GCN10_TILE_RAW;
-                    v->h_jobs[i].out_len = 0;
+                    v->jl.h_jobs[i].copy_w = v->jl.h_jobs[i].copy_h = 0;
+                    v->jl.h_jobs[i].in_len = 0;
+                    v->jl.h_jobs[i].flags = GCN10_TILE_RAW;
+                    v->jl.h_jobs[i].out_len = 0;
                 }
-            if (g->memcpy_h2d(w->ctx, v->d_jobs, v->h_jobs, n * sizeof *v->h_jobs, w->s_kernel) != 0 ||
-                g->memcpy_h2d(w->ctx, v->d_status, v->h_status, n * 4, w->s_kernel) != 0 ||
-                g->inflate_tiles(w->ctx, v->d_comp, v->d_jobs, (int)n, chunk_bytes, v->d_got, stride, v->d_status,
+            if (g->memcpy_h2d(w->ctx, v->jl.d_jobs, v->jl.h_jobs, n * sizeof *v->jl.h_jobs, w->s_kernel) != 0 ||
+                g->memcpy_h2d(w->ctx, v->jl.d_status, v->jl.h_status, n * 4, w->s_kernel) != 0 ||
+                g->inflate_tiles(w->ctx, v->d_comp, v->jl.d_jobs, (int)n, chunk_bytes, v->d_got, stride, v->jl.d_status,
                                  w->s_kernel) != 0 ||
-                g->memcpy_d2h(w->ctx, v->h_status, v->d_status, n * 4, w->s_kernel) != 0)
+                g->memcpy_d2h(w->ctx, v->jl.h_status, v->jl.d_status, n * 4, w->s_kernel) != 0)
                 goto gpu_fail;
         }
         if (want) {
@@ -585,19 +391,18 @@ static int verify_level(struct worker *w, struct vfile *files, int level, int Wk
         /* the strip's buffers, job lists and staging are reused by the next one */
         if (g->stream_sync(w->ctx, w->s_kernel) != 0)
             goto gpu_fail;
-        for (int i = 0; i < V_STAGE; i++)
-            v->stage_busy[i] = false;
+        gcn10_stager_idle(&v->stage);
         for (size_t i = 0; i < n; i++) {
             struct vfile *f = &files[v->owner[i]];
             const struct gcn10_chunk_ref *c = &v->chunks[i];
 
-            if (bad[i])
+            if (v->jl.bad[i])
                 set_finding(f, GCN10_VERIFY_CHUNK, "level %d: the %u bytes of the chunk at x=%u y=%d cannot be read%s",
-                            level, c->nbytes, c->dst_x, y0 + (int)c->dst_y, bad[i] == 2 ? " (too large to stage)" : "");
-            else if (v->h_status[i] != 0)
+                            level, c->nbytes, c->dst_x, y0 + (int)c->dst_y, v->jl.bad[i] == 2 ? " (too large to stage)" : "");
+            else if (v->jl.h_status[i] != 0)
                 set_finding(f, GCN10_VERIFY_DECODE, "level %d: the chunk at x=%u y=%d (%u bytes at offset %llu) does "
                             "not decode, status %u", level, c->dst_x, y0 + (int)c->dst_y, c->nbytes,
-                            (unsigned long long)c->file_off, v->h_status[i]);
+                            (unsigned long long)c->file_off, v->jl.h_status[i]);
         }
     }
     rc = 0;
@@ -606,7 +411,6 @@ static int verify_level(struct worker *w, struct vfile *files, int level, int Wk
 gpu_fail:
     wlog(w, "ERROR", true, "gpu: %s", g->last_error());
 out:
-    free(bad);
     return rc;
 }
 
@@ -614,80 +418,36 @@ out:
 /* one block                                                                 */
 /* ------------------------------------------------------------------------ */
 
-/* the overview levels of the files against nearest-neighbour levels: each a block of its own (pipeline.c walks the
- * same path when it writes them) */
+/* the overview levels of the files against nearest-neighbour levels: each a block of its own, made as the writer
+ * makes it (levels.c) */
 static int verify_nearest_levels(struct worker *w, struct block_in *in, struct vfile *files, int L)
 {
-    struct run *r = w->run;
-    const struct gcn10_gpu_api *g = r->gpu;
-    const int W = in->W, H = in->H;
-    const int W1 = (W + 1) / 2, H1 = (H + 1) / 2;
-    const size_t n_idx = (size_t)W1 + 4 + (size_t)H1;
-    int32_t *idx = malloc(n_idx * sizeof *idx);
-    int rc = -1;
-
-    if (!idx) {
-        wlog(w, "ERROR", true, "malloc failed for overview index maps");
-        return -1;
-    }
-    if (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov, &w->ov_cap, (size_t)W1 * (size_t)H1 + 16) != 0 ||
-        gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov_idx, &w->ov_idx_cap, n_idx * sizeof *idx) != 0)
-        goto out;
     for (int k = L; k >= 1; k--) {
-        const int Wk = level_dim(W, k), Hk = level_dim(H, k), half = 1 << (k - 1);
-        const size_t cj_at = ((size_t)Wk + 3) & ~(size_t)3;
+        const int32_t *d_cj;
+        int Wk, Hk;
 
-        for (int x = 0; x < Wk; x++)
-            idx[x] = in->h_ci[(int64_t)x * (1 << k) + half < W ? (int64_t)x * (1 << k) + half : W - 1];
-        for (int y = 0; y < Hk; y++)
-            idx[cj_at + y] = in->h_cj[(int64_t)y * (1 << k) + half < H ? (int64_t)y * (1 << k) + half : H - 1];
-        if (g->overview_nearest(w->ctx, in->d_block, W, H, k, w->d_ov, w->s_kernel) != 0 ||
-            g->memcpy_h2d(w->ctx, w->d_ov_idx, idx, (cj_at + (size_t)Hk) * sizeof *idx, w->s_kernel) != 0 ||
-            g->stream_sync(w->ctx, w->s_kernel) != 0 ||
-            g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, w->d_ov_idx, Wk, w->s_kernel) != 0) {
-            wlog(w, "ERROR", true, "gpu: %s", g->last_error());
-            goto out;
-        }
-        if (verify_level(w, files, k, Wk, Hk, w->d_ov, w->d_ov_idx + cj_at, NULL) != 0)
-            goto out;
+        if (gcn10_level_nearest(w, in, k, &Wk, &Hk, &d_cj) != 0 ||
+            verify_level(w, files, k, Wk, Hk, w->d_ov, d_cj, NULL) != 0)     /* (ends with its kernels done) */
+            return -1;
     }
-    rc = 0;
-out:
-    free(idx);
-    return rc;
+    return 0;
 }
 
-/* ... against averaged levels: the pyramid of every selected raster from gcn10_gpu_overview_average (the block's
- * tile is prepared), then level by level against those buffers */
+/* ... against averaged levels: the pyramid of every selected raster as the writer makes it (the block's tile is
+ * prepared), then level by level against those buffers */
 static int verify_average_levels(struct worker *w, struct block_in *in, struct vfile *files, int L)
 {
     struct run *r = w->run;
-    const struct gcn10_gpu_api *g = r->gpu;
-    const int W = in->W, H = in->H;
-    size_t lvl_off[V_LEVELS], total = 0;
     uint8_t *levels[GCN10_N_RASTERS * GCN10_COG_MAX_LEVELS];
 
-    for (int k = 1; k <= L; k++) {
-        lvl_off[k] = total;
-        total += ((size_t)level_dim(W, k) * (size_t)level_dim(H, k) + 255) & ~(size_t)255;
-    }
-    if (gcn10_ensure_dev_on(w, w->ctx, (void **)&w->d_ov, &w->ov_cap, total * (size_t)r->n_sel + 16) != 0)
+    if (gcn10_levels_average(w, in, L, r->strip_rows, levels) != 0)
         return -1;
-    for (int q = 0; q < r->n_sel; q++)
-        for (int k = 1; k <= L; k++)
-            levels[q * L + k - 1] = w->d_ov + (size_t)q * total + lvl_off[k];
-    for (int y0 = 0; y0 < H; y0 += r->strip_rows) {
-        const int rows = H - y0 < r->strip_rows ? H - y0 : r->strip_rows;
-
-        GPU_V(w, g->overview_average(w->ctx, in->d_block, W, H, y0, rows, in->d_cj, r->cond_mask, r->table_mask, L,
-                                     levels, w->s_kernel));
-    }
     for (int k = L; k >= 1; k--) {
         uint8_t *want[GCN10_N_RASTERS];
 
         for (int q = 0; q < r->n_sel; q++)
             want[q] = levels[q * L + k - 1];
-        if (verify_level(w, files, k, level_dim(W, k), level_dim(H, k), NULL, NULL, want) != 0)
+        if (verify_level(w, files, k, gcn10_level_dim(in->W, k), gcn10_level_dim(in->H, k), NULL, NULL, want) != 0)
             return -1;
     }
     return 0;
@@ -760,9 +520,9 @@ int gcn10_verify_block(struct worker *w, struct block_in *in)
         if (g->event_sync(w->ctx, in->ev_ready) != 0)
             goto gpu_fail;
         for (size_t i = 0; i < in->n_inflate && inputs_ok; i++)
-            if (in->h_status[i] != 0) {
+            if (in->jl.h_status[i] != 0) {
                 wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
-                                       "(stream %zu, reason %u)", in->xoff, in->yoff, W, H, i, in->h_status[i]);
+                                       "(stream %zu, reason %u)", in->xoff, in->yoff, W, H, i, in->jl.h_status[i]);
                 wlog(w, "ERROR", true, "esa load failed for block %d", block_id);
                 inputs_ok = false;
             }
@@ -847,8 +607,7 @@ gpu_fail:
 out:
     if (w->ctx)
         g->stream_sync(w->ctx, w->s_kernel);
-    for (int i = 0; i < V_STAGE; i++)
-        v->stage_busy[i] = false;
+    gcn10_stager_idle(&v->stage);
     for (int q = 0; q < r->n_sel; q++)
         for (int k = 0; k < V_LEVELS; k++)
             gcn10_tiff_close_reader(files[q].lv[k]);

@@ -184,9 +184,9 @@ int gcn10_zonal_block(struct worker *w, struct block_in *in)
         if (g->event_sync(w->ctx, in->ev_ready) != 0)
             goto gpu_fail;
         for (size_t i = 0; i < in->n_inflate; i++)
-            if (in->h_status[i] != 0) {
+            if (in->jl.h_status[i] != 0) {
                 wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
-                                       "(stream %zu, reason %u)", in->xoff, in->yoff, in->W, in->H, i, in->h_status[i]);
+                                       "(stream %zu, reason %u)", in->xoff, in->yoff, in->W, in->H, i, in->jl.h_status[i]);
                 wlog(w, "ERROR", true, "esa load failed for block %d", in->block_id);
                 gcn10_zonal_block_unreadable(w, in->block_id);
                 return 0;

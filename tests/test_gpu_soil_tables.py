@@ -36,8 +36,11 @@ class Tile:
         self.cj = np.minimum((np.arange(H) + 3) * hsy // (H + 3), hsy - 1).astype(np.int32) if cj is None else cj
         self.soil = self.coarse[self.cj][:, clamp_columns(self.ci, hsx)]
         self.tables, self._want, self._soil = tables, {}, {}
-        self.bufs = [eng.upload(a) for a in (self.esa, self.coarse, self.ci, self.cj)]
+        self.bufs = self.upload_inputs()
         self.outs = {}
+
+    def upload_inputs(self):
+        return [self.eng.upload(a) for a in (self.esa, self.coarse, self.ci, self.cj)]
 
     def prepare(self, stream=None):
         self.eng.prepare_tile(self.bufs[1].ptr, self.hsx, self.hsy, self.bufs[2].ptr, self.W, stream)

@@ -9,6 +9,7 @@
 #include "gcn10_deflate_internal.hpp"
 #include "gcn10_gpu.h"
 #include "gcn10_gpu_internal.hpp"
+#include "gcn10_soil_readers.hpp"
 
 using gcn10::as_stream;
 using gcn10::fail;
@@ -40,12 +41,10 @@ constexpr int kGroup = 6;            // rasters emitted by one workgroup of pass
 
 struct FusedJob {
     const uint8_t *esa;
-    const uint8_t *hx;
-    const int32_t *cj;
+    gcn10::SoilView soil;
     const uint8_t *class_of;        // [36][256]; class_val [18][256] follows
     uint16_t *tok;                  // [positions][kTokStride] token stream of each tile position (F-A -> F-C)
     uint32_t *n_tok;                // [positions] its length, end-of-block token included
-    uint32_t hx_stride, hx_rows;
     uint32_t seg_align;             // every raster's extent of the strip starts at a multiple of this (option arena_segment_align)
     uint32_t n_sel;                 // selected rasters, ascending
     uint8_t sel[GCN10_N_RASTERS];
@@ -65,11 +64,9 @@ __device__ __forceinline__ uint32_t class_pixels4(const FusedJob &job, uint32_t 
     const uint32_t W = job.t.W;
     uint32_t out = 0;
     if (y < job.t.rows && x < W) {
-        uint32_t srow = (uint32_t)job.cj[y];
-        srow = srow < job.hx_rows ? srow : job.hx_rows - 1u;
         const uint8_t *pe = job.esa + (size_t)y * W + x;
         // hx rows are padded by >= 16 bytes past W: a 4-byte read starting below W is safe
-        const uint32_t c4 = *reinterpret_cast<const u32_u *>(job.hx + (size_t)srow * job.hx_stride + x);
+        const uint32_t c4 = *reinterpret_cast<const u32_u *>(job.soil.ptr(y, x));
         uint32_t e4 = 0;
         if (x + 4u <= W) {
             e4 = *reinterpret_cast<const u32_u *>(pe);
@@ -103,14 +100,13 @@ __device__ __forceinline__ void load_class_tile(const FusedJob &job, uint32_t tx
     if ((tx + 1) * kTile <= job.t.W && (ty + 1) * kTile <= job.t.rows) {
         // interior tile: no edge cases
         const uint8_t *pe = job.esa + ((size_t)ty * kTile + (uint32_t)(t >> 6)) * job.t.W + x;
-        const uint8_t *ph = job.hx + x;
         for (int b = 0; b < kTile / 4; b += 16) {
             uint32_t e4[16], c4[16];
 #pragma unroll
             for (int i = 0; i < 16; i++) {
                 const int r = (b + i) * 4 + (t >> 6);
                 e4[i] = *reinterpret_cast<const u32_u *>(pe + (size_t)(b + i) * 4 * job.t.W);
-                c4[i] = *reinterpret_cast<const u32_u *>(ph + (size_t)soil_row[r] * job.hx_stride);
+                c4[i] = *reinterpret_cast<const u32_u *>(job.soil.at(soil_row[r], x));
             }
 #pragma unroll
             for (int i = 0; i < 16; i++) {
@@ -256,8 +252,7 @@ __global__ __launch_bounds__(kTile) void fused_stats_kernel(const FusedJob job)
         reinterpret_cast<uint32_t *>(sh.class_of)[i] = reinterpret_cast<const uint32_t *>(job.class_of)[i];
     {
         const uint32_t y = ty * kTile + (uint32_t)t;
-        uint32_t srow = y < job.t.rows ? (uint32_t)job.cj[y] : 0u;
-        sh.soil_row[t] = srow < job.hx_rows ? srow : job.hx_rows - 1u;
+        sh.soil_row[t] = job.soil.clamp(y < job.t.rows ? (uint32_t)job.soil.cj[y] : 0u);
     }
     __syncthreads();
     load_class_tile(job, tx, ty, sh.class_of, sh.soil_row, sh.tile, t);
@@ -506,8 +501,7 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
         reinterpret_cast<uint32_t *>(sh.class_of)[i] = reinterpret_cast<const uint32_t *>(job.class_of)[i];
     if (t < kTile) {
         const uint32_t y = ty * kTile + (uint32_t)t;
-        uint32_t srow = y < job.t.rows ? (uint32_t)job.cj[y] : 0u;
-        sh.soil_row[t] = srow < job.hx_rows ? srow : job.hx_rows - 1u;
+        sh.soil_row[t] = job.soil.clamp(y < job.t.rows ? (uint32_t)job.soil.cj[y] : 0u);
     }
     __syncthreads();
     // class tile: thread = 4 columns x 16 rows (rows (t >> 6) + 16 i)
@@ -517,12 +511,11 @@ __global__ __launch_bounds__(kFA2Threads, 8) void fused_stats_seg_kernel(const F
         const int r0 = t >> 6;
         if ((tx + 1) * kTile <= job.t.W && (ty + 1) * kTile <= job.t.rows) {
             const uint8_t *pe = job.esa + ((size_t)ty * kTile + (uint32_t)r0) * job.t.W + x;
-            const uint8_t *ph = job.hx + x;
             uint32_t e4[16], c4[16];
 #pragma unroll
             for (int i = 0; i < 16; i++) {
                 e4[i] = *reinterpret_cast<const u32_u *>(pe + (size_t)i * 16 * job.t.W);
-                c4[i] = *reinterpret_cast<const u32_u *>(ph + (size_t)sh.soil_row[r0 + 16 * i] * job.hx_stride);
+                c4[i] = *reinterpret_cast<const u32_u *>(job.soil.at(sh.soil_row[r0 + 16 * i], x));
             }
 #pragma unroll
             for (int i = 0; i < 16; i++) {
@@ -1541,16 +1534,21 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    if (ctx->n_tables == 0)
-        return fail(GCN10_E_STATE, "gcn10_gpu_deflate_fused_strip: call gcn10_gpu_set_tables first");
+    const char *const who = "gcn10_gpu_deflate_fused_strip";
+    hipStream_t s = as_stream(ctx, stream);
+    if ((rc = gcn10::check_tables(ctx, who)) != GCN10_OK)
+        return rc;
     if (ctx->n_classes == 0)
         return fail(GCN10_E_STATE, "gcn10_gpu_deflate_fused_strip: the lookup tables define more than 256 pixel "
                                    "classes; use gcn10_gpu_cn_strip + gcn10_gpu_deflate_strip");
-    if (!ctx->d_hx || ctx->hx_W == 0 || (uint32_t)W != ctx->hx_W)
-        return fail(GCN10_E_STATE, "gcn10_gpu_deflate_fused_strip: call gcn10_gpu_prepare_tile for W=%d first", W);
-    if (W <= 0 || rows < 0 || cond_mask == 0 || (cond_mask & ~3u) || table_mask == 0 ||
-        (table_mask >> ctx->n_tables))
-        return fail(GCN10_E_INVAL, "gcn10_gpu_deflate_fused_strip: bad shape or masks");
+    FusedJob job;
+    memset(&job, 0, sizeof job);
+    if ((rc = gcn10::bind_soil(ctx, who, W, s, cj, &job.soil)) != GCN10_OK)
+        return rc;
+    if (rows < 0)
+        return fail(GCN10_E_INVAL, "gcn10_gpu_deflate_fused_strip: rows=%d", rows);
+    if ((rc = gcn10::check_masks(ctx, who, cond_mask, table_mask)) != GCN10_OK)
+        return rc;
     if (rows == 0)
         return GCN10_OK;
     if (!esa || !cj || !arena_dev || !table_dev || !cursor_dev)
@@ -1558,18 +1556,11 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
     if ((reinterpret_cast<uintptr_t>(arena_dev) & 15u) != 0)
         return fail(GCN10_E_INVAL, "gcn10_gpu_deflate_fused_strip: arena must be 16-byte aligned");
 
-    FusedJob job;
-    memset(&job, 0, sizeof job);
     job.esa = esa;
-    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &job.hx)) != GCN10_OK)     // made on first use
-        return rc;
-    job.cj = cj;
     job.class_of = ctx->d_class_of;
-    job.hx_stride = ctx->hx_stride;
-    job.hx_rows = ctx->hx_rows;
     job.seg_align = (uint32_t)ctx->arena_segment_align;
     for (int r = 0; r < GCN10_N_RASTERS; r++)
-        if ((cond_mask >> (r / 9)) & 1u && (table_mask >> (r % 9)) & 1u)
+        if (gcn10::selected(r, cond_mask, table_mask))
             job.sel[job.n_sel++] = (uint8_t)r;
     job.t.arena = arena_dev;
     job.t.table = table_dev;
@@ -1627,7 +1618,6 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SharedFC)));
         ctx->fused_ready = true;
     }
-    hipStream_t s = as_stream(ctx, stream);
     if (ctx->fused_parse == 0)
         hipLaunchKernelGGL(fused_stats_kernel, dim3(positions), dim3(kTile), sizeof(SharedFA), s, job);
     else

@@ -41,9 +41,14 @@
 
 #include "gcn10_gpu.h"
 #include "gcn10_gpu_internal.hpp"
+#include "gcn10_soil_readers.hpp"
 
 using gcn10::as_stream;
 using gcn10::fail;
+using gcn10::kLut16Bytes;
+using gcn10::kLut16Plane;
+using gcn10::kPlanes;
+using gcn10::SoilView;
 using gcn10::u32x4;
 using gcn10::use_device;
 
@@ -55,13 +60,8 @@ namespace {
 constexpr int kThreads = 256;           // 4 waves per workgroup
 constexpr int kPxPerLane = 16;          // one dwordx4 per lane per stream
 constexpr int kChunk = kThreads * kPxPerLane;   // 4096 px per workgroup step
-constexpr int kPlanes = 6;              // soil groups 0..4 + "invalid" plane
-constexpr int kInvalidPlane = 5;
-// LDS plane stride for the 16-byte-row table: 256 rows + one row of padding so
-// that equal landcover classes in different planes fall in different banks.
-constexpr int kPlane16 = 256 * 16 + 16;
-constexpr int kLut16Bytes = kPlanes * kPlane16;
-static_assert(kPlane16 == gcn10::kLut16Plane && kLut16Bytes == gcn10::kLut16Bytes, "gcn10_verify.hip reads this image");
+constexpr int kInvalidPlane = kPlanes - 1;  // soil groups 0..4 + the "invalid" plane
+// (the all-tables image: kLut16Plane / kLut16Bytes of gcn10_soil_readers.hpp)
 // LDS plane stride for the single-table byte LUT (+4 B pad: next bank).
 constexpr int kPlane1 = 256 + 4;
 constexpr int kLut1Bytes = kPlanes * kPlane1;
@@ -69,16 +69,13 @@ constexpr int kLut1Bytes = kPlanes * kPlane1;
 
 struct StripParams {
     const uint8_t *esa;
-    const uint8_t *hx;      // x-expanded soil codes (null when the strip reads the soil tables)
-    const int32_t *cj;      // coarse row of every strip row
+    SoilView soil;          // x-expanded soil codes (hx null when the strip reads the soil tables), coarse row of every strip row
     const uint8_t *lut;     // device image of the LDS table (lut16 or lut1[k])
     uint8_t *out[GCN10_N_RASTERS];
     uint32_t W;
     uint32_t rows;
     uint32_t npix;          // W*rows (< 2^31, as the reference's int npix, src/cn.c:208)
     uint32_t nvec16;        // npix rounded down to a multiple of 16: the part done in 16-byte lane groups
-    uint32_t hx_stride;
-    uint32_t hx_rows;       // rows in hx; cj is clamped to it defensively
     uint32_t nchunks;
     uint32_t table_mask;
     uint32_t single_k;      // table index for the single-table variant
@@ -112,37 +109,6 @@ __host__ __device__ inline uint8_t soil_code(uint8_t h)
 // device helpers
 // ------------------------------------------------------------------------
 
-// v_perm_b32: result byte i = byte sel[i] of the 8-byte pool {hi:lo}
-// (selector 0..3 -> lo bytes 0..3, 4..7 -> hi bytes 0..3).
-__device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel)
-{
-    return __builtin_amdgcn_perm(hi, lo, sel);
-}
-
-// 4x4 byte transpose: in a,b,c,d = one dword (4 table values) of pixels 0..3;
-// out o[k] = {a.byte k, b.byte k, c.byte k, d.byte k} (pixel 0 in the low byte).
-__device__ __forceinline__ void transpose4x4(uint32_t a, uint32_t b, uint32_t c,
-                                             uint32_t d, uint32_t &o0, uint32_t &o1,
-                                             uint32_t &o2, uint32_t &o3)
-{
-    uint32_t t0 = perm(b, a, 0x05010400u);  // a0 b0 a1 b1
-    uint32_t t1 = perm(b, a, 0x07030602u);  // a2 b2 a3 b3
-    uint32_t t2 = perm(d, c, 0x05010400u);  // c0 d0 c1 d1
-    uint32_t t3 = perm(d, c, 0x07030602u);  // c2 d2 c3 d3
-    o0 = perm(t2, t0, 0x05040100u);         // a0 b0 c0 d0
-    o1 = perm(t2, t0, 0x07060302u);         // a1 b1 c1 d1
-    o2 = perm(t3, t1, 0x05040100u);         // a2 b2 c2 d2
-    o3 = perm(t3, t1, 0x07060302u);         // a3 b3 c3 d3
-}
-
-__device__ __forceinline__ uint32_t gather_byte0(uint32_t a, uint32_t b, uint32_t c,
-                                                 uint32_t d)
-{
-    uint32_t t0 = perm(b, a, 0x0c0c0400u);  // a0 b0 0 0
-    uint32_t t1 = perm(d, c, 0x04000c0cu);  // 0 0 c0 d0
-    return t0 | t1;
-}
-
 __device__ __forceinline__ u32x4 load16_aligned_nt(const uint8_t *p)
 {
     return __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(p));
@@ -168,21 +134,6 @@ __device__ __forceinline__ void store16(uint8_t *p, u32x4 v)
         __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(p));
     else
         *reinterpret_cast<u32x4 *>(p) = v;
-}
-
-// Coarse soil row of strip row y.  cj comes from the caller (host-built, already
-// clamped as src/cn.c:229 does); the extra min() only keeps a bad map from
-// reading outside the workspace.
-__device__ __forceinline__ uint32_t soil_row(const StripParams &p, uint32_t y)
-{
-    const uint32_t r = (uint32_t)p.cj[y];
-    return r < p.hx_rows ? r : p.hx_rows - 1u;
-}
-
-__device__ __forceinline__ uint32_t clamp_row(const StripParams &p, int32_t r)
-{
-    const uint32_t u = (uint32_t)r;
-    return u < p.hx_rows ? u : p.hx_rows - 1u;
 }
 
 // cj[i] for a wave-uniform i through the scalar data cache (s_load_dword):
@@ -282,8 +233,8 @@ __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, 
         const uint32_t wbc = wb[u] < p.npix ? wb[u] : 0u;   // a wave past the end only needs valid addresses
         const uint32_t y = wbc / p.W;
         xb[u] = wbc - y * p.W;
-        r0[u] = (uint32_t)scalar_load_i32(p.cj, y);
-        r1[u] = (uint32_t)scalar_load_i32(p.cj, y + 1u < p.rows ? y + 1u : y);
+        r0[u] = (uint32_t)scalar_load_i32(p.soil.cj, y);
+        r1[u] = (uint32_t)scalar_load_i32(p.soil.cj, y + 1u < p.rows ? y + 1u : y);
     }
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
@@ -296,7 +247,7 @@ __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, 
         uint32_t xl = xb[u] + lane_off;
         const bool wrap = xl >= p.W;
         xl = wrap ? xl - p.W : xl;
-        const uint32_t row = clamp_row(p, (int32_t)(wrap ? r1[u] : r0[u]));
+        const uint32_t row = p.soil.clamp(wrap ? r1[u] : r0[u]);
         if (SOIL == kSoilWords) {
             tr.c16[u] = u32x4{ p.hx4[(size_t)row * p.hx4_stride + (xl >> 4)], 0u, 0u, 0u };
             continue;
@@ -320,14 +271,14 @@ __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, 
             tr.c16[u] = a;
             continue;
         }
-        const uint8_t *pa = p.hx + (size_t)row * p.hx_stride + xl;
+        const uint8_t *pa = p.soil.at(row, xl);
         u32x4 a = load16_any(pa);
         if (p.W & 15u) {
             const uint32_t n = p.W - xl;            // pixels of this lane that are still in its row
             const bool strad = !wrap && n < (uint32_t)kPxPerLane;
             if (__builtin_amdgcn_ballot_w64(strad) != 0ull) {
                 // the other lanes of this wave re-read their own vector (an L1 hit)
-                const uint8_t *pb = strad ? p.hx + (size_t)clamp_row(p, (int32_t)r1[u]) * p.hx_stride - n : pa;
+                const uint8_t *pb = strad ? p.soil.at(p.soil.clamp(r1[u]), 0u) - n : pa;
                 const u32x4 b = load16_any(pb);
                 const uint32_t nn = strad ? n : (uint32_t)kPxPerLane;
 #pragma unroll
@@ -373,24 +324,7 @@ __device__ __forceinline__ void finish_trip(const StripParams &p, const uint8_t 
                 continue;
             if (KIND == kLut16) {
                 uint32_t acc[9][4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const uint32_t e = tr.e16[u][j];
-                    const uint32_t cd = c16[j];
-                    u32x4 r4[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const uint32_t lc16 = q == 0 ? (e << 4) & 0xff0u : (e >> (8 * q - 4)) & 0xff0u;
-                        const uint32_t s = (cd >> (8 * q + 4 * c)) & 0xfu;
-                        const uint32_t addr = s * (uint32_t)kPlane16 + lc16;
-                        r4[q] = *reinterpret_cast<const u32x4 *>(lut + addr);
-                    }
-                    transpose4x4(r4[0][0], r4[1][0], r4[2][0], r4[3][0], acc[0][j], acc[1][j],
-                                 acc[2][j], acc[3][j]);
-                    transpose4x4(r4[0][1], r4[1][1], r4[2][1], r4[3][1], acc[4][j], acc[5][j],
-                                 acc[6][j], acc[7][j]);
-                    acc[8][j] = gather_byte0(r4[0][2], r4[1][2], r4[2][2], r4[3][2]);
-                }
+                gcn10::gather16(lut, tr.e16[u], c16, c, acc);
                 if (live) {
 #pragma unroll
                     for (int k = 0; k < 9; k++) {
@@ -470,10 +404,7 @@ __global__ __launch_bounds__(kThreads) void cn_strip_kernel(const StripParams p)
     __shared__ __attribute__((aligned(16))) uint8_t lut[kLutBytes];
 
     if (KIND == kLut16) {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(p.lut);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(lut);
-        for (int i = threadIdx.x; i < kLutBytes / 16; i += kThreads)
-            dst[i] = src[i];
+        gcn10::stage_lut16<kThreads>(lut, p.lut);
     }
     else {
         const uint32_t *src = reinterpret_cast<const uint32_t *>(p.lut);
@@ -502,15 +433,15 @@ __global__ __launch_bounds__(kThreads) void cn_strip_kernel(const StripParams p)
         const uint32_t y = i / p.W;
         const uint32_t x = i - y * p.W;
         const uint32_t lc = p.esa[i];
-        // (a strip that reads the soil tables has W % 16 == 0, so no tail: p.hx is set whenever this runs)
-        const uint32_t cd = p.hx[(size_t)soil_row(p, y) * p.hx_stride + x];
+        // (a strip that reads the soil tables has W % 16 == 0, so no tail: p.soil.hx is set whenever this runs)
+        const uint32_t cd = *p.soil.ptr(y, x);
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if (!(COND_MASK & (1 << c)))
                 continue;
             const uint32_t s = (cd >> (4 * c)) & 0xfu;
             if (KIND == kLut16) {
-                const uint8_t *row = lut + s * (uint32_t)kPlane16 + lc * 16u;
+                const uint8_t *row = gcn10::lut16_row(lut, s, lc);
                 for (int k = 0; k < 9; k++)
                     if (tmask & (1u << k))
                         p.out[c * 9 + k][i] = row[k];
@@ -555,8 +486,7 @@ __global__ __launch_bounds__(kThreads) void cn_strip_bytes(const StripParams p,
                                                            uint32_t cond_mask)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lut[kLut16Bytes];
-    for (int i = threadIdx.x; i < kLut16Bytes; i += kThreads)
-        lut[i] = p.lut[i];
+    gcn10::stage_lut16<kThreads>(lut, p.lut);
     __syncthreads();
 
     const uint32_t stride = gridDim.x * blockDim.x;
@@ -564,12 +494,12 @@ __global__ __launch_bounds__(kThreads) void cn_strip_bytes(const StripParams p,
         const uint32_t y = i / p.W;
         const uint32_t x = i - y * p.W;
         const uint32_t lc = p.esa[i];
-        const uint32_t cd = p.hx[(size_t)soil_row(p, y) * p.hx_stride + x];
+        const uint32_t cd = *p.soil.ptr(y, x);
         for (int c = 0; c < 2; c++) {
             if (!(cond_mask & (1u << c)))
                 continue;
             const uint32_t s = (cd >> (4 * c)) & 0xfu;
-            const uint8_t *row = lut + s * (uint32_t)kPlane16 + lc * 16u;
+            const uint8_t *row = gcn10::lut16_row(lut, s, lc);
             for (int k = 0; k < 9; k++)
                 if (p.table_mask & (1u << k))
                     p.out[c * 9 + k][i] = row[k];
@@ -1001,6 +931,48 @@ int soil_bytes(gcn10_gpu_ctx *ctx, hipStream_t stream, const uint8_t **hx)
     return GCN10_OK;
 }
 
+int check_tables(gcn10_gpu_ctx *ctx, const char *who)
+{
+    if (ctx->n_tables == 0)
+        return fail(GCN10_E_STATE, "%s: call gcn10_gpu_set_tables first", who);
+    return GCN10_OK;
+}
+
+int check_tile(gcn10_gpu_ctx *ctx, const char *who)
+{
+    if (!ctx->d_hx || ctx->hx_W == 0)
+        return fail(GCN10_E_STATE, "%s: call gcn10_gpu_prepare_tile first", who);
+    return GCN10_OK;
+}
+
+int bind_soil(gcn10_gpu_ctx *ctx, const char *who, int W, hipStream_t stream, const int32_t *cj, SoilView *view)
+{
+    int rc = check_tile(ctx, who);
+    if (rc)
+        return rc;
+    if (W <= 0 || (uint32_t)W != ctx->hx_W)
+        return fail(GCN10_E_STATE, "%s: the prepared tile is %u wide: call gcn10_gpu_prepare_tile for W=%d first", who,
+                    ctx->hx_W, W);
+    view->cj = cj;
+    view->stride = ctx->hx_stride;
+    view->rows = ctx->hx_rows;
+    return soil_bytes(ctx, stream, &view->hx);      // made on first use
+}
+
+int check_masks(gcn10_gpu_ctx *ctx, const char *who, unsigned cond_mask, unsigned table_mask)
+{
+    if (cond_mask == 0 || (cond_mask & ~3u))
+        return fail(GCN10_E_INVAL, "%s: cond_mask 0x%x", who, cond_mask);
+    if (table_mask == 0 || (table_mask >> ctx->n_tables))
+        return fail(GCN10_E_INVAL, "%s: table_mask 0x%x with %d tables loaded", who, table_mask, ctx->n_tables);
+    return GCN10_OK;
+}
+
+uint32_t grid_cap(const gcn10_gpu_ctx *ctx, int per_cu)
+{
+    return (uint32_t)(ctx->n_cus > 0 ? ctx->n_cus : 256) * (uint32_t)per_cu;
+}
+
 }  // namespace gcn10
 
 namespace {
@@ -1015,6 +987,20 @@ uint32_t stream_grid(const gcn10_gpu_ctx *ctx, uint64_t nchunks, int blocks_per_
         cap = 8;
     uint64_t g = nchunks < cap ? nchunks : cap;
     return (uint32_t)(g ? g : 1);
+}
+
+// Launches a kernel of kThreads threads.  A pair of events left by gcn10_gpu_time_next_strip is attached to the
+// dispatch itself (they bracket the kernel, not the command-processor gaps around separately recorded events) and
+// used up.
+hipError_t launch_timed(gcn10_gpu_ctx *ctx, const void *fn, uint32_t grid, void **args, hipStream_t s)
+{
+    if (!ctx->time_start || !ctx->time_stop)
+        return hipLaunchKernel(fn, dim3(grid), dim3(kThreads), args, 0, s);
+    const hipError_t e = hipExtLaunchKernel(fn, dim3(grid), dim3(kThreads), args, 0, s, ctx->time_start,
+                                            ctx->time_stop, 0);
+    if (e == hipSuccess)
+        ctx->time_start = ctx->time_stop = nullptr;
+    return e;
 }
 
 }  // namespace
@@ -1370,7 +1356,7 @@ int gcn10_gpu_set_tables(gcn10_gpu_ctx *ctx, const int *tables, int n_tables)
                 // truncating (uint8_t) cast; everything else leaves the 255
                 // the raster was memset to (src/cn.c:289).
                 const uint8_t b = v < GCN10_NODATA ? (uint8_t)v : (uint8_t)GCN10_NODATA;
-                img16[s * kPlane16 + lc * 16 + k] = b;
+                img16[s * kLut16Plane + lc * 16 + k] = b;
                 img1[k * kLut1Bytes + s * kPlane1 + lc] = b;
             }
         }
@@ -1399,7 +1385,7 @@ int gcn10_gpu_set_tables(gcn10_gpu_ctx *ctx, const int *tables, int n_tables)
                 for (int r = 0; r < GCN10_N_RASTERS; r++) {
                     const int sgrp = r < 9 ? sd : su;
                     const int k = r % 9;
-                    v[r] = (sgrp < 5 && k < n_tables) ? img16[sgrp * kPlane16 + lc * 16 + k]
+                    v[r] = (sgrp < 5 && k < n_tables) ? img16[sgrp * kLut16Plane + lc * 16 + k]
                                                       : (uint8_t)GCN10_NODATA;
                 }
                 int id = -1;
@@ -1483,8 +1469,8 @@ int gcn10_gpu_calculate_cn(gcn10_gpu_ctx *ctx, const uint8_t *esa, const uint8_t
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    if (ctx->n_tables == 0)
-        return fail(GCN10_E_STATE, "gcn10_gpu_calculate_cn: call gcn10_gpu_set_tables first");
+    if ((rc = gcn10::check_tables(ctx, "gcn10_gpu_calculate_cn")) != GCN10_OK)
+        return rc;
     if (table_index < 0 || table_index >= ctx->n_tables)
         return fail(GCN10_E_INVAL, "gcn10_gpu_calculate_cn: table %d not loaded (have %d)",
                     table_index, ctx->n_tables);
@@ -1581,20 +1567,17 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    if (ctx->n_tables == 0)
-        return fail(GCN10_E_STATE, "gcn10_gpu_cn_strip: call gcn10_gpu_set_tables first");
-    if (!ctx->d_hx || ctx->hx_W == 0)
-        return fail(GCN10_E_STATE, "gcn10_gpu_cn_strip: call gcn10_gpu_prepare_tile first");
+    const char *const who = "gcn10_gpu_cn_strip";
+    if ((rc = gcn10::check_tables(ctx, who)) != GCN10_OK || (rc = gcn10::check_tile(ctx, who)) != GCN10_OK)
+        return rc;
+    // (a width other than the prepared tile's is a bad argument here, a bad state to the other readers)
     if (W <= 0 || rows < 0 || (uint32_t)W != ctx->hx_W)
         return fail(GCN10_E_INVAL, "gcn10_gpu_cn_strip: W=%d rows=%d does not match prepared tile W=%u",
                     W, rows, ctx->hx_W);
     if ((uint64_t)W * (uint64_t)rows > 0x7fffffffull)
         return fail(GCN10_E_INVAL, "gcn10_gpu_cn_strip: strip of %d x %d exceeds 2^31-1 pixels", W, rows);
-    if (cond_mask == 0 || (cond_mask & ~3u))
-        return fail(GCN10_E_INVAL, "gcn10_gpu_cn_strip: cond_mask 0x%x", cond_mask);
-    if (table_mask == 0 || (table_mask >> ctx->n_tables))
-        return fail(GCN10_E_INVAL, "gcn10_gpu_cn_strip: table_mask 0x%x with %d tables loaded",
-                    table_mask, ctx->n_tables);
+    if ((rc = gcn10::check_masks(ctx, who, cond_mask, table_mask)) != GCN10_OK)
+        return rc;
     if (rows == 0)
         return GCN10_OK;
     if (!esa || !cj || !out)
@@ -1603,24 +1586,18 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
     StripParams p;
     memset(&p, 0, sizeof p);
     bool all_aligned = aligned16(esa);
-    for (int c = 0; c < 2; c++) {
-        for (int k = 0; k < 9; k++) {
-            const int r = c * 9 + k;
-            if ((cond_mask & (1u << c)) && (table_mask & (1u << k))) {
-                if (!out[r])
-                    return fail(GCN10_E_INVAL, "gcn10_gpu_cn_strip: out[%d] is null but selected", r);
-                p.out[r] = out[r];
-                all_aligned = all_aligned && aligned16(out[r]);
-            }
-        }
+    for (int r = 0; r < GCN10_N_RASTERS; r++) {
+        if (!gcn10::selected(r, cond_mask, table_mask))
+            continue;
+        if (!out[r])
+            return fail(GCN10_E_INVAL, "gcn10_gpu_cn_strip: out[%d] is null but selected", r);
+        p.out[r] = out[r];
+        all_aligned = all_aligned && aligned16(out[r]);
     }
     p.esa = esa;
-    p.cj = cj;
     p.W = (uint32_t)W;
     p.rows = (uint32_t)rows;
     p.npix = (uint32_t)((uint64_t)W * (uint64_t)rows);
-    p.hx_stride = ctx->hx_stride;
-    p.hx_rows = ctx->hx_rows;
     p.nchunks = (p.npix + kChunk - 1) / kChunk;
     p.table_mask = table_mask;
     hipStream_t s = as_stream(ctx, stream);
@@ -1632,6 +1609,7 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
         all_aligned = false;
     if (all_aligned && ctx->compact_soil && (p.W & 15u) == 0u) {
         // rows are 16-byte aligned: a lane's 16 pixels are one column group of the compact soil words
+        p.soil = SoilView{ nullptr, cj, ctx->hx_stride, ctx->hx_rows };
         p.hx4 = ctx->d_hx4;
         p.hx4_stride = ctx->hx_stride / 16u;
         p.cx = ctx->d_cx;
@@ -1641,22 +1619,15 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
         p.soil_gen = ctx->soil_gen;
     }
     else {
-        rc = gcn10::soil_bytes(ctx, s, &p.hx);
+        rc = gcn10::bind_soil(ctx, who, W, s, cj, &p.soil);
         if (rc)
             return rc;
     }
     if (!all_aligned) {
         p.lut = ctx->d_lut16;
         const uint32_t g = stream_grid(ctx, ((uint64_t)p.npix + kThreads - 1) / kThreads);
-        if (ctx->time_start && ctx->time_stop) {
-            void *args[] = { &p, &cond_mask };
-            HIP_TRY(hipExtLaunchKernel(reinterpret_cast<const void *>(cn_strip_bytes), dim3(g), dim3(kThreads), args, 0,
-                                       s, ctx->time_start, ctx->time_stop, 0));
-            ctx->time_start = ctx->time_stop = nullptr;
-        }
-        else {
-            hipLaunchKernelGGL(cn_strip_bytes, dim3(g), dim3(kThreads), 0, s, p, cond_mask);
-        }
+        void *args[] = { &p, &cond_mask };
+        HIP_TRY(launch_timed(ctx, reinterpret_cast<const void *>(cn_strip_bytes), g, args, s));
         ctx->last_kernel = "cn_strip_bytes";
     }
     else {
@@ -1683,17 +1654,8 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
         strip_kernel_t fn = pick_strip_kernel(single, cond_mask, all, ilp, nt, pf);
         if (!fn)
             return fail(GCN10_E_INVAL, "gcn10_gpu_cn_strip: no kernel for ilp=%d", ilp);
-        if (ctx->time_start && ctx->time_stop) {
-            // events attached to the dispatch itself: they bracket the kernel, not the
-            // command-processor gaps around separately recorded events
-            void *args[] = { &p };
-            HIP_TRY(hipExtLaunchKernel(reinterpret_cast<const void *>(fn), dim3(grid), dim3(kThreads), args, 0,
-                                       s, ctx->time_start, ctx->time_stop, 0));
-            ctx->time_start = ctx->time_stop = nullptr;
-        }
-        else {
-            hipLaunchKernelGGL(fn, dim3(grid), dim3(kThreads), 0, s, p);
-        }
+        void *args[] = { &p };
+        HIP_TRY(launch_timed(ctx, reinterpret_cast<const void *>(fn), grid, args, s));
         // the instantiation's name as rocprofv3 prints it: <KIND, COND_MASK, ALL_TABLES, ILP, NT, PF>
         snprintf(ctx->kernel_name, sizeof ctx->kernel_name, "cn_strip_kernel<%d, %u, %s, %d, %s, %s>",
                  single ? 1 : 0, cond_mask, (all || single) ? "true" : "false", ilp, nt ? "true" : "false",
@@ -1791,15 +1753,8 @@ int gcn10_gpu_stream_copy(gcn10_gpu_ctx *ctx, const void *src, void *dst, size_t
     uint32_t ntrips = (nvec + 2u * kThreads - 1u) / (2u * kThreads);
     const uint32_t grid = stream_grid(ctx, ntrips);
     hipStream_t s = as_stream(ctx, stream);
-    if (ctx->time_start && ctx->time_stop) {
-        void *args[] = { &in, &out, &nvec, &ntrips };
-        HIP_TRY(hipExtLaunchKernel(reinterpret_cast<const void *>(stream_copy_kernel), dim3(grid), dim3(kThreads),
-                                   args, 0, s, ctx->time_start, ctx->time_stop, 0));
-        ctx->time_start = ctx->time_stop = nullptr;
-    }
-    else {
-        hipLaunchKernelGGL(stream_copy_kernel, dim3(grid), dim3(kThreads), 0, s, in, out, nvec, ntrips);
-    }
+    void *args[] = { &in, &out, &nvec, &ntrips };
+    HIP_TRY(launch_timed(ctx, reinterpret_cast<const void *>(stream_copy_kernel), grid, args, s));
     HIP_TRY(hipGetLastError());
     return GCN10_OK;
 }

@@ -28,8 +28,23 @@ hipStream_t as_stream(gcn10_gpu_ctx *ctx, gcn10_stream_t s);
 int grow_workspace(void **ws, size_t *cap, size_t need);
 // The soil code bytes of the prepared tile (gcn10_gpu_ctx::d_hx), valid for work that `stream` runs after this call:
 // the first caller after a gcn10_gpu_prepare_tile expands them from the tile's tables on its own stream, every later
-// caller's stream is made to wait for that expansion (no cost on the stream that ran it).  Every kernel that reads the bytes gets them here.
+// caller's stream is made to wait for that expansion (no cost on the stream that ran it).  prepare_tile and bind_soil
+// call it; every kernel that reads the bytes gets them through bind_soil.
 int soil_bytes(gcn10_gpu_ctx *ctx, hipStream_t stream, const uint8_t **hx);
+
+// ---- the host preamble of the soil readers (gcn10_soil_readers.hpp has their device side) ----
+struct SoilView;
+// GCN10_E_STATE unless gcn10_gpu_set_tables has run
+int check_tables(gcn10_gpu_ctx *ctx, const char *who);
+// GCN10_E_STATE unless a tile is prepared
+int check_tile(gcn10_gpu_ctx *ctx, const char *who);
+// GCN10_E_STATE unless a tile is prepared, and for width W; then the view of its code bytes (soil_bytes on `stream`)
+// for a strip whose rows cj maps
+int bind_soil(gcn10_gpu_ctx *ctx, const char *who, int W, hipStream_t stream, const int32_t *cj, SoilView *view);
+// GCN10_E_INVAL unless the masks name at least one condition and one loaded table, and nothing else
+int check_masks(gcn10_gpu_ctx *ctx, const char *who, unsigned cond_mask, unsigned table_mask);
+// the most workgroups a reader that loops over its work launches: per_cu on every compute unit
+uint32_t grid_cap(const gcn10_gpu_ctx *ctx, int per_cu);
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -53,24 +68,18 @@ void launch_lzw_decode(const uint8_t *comp_dev, const gcn10_inflate_tile *tiles_
 // compact index = drained * 6 + undrained
 constexpr int kClassCodes = 36;
 
-// device image of the all-tables lookup (gcn10_gpu_ctx::d_lut16, written by gcn10_gpu_set_tables): six soil planes
-// (0..4 and "invalid") of 256 rows of 16 bytes -- byte k = table k's value for (plane, landcover), 255 where there is
-// none -- and one row of padding per plane, so that equal classes of different planes fall in different LDS banks
-constexpr int kLut16Plane = 256 * 16 + 16;
-constexpr int kLut16Bytes = 6 * kLut16Plane;
-
 }  // namespace gcn10
 
 struct gcn10_gpu_ctx {
     int device = -1;
     int n_cus = 0;
     hipStream_t main_stream = nullptr;
-    uint8_t *d_lut16 = nullptr;     // kLut16Bytes
+    uint8_t *d_lut16 = nullptr;     // kLut16Bytes: the all-tables image (gcn10_soil_readers.hpp)
     uint8_t *d_lut1 = nullptr;      // 9 * kLut1Bytes
     int n_tables = 0;
     // Soil workspace of the prepared tile (one allocation, grown by gcn10_gpu_prepare_tile):
     //   d_hx      [hx_rows][hx_stride]      soil code bytes, one per fine column.  Allocated with the tile, FILLED ON
-    //                                        DEMAND: every reader gets the pointer from gcn10::soil_bytes()
+    //                                        DEMAND: every reader gets them as a gcn10::SoilView from bind_soil()
     //   d_hx4     [hx_rows][hx_stride / 16] compact soil words, one per 16-px column group and coarse row
     //   d_cx      [hx_stride]               clamped coarse column of every fine column; hsx = padding
     //   d_codes   [hx_rows][codes_stride]   soil code of every coarse cell; columns >= hsx hold the padding code

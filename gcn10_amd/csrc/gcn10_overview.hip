@@ -16,15 +16,13 @@
 #include <cstdint>
 
 #include "gcn10_gpu_internal.hpp"
+#include "gcn10_soil_readers.hpp"
 
 using namespace gcn10;
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kPlanes = 6;                  // soil groups 0..4 + the "invalid" plane (gcn10_gpu.hip)
-constexpr int kPlane16 = 256 * 16 + 16;     // one 16-byte row of the nine tables per landcover value
-constexpr int kLut16Bytes = kPlanes * kPlane16;
 constexpr int kMaxLevels = 8;               // a 256 x 256 full-resolution tile holds whole pixels of levels 1..8
 constexpr int kL1Tile = 128;                // level-1 pixels per workgroup side (= 256 full-resolution pixels)
 // level-1 rows per workgroup of the level-1 kernel; per 36000² block: 1 row 9.5 ms, 4 rows 9.2, 32 rows 10.5
@@ -62,10 +60,8 @@ __global__ __launch_bounds__(kThreads) void overview_nearest_kernel(const Neares
 // address (a broadcast); per-raster byte look-ups, one per raster and pixel, would cost 18x the LDS instructions.
 struct AvgParams {
     const uint8_t *esa;         // block row 0
-    const int32_t *cj;          // block's soil row of every row
+    SoilView soil;              // prepared soil codes, block's soil row of every row
     const uint8_t *lut16;
-    const uint8_t *hx;          // prepared soil codes: drained plane | undrained plane << 4
-    uint32_t hx_stride, hx_rows;
     uint32_t W, H, y1_begin, y1_end;        // level-1 rows of this strip
     uint32_t cond_mask, table_mask;
     uint32_t n_levels;
@@ -81,8 +77,7 @@ __device__ __forceinline__ void level1_pixel(const AvgParams &p, const uint8_t *
 __global__ __launch_bounds__(kThreads) void overview_avg_level1_kernel(const AvgParams p)
 {
     __shared__ __attribute__((aligned(16))) uint8_t lut[kLut16Bytes];
-    for (int i = threadIdx.x * 16; i < kLut16Bytes; i += kThreads * 16)
-        *reinterpret_cast<u32x4 *>(lut + i) = *reinterpret_cast<const u32x4 *>(p.lut16 + i);
+    stage_lut16<kThreads>(lut, p.lut16);
     __syncthreads();
 
     const uint32_t W1 = (p.W + 1u) >> 1;
@@ -105,19 +100,19 @@ __device__ __forceinline__ void level1_pixel(const AvgParams &p, const uint8_t *
         const uint32_t y = 2u * y1 + dy;
         if (y >= p.H)
             break;
-        const uint32_t crow = min((uint32_t)p.cj[y], p.hx_rows - 1u);
+        const uint32_t crow = p.soil.row(y);
         for (uint32_t dx = 0; dx < 2; dx++) {
             const uint32_t x = 2u * x1 + dx;
             if (x >= p.W)
                 break;
             const uint32_t lc = p.esa[(size_t)y * p.W + x];
-            const uint32_t cd = p.hx[(size_t)crow * p.hx_stride + x];
+            const uint32_t cd = *p.soil.at(crow, x);
 #pragma unroll
             for (int c = 0; c < 2; c++) {
                 if (!(p.cond_mask & (1u << c)))
                     continue;
                 const uint32_t plane = min((cd >> (4 * c)) & 0xfu, (uint32_t)kPlanes - 1u);
-                const u32x4 row = *reinterpret_cast<const u32x4 *>(lut + plane * kPlane16 + lc * 16u);
+                const u32x4 row = *reinterpret_cast<const u32x4 *>(lut16_row(lut, plane, lc));
 #pragma unroll
                 for (int k = 0; k < 9; k++) {
                     const uint32_t v = (row[k >> 2] >> (8 * (k & 3))) & 0xffu;
@@ -131,7 +126,7 @@ __device__ __forceinline__ void level1_pixel(const AvgParams &p, const uint8_t *
 #pragma unroll
     for (int r = 0; r < GCN10_N_RASTERS; r++) {
         uint8_t *o = p.out[r][0];
-        if (o && (p.cond_mask >> (r / 9)) & 1u && (p.table_mask >> (r % 9)) & 1u)
+        if (o && selected(r, p.cond_mask, p.table_mask))
             o[(size_t)y1 * W1 + x1] = avg_of(s[r], n[r]);
     }
 }
@@ -145,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void overview_avg_deeper_kernel(const Avg
     __shared__ uint8_t a[kL1Tile * kL1Tile];
     __shared__ uint8_t b[(kL1Tile / 2) * (kL1Tile / 2)];
     const uint32_t r = blockIdx.z;
-    if (!((p.cond_mask >> (r / 9)) & 1u) || !((p.table_mask >> (r % 9)) & 1u) || !p.out[r][0])
+    if (!selected(r, p.cond_mask, p.table_mask) || !p.out[r][0])
         return;
     const uint32_t tx = blockIdx.x, ty = ty0 + blockIdx.y;
     uint32_t Wl = (p.W + 1u) >> 1, Hl = (p.H + 1u) >> 1;     // level-1 size
@@ -225,24 +220,19 @@ int gcn10_gpu_overview_average(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, in
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    if (ctx->n_tables == 0)
-        return fail(GCN10_E_STATE, "gcn10_gpu_overview_average: call gcn10_gpu_set_tables first");
-    if (!ctx->d_hx || (int)ctx->hx_W != W)
-        return fail(GCN10_E_STATE, "gcn10_gpu_overview_average: prepare the block's tile (W=%d) first", W);
+    const char *const who = "gcn10_gpu_overview_average";
+    hipStream_t s = as_stream(ctx, stream);
+    AvgParams p = {};
+    if ((rc = check_tables(ctx, who)) != GCN10_OK || (rc = bind_soil(ctx, who, W, s, cj, &p.soil)) != GCN10_OK)
+        return rc;
     if (!esa || !cj || !levels || W <= 0 || H <= 0 || n_levels < 1 || n_levels > kMaxLevels || y0 < 0 ||
         rows <= 0 || y0 % 256 != 0 || y0 + rows > H || (rows % 256 != 0 && y0 + rows != H))
         return fail(GCN10_E_INVAL, "gcn10_gpu_overview_average: bad strip y0=%d rows=%d of %dx%d, %d levels "
                     "(strips start and end on multiples of 256 rows, 1..8 levels)", y0, rows, W, H, n_levels);
-    if (cond_mask == 0 || (cond_mask & ~3u) || table_mask == 0 || (table_mask >> ctx->n_tables) != 0)
-        return fail(GCN10_E_INVAL, "gcn10_gpu_overview_average: bad masks cond=%#x table=%#x", cond_mask, table_mask);
-    AvgParams p = {};
-    p.esa = esa;
-    p.cj = cj;
-    p.lut16 = ctx->d_lut16;
-    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &p.hx)) != GCN10_OK)     // made on first use
+    if ((rc = check_masks(ctx, who, cond_mask, table_mask)) != GCN10_OK)
         return rc;
-    p.hx_stride = ctx->hx_stride;
-    p.hx_rows = ctx->hx_rows;
+    p.esa = esa;
+    p.lut16 = ctx->d_lut16;
     p.W = (uint32_t)W;
     p.H = (uint32_t)H;
     p.cond_mask = cond_mask;
@@ -250,7 +240,7 @@ int gcn10_gpu_overview_average(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, in
     p.n_levels = (uint32_t)n_levels;
     int q = 0;
     for (int r = 0; r < GCN10_N_RASTERS; r++) {
-        if (!((cond_mask >> (r / 9)) & 1u) || !((table_mask >> (r % 9)) & 1u))
+        if (!selected(r, cond_mask, table_mask))
             continue;
         for (int k = 0; k < n_levels; k++) {
             p.out[r][k] = levels[q * n_levels + k];
@@ -262,7 +252,6 @@ int gcn10_gpu_overview_average(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, in
     const uint32_t W1 = ((uint32_t)W + 1u) >> 1;
     p.y1_begin = (uint32_t)y0 / 2u;
     p.y1_end = ((uint32_t)(y0 + rows) + 1u) / 2u;
-    hipStream_t s = as_stream(ctx, stream);
     dim3 grid1((W1 + kThreads - 1) / kThreads, (p.y1_end - p.y1_begin + kL1Rows - 1) / kL1Rows);
     hipLaunchKernelGGL(overview_avg_level1_kernel, grid1, dim3(kThreads), 0, s, p);
     HIP_TRY(hipGetLastError());

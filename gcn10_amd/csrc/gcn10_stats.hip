@@ -18,6 +18,7 @@
 
 #include "gcn10_gpu_internal.hpp"
 #include "gcn10_pair_hist.hpp"
+#include "gcn10_soil_readers.hpp"
 
 using namespace gcn10;
 using namespace gcn10::pair_hist;
@@ -31,10 +32,9 @@ constexpr int kGridPerCu = 4;
 
 struct HistParams {
     const uint8_t *esa;         // strip, W x rows, row major
-    const uint8_t *hx;          // x-expanded soil codes, hx_rows rows of hx_stride bytes
-    const int32_t *cj;          // soil row of every strip row
+    SoilView soil;              // x-expanded soil codes, soil row of every strip row
     unsigned long long *hist;   // [kBins][256]
-    uint32_t W, rows, hx_stride, hx_rows, per_row;
+    uint32_t W, rows, per_row;
 };
 
 __global__ __launch_bounds__(kThreads) void pair_histogram_kernel(const HistParams p)
@@ -57,10 +57,8 @@ __global__ __launch_bounds__(kThreads) void pair_histogram_kernel(const HistPara
 #pragma unroll
         for (uint32_t j = 0; j < kRowsPerItem; j++) {
             const uint32_t y = y0 + min(j, ny - 1u);
-            uint32_t r = (uint32_t)p.cj[y];
-            r = r < p.hx_rows ? r : p.hx_rows - 1u;
             erow[j] = p.esa + (size_t)y * p.W + x0;
-            srow[j] = p.hx + (size_t)r * p.hx_stride + x0;
+            srow[j] = p.soil.ptr(y, x0);
         }
         if (x0 + kPxPerLane <= p.W) {
             // 16 pixels inside the row: one 16-byte load of each (landcover rows start anywhere, soil rows on 16)
@@ -110,25 +108,20 @@ int gcn10_gpu_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int 
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    if (!ctx->d_hx || (int)ctx->hx_W != W)
-        return fail(GCN10_E_STATE, "gcn10_gpu_pair_histogram: prepare the block's tile (W=%d) first", W);
+    HistParams p = {};
+    if ((rc = bind_soil(ctx, "gcn10_gpu_pair_histogram", W, as_stream(ctx, stream), cj, &p.soil)) != GCN10_OK)
+        return rc;
     if (!esa || !cj || !hist_dev || W <= 0 || rows < 0)
         return fail(GCN10_E_INVAL, "gcn10_gpu_pair_histogram: bad arguments W=%d rows=%d", W, rows);
     if (rows == 0)
         return GCN10_OK;
-    HistParams p = {};
     p.esa = esa;
-    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &p.hx)) != GCN10_OK)     // made on first use
-        return rc;
-    p.cj = cj;
     p.hist = hist_dev;
     p.W = (uint32_t)W;
     p.rows = (uint32_t)rows;
-    p.hx_stride = ctx->hx_stride;
-    p.hx_rows = ctx->hx_rows;
     p.per_row = ((uint32_t)W + kChunk - 1u) / kChunk;
     const uint64_t items = (uint64_t)((p.rows + kRowsPerItem - 1u) / kRowsPerItem) * p.per_row;
-    const uint64_t cap = (uint64_t)(ctx->n_cus > 0 ? ctx->n_cus : 256) * kGridPerCu;
+    const uint64_t cap = grid_cap(ctx, kGridPerCu);
     const uint32_t grid = (uint32_t)(items < cap ? items : cap);
     hipLaunchKernelGGL(pair_histogram_kernel, dim3(grid), dim3(kThreads), 0, as_stream(ctx, stream), p);
     HIP_TRY(hipGetLastError());

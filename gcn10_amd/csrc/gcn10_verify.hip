@@ -2,8 +2,9 @@
 // "Verification").
 //
 // gcn10_gpu_verify_strip: one pass over a landcover strip.  Every lane takes 16 consecutive pixels of one row, forms
-// their soil codes and the up to 18 table values exactly as the all-tables strip kernel does (one 16-byte LDS row
-// per pixel and drainage condition, 4x4 byte transposes), and XORs them with the 16 bytes of each selected file
+// their soil codes and the up to 18 table values with the all-tables strip kernel's own gather -- gcn10::gather16 of
+// gcn10_soil_readers.hpp over the same LDS image, which finish_trip of gcn10_gpu.hip calls too (one 16-byte LDS row
+// per pixel and drainage condition, 4x4 byte transposes) -- and XORs them with the 16 bytes of each selected file
 // raster.  The kernel only loads: 19 bytes per pixel with all rasters selected, all of a lane's loads issued before
 // the first is used.  The expected rasters never exist in memory.
 //
@@ -24,6 +25,7 @@
 #include <cstring>
 
 #include "gcn10_gpu_internal.hpp"
+#include "gcn10_soil_readers.hpp"
 
 using namespace gcn10;
 
@@ -36,15 +38,13 @@ constexpr int kGridPerCu = 4;
 
 struct VerifyParams {
     const uint8_t *esa;                     // strip, W x rows, row major                 (strip form)
-    const uint8_t *hx;                      // x-expanded soil codes                      (strip form)
-    const int32_t *cj;                      // soil row of every strip row                (strip form)
+    SoilView soil;                          // x-expanded soil codes, soil row of every strip row (strip form)
     const uint8_t *lut;                     // device image of the 16-byte-row table      (strip form)
     const uint8_t *want[GCN10_N_RASTERS];   // expected rasters                           (buffer form)
     const uint8_t *got[GCN10_N_RASTERS];
     gcn10_verify_count *counts;
     uint64_t want_stride, got_stride;
     uint32_t W, rows, y0;
-    uint32_t hx_stride, hx_rows;
     uint32_t groups_per_row;                // W / 16
     uint32_t n_groups;                      // rows * groups_per_row
     uint32_t sel;                           // bit r: raster r is compared
@@ -61,28 +61,6 @@ __device__ __forceinline__ u32x4 load16(const uint8_t *p)
 __device__ __forceinline__ u32x4 load16_once(const uint8_t *p)
 {
     return __builtin_nontemporal_load(reinterpret_cast<const u32x4_u *>(p));
-}
-
-__device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel)
-{
-    return __builtin_amdgcn_perm(hi, lo, sel);
-}
-
-// 4x4 byte transpose: a..d = one dword (4 table values) of pixels 0..3 -> o[k] = value k of the four pixels
-__device__ __forceinline__ void transpose4x4(uint32_t a, uint32_t b, uint32_t c, uint32_t d, uint32_t &o0,
-                                             uint32_t &o1, uint32_t &o2, uint32_t &o3)
-{
-    const uint32_t t0 = perm(b, a, 0x05010400u), t1 = perm(b, a, 0x07030602u);
-    const uint32_t t2 = perm(d, c, 0x05010400u), t3 = perm(d, c, 0x07030602u);
-    o0 = perm(t2, t0, 0x05040100u);
-    o1 = perm(t2, t0, 0x07060302u);
-    o2 = perm(t3, t1, 0x05040100u);
-    o3 = perm(t3, t1, 0x07060302u);
-}
-
-__device__ __forceinline__ uint32_t gather_byte0(uint32_t a, uint32_t b, uint32_t c, uint32_t d)
-{
-    return perm(b, a, 0x0c0c0400u) | perm(d, c, 0x04000c0cu);
 }
 
 // 0x80 in every byte of d that is not zero
@@ -140,32 +118,6 @@ __device__ __forceinline__ void tally_wave(Tally &t, int r, const uint32_t d[4],
     }
 }
 
-// the table values of a lane's 16 pixels for one drainage condition: acc[k][j] = table k, pixels 4j .. 4j+3
-template <int C>
-__device__ __forceinline__ void gather16(const uint8_t *lut, const u32x4 &e16, const u32x4 &c16, uint32_t acc[9][4])
-{
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const uint32_t e = e16[j], cd = c16[j];
-        u32x4 r4[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t lc16 = q == 0 ? (e << 4) & 0xff0u : (e >> (8 * q - 4)) & 0xff0u;
-            const uint32_t s = (cd >> (8 * q + 4 * C)) & 0xfu;
-            r4[q] = *reinterpret_cast<const u32x4 *>(lut + s * (uint32_t)kLut16Plane + lc16);
-        }
-        transpose4x4(r4[0][0], r4[1][0], r4[2][0], r4[3][0], acc[0][j], acc[1][j], acc[2][j], acc[3][j]);
-        transpose4x4(r4[0][1], r4[1][1], r4[2][1], r4[3][1], acc[4][j], acc[5][j], acc[6][j], acc[7][j]);
-        acc[8][j] = gather_byte0(r4[0][2], r4[1][2], r4[2][2], r4[3][2]);
-    }
-}
-
-__device__ __forceinline__ uint32_t soil_row(const VerifyParams &p, uint32_t y)
-{
-    const uint32_t r = (uint32_t)p.cj[y];
-    return r < p.hx_rows ? r : p.hx_rows - 1u;
-}
-
 template <int C, bool ALL>
 __device__ __forceinline__ void compare_cond(const VerifyParams &p, Tally &t, const uint8_t *lut, const u32x4 &e,
                                              const u32x4 &s, const u32x4 *g, bool live, uint32_t x, uint32_t y)
@@ -173,7 +125,7 @@ __device__ __forceinline__ void compare_cond(const VerifyParams &p, Tally &t, co
     if (!ALL && !((p.sel >> (9 * C)) & 0x1ffu))
         return;
     uint32_t acc[9][4];
-    gather16<C>(lut, e, s, acc);
+    gather16(lut, e, s, C, acc);
 #pragma unroll
     for (int k = 0; k < 9; k++) {
         const int r = C * 9 + k;
@@ -194,12 +146,7 @@ __global__ __launch_bounds__(kThreads) void verify_strip_kernel(const VerifyPara
 {
     __shared__ __attribute__((aligned(16))) uint8_t lut[kLut16Bytes];
     __shared__ Tally tally;
-    {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(p.lut);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(lut);
-        for (int i = threadIdx.x; i < kLut16Bytes / 16; i += kThreads)
-            dst[i] = src[i];
-    }
+    stage_lut16<kThreads>(lut, p.lut);
     tally_clear(tally);
 
     // the trip count is the same for every lane of the workgroup, so whole waves reach the votes and shuffles
@@ -211,7 +158,7 @@ __global__ __launch_bounds__(kThreads) void verify_strip_kernel(const VerifyPara
         const uint32_t y = gic / p.groups_per_row;
         const uint32_t x = (gic - y * p.groups_per_row) * kPxPerLane;
         const u32x4 e = load16(p.esa + (size_t)y * p.W + x);
-        const u32x4 s = *reinterpret_cast<const u32x4 *>(p.hx + (size_t)soil_row(p, y) * p.hx_stride + x);
+        const u32x4 s = *reinterpret_cast<const u32x4 *>(p.soil.ptr(y, x));
         u32x4 g[GCN10_N_RASTERS];
 #pragma unroll
         for (int r = 0; r < GCN10_N_RASTERS; r++)
@@ -228,12 +175,12 @@ __global__ __launch_bounds__(kThreads) void verify_strip_kernel(const VerifyPara
         const uint32_t y = i / tail;
         const uint32_t x = p.W - tail + (i - y * tail);
         const uint32_t lc = p.esa[(size_t)y * p.W + x];
-        const uint32_t cd = p.hx[(size_t)soil_row(p, y) * p.hx_stride + x];
+        const uint32_t cd = *p.soil.ptr(y, x);
         for (int r = 0; r < GCN10_N_RASTERS; r++) {
             if (!(p.sel & (1u << r)))
                 continue;
             const uint32_t plane = (cd >> (r >= 9 ? 4 : 0)) & 0xfu;
-            const uint32_t want = lut[plane * (uint32_t)kLut16Plane + lc * 16u + (uint32_t)(r % 9)];
+            const uint32_t want = lut16_value(lut, plane, lc, (uint32_t)(r % 9));
             if (want != p.got[r][(size_t)y * p.got_stride + x]) {
                 atomicAdd(&tally.count[r], 1ull);
                 atomicMin(&tally.first[r], ((unsigned long long)(p.y0 + y) << 32) | x);
@@ -313,9 +260,9 @@ __global__ void verify_first_kernel(const VerifyParams p)
     uint32_t want;
     if (FROM_TABLES) {
         const uint32_t lc = p.esa[(size_t)ys * p.W + x];
-        const uint32_t cd = p.hx[(size_t)soil_row(p, ys) * p.hx_stride + x];
+        const uint32_t cd = *p.soil.ptr(ys, (uint32_t)x);
         const uint32_t plane = (cd >> (r >= 9 ? 4 : 0)) & 0xfu;
-        want = p.lut[plane * (uint32_t)kLut16Plane + lc * 16u + r % 9u];
+        want = lut16_value(p.lut, plane, lc, r % 9u);
     }
     else {
         want = p.want[r][(size_t)ys * p.want_stride + x];
@@ -329,7 +276,7 @@ uint32_t grid_for(const gcn10_gpu_ctx *ctx, const VerifyParams &p)
     const uint32_t trips = (p.n_groups + kThreads - 1u) / kThreads;
     const uint32_t tail = (p.W - p.groups_per_row * kPxPerLane) * p.rows;
     const uint32_t want = trips > (tail + kThreads - 1u) / kThreads ? trips : (tail + kThreads - 1u) / kThreads;
-    const uint32_t cap = (uint32_t)(ctx->n_cus > 0 ? ctx->n_cus : 256) * kGridPerCu;
+    const uint32_t cap = grid_cap(ctx, kGridPerCu);
     return want < cap ? (want ? want : 1u) : cap;
 }
 
@@ -359,44 +306,29 @@ int gcn10_gpu_verify_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int ro
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    if (!ctx->d_lut16 || ctx->n_tables == 0)
-        return fail(GCN10_E_STATE, "gcn10_gpu_verify_strip: call gcn10_gpu_set_tables first");
-    if (!ctx->d_hx || (int)ctx->hx_W != W)
-        return fail(GCN10_E_STATE, "gcn10_gpu_verify_strip: prepare the block's tile (W=%d) first", W);
-    if (cond_mask == 0 || (cond_mask & ~3u))
-        return fail(GCN10_E_INVAL, "gcn10_gpu_verify_strip: cond_mask 0x%x", cond_mask);
-    if (table_mask == 0 || (table_mask >> ctx->n_tables))
-        return fail(GCN10_E_INVAL, "gcn10_gpu_verify_strip: table_mask 0x%x with %d tables loaded", table_mask,
-                    ctx->n_tables);
+    const char *const who = "gcn10_gpu_verify_strip";
+    hipStream_t s = as_stream(ctx, stream);
     VerifyParams p;
     memset(&p, 0, sizeof p);
-    rc = fill_shape(p, "gcn10_gpu_verify_strip", W, rows, y0, got_stride);
-    if (rc)
+    if ((rc = check_tables(ctx, who)) != GCN10_OK || (rc = bind_soil(ctx, who, W, s, cj, &p.soil)) != GCN10_OK ||
+        (rc = check_masks(ctx, who, cond_mask, table_mask)) != GCN10_OK ||
+        (rc = fill_shape(p, who, W, rows, y0, got_stride)) != GCN10_OK)
         return rc;
     if (rows == 0)
         return GCN10_OK;
     if (!esa || !cj || !got || !counts_dev)
         return fail(GCN10_E_INVAL, "gcn10_gpu_verify_strip: null pointer");
-    for (int c = 0; c < GCN10_N_CONDS; c++) {
-        for (int k = 0; k < GCN10_N_TABLES; k++) {
-            const int r = c * GCN10_N_TABLES + k;
-            if (!(cond_mask & (1u << c)) || !(table_mask & (1u << k)))
-                continue;
-            if (!got[r])
-                return fail(GCN10_E_INVAL, "gcn10_gpu_verify_strip: got[%d] is null but selected", r);
-            p.got[r] = got[r];
-            p.sel |= 1u << r;
-        }
+    for (int r = 0; r < GCN10_N_RASTERS; r++) {
+        if (!selected(r, cond_mask, table_mask))
+            continue;
+        if (!got[r])
+            return fail(GCN10_E_INVAL, "gcn10_gpu_verify_strip: got[%d] is null but selected", r);
+        p.got[r] = got[r];
+        p.sel |= 1u << r;
     }
     p.esa = esa;
-    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &p.hx)) != GCN10_OK)     // made on first use
-        return rc;
-    p.cj = cj;
     p.lut = ctx->d_lut16;
     p.counts = counts_dev;
-    p.hx_stride = ctx->hx_stride;
-    p.hx_rows = ctx->hx_rows;
-    hipStream_t s = as_stream(ctx, stream);
     if (p.sel == (1u << GCN10_N_RASTERS) - 1u)
         hipLaunchKernelGGL(verify_strip_kernel<true>, dim3(grid_for(ctx, p)), dim3(kThreads), 0, s, p);
     else

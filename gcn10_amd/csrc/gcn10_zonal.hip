@@ -19,6 +19,7 @@
 
 #include "gcn10_gpu_internal.hpp"
 #include "gcn10_pair_hist.hpp"
+#include "gcn10_soil_readers.hpp"
 
 using namespace gcn10;
 using namespace gcn10::pair_hist;
@@ -33,12 +34,11 @@ constexpr uint32_t kWaves = kThreads / 64;
 
 struct ZonalParams {
     const uint8_t *esa;             // strip, W x rows, row major
-    const uint8_t *hx;              // x-expanded soil codes, hx_rows rows of hx_stride bytes
-    const int32_t *cj;              // soil row of every strip row
+    SoilView soil;                  // x-expanded soil codes, soil row of every strip row
     const gcn10_zone_span *spans;
     const gcn10_zone_item *items;
     unsigned long long *hist;       // [n_zones][kHistWords]
-    uint32_t W, hx_stride, hx_rows, n_items, items_per_wg;
+    uint32_t W, n_items, items_per_wg;
 };
 
 // pixels [a, b) of a lane's 16: the run folding of count16 over the unmasked ones
@@ -139,10 +139,8 @@ __global__ __launch_bounds__(kThreads) void zonal_pair_histogram_kernel(const Zo
                 const uint32_t x0 = (uint32_t)sx0[lo], x1 = (uint32_t)sx1[lo], y = (uint32_t)sy[lo];
                 const uint32_t gx = ((x0 >> 4) + (q - pre[lo])) << 4;       // first column of the group
                 const uint32_t a = max(gx, x0), b = min(gx + kPxPerLane, x1);
-                uint32_t r = (uint32_t)p.cj[y];
-                r = r < p.hx_rows ? r : p.hx_rows - 1u;
                 const uint8_t *erow = p.esa + (size_t)y * p.W + gx;
-                const uint8_t *srow = p.hx + (size_t)r * p.hx_stride + gx;
+                const uint8_t *srow = p.soil.ptr(y, gx);
                 if (gx + kPxPerLane <= p.W) {
                     typedef u32x4 u32x4_u __attribute__((aligned(1)));
                     const u32x4 e = *reinterpret_cast<const u32x4_u *>(erow);
@@ -177,25 +175,20 @@ int gcn10_gpu_zonal_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W
         return rc;
     if (n_items == 0)
         return GCN10_OK;
-    if (!ctx->d_hx || (int)ctx->hx_W != W)
-        return fail(GCN10_E_STATE, "gcn10_gpu_zonal_pair_histogram: prepare the block's tile (W=%d) first", W);
+    ZonalParams p = {};
+    if ((rc = bind_soil(ctx, "gcn10_gpu_zonal_pair_histogram", W, as_stream(ctx, stream), cj, &p.soil)) != GCN10_OK)
+        return rc;
     if (!esa || !cj || !spans_dev || !items_dev || !hist_dev || W <= 0 || rows <= 0 || n_zones <= 0 ||
         n_items > 0xffffffffu)
         return fail(GCN10_E_INVAL, "gcn10_gpu_zonal_pair_histogram: bad arguments W=%d rows=%d zones=%d items=%zu", W,
                     rows, n_zones, n_items);
-    ZonalParams p = {};
     p.esa = esa;
-    if ((rc = gcn10::soil_bytes(ctx, gcn10::as_stream(ctx, stream), &p.hx)) != GCN10_OK)     // made on first use
-        return rc;
-    p.cj = cj;
     p.spans = spans_dev;
     p.items = items_dev;
     p.hist = hist_dev;
     p.W = (uint32_t)W;
-    p.hx_stride = ctx->hx_stride;
-    p.hx_rows = ctx->hx_rows;
     p.n_items = (uint32_t)n_items;
-    const uint64_t cap = (uint64_t)(ctx->n_cus > 0 ? ctx->n_cus : 256) * kZonalGridPerCu;
+    const uint64_t cap = grid_cap(ctx, kZonalGridPerCu);
     const uint32_t grid = (uint32_t)(n_items < cap ? n_items : cap);
     p.items_per_wg = (p.n_items + grid - 1u) / grid;
     hipLaunchKernelGGL(zonal_pair_histogram_kernel, dim3(grid), dim3(kThreads), 0, as_stream(ctx, stream), p);

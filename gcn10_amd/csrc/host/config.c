@@ -147,6 +147,23 @@ int gcn10_parse_zonal(const char *text, int *zonal)
     return gcn10_parse_cog(text, zonal);       /* the same "0" | "1" */
 }
 
+int gcn10_parse_aggregate(const char *text, int *factor)
+{
+    int v = 0;
+
+    if (!text || !*text)
+        return -1;
+    for (const char *c = text; *c; c++) {
+        if (*c < '0' || *c > '9' || c - text >= 3)
+            return -1;
+        v = v * 10 + (*c - '0');
+    }
+    if (v != 0 && (v < 2 || v > 256))
+        return -1;
+    *factor = v;
+    return 0;
+}
+
 int gcn10_parse_nodata(const char *text, int *nodata)
 {
     int v = 0;
@@ -283,6 +300,12 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
         else if (!strcmp(key, "zonal") && gcn10_parse_zonal(val, &cfg->zonal) != 0) {
             fclose(f);
             snprintf(err, errcap, "bad value for zonal: '%s' (0 or 1)", val);
+            gcn10_config_free(cfg);
+            return -3;
+        }
+        else if (!strcmp(key, "aggregate") && gcn10_parse_aggregate(val, &cfg->aggregate) != 0) {
+            fclose(f);
+            snprintf(err, errcap, "bad value for aggregate: '%s' (0 or an integer 2..256)", val);
             gcn10_config_free(cfg);
             return -3;
         }

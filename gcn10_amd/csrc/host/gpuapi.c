@@ -96,6 +96,8 @@ static void load_once(void)
     *(void **)(&g_api.verify_buffers) = dlsym(h, "gcn10_gpu_verify_buffers");
     /* the pair histogram per zone: needed by zonal=1 runs only, which check for it */
     *(void **)(&g_api.zonal_pair_histogram) = dlsym(h, "gcn10_gpu_zonal_pair_histogram");
+    /* the area means on a coarser grid: needed by aggregate=<f> runs only, which check for it */
+    *(void **)(&g_api.aggregate) = dlsym(h, "gcn10_gpu_aggregate");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -85,6 +85,10 @@ void gcn10_read_plan_free(struct gcn10_read_plan *plan);
 void gcn10_raster_histogram_sparse(const uint16_t *at, const uint64_t *n, size_t m, const uint8_t codes[16],
                                    const int table[256][5], int drained, uint64_t hist[256]);
 
+/* zones.c: the ownership rule of gcn10_zones_build_plan alone -- the pixels [*x0, *x1) x [*y0, *y1) of a north-up
+ * W x H block whose centres lie in own = {minx, miny, maxx, maxy}: own[0] <= px < own[2], own[1] < py <= own[3] */
+void gcn10_owned_window(const double gt[6], int W, int H, const double own[4], int *x0, int *x1, int *y0, int *y1);
+
 /* gpuapi.c: include/gcn10_gpu.h bound with dlopen */
 struct gcn10_gpu_api {
     bool loaded;
@@ -147,6 +151,9 @@ struct gcn10_gpu_api {
     /* optional: NULL when the library has none (needed by zonal=1 only) */
     int (*zonal_pair_histogram)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const gcn10_zone_span *,
                                 const gcn10_zone_item *, size_t, int, unsigned long long *, gcn10_stream_t);
+    /* optional: NULL when the library has none (needed by aggregate=<f> only) */
+    int (*aggregate)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, int, int, int, unsigned, unsigned,
+                     uint8_t *const *, size_t, gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -7,7 +7,7 @@
  * --conditions to produce a subset of the 18 rasters (BASELINE config 3: "single lookup"), and --compress to
  * write LZW instead of DEFLATE GeoTIFFs, --stats / --nodata for GDAL band statistics and a NoData tag, and --verify
  * to check the rasters a run has written instead of writing them, and --zonal / --zones for the composite curve
- * numbers of the polygons of a shapefile instead of rasters.
+ * numbers of the polygons of a shapefile instead of rasters, and --aggregate for area-mean rasters on a coarser grid.
  * No mpirun: one process drives every GPU of the node.
  */
 #include "gcn10_host.h"
@@ -24,7 +24,7 @@ static void usage(FILE *fp)
             "  gcn10 --config <config.txt> [--blocks <blocks.txt>] [--overwrite] [--gpus <n>]\n"
             "        [--lookups <names>] [--conditions drained|undrained|both] [--compress deflate|lzw]\n"
             "        [--cog] [--overview-resampling nearest|average] [--stats] [--nodata none|<0..255>]\n"
-            "        [--verify] [--zonal] [--zones <zones.shp>]\n"
+            "        [--verify] [--zonal] [--zones <zones.shp>] [--aggregate <f>]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -47,6 +47,9 @@ static void usage(FILE *fp)
             "\t\t\traster, counted on the GPU (config key zonal=1); not with --overwrite or --verify\n"
             "  --zones <file.shp>\tthe zone polygons, in the landcover's CRS (config key zones_shp_path; the zone id\n"
             "\t\t\tis the numeric field zones_id_field, default ID); implies --zonal\n"
+            "  --aggregate <f>\twrite no 10 m raster but, under cn_rasters_<cond>_x<f>/, the mean of every selected\n"
+            "\t\t\traster over cells of f x f landcover pixels (f = 2..256), reduced on the GPU (config key\n"
+            "\t\t\taggregate=<f>); not with --verify or --zonal\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -97,6 +100,8 @@ int main(int argc, char **argv)
             opt.nodata = argv[++i];
         else if (!strcmp(argv[i], "--verify"))
             opt.verify = true;
+        else if (!strcmp(argv[i], "--aggregate") && i + 1 < argc)
+            opt.aggregate = argv[++i];
         else if (!strcmp(argv[i], "--zonal"))
             opt.zonal = true;
         else if (!strcmp(argv[i], "--zones") && i + 1 < argc) {

@@ -416,7 +416,7 @@ static int ensure_strip_buffers(struct worker *w, int W)
                 GPU_OR_RETURN(w, -1, g->host_alloc(w->ctx, px, (void **)&b->h_out[k]));
                 atomic_fetch_add(&w->run->pinned_bytes, (long long)px);
             }
-            if (!w->fused)
+            if (!w->fused && !w->run->aggregate)        /* (an aggregate run makes no full-resolution strip) */
                 GPU_OR_RETURN(w, -1, g->malloc(w->ctx, px, (void **)&b->d_out[k]));
         }
         if (w->run->gpu_deflate) {
@@ -439,7 +439,7 @@ static int ensure_strip_buffers(struct worker *w, int W)
             GPU_OR_RETURN(w, -1, g->host_alloc(w->ctx, tiles * GCN10_N_RASTERS * 8, (void **)&b->h_table));
             GPU_OR_RETURN(w, -1, g->malloc(w->ctx, 8, (void **)&b->d_cursor));
             GPU_OR_RETURN(w, -1, g->host_alloc(w->ctx, 8, (void **)&b->h_cursor));
-            if (!w->fused) {
+            if (!w->fused && !w->run->aggregate) {
                 /* the per-raster encoder takes the selected strips, packed in raster order */
                 uint8_t *packed[GCN10_N_RASTERS] = { 0 };
 
@@ -495,16 +495,16 @@ int gcn10_ensure_dev_on(struct worker *w, gcn10_gpu_ctx *ctx, void **p, size_t *
 
 /* output path with the reference's non-overwrite rule: an existing file is left
  * alone and the new one gets a trailing underscore (src/cn.c:320-360) */
-static void output_path(char *out, size_t cap, const char *cond, const char *hc, const char *arc,
+static void output_path(char *out, size_t cap, const char *cond, const char *suffix, const char *hc, const char *arc,
                         int block_id, bool overwrite)
 {
-    snprintf(out, cap, "cn_rasters_%s/cn_%s_%s_%d.tif", cond, hc, arc, block_id);  /* src/cn.c:308 */
+    snprintf(out, cap, "cn_rasters_%s%s/cn_%s_%s_%d.tif", cond, suffix, hc, arc, block_id);  /* src/cn.c:308 */
     if (!overwrite) {
         FILE *f = fopen(out, "r");
 
         if (f) {
             fclose(f);
-            snprintf(out, cap, "cn_rasters_%s/cn_%s_%s_%d_.tif", cond, hc, arc, block_id); /* :341 */
+            snprintf(out, cap, "cn_rasters_%s%s/cn_%s_%s_%d_.tif", cond, suffix, hc, arc, block_id); /* :341 */
         }
     }
 }
@@ -524,7 +524,13 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
     struct run *r = w->run;
     char err[1024] = "";
     double t_mark = now_seconds();
+    /* an aggregate run: the block's grid of cells instead of its window, under cn_rasters_<cond>_x<f> */
+    const int OW = r->aggregate ? in->agg.Wa : in->W, OH = r->aggregate ? in->agg.Ha : in->H;
+    const double *ogt = r->aggregate ? in->agg.gt : in->gt;
+    char suffix[16] = "";
 
+    if (r->aggregate)
+        snprintf(suffix, sizeof suffix, "_x%d", r->aggregate);
     memset(in->tifs, 0, sizeof in->tifs);
     in->tifs_ok = false;
     if (r->null_sink) {
@@ -536,7 +542,7 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
 
         if (!(r->cond_mask & (1u << c)))
             continue;
-        snprintf(dir, sizeof dir, "cn_rasters_%s", gcn10_conds[c]);
+        snprintf(dir, sizeof dir, "cn_rasters_%s%s", gcn10_conds[c], suffix);
         if (mkdir(dir, 0755) != 0 && errno != EEXIST) {
             wlog(w, "ERROR", true, "failed to create output directory %s", dir);       /* src/cn.c:250 */
             return -1;
@@ -546,13 +552,13 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
         const int k = r->sel[q];
         char path[PATH_MAX];
 
-        output_path(path, sizeof path, gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3],
+        output_path(path, sizeof path, gcn10_conds[k / 9], suffix, gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3],
                     in->block_id, r->opt.overwrite);
         if (r->cog)
             in->tifs[k] = gcn10_tiff_create_cog(path, in->W, in->H, in->gt, gcn10_raster_georef(w->esa),
                                                 cog_levels_of(in->W, in->H), err, sizeof err);
         else
-            in->tifs[k] = gcn10_tiff_create(path, in->W, in->H, in->gt, gcn10_raster_georef(w->esa), err, sizeof err);
+            in->tifs[k] = gcn10_tiff_create(path, OW, OH, ogt, gcn10_raster_georef(w->esa), err, sizeof err);
         if (!in->tifs[k]) {
             wlog(w, "ERROR", true, "%s", err);          /* save_raster logs and goes on, src/raster.c:220-223 */
             gcn10_abort_outputs(in);
@@ -589,13 +595,13 @@ void gcn10_abort_outputs(struct block_in *in)
 
 /* The strips of one raster (a block, or a level of its overviews) through the encoder and the sink.  d_block / d_cj:
  * its landcover and soil rows, for the prepared tile of width W.  premade (device, [strip][GCN10_N_RASTERS]): the
- * selected rasters are already made (average overviews), strip s's n_sel pointers at premade + s * GCN10_N_RASTERS,
- * and only the per-raster encoder runs.  hist (device, stats=1, the block's own strips only): every strip's
+ * selected rasters are already made (average overviews, aggregated rasters), strip s's n_sel pointers at
+ * premade + s * GCN10_N_RASTERS, and only the per-raster encoder runs.  hist (device, stats=1, the block's own strips only): every strip's
  * (landcover, soil code) pairs are added to it, behind the strip's encoder on the same stream.  Every strip has been
  * handed to the sink, and the sink is done, on return.  0, or -1 (logged) for errors the reference answers with
  * MPI_Abort. */
-static int run_strips(struct worker *w, int W, int H, const uint8_t *d_block, const int32_t *d_cj,
-                      const uint8_t *const *premade, unsigned long long *hist, gcn10_tiff_writer *tifs[GCN10_N_RASTERS])
+int gcn10_run_strips(struct worker *w, int W, int H, const uint8_t *d_block, const int32_t *d_cj,
+                     const uint8_t *const *premade, unsigned long long *hist, gcn10_tiff_writer *tifs[GCN10_N_RASTERS])
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
@@ -720,7 +726,7 @@ static int encode_overviews(struct worker *w, struct block_in *in, gcn10_tiff_wr
                 return -1;
             for (int q = 0; q < GCN10_N_RASTERS; q++)
                 lv[q] = tifs[q] ? gcn10_tiff_level(tifs[q], k) : NULL;
-            if (run_strips(w, Wk, Hk, w->d_ov, d_cj, NULL, NULL, lv) != 0)
+            if (gcn10_run_strips(w, Wk, Hk, w->d_ov, d_cj, NULL, NULL, lv) != 0)
                 return -1;
             /* the next level overwrites the index maps and the level's landcover: this one's kernels are done */
             GPU_OR_RETURN(w, -1, g->stream_sync(w->ctx, w->s_kernel));
@@ -761,7 +767,7 @@ static int encode_overviews(struct worker *w, struct block_in *in, gcn10_tiff_wr
             free(tab);
             for (int q = 0; q < GCN10_N_RASTERS; q++)
                 lv[q] = tifs[q] ? gcn10_tiff_level(tifs[q], k) : NULL;
-            if (run_strips(w, Wk, Hk, NULL, NULL, (const uint8_t *const *)w->d_ov_ptrs, NULL, lv) != 0)
+            if (gcn10_run_strips(w, Wk, Hk, NULL, NULL, (const uint8_t *const *)w->d_ov_ptrs, NULL, lv) != 0)
                 return -1;
             GPU_OR_RETURN(w, -1, g->stream_sync(w->ctx, w->s_kernel));    /* the pointer table is rewritten next */
         }
@@ -801,7 +807,7 @@ static int encode_block(struct worker *w, struct block_in *in)
 
     /* device side of the block: the encoder waits (on the device) for the input side's copies and kernels */
     w->strip_rows = r->strip_rows;
-    if (ensure_strip_buffers(w, W) != 0) {
+    if (ensure_strip_buffers(w, r->aggregate ? in->agg.Wa : W) != 0) {
         rc = -1;
         goto out;
     }
@@ -841,7 +847,8 @@ static int encode_block(struct worker *w, struct block_in *in)
     }
     if (r->stats && g->memset(w->ctx, w->d_hist, 0, GCN10_PAIR_HIST_SIZE * sizeof *w->d_hist, w->s_kernel) != 0)
         goto gpu_fail;
-    if (run_strips(w, W, H, in->d_block, in->d_cj, NULL, r->stats ? w->d_hist : NULL, tifs) != 0) {
+    if ((r->aggregate ? gcn10_aggregate_block(w, in, tifs)
+                      : gcn10_run_strips(w, W, H, in->d_block, in->d_cj, NULL, r->stats ? w->d_hist : NULL, tifs)) != 0) {
         rc = -1;
         goto out;
     }
@@ -1467,6 +1474,21 @@ int gcn10_run(const gcn10_run_options *opt)
             return 1;
         }
     }
+    /* an aggregate run: the factor, and the refused combinations, before any GPU is opened */
+    if (opt->aggregate && gcn10_parse_aggregate(opt->aggregate, &r->cfg.aggregate) != 0) {
+        fprintf(stderr, "[rank 0] bad value for aggregate: '%s' (0 or an integer 2..256)\n", opt->aggregate);
+        gcn10_zonal_end(r);
+        gcn10_config_free(&r->cfg);
+        free(r);
+        return 1;
+    }
+    r->aggregate = r->cfg.aggregate;
+    if (r->aggregate && gcn10_aggregate_start(r) != 0) {
+        gcn10_zonal_end(r);
+        gcn10_config_free(&r->cfg);
+        free(r);
+        return 1;
+    }
     r->null_sink = sink && strcmp(sink, "null") == 0;
     /* Rows per strip.  Rounds 2 and 3 ran 768 rows (three tile rows of a 36000-px block = 423 tile positions, one round
      * of the fused statistics pass's 512 workgroup slots); larger strips lost end to end to the coarser hand-over between
@@ -1487,6 +1509,12 @@ int gcn10_run(const gcn10_run_options *opt)
     r->stats = r->cfg.stats != 0;
     r->nodata = r->cfg.nodata;
     r->fused = r->cfg.gpu_deflate == 2 && !r->lzw;     /* the fused encoder is DEFLATE-only */
+    if (r->aggregate) {
+        /* the aggregated rasters are made on the device and go through the per-raster GPU encoder, whatever
+         * "gpu_deflate" says; they carry neither overviews nor statistics */
+        r->gpu_deflate = true;
+        r->cog = r->stats = false;
+    }
     r->gpu_inflate = r->cfg.gpu_inflate != 0;
     r->direct_io = r->cfg.direct_io != 0 || (getenv("GCN10_DIRECT_IO") && atoi(getenv("GCN10_DIRECT_IO")) != 0);
     r->prefetch = r->cfg.prefetch_blocks != 0 && !(getenv("GCN10_PREFETCH_BLOCKS") && atoi(getenv("GCN10_PREFETCH_BLOCKS")) == 0);
@@ -1523,6 +1551,11 @@ int gcn10_run(const gcn10_run_options *opt)
     if (r->zonal && (!r->gpu->zonal_pair_histogram || !r->gpu->pair_histogram_codes ||
                      r->gpu->pair_histogram_codes(r->hist_codes) != GCN10_PAIR_HIST_BINS)) {
         fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_zonal_pair_histogram (needed by zonal=1)\n", gcn10_gpu_library_path());
+        goto done;
+    }
+    if (r->aggregate && !r->gpu->aggregate) {
+        fprintf(stderr, "[rank 0] %s lacks gcn10_gpu_aggregate (needed by aggregate=%d)\n", gcn10_gpu_library_path(),
+                r->aggregate);
         goto done;
     }
     if (r->verify && (!r->gpu->verify_strip || !r->gpu->verify_buffers)) {
@@ -1734,6 +1767,8 @@ int gcn10_run(const gcn10_run_options *opt)
         closing_barrier(r, log0);           /* MPI_Barrier + rank 0's summary, src/main.c:187-194 */
     if (r->verify)
         verify_found = verify_summary(r, log0);
+    if (r->aggregate)
+        gcn10_aggregate_finish(r, log0);
     if (r->zonal) {
         double plan = 0, accum = 0;
         int done_blocks = 0;

@@ -275,6 +275,11 @@ static int fill_block(struct worker *w, struct block_in *in, int block_id)
         }
         return 0;
     }
+    if (r->aggregate && gcn10_aggregate_plan_block(w, in, r->blocks.bbox[bi]) != 0) {
+        g->stream_sync(w->in_ctx, w->s_in);
+        gcn10_stager_idle(&w->ring);
+        return 1;
+    }
     rc = gcn10_create_outputs(w, in);
     if (rc < 0)
         return -1;

@@ -1,5 +1,5 @@
 /* pipeline_internal.h -- the worker and run state shared by pipeline.c (block queue, strips,
- * sink), pipeline_input.c (landcover input through the GPU decoder), verify.c and zonal.c, and what the
+ * sink), pipeline_input.c (landcover input through the GPU decoder), verify.c, zonal.c and aggregate.c, and what the
  * writer and the verifier have in common: the chunk stager (stage.c) and the overview levels (levels.c). */
 #ifndef GCN10_PIPELINE_INTERNAL_H
 #define GCN10_PIPELINE_INTERNAL_H
@@ -142,6 +142,7 @@ struct block_in {
     gcn10_tiff_writer *tifs[GCN10_N_RASTERS];
     bool tifs_ok;                           /* all of the run's rasters have their file */
     gcn10_zone_plan zplan;                  /* zonal=1: the zones' spans and items over this block (zones.c) */
+    gcn10_aggregate_geom agg;               /* aggregate=<f>: the block's owned pixels and its grid of cells (aggregate.c) */
 };
 
 struct worker {
@@ -255,6 +256,8 @@ struct run {
     gcn10_zones zones;
     struct gcn10_zonal_table *zonal_table;
     atomic_int zonal_incomplete;            /* a block's inputs could not be read: the table lacks it, exit code 1 */
+    /* aggregate=<f>: no 10 m raster is written but every selected raster's area means over f x f pixels (aggregate.c) */
+    int aggregate;
 };
 
 double gcn10_now_seconds(void);
@@ -296,6 +299,19 @@ int gcn10_levels_average(struct worker *w, const struct block_in *in, int L, int
  * (logged like save_raster logs, the block is given up), -1 = an output directory cannot be made (fatal, src/cn.c:250) */
 int gcn10_create_outputs(struct worker *w, struct block_in *in);
 void gcn10_abort_outputs(struct block_in *in);
+/* pipeline.c: the strips of one W x H raster through the run's encoder and the sink (see there); aggregate.c hands it
+ * the aggregated rasters as `premade` ones */
+int gcn10_run_strips(struct worker *w, int W, int H, const uint8_t *d_block, const int32_t *d_cj,
+                     const uint8_t *const *premade, unsigned long long *hist, gcn10_tiff_writer *tifs[GCN10_N_RASTERS]);
+/* aggregate.c: the refused combinations (before any GPU is opened; 0, or -1 with a line on stderr); the grid of a
+ * staged block, made by the input side (0, or 1: logged, the block is given up); a staged block reduced into the
+ * worker's overview buffers and handed to the encoder and the sink (0, or -1 for errors that end the run); the closing
+ * console line.  The worker's buffers are those of the overview phase, which an aggregate run does not have, so there
+ * is nothing of its own to tear down. */
+int gcn10_aggregate_start(struct run *r);
+int gcn10_aggregate_plan_block(struct worker *w, struct block_in *in, const double own[4]);
+int gcn10_aggregate_block(struct worker *w, struct block_in *in, gcn10_tiff_writer *tifs[GCN10_N_RASTERS]);
+void gcn10_aggregate_finish(struct run *r, gcn10_log *log0);
 /* verify.c: a staged block's files against the values computed now (0, or -1 for errors that end the run); a block
  * whose inputs could not be staged; the worker's verify buffers */
 int gcn10_verify_block(struct worker *w, struct block_in *in);

@@ -580,6 +580,17 @@ NO_CONTRACT static int scan_zone(const gcn10_zones *z, int zi, const double gt[6
     return 0;
 }
 
+/* the owned pixel rectangle [*x0, *x1) x [*y0, *y1) of a W x H block: centres with own[0] <= px < own[2] and
+ * own[1] < py <= own[3] (north up, checked by the callers) */
+NO_CONTRACT void gcn10_owned_window(const double gt[6], int W, int H, const double own[4], int *x0, int *x1, int *y0,
+                                    int *y1)
+{
+    *x0 = first_index(gt[0], gt[1], 0, W, own[0], GE);
+    *x1 = first_index(gt[0], gt[1], 0, W, own[2], GE);
+    *y0 = first_index(gt[3], gt[5], 0, H, own[3], LE);
+    *y1 = first_index(gt[3], gt[5], 0, H, own[1], LE);
+}
+
 NO_CONTRACT int gcn10_zones_build_plan(const gcn10_zones *z, const double gt[6], int W, int H, const double own[4],
                                        uint32_t max_span_px, uint32_t max_item_px, gcn10_zone_plan *out, char *err,
                                        size_t errcap)
@@ -598,11 +609,8 @@ NO_CONTRACT int gcn10_zones_build_plan(const gcn10_zones *z, const double gt[6],
     }
     bounds_of(&max_span_px, &max_item_px);
     if (own) {
-        /* own[0] <= px < own[2] and own[1] < py <= own[3] */
-        ox0 = first_index(gt[0], gt[1], 0, W, own[0], GE);
-        ox1 = first_index(gt[0], gt[1], 0, W, own[2], GE);
-        oy0 = first_index(gt[3], gt[5], 0, H, own[3], LE);
-        oy1 = first_index(gt[3], gt[5], 0, H, own[1], LE) - 1;
+        gcn10_owned_window(gt, W, H, own, &ox0, &ox1, &oy0, &oy1);
+        oy1--;
     }
     for (int zi = 0; zi < z->n && ox0 < ox1 && oy0 <= oy1; zi++) {
         const double *b = z->bbox[zi];

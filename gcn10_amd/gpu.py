@@ -46,6 +46,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_inflate_codecs", "gcn10_gpu_overview_nearest", "gcn10_gpu_overview_average",
     "gcn10_gpu_pair_histogram_codes", "gcn10_gpu_pair_histogram",
     "gcn10_gpu_verify_strip", "gcn10_gpu_verify_buffers", "gcn10_gpu_zonal_pair_histogram",
+    "gcn10_gpu_aggregate",
 )
 
 
@@ -142,6 +143,7 @@ def lib():
             "gcn10_gpu_verify_strip": (i, [vp, vp, i, i, vp, C.c_uint, C.c_uint, vp, sz, i, vp, vp]),
             "gcn10_gpu_verify_buffers": (i, [vp, vp, sz, vp, sz, i, i, i, C.c_uint, vp, vp]),
             "gcn10_gpu_zonal_pair_histogram": (i, [vp, vp, i, i, vp, vp, vp, sz, i, vp, vp]),
+            "gcn10_gpu_aggregate": (i, [vp, vp, i, i, vp, i, i, i, u, u, C.POINTER(vp), sz, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -426,6 +428,16 @@ class Engine:
         arr = (C.c_void_p * len(level_ptrs))(*[int(p) for p in level_ptrs])
         self._chk(lib().gcn10_gpu_overview_average(self._ctx, esa_ptr, W, H, y0, rows, cj_ptr, cond_mask, table_mask,
                                                    n_levels, arr, stream), "gcn10_gpu_overview_average")
+
+    def aggregate(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, x0: int, x1: int, factor: int, cond_mask: int,
+                  table_mask: int, out_ptrs: Sequence[int], out_stride: int, stream=None):
+        """Area means of the selected rasters over factor x factor pixels, columns [x0, x1) of a W x rows device strip
+        that starts at a cell-row boundary, with the soil of the last prepare_tile (gcn10_gpu_aggregate).  out_ptrs[q]:
+        device raster of the q-th selected raster, ceil(rows / factor) rows of ceil((x1 - x0) / factor) bytes,
+        out_stride bytes apart.  Asynchronous on `stream`."""
+        arr = (C.c_void_p * max(len(out_ptrs), 1))(*[int(p) if p else None for p in out_ptrs])
+        self._chk(lib().gcn10_gpu_aggregate(self._ctx, esa_ptr, W, rows, cj_ptr, x0, x1, factor, cond_mask, table_mask,
+                                            arr, out_stride, stream), "gcn10_gpu_aggregate")
 
     def zonal_pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans, items, n_zones: int,
                              hist_ptr: int, stream=None):

@@ -125,6 +125,8 @@ def lib():
         L.gcn10_zones_build_plan.restype = C.c_int
         L.gcn10_zone_plan_free.argtypes = [C.POINTER(ZonePlan)]
         L.gcn10_zone_plan_free.restype = None
+        L.gcn10_aggregate_geometry.argtypes = [C.c_int, C.c_int, _f64p, vp, C.c_int, C.POINTER(AggregateGeom)]
+        L.gcn10_aggregate_geometry.restype = C.c_int
         L.gcn10_zone_items_build.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(ZonePlan)]
         L.gcn10_zone_items_build.restype = C.c_int
         L.gcn10_tiff_abort.argtypes = [vp]
@@ -155,7 +157,7 @@ class ConfigFull(Config):
     field list is pinned by the tests of that change); fields appended to the C struct since then are appended here.
     ``Config`` ends on a multiple of 8 bytes, so the fields below lie where the C compiler puts them."""
     _fields_ = [("verify", C.c_int), ("zonal", C.c_int), ("zones_shp_path", C.c_char_p),
-                ("zones_id_field", C.c_char_p), ("zonal_output", C.c_char_p)]
+                ("zones_id_field", C.c_char_p), ("zonal_output", C.c_char_p), ("aggregate", C.c_int)]
 
 
 assert C.sizeof(Config) % 8 == 0
@@ -182,6 +184,12 @@ class ZonePlan(C.Structure):
     """``gcn10_zone_plan`` of include/gcn10_host.h."""
     _fields_ = [("n_local", C.c_int), ("local_zone", C.POINTER(C.c_int32)), ("local_pixels", C.POINTER(C.c_uint64)),
                 ("n_spans", C.c_size_t), ("n_items", C.c_size_t), ("spans", C.c_void_p), ("items", C.c_void_p)]
+
+
+class AggregateGeom(C.Structure):
+    """``gcn10_aggregate_geom`` of include/gcn10_host.h."""
+    _fields_ = [("x0", C.c_int), ("x1", C.c_int), ("y0", C.c_int), ("y1", C.c_int), ("Wa", C.c_int), ("Ha", C.c_int),
+                ("gt", C.c_double * 6)]
 
 
 # struct gcn10_zone_span / gcn10_zone_item (include/gcn10_host.h, include/gcn10_gpu.h)
@@ -275,6 +283,19 @@ def zone_items(spans, max_span_px: int = 0, max_item_px: int = 0):
         raise HostError("gcn10_zone_items_build: an empty span, or out of memory")
     out = _plan_out(plan)
     return out["spans"], out["items"]
+
+
+def aggregate_geometry(W: int, H: int, gt, own, f: int) -> dict:
+    """The grid of f x f pixel cells over the owned pixels of a W x H block (``gcn10_aggregate_geometry``): x0, x1, y0,
+    y1, Wa, Ha and gt (float64[6]).  own: the block's box {minx, miny, maxx, maxy}, None = every pixel."""
+    geom = AggregateGeom()
+    o = None if own is None else _f(own, 4)
+    if lib().gcn10_aggregate_geometry(int(W), int(H), _f(gt, 6), None if o is None else o.ctypes.data, int(f),
+                                      C.byref(geom)) != 0:
+        raise HostError("gcn10_aggregate_geometry: factor outside 2..256, a block that is not north up, or no owned pixel")
+    out = {name: getattr(geom, name) for name in ("x0", "x1", "y0", "y1", "Wa", "Ha")}
+    out["gt"] = np.array(list(geom.gt), np.float64)
+    return out
 
 
 def parse_config(path: str) -> dict:

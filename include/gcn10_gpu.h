@@ -40,7 +40,8 @@ extern "C" {
  *    Added within 3: the LZW encoder (gcn10_gpu_lzw_*), LZW tiles of gcn10_gpu_inflate_tiles (GCN10_TILE_LZW)
  *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*); the pair histogram
  *    of the band statistics (gcn10_gpu_pair_histogram*); the raster verifier (gcn10_gpu_verify_*); the pair histogram
- *    per zone of the zonal composites (gcn10_gpu_zonal_pair_histogram).
+ *    per zone of the zonal composites (gcn10_gpu_zonal_pair_histogram); the area means on a coarser grid
+ *    (gcn10_gpu_aggregate).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -371,6 +372,24 @@ int gcn10_gpu_zonal_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W
                                    const gcn10_zone_span *spans_dev, const gcn10_zone_item *items_dev, size_t n_items,
                                    int n_zones, unsigned long long *hist_dev /* [n_zones][GCN10_PAIR_HIST_SIZE] */,
                                    gcn10_stream_t stream);
+
+/* Area-mean rasters on a coarser grid (config key aggregate=<f>).  Added in ABI 3 without a version change; the host
+ * looks it up for aggregate runs only.
+ *
+ * gcn10_gpu_aggregate: `esa`, W, rows, `cj` and the soil prepared by gcn10_gpu_prepare_tile are those of
+ *   gcn10_gpu_pair_histogram: `rows` landcover rows of width W, which must start at a cell-row boundary.  Cell
+ *   (cx, cy) covers columns x0 + cx f .. min(x0 + (cx + 1) f, x1) - 1 and rows cy f .. min((cy + 1) f, rows) - 1.
+ *   With v the value gcn10_gpu_cn_strip writes for a raster at a pixel, s the sum and n the count of the
+ *   footprint's v != 255, the cell is (2 s + n) / (2 n) in integers (round half up), 255 when n = 0.  out[q] is the
+ *   q-th selected raster in ascending raster order (host array of device pointers): ceil(rows / f) rows of
+ *   ceil((x1 - x0) / f) bytes, out_stride bytes apart; nothing else of out is written.  The call writes whole
+ *   output rows: a caller that cuts a block into bands gives every band but the last a multiple of f rows.  Calls
+ *   never add to each other's cells; the bytes do not depend on the launch shape.  Any W, any alignment of esa.
+ *   GCN10_E_INVAL: factor outside 2..256, x0 < 0, x0 >= x1, x1 > W, rows <= 0, out_stride < ceil((x1 - x0) / f), the
+ *   masks.  Asynchronous on `stream`. */
+int gcn10_gpu_aggregate(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                        int x0, int x1, int factor, unsigned cond_mask, unsigned table_mask,
+                        uint8_t *const *out, size_t out_stride, gcn10_stream_t stream);
 
 /* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
  * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.

@@ -132,6 +132,8 @@ typedef struct gcn10_config {
     char *zones_shp_path;   /* "zones_shp_path": polygon shapefile of the zones, in the landcover's CRS (needed by zonal=1) */
     char *zones_id_field;   /* "zones_id_field": numeric .dbf field that names a zone (absent = "ID") */
     char *zonal_output;     /* "zonal_output": the table's path, relative to the CWD as the rasters are (absent = zonal_cn.csv) */
+    int aggregate;          /* "aggregate": f = 2..256: no 10 m raster is written but the area mean of every selected raster
+                               over cells of f x f landcover pixels, reduced on the GPU (aggregate.c); 0 (default) = off */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -151,9 +153,11 @@ int gcn10_parse_stats(const char *text, int *stats);
 int gcn10_parse_nodata(const char *text, int *nodata);
 int gcn10_parse_verify(const char *text, int *verify);      /* "0" | "1".  0, or -1 for another value. */
 int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or -1 for another value. */
+/* "0" (off) | an integer 2..256 -> aggregate.  0, or -1 for another value. */
+int gcn10_parse_aggregate(const char *text, int *factor);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -385,6 +389,27 @@ int gcn10_zone_items_build(const gcn10_zone_span *spans, size_t n_spans, uint32_
                            gcn10_zone_plan *out);
 
 /* ------------------------------------------------------------------------ */
+/* aggregated rasters (config key "aggregate", --aggregate): no counterpart in the reference                */
+/* ------------------------------------------------------------------------ */
+
+/* The grid of f x f landcover pixels a block's aggregated rasters live on.  The block has W x H pixels and the clipped
+ * geotransform gt (gcn10_raster_window; north up, no rotation); own = its shapefile bounding box {minx, miny, maxx,
+ * maxy}, NULL = every pixel.  [x0, x1) x [y0, y1) is the owned pixel rectangle by the ownership rule of
+ * gcn10_zones_build_plan (pixel centres gt[0] + (x + 0.5) * gt[1], gt[3] + (y + 0.5) * gt[5] with own[0] <= px <
+ * own[2], own[1] < py <= own[3]); cell (cx, cy) covers columns x0 + cx f .. min(x0 + (cx + 1) f, x1) - 1 and rows
+ * likewise, so Wa = ceil((x1 - x0) / f), Ha = ceil((y1 - y0) / f), and no cell is shared between blocks.  The
+ * geotransform of the Wa x Ha raster, in IEEE double, this order, no FMA:
+ *   out_gt[0] = gt[0] + x0 * gt[1];  out_gt[3] = gt[3] + y0 * gt[5];  out_gt[1] = f * gt[1];  out_gt[5] = f * gt[5];
+ *   out_gt[2] = out_gt[4] = 0.
+ * 0; -1 for f outside 2..256, a block that is not north up, or one that owns no pixel. */
+typedef struct gcn10_aggregate_geom {
+    int x0, x1, y0, y1;
+    int Wa, Ha;
+    double gt[6];
+} gcn10_aggregate_geom;
+int gcn10_aggregate_geometry(int W, int H, const double gt[6], const double own[4], int f, gcn10_aggregate_geom *out);
+
+/* ------------------------------------------------------------------------ */
 /* the run: src/main.c:58-203 + process_block, src/cn.c:134-384              */
 /* ------------------------------------------------------------------------ */
 
@@ -403,6 +428,7 @@ typedef struct gcn10_run_options {
     bool verify;                /* --verify: check the rasters that exist instead of writing (sets the config key "verify") */
     bool zonal;                 /* --zonal: composite curve numbers per zone instead of rasters (sets the config key "zonal") */
     const char *zones;          /* --zones <file.shp>: overrides the config key "zones_shp_path" and implies --zonal */
+    const char *aggregate;      /* --aggregate <f>: overrides the config key "aggregate" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -436,7 +462,9 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * where the reference calls MPI_Abort(.., 1).  A verify run (opt->verify / "verify=1") writes no raster: 0 = every
  * selected raster of every block verified, 2 = it ran to its end and found a bad or missing file, 1 as above.  A zonal
  * run (opt->zonal / "zonal=1") writes no raster either, only its table: exit codes as for a write run, and 1 as well
- * when a block's inputs could not be read (the table is written, but lacks that block). */
+ * when a block's inputs could not be read (the table is written, but lacks that block).  An aggregate run
+ * (opt->aggregate / "aggregate=<f>") writes cn_rasters_<cond>_x<f>/ instead of the 10 m rasters: exit codes as for a
+ * write run. */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

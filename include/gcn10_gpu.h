@@ -168,9 +168,9 @@ int gcn10_gpu_calculate_cn(gcn10_gpu_ctx *ctx, const uint8_t *esa,
  * from the cell codes through the column map
  * (gcn10_gpu_soil_words_state).  Everything else that needs soil -- strips of
  * other widths or of unaligned rasters, strips with "compact_soil" off, the
- * fused encoder, verify, the pair histograms, the average overviews -- reads
- * one code byte per fine column and coarse row from a workspace (hsy rows of
- * W bytes) that is allocated here and filled from the tables by the first
+ * fused encoder, verify, the pair histograms, the average overviews, the
+ * area means of gcn10_gpu_aggregate -- reads one code byte per fine column
+ * and coarse row from a workspace (hsy rows of W bytes) that is allocated here and filled from the tables by the first
  * such call after prepare_tile, on that call's stream; a later reader on
  * another stream waits for that through an event of the context.  The order
  * the caller has to provide is the one below and no other: every reader's

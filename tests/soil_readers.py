@@ -2,7 +2,7 @@
 tests/test_soil_reader_references.py).
 
 A TILE is a landcover strip, a soil window and the two index maps (tests/test_gpu_soil_tables.Tile); tile_specs()
-names the ones of cases A to G.  A READER is one of the six paths that read the code bytes of the prepared tile:
+names the ones of cases A to G.  A READER is one of the seven paths that read the code bytes of the prepared tile:
 it allocates and uploads everything it needs when it is made, launch(stream) queues its work, and check() compares
 what came back with numpy and the oracle -- never with another GPU path.
 """
@@ -12,6 +12,7 @@ import zlib
 import numpy as np
 
 from gcn10_amd import gpu, host
+from tests import aggutil
 from tests.fullblock import average_levels
 from tests.test_gpu_soil_tables import K1, Tile, _with_complex_group, clamp_columns
 from tests.test_gpu_stats import model_histogram, soil_code
@@ -20,7 +21,7 @@ from tests.util import ESA_NASTY, HSG_NASTY
 GUARD = 256
 HIST = 16 * 256
 NONE = gpu.VERIFY_NONE
-READERS = ("strip", "verify", "histogram", "zonal", "overview", "fused")
+READERS = ("strip", "verify", "histogram", "zonal", "overview", "fused", "aggregate")
 SHIFTED = (3, 1, 4, 0)      # case G: byte offsets of esa, coarse, ci and cj in their buffers (ci: not 16-byte aligned)
 SHIFTED_MAPS = (0, 1, 4, 0)     # the same with the landcover aligned, so that strips may read the compact words
 _REFERENCES = {}            # spec id -> (rasters, soils) of the oracle, computed once and shared
@@ -132,6 +133,18 @@ def make_tile(eng, tables, name, offsets=None):
     return ReaderTile(eng, tables, key=name, offsets=offsets, **SPECS[name])
 
 
+class _NoDevice:
+    """In place of the engine where only the host side of a tile is wanted: nothing is uploaded."""
+
+    def upload(self, a):
+        return None
+
+
+def host_tile(tables, name):
+    """The tile `name` without a device: its inputs and the oracle's rasters, for the CPU checks of the references."""
+    return ReaderTile(_NoDevice(), tables, key=name, **SPECS[name])
+
+
 # ---- references ------------------------------------------------------------------------------------------------
 
 def pair_keys(esa, soil):
@@ -182,6 +195,43 @@ def strips_inside_a_soil_row(cj):
 
 def selected(cond_mask, table_mask):
     return [c * 9 + k for c in range(2) for k in range(9) if cond_mask >> c & 1 and table_mask >> k & 1]
+
+
+AGG_SMALL, AGG_WIDE = "aggregate_small_kernel", "aggregate_kernel"      # the kernels for f < 16 and f >= 16
+
+
+def aggregate_passes(W, cj):
+    """The passes of AggregateReader over a tile W wide whose rows have the soil rows cj: dicts of the factor f, the
+    columns [x0, x1), the masks, the strips [(y0, rows)] of one call each, and the kernel that runs them.
+
+      f = 3   all columns, all rasters, the two strips of strips_inside_a_soil_row: the kernel for f < 16
+      f = 16  all columns, all rasters, ONE ROW per call: a cell is 16 pixels of one row, so that every soil byte is
+              1/16 of a cell (an area mean over a whole tile hides a wrong byte; tests/test_soil_reader_references.py
+              counts what each pass lets through)
+      f = 25  a subset of the rasters in the two strips: the row walk across changing soil rows, with a first and
+              a last column inside a 16-pixel group: [1, W - 1), or [1, W - 2) where W - 1 is a multiple of 16
+
+    A strip's cells are reduced by themselves, whatever the factor: that a strip starts at a cell-row boundary is the
+    caller's convention, nothing gcn10_gpu_aggregate knows."""
+    two, by_row = strips_inside_a_soil_row(cj), [(y, 1) for y in range(len(cj))]
+    x0, x1 = (1, W - 1) if W >= 3 else (0, W)
+    if x1 % 16 == 0 and x1 - 1 > x0:
+        x1 -= 1
+    passes = [dict(f=3, x0=0, x1=W, masks=(3, 0x1FF), strips=two),
+              dict(f=16, x0=0, x1=W, masks=(3, 0x1FF), strips=by_row),
+              dict(f=25, x0=x0, x1=x1, masks=(2, 0x0A1), strips=two)]
+    for p in passes:
+        p["form"] = AGG_SMALL if p["f"] < 16 else AGG_WIDE
+        p["sel"] = selected(*p["masks"])
+        p["Wa"] = aggutil.cells(p["x1"] - p["x0"], p["f"])
+        p["cell_rows"] = [aggutil.cells(rows, p["f"]) for _y0, rows in p["strips"]]
+    return passes
+
+
+def reduce_strips(raster, x0, x1, f, strips):
+    """uint8[sum of the strips' cell rows][cells]: every strip reduced by itself (aggutil.reduce_raster), the cell
+    rows of a strip behind those of the strip before."""
+    return np.vstack([aggutil.reduce_raster(raster[y0:y0 + rows], x0, x1, f) for y0, rows in strips])
 
 
 # ---- the readers -----------------------------------------------------------------------------------------------
@@ -387,8 +437,54 @@ class FusedReader(Reader):
                             "fused %#x/%#x: raster %d tile (%d, %d)" % (cm, tm, r, ty, tx)
 
 
+class AggregateReader(Reader):
+    """gcn10_gpu_aggregate in the passes of aggregate_passes -- both kernels, every column in cells small enough to
+    show it -- into poisoned rasters: spare bytes behind every row of cells and a guard around every raster."""
+    name = "aggregate"
+    SPARE = 7
+
+    def __init__(self, tile):
+        super().__init__(tile)
+        self.passes = aggregate_passes(tile.W, tile.cj)
+        self.total = GUARD
+        for p in self.passes:
+            p["stride"], p["offs"] = p["Wa"] + self.SPARE, []
+            for _r in p["sel"]:
+                p["offs"].append(self.total)
+                self.total += sum(p["cell_rows"]) * p["stride"] + GUARD
+        self.out = self.alloc(self.total)
+
+    def launch(self, stream=None):
+        t = self.t
+        self.eng.memset(self.out.ptr, 0xA5, self.total, stream)
+        for p in self.passes:
+            cy = 0
+            for (y0, rows), n in zip(p["strips"], p["cell_rows"]):
+                ptrs = [self.out.at(o + cy * p["stride"]) for o in p["offs"]]
+                self.eng.aggregate(self.esa.at(y0 * t.W), t.W, rows, self.cj.at(4 * y0), p["x0"], p["x1"], p["f"],
+                                   p["masks"][0], p["masks"][1], ptrs, p["stride"], stream)
+                cy += n
+
+    def check(self):
+        t = self.t
+        got = self.eng.download(self.out.ptr, (self.total,))
+        poison = np.ones(self.total, bool)
+        for p in self.passes:
+            Ha, Wa, stride = sum(p["cell_rows"]), p["Wa"], p["stride"]
+            for o, r in zip(p["offs"], p["sel"]):
+                cells = got[o:o + Ha * stride].reshape(Ha, stride)[:, :Wa]
+                poison[o:o + Ha * stride].reshape(Ha, stride)[:, :Wa] = False
+                want = reduce_strips(t.want(r), p["x0"], p["x1"], p["f"], p["strips"])
+                bad = np.argwhere(cells != want).tolist()
+                at = tuple(bad[0]) if bad else None
+                assert not bad, "aggregate f=%d columns [%d, %d) in %d strips, raster %d: %d cells differ, first " \
+                    "(cell row, cell) = %s: got %d, want %d" % (p["f"], p["x0"], p["x1"], len(p["strips"]), r, len(bad),
+                                                                at, cells[at], want[at])
+        assert (got[poison] == 0xA5).all(), "aggregate: a byte outside the cells was written"
+
+
 READER_CLASSES = {c.name: c for c in (StripReader, VerifyReader, HistogramReader, ZonalReader, OverviewReader,
-                                      FusedReader)}
+                                      FusedReader, AggregateReader)}
 assert tuple(READER_CLASSES) == READERS
 
 

@@ -1,15 +1,16 @@
 """GPU: every reader of the code bytes of a prepared tile -- the byte and vector strip kernels, the fused tile
-encoder, verify_strip, the pair histogram, the zonal pair histogram and the average overviews -- held to the contract
-of gcn10_gpu_prepare_tile in include/gcn10_gpu.h, on the tiles A to I where that machinery can go wrong: column maps
-that are not monotone or leave the window, one complex group, one soil column or row, cells narrower than a pixel,
-widths around the 16-px group, two tile rows, pointers at odd offsets, the caller's buffers overwritten after
+encoder, verify_strip, the pair histogram, the zonal pair histogram, the average overviews and the area means of
+gcn10_gpu_aggregate (seven readers, tests/soil_readers.READERS) -- held to the contract of gcn10_gpu_prepare_tile
+in include/gcn10_gpu.h, on the tiles A to I where that machinery can go wrong: column maps that are not monotone
+or leave the window, one complex group, one soil column or row, cells narrower than a pixel, widths around the 16-px group, two tile rows, pointers at odd offsets, the caller's buffers overwritten after
 prepare_tile, and tile after tile on one context.  On every tile every reader is the first call after a
 prepare_tile of its own, so it is the one that makes the bytes (or, where the width is no multiple of 16, waits
 for the ones prepare_tile made).  Needs an MI355X.
 
 Expected values: the oracle's calculate_cn / modify_hysogs_data over coarse[cj][:, clamp_columns(ci, hsx)] by plain
-numpy indexing, numpy pair counts and the numpy model of the average overviews (tests/soil_readers.py, whose
-references tests/test_soil_reader_references.py checks on the CPU) -- never another GPU path.
+numpy indexing, numpy pair counts, the numpy model of the average overviews and the numpy reduction of the oracle's
+rasters to cells (tests/soil_readers.py, whose references tests/test_soil_reader_references.py checks on the CPU) --
+never another GPU path.
 """
 import numpy as np
 import pytest
@@ -171,10 +172,10 @@ def test_two_readers_on_two_streams(eng9, tables, delay, first, second, W):
     and `second` waits on the context's event for them; W = 2051: prepare_tile made them and both wait.
 
     Truly concurrent -- both launches are queued before either is awaited -- are the pairs whose FIRST reader is
-    strip, verify, histogram, zonal or overview (cn_strip, verify_strip, pair_histogram,
-    zonal_pair_histogram_device and overview_average return at once); with fused second, its kernels are queued
-    behind the event while the first reader may still run.  Only ordered are the six pairs whose first reader is
-    fused: deflate_fused downloads its streams and frees its arena, so stream 1 is idle when `second` is launched --
+    strip, verify, histogram, zonal, overview or aggregate (cn_strip, verify_strip, pair_histogram,
+    zonal_pair_histogram_device, overview_average and aggregate return at once); with fused second, its kernels are
+    queued behind the event while the first reader may still run.  Only ordered are the seven pairs whose first reader
+    is fused: deflate_fused downloads its streams and frees its arena, so stream 1 is idle when `second` is launched --
     those pairs show that a reader on another stream finds the bytes, not that it waits for them.
 
     Stream 1 first copies 256 MiB, so that `second` is queued on an idle stream 2 before `first` has made the

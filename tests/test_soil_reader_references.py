@@ -6,6 +6,7 @@ import pytest
 
 from gcn10_amd import host
 from oracle import cn_oracle_c as oc
+from tests import aggutil
 from tests import soil_readers as sr
 from tests.test_gpu_stats import model_histogram
 from tests.util import ESA_NASTY, HSG_NASTY, make_block
@@ -86,6 +87,211 @@ def test_the_spans_and_strips_of_the_readers_have_the_shapes_the_cases_name(name
     assert len(strips) == 2 and strips[0][1] + strips[1][1] == H and cj[strips[1][0]] == cj[strips[1][0] - 1]
     assert cj.min() >= 0 and cj.max() < spec["hsy"]
 
+
+    # the passes of the aggregate reader
+    passes = sr.aggregate_passes(W, cj.astype(np.int32))
+    assert [p["f"] for p in passes] == [3, 16, 25] and {p["form"] for p in passes} == {sr.AGG_SMALL, sr.AGG_WIDE}
+    for p in passes:
+        assert 0 <= p["x0"] < p["x1"] <= W and p["Wa"] >= 1 and p["sel"]
+        assert len(p["cell_rows"]) == len(p["strips"]) and min(p["cell_rows"]) >= 1
+        assert [y0 for y0, _ in p["strips"]] == np.cumsum([0] + [n for _, n in p["strips"]])[:-1].tolist()
+        assert sum(n for _, n in p["strips"]) == H                  # the strips tile the rows, in order
+    assert passes[0]["strips"] == strips and passes[2]["strips"] == strips and len(passes[1]["strips"]) == H
+    assert (passes[0]["x0"], passes[0]["x1"]) == (0, W) == (passes[1]["x0"], passes[1]["x1"])
+    assert len(passes[2]["sel"]) < 18
+    if W >= 32:                                      # first and last column inside a 16-px group
+        assert passes[2]["x0"] % 16 != 0 and passes[2]["x1"] % 16 != 0
+        assert passes[2]["x0"] == 1 and W - 2 <= passes[2]["x1"] <= W - 1
+
+
+# ---- the reference of the aggregate reader ---------------------------------------------------------------------------
+
+def cells_by_hand(raster, x0, x1, f, strips):
+    """The cells of the strips in Python integers, cell by cell: (2 s + n) // (2 n) over the values != 255, 255 where
+    there is none."""
+    v = np.asarray(raster).tolist()
+    out = []
+    for y0, rows in strips:
+        for top in range(y0, y0 + rows, f):
+            line = []
+            for left in range(x0, x1, f):
+                s = n = 0
+                for y in range(top, min(top + f, y0 + rows)):
+                    for value in v[y][left:min(left + f, x1)]:
+                        if value != 255:
+                            s, n = s + value, n + 1
+                line.append((2 * s + n) // (2 * n) if n else 255)
+            out.append(line)
+    return out
+
+
+def check_reduction(rasters, W, cj):
+    seen = set()
+    for p in sr.aggregate_passes(W, cj):
+        for r in (p["sel"][0], p["sel"][-1]):
+            got = sr.reduce_strips(rasters[r], p["x0"], p["x1"], p["f"], p["strips"])
+            assert got.dtype == np.uint8 and got.shape == (sum(p["cell_rows"]), p["Wa"])
+            assert got.tolist() == cells_by_hand(rasters[r], p["x0"], p["x1"], p["f"], p["strips"]), (p["f"], r)
+            seen |= set(got.ravel().tolist())
+    return seen
+
+
+@pytest.mark.parametrize("name", [k for k in sr.SPECS if k[0] == "E"])
+def test_the_strip_wise_reduction_equals_a_loop_over_cells(tables, name):
+    t = sr.host_tile(tables, name)
+    passes = sr.aggregate_passes(t.W, t.cj)
+    check_reduction({r: t.want(r) for p in passes for r in (p["sel"][0], p["sel"][-1])}, t.W, t.cj)
+
+
+def test_the_strip_wise_reduction_equals_a_loop_over_cells_300_x_27():
+    """Values of the whole byte range, a third of them 255, so that cells without a value and ties occur."""
+    rng = np.random.default_rng(27)
+    W, H = 300, 27
+    raster = np.where(rng.integers(0, 3, size=(H, W)) == 0, 255, rng.integers(0, 256, size=(H, W))).astype(np.uint8)
+    cj = np.minimum((np.arange(H) + 3) * 4 // (H + 3), 3).astype(np.int32)
+    seen = check_reduction({r: raster for r in range(18)}, W, cj)
+    assert 255 in seen and len(seen) > 100
+
+
+def rasters_of(t, soil):
+    return aggutil.oracle_rasters(t.esa, soil, t.tables)
+
+
+def neighbour_soil(t):
+    """The tile's soil with every column reading the soil cell next to its own."""
+    return t.coarse[t.cj][:, (sr.clamp_columns(t.ci, t.hsx) + 1) % t.hsx]
+
+
+def columns_that_differ(want, other):
+    return np.any([(want[r] != other[r]).any(axis=0) for r in range(18)], axis=0)
+
+
+def _sums(raster):
+    v = raster.astype(np.int64)
+    ok = v != 255
+    return np.where(ok, v, 0), ok.astype(np.int64)
+
+
+def _mean(s, n):
+    out = np.full(s.shape, 255, np.int64)
+    np.floor_divide(2 * s + n, 2 * n, out=out, where=n > 0)
+    return out
+
+
+def _over_cell_rows(a, strips, f):
+    return np.vstack([np.add.reduceat(a[y0:y0 + rows], np.arange(0, rows, f), axis=0) for y0, rows in strips])
+
+
+def columns_seen(p, want, other):
+    """bool[W]: the columns x for which the bytes the pass expects change when column x ALONE is taken from `other`.
+    Per cell s' = s - (the column's sum in the cell) + (the other column's), and likewise n: no reduction per column."""
+    x0, x1, f = p["x0"], p["x1"], p["f"]
+    W = want[p["sel"][0]].shape[1]
+    starts, cell = np.arange(0, x1 - x0, f), np.arange(x1 - x0) // f
+    seen = np.zeros(W, bool)
+    for r in p["sel"]:
+        col = [_over_cell_rows(a[:, x0:x1], p["strips"], f) for a in _sums(want[r]) + _sums(other[r])]
+        s, n = (np.add.reduceat(a, starts, axis=1) for a in col[:2])
+        swapped = _mean(s[:, cell] - col[0] + col[2], n[:, cell] - col[1] + col[3])
+        seen[x0:x1] |= (swapped != _mean(s, n)[:, cell]).any(axis=0)
+    return seen
+
+
+def rows_unseen(t, p, want):
+    """The rows y whose soil, replaced by the next soil row's, gives other full-resolution rasters in that row -- in
+    the rasters and columns the pass reads -- and the same expected bytes.  Per cell as in columns_seen."""
+    x0, x1, f = p["x0"], p["x1"], p["f"]
+    other = rasters_of(t, t.coarse[(t.cj + 1) % t.hsy][:, sr.clamp_columns(t.ci, t.hsx)])
+    differ = np.any([(want[r][:, x0:x1] != other[r][:, x0:x1]).any(axis=1) for r in p["sel"]], axis=0)
+    starts = np.arange(0, x1 - x0, f)
+    cell_row, first = np.zeros(t.H, np.int64), 0
+    for (y0, rows), n in zip(p["strips"], p["cell_rows"]):
+        cell_row[y0:y0 + rows] = first + np.arange(rows) // f
+        first += n
+    seen = np.zeros(t.H, bool)
+    for r in p["sel"]:
+        row = [np.add.reduceat(a[:, x0:x1], starts, axis=1) for a in _sums(want[r]) + _sums(other[r])]
+        s, n = (_over_cell_rows(a, p["strips"], f) for a in row[:2])
+        swapped = _mean(s[cell_row] - row[0] + row[2], n[cell_row] - row[1] + row[3])
+        seen |= (swapped != _mean(s, n)[cell_row]).any(axis=1)
+    return int(differ.sum()), np.flatnonzero(differ & ~seen).tolist()
+
+
+# pass (b) BY ITSELF lets these columns through -- the only ones on any tile; pass (c), the same kernel, shows them
+ONLY_PASS_C_SEES = {"E-5": [2], "E-17": [13]}
+
+
+@pytest.mark.parametrize("name", [k for k, s in sr.SPECS.items() if s["hsx"] > 1])
+def test_every_column_is_observable_by_both_aggregate_kernels(tables, name):
+    """An area mean hides a wrong soil byte: a whole 40-row tile at f = 25 leaves up to 33 columns of these tiles
+    (f = 16: up to 5) whose soil could be the neighbouring cell's without one expected byte changing.  The passes of
+    the aggregate reader leave NONE, for either kernel, on any tile: every column whose full-resolution rasters differ
+    anywhere between its soil and the neighbouring soil cell's changes, swapped alone, at least one expected byte of
+    the pass for f < 16 and, separately, at least one of the passes for f >= 16."""
+    t = sr.host_tile(tables, name)
+    want, other = rasters_of(t, t.soil), rasters_of(t, neighbour_soil(t))
+    for r in range(18):
+        np.testing.assert_array_equal(want[r], t.want(r))
+    counts = columns_that_differ(want, other)
+    assert counts.sum() >= t.W // 2, "hardly a column of this tile would show its soil at full resolution"
+    passes = sr.aggregate_passes(t.W, t.cj)
+    seen = {p["f"]: columns_seen(p, want, other) for p in passes}
+    assert not seen[25][:passes[2]["x0"]].any() and not seen[25][passes[2]["x1"]:].any()
+    small, wide = seen[3], seen[16] | seen[25]
+    assert passes[0]["form"] == sr.AGG_SMALL and passes[1]["form"] == passes[2]["form"] == sr.AGG_WIDE
+    assert np.flatnonzero(counts & ~small).tolist() == [], sr.AGG_SMALL
+    assert np.flatnonzero(counts & ~wide).tolist() == [], sr.AGG_WIDE
+    assert np.flatnonzero(counts & ~seen[16]).tolist() == ONLY_PASS_C_SEES.get(name, []), "pass (b) alone"
+
+
+@pytest.mark.parametrize("name,columns", [("E-5", range(5)), ("E-17", range(17)),
+                                          ("A-zig-zag", (0, 1, 1039, 2046, 2047))])
+def test_the_per_cell_update_equals_a_reduction_of_the_swapped_tile(tables, name, columns):
+    """columns_seen against the statement it abbreviates: the oracle over the soil with ONE column swapped, reduced by
+    the reader's own reference."""
+    t = sr.host_tile(tables, name)
+    want, soil2 = rasters_of(t, t.soil), neighbour_soil(t)
+    other = rasters_of(t, soil2)
+    passes = sr.aggregate_passes(t.W, t.cj)
+    seen = [columns_seen(p, want, other) for p in passes]
+    for x in columns:
+        soil = t.soil.copy()
+        soil[:, x] = soil2[:, x]
+        swapped = rasters_of(t, soil)
+        for p, s in zip(passes, seen):
+            changed = any((sr.reduce_strips(swapped[r], p["x0"], p["x1"], p["f"], p["strips"]) !=
+                           sr.reduce_strips(want[r], p["x0"], p["x1"], p["f"], p["strips"])).any() for r in p["sel"])
+            assert changed == bool(s[x]), (x, p["f"])
+
+
+@pytest.mark.parametrize("name", [k for k, s in sr.SPECS.items() if s["hsx"] == 1])
+def test_one_soil_column_another_class_changes_bytes_of_both_kernels(tables, name):
+    """hsx = 1: there is no neighbouring cell.  The whole tile on one other soil class, whichever of A to D, changes
+    expected bytes of every pass."""
+    t = sr.host_tile(tables, name)
+    want = rasters_of(t, t.soil)
+    judged = 0
+    for hsg in (1, 2, 3, 4):
+        other = rasters_of(t, np.full_like(t.soil, hsg))
+        if not any((want[r] != other[r]).any() for r in range(18)):
+            continue
+        judged += 1
+        for p in sr.aggregate_passes(t.W, t.cj):
+            assert any((sr.reduce_strips(other[r], p["x0"], p["x1"], p["f"], p["strips"]) !=
+                        sr.reduce_strips(want[r], p["x0"], p["x1"], p["f"], p["strips"])).any() for r in p["sel"]), \
+                (hsg, p["f"])
+    assert judged >= 3
+
+
+@pytest.mark.parametrize("name", [k for k, s in sr.SPECS.items() if s["hsy"] > 1])
+def test_every_soil_row_is_observable_by_the_row_walk(tables, name):
+    """Pass (c) walks the rows of a cell row across changing soil rows: one strip row on the NEXT soil row's soil
+    changes an expected byte wherever it changes the full-resolution rasters the pass reads in that row."""
+    t = sr.host_tile(tables, name)
+    p = sr.aggregate_passes(t.W, t.cj)[2]
+    judged, unseen = rows_unseen(t, p, rasters_of(t, t.soil))
+    assert unseen == []
+    assert judged >= t.H // 2       # (a tile on ONE soil column, A-constant, has soil rows of the same class)
 
 def test_the_tiles_of_case_i_differ_in_more_than_half_of_their_soil():
     soils = sr.case_i_soils()

@@ -5,6 +5,8 @@
 #include "gcn10_gpu.h"
 #include "gcn10_host.h"
 
+#include <pthread.h>
+
 struct gcn10_tiff;      /* tiff.c: one open TIFF file */
 struct gcn10_tiff *gcn10_tiff_open_reader(const char *path, char *err, size_t errcap);
 /* directory `level` of the file (0 = the raster, k = overview k of a COG); *why (optional): GCN10_TIFF_E_* of a NULL */
@@ -35,6 +37,18 @@ void gcn10_pool_destroy(gcn10_pool *p);     /* drains the queue first */
 double gcn10_pool_cpu_seconds(gcn10_pool *p);   /* CPU time its (live) threads have used so far */
 double gcn10_pool_cpu_of(gcn10_pool *p, gcn10_job_fn fn, long *n_jobs);     /* ... in jobs of one kind */
 double gcn10_thread_cpu_seconds(void);          /* ... the calling thread */
+/* The jobs someone has handed out and waits for: add before a job is submitted, done as the job's last step, wait
+ * until every job added is done.  A group may be added to again while it is waited for (a job that hands out more). */
+struct gcn10_job_group {
+    pthread_mutex_t mu;
+    pthread_cond_t cv;
+    int pending;
+};
+void gcn10_job_group_init(struct gcn10_job_group *g);
+void gcn10_job_group_destroy(struct gcn10_job_group *g);
+void gcn10_job_group_add(struct gcn10_job_group *g, int n);
+void gcn10_job_group_done(struct gcn10_job_group *g);
+void gcn10_job_group_wait(struct gcn10_job_group *g);
 void gcn10_tiff_cache_stats(uint64_t *hits, uint64_t *misses, size_t *bytes);     /* decoded-chunk cache of tiff.c */
 
 /* Like gcn10_tiff_read_window / gcn10_raster_read, with the tiles or strips of the

@@ -1,6 +1,7 @@
-/* pipeline_internal.h -- the worker and run state shared by pipeline.c (block queue, strips,
- * sink), pipeline_input.c (landcover input through the GPU decoder), verify.c, zonal.c and aggregate.c, and what the
- * writer and the verifier have in common: the chunk stager (stage.c) and the overview levels (levels.c). */
+/* pipeline_internal.h -- the worker and run state shared by run.c (the run's steps), pipeline.c (workers, a block's
+ * strips), sink.c (strip buffers, sink jobs), pipeline_input.c (landcover input through the GPU decoder), launcher.c,
+ * verify.c, zonal.c and aggregate.c, and what the writer and the verifier have in common: the chunk stager (stage.c)
+ * and the overview levels (levels.c). */
 #ifndef GCN10_PIPELINE_INTERNAL_H
 #define GCN10_PIPELINE_INTERNAL_H
 
@@ -57,15 +58,14 @@ struct gcn10_stager {
     gcn10_event_t ev[GCN10_STAGER_MAX];
     bool busy[GCN10_STAGER_MAX];            /* a copy out of the buffer was issued and not yet waited for */
     /* the batch being read: pool jobs take slices of [next, end) in turn */
-    pthread_mutex_t mu;
-    pthread_cond_t cv;
+    struct gcn10_job_group reads;
     const struct gcn10_chunk_ref *chunks;
     const gcn10_inflate_tile *jobs;
     int *bad;
     uint8_t *dst;
     uint64_t base;
-    size_t next, end;
-    int pending;
+    atomic_size_t next;
+    size_t end;
 };
 /* n_buffers events, and buffers of `bytes` (0: none before the first gcn10_stager_ensure) */
 int gcn10_stager_setup(struct gcn10_stager *s, const struct gcn10_gpu_api *g, gcn10_gpu_ctx *ctx, gcn10_pool *pool,
@@ -99,10 +99,7 @@ struct strip_buf {
     uint32_t *d_table, *h_table;            /* [18][tiles][2]; h_table pinned */
     unsigned long long *d_cursor, *h_cursor;
     const uint8_t **d_ptrs;                 /* device array of the 18 d_out pointers */
-    /* compression jobs of the strip currently held by this buffer */
-    pthread_mutex_t mu;
-    pthread_cond_t cv;
-    int pending;
+    struct gcn10_job_group jobs;            /* sink jobs of the strip currently held by this buffer */
     bool d2h_issued;
     int y0, rows;                           /* strip held */
     struct worker *owner;
@@ -273,9 +270,32 @@ void gcn10_wlog(struct worker *w, const char *level, bool console, const char *f
         }                                                                              \
     } while (0)
 
-/* device / pinned buffer of at least `need` bytes on context `ctx` (grown by reallocation); -1 and a log line on failure */
+/* sink.c: device / pinned buffer of at least `need` bytes on context `ctx` (grown by reallocation); -1 and a log line
+ * on failure */
 int gcn10_ensure_dev_on(struct worker *w, gcn10_gpu_ctx *ctx, void **p, size_t *cap, size_t need);
 int gcn10_ensure_pinned_on(struct worker *w, gcn10_gpu_ctx *ctx, void **p, size_t *cap, size_t need);
+/* sink.c: the worker's strip buffers, sized for blocks W wide (0, or -1: logged).  gcn10_sink_drain hands the finished
+ * strip held by buffer b (none: nothing happens) to the pool's sink jobs, gcn10_sink_wait waits for them; once every
+ * strip of a block is drained, gcn10_sink_finish_files closes the block's files (ok) or gives them up.
+ * gcn10_sink_job_cpu: the pool's CPU seconds and job counts in appending extents, waiting for a strip's bytes,
+ * finishing files and host deflate, in this order. */
+struct gcn10_job_cpu {
+    double seconds;
+    long n;
+};
+int gcn10_sink_ensure_buffers(struct worker *w, int W);
+void gcn10_sink_free_buffers(struct worker *w);
+int gcn10_sink_drain(struct worker *w, struct strip_buf *b, gcn10_tiff_writer *tifs[GCN10_N_RASTERS], int W, int H);
+void gcn10_sink_wait(struct strip_buf *b);
+void gcn10_sink_finish_files(struct worker *w, gcn10_tiff_writer *tifs[GCN10_N_RASTERS], bool ok, int block_id);
+void gcn10_sink_job_cpu(gcn10_pool *pool, struct gcn10_job_cpu by_kind[4]);
+/* pipeline.c: a worker's thread, from its set-up to its teardown */
+void *gcn10_worker_main(void *arg);
+/* launcher.c: rank and size of this process under mpirun / srun (0 of 1 without); the launch's name in file names;
+ * the closing barrier through <log_dir>/.done_<job>_<rank> and launcher rank 0's line of totals */
+void gcn10_outer_from_env(int *rank, int *size);
+void gcn10_job_tag(char job[96]);
+void gcn10_closing_barrier(struct run *r, gcn10_log *log0);
 
 /* levels.c: the overview levels of a staged block, for the writer and the verifier alike.
  * gcn10_level_nearest: level k by nearest-neighbour sampling, ready as a block of its own -- its landcover in w->d_ov,
@@ -313,10 +333,13 @@ int gcn10_aggregate_plan_block(struct worker *w, struct block_in *in, const doub
 int gcn10_aggregate_block(struct worker *w, struct block_in *in, gcn10_tiff_writer *tifs[GCN10_N_RASTERS]);
 void gcn10_aggregate_finish(struct run *r, gcn10_log *log0);
 /* verify.c: a staged block's files against the values computed now (0, or -1 for errors that end the run); a block
- * whose inputs could not be staged; the worker's verify buffers */
+ * whose inputs could not be staged; the worker's verify buffers; the end of the run -- this process's counts left for
+ * launcher rank 0, then the closing line and verify_failed_blocks.txt (returns the bad + missing files it knows of) */
 int gcn10_verify_block(struct worker *w, struct block_in *in);
 void gcn10_verify_block_unreadable(struct worker *w, int block_id);
 void gcn10_verify_teardown(struct worker *w);
+void gcn10_verify_leave_part(struct run *r);
+int gcn10_verify_summary(struct run *r, gcn10_log *log0);
 /* zonal.c: the zones and the table of the run (start: before any GPU is opened; finish: the table and the closing
  * line; end: frees both); the spans of a staged block, made by the input side; a staged block counted (0, or -1 for
  * errors that end the run); a block whose inputs could not be staged; the worker's zonal buffers */

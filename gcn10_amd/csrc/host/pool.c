@@ -1,7 +1,7 @@
-/* pool.c -- a fixed pool of threads that compress raster tiles.
+/* pool.c -- a fixed pool of threads that compress raster tiles, and the count of jobs someone waits for.
  *
  * GDAL deflates every 256x256 block inside the one blocking GDALRasterIO call of
- * save_raster() (/root/reference/src/raster.c:217-219), on the rank's only
+ * save_raster() (src/raster.c:217-219), on the rank's only
  * thread; the paper names this as what dominates the run
  * (paper/paper.md:152-153).  Here the tiles of all 18 rasters of a strip are
  * independent jobs for all host cores while the GPU works on the next strip.
@@ -27,8 +27,6 @@ struct gcn10_pool {
     bool stop;
     struct { gcn10_job_fn fn; double cpu; long n; } by_fn[16];   /* CPU time by kind of job (timing lines) */
 };
-
-double gcn10_thread_cpu_seconds(void);
 
 static void *pool_main(void *arg)
 {
@@ -174,4 +172,40 @@ void gcn10_pool_destroy(gcn10_pool *p)
     pthread_cond_destroy(&p->cv);
     free(p->threads);
     free(p);
+}
+
+void gcn10_job_group_init(struct gcn10_job_group *g)
+{
+    pthread_mutex_init(&g->mu, NULL);
+    pthread_cond_init(&g->cv, NULL);
+    g->pending = 0;
+}
+
+void gcn10_job_group_destroy(struct gcn10_job_group *g)
+{
+    pthread_mutex_destroy(&g->mu);
+    pthread_cond_destroy(&g->cv);
+}
+
+void gcn10_job_group_add(struct gcn10_job_group *g, int n)
+{
+    pthread_mutex_lock(&g->mu);
+    g->pending += n;
+    pthread_mutex_unlock(&g->mu);
+}
+
+void gcn10_job_group_done(struct gcn10_job_group *g)
+{
+    pthread_mutex_lock(&g->mu);
+    if (--g->pending == 0)
+        pthread_cond_broadcast(&g->cv);
+    pthread_mutex_unlock(&g->mu);
+}
+
+void gcn10_job_group_wait(struct gcn10_job_group *g)
+{
+    pthread_mutex_lock(&g->mu);
+    while (g->pending > 0)
+        pthread_cond_wait(&g->cv, &g->mu);
+    pthread_mutex_unlock(&g->mu);
 }

@@ -89,8 +89,7 @@ int gcn10_stager_setup(struct gcn10_stager *s, const struct gcn10_gpu_api *g, gc
     s->pool = pool;
     s->pinned_bytes = pinned_bytes;
     s->n = n_buffers;
-    pthread_mutex_init(&s->mu, NULL);
-    pthread_cond_init(&s->cv, NULL);
+    gcn10_job_group_init(&s->reads);
     for (int k = 0; k < s->n; k++)
         if ((rc = g->event_create(ctx, &s->ev[k])) != 0)
             return rc;
@@ -105,8 +104,7 @@ void gcn10_stager_teardown(struct gcn10_stager *s)
         if (s->h[k]) s->gpu->host_free(s->ctx, s->h[k]);
         if (s->ev[k]) s->gpu->event_destroy(s->ctx, s->ev[k]);
     }
-    pthread_mutex_destroy(&s->mu);
-    pthread_cond_destroy(&s->cv);
+    gcn10_job_group_destroy(&s->reads);
     memset(s, 0, sizeof *s);
 }
 
@@ -170,13 +168,8 @@ int gcn10_stager_ensure(struct gcn10_stager *s, size_t bytes)
 static void read_slice(void *arg)
 {
     struct gcn10_stager *s = arg;
-    size_t i0, i1;
+    const size_t i0 = atomic_fetch_add(&s->next, SLICE), i1 = s->end - i0 < SLICE ? s->end : i0 + SLICE;
 
-    pthread_mutex_lock(&s->mu);
-    i0 = s->next;
-    s->next += SLICE;
-    pthread_mutex_unlock(&s->mu);
-    i1 = s->end - i0 < SLICE ? s->end : i0 + SLICE;
     for (size_t i = i0; i < i1; i++) {
         uint8_t *const p0 = s->dst + (s->jobs[i].in_off - s->base), *p = p0;
         size_t left = s->chunks[i].nbytes;
@@ -197,10 +190,7 @@ static void read_slice(void *arg)
         }
         memset(p, 0, 16);               /* the decoder's bit reader may look a few bytes ahead */
     }
-    pthread_mutex_lock(&s->mu);
-    if (--s->pending == 0)
-        pthread_cond_broadcast(&s->cv);
-    pthread_mutex_unlock(&s->mu);
+    gcn10_job_group_done(&s->reads);
 }
 
 int gcn10_stager_stage(struct gcn10_stager *s, const struct gcn10_chunk_ref *chunks, const gcn10_inflate_tile *jobs,
@@ -236,19 +226,16 @@ int gcn10_stager_stage(struct gcn10_stager *s, const struct gcn10_chunk_ref *chu
         s->bad = bad;
         s->dst = s->h[k];
         s->base = base;
-        s->next = i0;
+        atomic_store(&s->next, i0);
         s->end = i1;
-        s->pending = n_slices;
+        gcn10_job_group_add(&s->reads, n_slices);
         for (int j = 0; j < n_slices; j++) {
             if (s->pool)
                 gcn10_pool_submit(s->pool, read_slice, s);
             else
                 read_slice(s);
         }
-        pthread_mutex_lock(&s->mu);
-        while (s->pending > 0)
-            pthread_cond_wait(&s->cv, &s->mu);
-        pthread_mutex_unlock(&s->mu);
+        gcn10_job_group_wait(&s->reads);
         if ((rc = s->gpu->memcpy_h2d(s->ctx, d_comp + base, s->h[k], (size_t)(end - base), stream)) != 0 ||
             (rc = gcn10_stager_sent(s, k, stream)) != 0)
             return rc;

@@ -20,6 +20,7 @@
 #include <errno.h>
 #include <fcntl.h>
 #include <pthread.h>
+#include <stdatomic.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -820,11 +821,8 @@ struct chunk_job {
     int xoff, yoff, xcount, ycount;
     uint8_t *dst;
     size_t dst_stride;
-    /* completion */
-    pthread_mutex_t *mu;
-    pthread_cond_t *cv;
-    int *pending;
-    int *failed;
+    struct gcn10_job_group *group;  /* the window's jobs */
+    atomic_int *failed;             /* ... and whether any of them failed */
 };
 
 static int read_chunk(const struct chunk_job *j)
@@ -927,14 +925,10 @@ static int read_chunk(const struct chunk_job *j)
 static void chunk_job_run(void *arg)
 {
     struct chunk_job *j = arg;
-    int rc = read_chunk(j);
 
-    pthread_mutex_lock(j->mu);
-    if (rc != 0)
-        *j->failed = 1;
-    if (--*j->pending == 0)
-        pthread_cond_broadcast(j->cv);
-    pthread_mutex_unlock(j->mu);
+    if (read_chunk(j) != 0)
+        atomic_store(j->failed, 1);
+    gcn10_job_group_done(j->group);
     free(j);
 }
 
@@ -942,9 +936,8 @@ int gcn10_tiff_read_window_mt(struct gcn10_tiff *t, int xoff, int yoff, int xcou
                               uint8_t *dst, size_t dst_stride, gcn10_pool *pool, char *err,
                               size_t errcap)
 {
-    pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
-    pthread_cond_t cv = PTHREAD_COND_INITIALIZER;
-    int pending = 0, failed = 0;
+    struct gcn10_job_group group;
+    atomic_int failed = 0;
 
     if (xoff < 0 || yoff < 0 || xcount <= 0 || ycount <= 0 ||
         (uint64_t)xoff + (uint64_t)xcount > t->width || (uint64_t)yoff + (uint64_t)ycount > t->height) {
@@ -952,29 +945,25 @@ int gcn10_tiff_read_window_mt(struct gcn10_tiff *t, int xoff, int yoff, int xcou
                  t->width, t->height);
         return -1;
     }
+    gcn10_job_group_init(&group);
     for (uint32_t cy = (uint32_t)yoff / t->ch; cy <= (uint32_t)(yoff + ycount - 1) / t->ch; cy++) {
         for (uint32_t cx = (uint32_t)xoff / t->cw; cx <= (uint32_t)(xoff + xcount - 1) / t->cw; cx++) {
-            struct chunk_job job = { t, cx, cy, xoff, yoff, xcount, ycount, dst, dst_stride,
-                                     &mu, &cv, &pending, &failed };
+            struct chunk_job job = { t, cx, cy, xoff, yoff, xcount, ycount, dst, dst_stride, &group, &failed };
             struct chunk_job *j = pool ? malloc(sizeof *j) : NULL;
 
             if (!j) {               /* no pool (or no memory for the job): decode here */
                 if (read_chunk(&job) != 0)
-                    failed = 1;
+                    atomic_store(&failed, 1);
                 continue;
             }
             *j = job;
-            pthread_mutex_lock(&mu);
-            pending++;
-            pthread_mutex_unlock(&mu);
+            gcn10_job_group_add(&group, 1);
             gcn10_pool_submit(pool, chunk_job_run, j);
         }
     }
-    pthread_mutex_lock(&mu);
-    while (pending > 0)
-        pthread_cond_wait(&cv, &mu);
-    pthread_mutex_unlock(&mu);
-    if (failed) {
+    gcn10_job_group_wait(&group);
+    gcn10_job_group_destroy(&group);
+    if (atomic_load(&failed)) {
         snprintf(err, errcap, "gdalrasterio error: cannot decode a %s of the window %d,%d %dx%d",
                  t->tiled ? "tile" : "strip", xoff, yoff, xcount, ycount);
         return -1;

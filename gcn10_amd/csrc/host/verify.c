@@ -12,7 +12,7 @@
  *      of its own, an average level against gcn10_gpu_overview_average's buffers (gcn10_gpu_verify_buffers).
  * A window the planner leaves to the host reader (PackBits, very wide raw strips) is decoded by it and uploaded.
  * The per-chunk status words of the decoder are findings: a stream that does not decode makes its file unreadable,
- * it never faults the device.
+ * it never faults the device.  At the bottom: the run's closing summary and verify_failed_blocks.txt.
  */
 #include "pipeline_internal.h"
 
@@ -612,4 +612,98 @@ out:
         for (int k = 0; k < V_LEVELS; k++)
             gcn10_tiff_close_reader(files[q].lv[k]);
     return rc;
+}
+
+static int by_int(const void *a, const void *b)
+{
+    const int x = *(const int *)a, y = *(const int *)b;
+
+    return x < y ? -1 : (x > y ? 1 : 0);
+}
+
+/* The end of a verify run: the closing console line and <log_dir>/verify_failed_blocks.txt, the ids of the blocks
+ * with a bad or missing file, ascending, one per line (what -l reads).  Under an MPI launcher every process leaves
+ * its counts and ids in "<log_dir>/.verify_<job>_<rank>" BEFORE the closing barrier, and launcher rank 0 merges
+ * them behind it, the way it prints the run's totals.  Returns the number of bad + missing files it knows of. */
+void gcn10_verify_leave_part(struct run *r)
+{
+    char job[96], path[PATH_MAX];
+    FILE *f;
+
+    gcn10_job_tag(job);
+    snprintf(path, sizeof path, "%s/.verify_%s_%d", r->cfg.log_dir, job, r->outer_rank);
+    f = fopen(path, "w");
+    if (!f)
+        return;
+    fprintf(f, "%d %d %d %d %d %d\n", r->n_blocks, atomic_load(&r->verify_n_ok), atomic_load(&r->verify_n_bad),
+            atomic_load(&r->verify_n_missing), atomic_load(&r->verify_n_unchecked), r->verify_n_failed);
+    for (int i = 0; i < r->verify_n_failed; i++)
+        fprintf(f, "%d\n", r->verify_failed[i]);
+    fclose(f);
+}
+
+int gcn10_verify_summary(struct run *r, gcn10_log *log0)
+{
+    int blocks = r->n_blocks, ok = atomic_load(&r->verify_n_ok), bad = atomic_load(&r->verify_n_bad);
+    int missing = atomic_load(&r->verify_n_missing), unchecked = atomic_load(&r->verify_n_unchecked);
+    int *ids = r->verify_failed, n_ids = r->verify_n_failed;
+    const int mine = bad + missing;
+    char path[PATH_MAX], msg[PATH_MAX + 64];
+    FILE *f;
+
+    if (r->outer_size > 1) {
+        char job[96];
+
+        if (r->outer_rank != 0)
+            return mine;
+        gcn10_job_tag(job);
+        for (int p = 1; p < r->outer_size; p++) {
+            int b, o, x, m, u, n;
+
+            snprintf(path, sizeof path, "%s/.verify_%s_%d", r->cfg.log_dir, job, p);
+            f = fopen(path, "r");
+            if (!f)
+                continue;               /* (the barrier has said so: "some processes did not report in time") */
+            if (fscanf(f, "%d %d %d %d %d %d", &b, &o, &x, &m, &u, &n) == 6 && n >= 0) {
+                int *g = realloc(ids == r->verify_failed ? NULL : ids, (size_t)(n_ids + n + 1) * sizeof *g);
+
+                if (g) {
+                    if (ids == r->verify_failed && n_ids > 0)
+                        memcpy(g, r->verify_failed, (size_t)n_ids * sizeof *g);
+                    ids = g;
+                    for (int i = 0; i < n && fscanf(f, "%d", &ids[n_ids]) == 1; i++)
+                        n_ids++;
+                }
+                blocks += b;
+                ok += o;
+                bad += x;
+                missing += m;
+                unchecked += u;
+            }
+            fclose(f);
+            unlink(path);
+        }
+        snprintf(path, sizeof path, "%s/.verify_%s_0", r->cfg.log_dir, job);
+        unlink(path);
+    }
+    if (n_ids > 0)
+        qsort(ids, (size_t)n_ids, sizeof *ids, by_int);
+    snprintf(path, sizeof path, "%s/verify_failed_blocks.txt", r->cfg.log_dir);
+    f = fopen(path, "w");
+    if (f) {
+        for (int i = 0; i < n_ids; i++)
+            if (i == 0 || ids[i] != ids[i - 1])
+                fprintf(f, "%d\n", ids[i]);
+        fclose(f);
+    }
+    else {
+        snprintf(msg, sizeof msg, "cannot write %s", path);
+        gcn10_log_message(log0, "ERROR", msg, true);
+    }
+    snprintf(msg, sizeof msg, "verify: %d blocks, %d files verified, %d bad, %d missing, %d overview levels not checked",
+             blocks, ok, bad, missing, unchecked);
+    gcn10_log_message(log0, bad + missing ? "ERROR" : "INFO", msg, true);
+    if (ids != r->verify_failed)
+        free(ids);
+    return bad + missing > mine ? bad + missing : mine;
 }

@@ -1,7 +1,7 @@
 /* stub_gpu.c -- a host-only stand-in for libgcn10_gpu.so.  TEST INFRASTRUCTURE ONLY.
  *
- * Purpose: run the threaded host program (gcn10_amd/csrc/host/pipeline.c: block workers, strip-buffer
- * hand-over, sink pool) under ThreadSanitizer, which needs no GPU (`make tsan-host`).  It implements
+ * Purpose: run the threaded host program (gcn10_amd/csrc/host: block workers and strip-buffer hand-over in
+ * pipeline.c, sink jobs in sink.c, the pool and its job counter in pool.c) under ThreadSanitizer, which needs no GPU (`make tsan-host`).  It implements
  * the entry points of include/gcn10_gpu.h that the pipeline binds (gpuapi.c) with plain loops, and --
  * so that the sanitizer sees the same ordering problem the real device poses -- with ASYNCHRONOUS
  * streams: every stream is a thread that executes its operations in order, events are recorded and

@@ -1378,7 +1378,7 @@ __global__ __launch_bounds__(128) void inflate_kernel(const uint8_t *comp, const
 // (GCN10_TILE_RAW: TIFF Compression 1) is read where it lies among the staged bytes; a tile
 // written with TIFF Predictor 2 (horizontal differencing, per chunk row) is summed back on the
 // way: byte x of a row = sum of the stored bytes 0..x of that row, modulo 256 -- the inverse the
-// host reader applies in tiff.c, decode_chunk().
+// host reader applies in tiff_codec.c, gcn10_tiff_decode_chunk().
 __global__ __launch_bounds__(256) void untile_kernel(const TileIn *tiles, const uint8_t *scratch, uint32_t slot_bytes,
                                                      const uint8_t *comp, uint8_t *dst, unsigned long long dst_stride)
 {

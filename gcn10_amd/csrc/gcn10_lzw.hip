@@ -7,7 +7,7 @@
 // exactly as the DEFLATE tile encoders pack theirs (their placement pass, pass B', is reused), and the
 // sink, direct_io and the spill path of the host consume it unchanged.  The bytes are not libtiff's;
 // decoded pixels are the parity target (tests decode every stream with a strict decoder of their own, with
-// libtiff through PIL, and with the host reader, tiff.c lzw_decode).
+// libtiff through PIL, and with the host reader, tiff_codec.c lzw_decode).
 //
 // Stream format: MSB-first codes of 9..12 bits (here 9 and 10), ClearCode 256, EndOfInformation 257, "early
 // change" of the code width, EOI at the end, padded to a byte.  Every stream starts with ClearCode: libtiff

@@ -3,11 +3,11 @@
 //
 // What it is for: `gdal_translate -co COMPRESS=LZW` is how most users repack or clip the landcover, and the
 // program's own compress=lzw output is LZW too.  Without this kernel such windows went through the host
-// reader (tiff.c lzw_decode on the I/O pool) and 1.3 GB of decoded pixels per 36000^2 block crossed PCIe.
+// reader (tiff_codec.c lzw_decode on the I/O pool) and 1.3 GB of decoded pixels per 36000^2 block crossed PCIe.
 // Here the compressed chunks cross, as for DEFLATE, and are decoded into the same linear scratch slots
 // inflate_kernel uses, so untile_kernel does the window copy and the predictor-2 sum-back unchanged.
 //
-// Semantics are those of tiff.c lzw_decode, exactly: MSB-first codes of 9..12 bits with the "early change"
+// Semantics are those of tiff_codec.c lzw_decode, exactly: MSB-first codes of 9..12 bits with the "early change"
 // of the width, ClearCode 256, EndOfInformation 257, KwKwK (code == next), a dictionary that stops growing
 // at 4096 entries (codes stay 12 bits until a Clear), codes after out_len bytes are padding, output past
 // out_len is cut, an early EOI leaves zeros in the rest of the chunk.  Errors (status): a code beyond the

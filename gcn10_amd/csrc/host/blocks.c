@@ -9,6 +9,7 @@
  * Description (1998) and the dBASE III header layout are the format sources.
  */
 #include "gcn10_host.h"
+#include "bytes.h"
 
 #include <ctype.h>
 #include <stdio.h>
@@ -45,27 +46,6 @@ int *gcn10_read_block_list(const char *path, int *n_blocks)
     fclose(f);
     *n_blocks = n;
     return ids;
-}
-
-static uint32_t be32(const unsigned char *p)
-{
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-static uint32_t le32(const unsigned char *p)
-{
-    return ((uint32_t)p[3] << 24) | ((uint32_t)p[2] << 16) | ((uint32_t)p[1] << 8) | p[0];
-}
-
-static double le_f64(const unsigned char *p)
-{
-    uint64_t v = 0;
-    double d;
-
-    for (int i = 7; i >= 0; i--)
-        v = (v << 8) | p[i];
-    memcpy(&d, &v, sizeof d);
-    return d;
 }
 
 static unsigned char *slurp(const char *path, size_t *len)

@@ -7,7 +7,7 @@
 
 #include <pthread.h>
 
-struct gcn10_tiff;      /* tiff.c: one open TIFF file */
+struct gcn10_tiff;      /* tiff_internal.h: one open TIFF file (tiff_open.c) */
 struct gcn10_tiff *gcn10_tiff_open_reader(const char *path, char *err, size_t errcap);
 /* directory `level` of the file (0 = the raster, k = overview k of a COG); *why (optional): GCN10_TIFF_E_* of a NULL */
 enum { GCN10_TIFF_E_STRUCTURE = 1, GCN10_TIFF_E_MISSING = 2, GCN10_TIFF_E_NOT_BYTE = 3, GCN10_TIFF_E_NO_IFD = 4 };
@@ -49,7 +49,7 @@ void gcn10_job_group_destroy(struct gcn10_job_group *g);
 void gcn10_job_group_add(struct gcn10_job_group *g, int n);
 void gcn10_job_group_done(struct gcn10_job_group *g);
 void gcn10_job_group_wait(struct gcn10_job_group *g);
-void gcn10_tiff_cache_stats(uint64_t *hits, uint64_t *misses, size_t *bytes);     /* decoded-chunk cache of tiff.c */
+void gcn10_tiff_cache_stats(uint64_t *hits, uint64_t *misses, size_t *bytes);     /* decoded-chunk cache of tiff_cache.c */
 
 /* Like gcn10_tiff_read_window / gcn10_raster_read, with the tiles or strips of the
  * window decoded concurrently on `pool` (NULL = on the calling thread). */

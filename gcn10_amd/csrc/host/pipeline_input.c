@@ -8,7 +8,7 @@
  * block N, the thread
  *   - takes the next block id from the run's counter and computes its windows (geo.c, bit exact),
  *   - reads the soil window and builds the index maps into pinned memory, copies them to HBM,
- *   - PLANS the landcover window (raster.c / tiff.c: which chunks of which files, clipped how),
+ *   - PLANS the landcover window (raster.c / tiff_window.c: which chunks of which files, clipped how),
  *     has the I/O pool pread the chunks -- compressed or raw, as they lie in the files -- into
  *     a ring of pinned buffers, and copies batch k to HBM (hipMemcpyAsync on its stream) while the
  *     pool fills batch k+1: the "pinned-host staging, double-buffered" of the north star,

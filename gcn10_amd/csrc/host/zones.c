@@ -12,6 +12,7 @@
  * never decides a pixel.
  */
 #include "gcn10_host.h"
+#include "bytes.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -38,27 +39,6 @@ enum { DEFAULT_SPAN_PX = 16384, DEFAULT_ITEM_PX = 65536 };
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* reader                                                                                                            */
 /* ---------------------------------------------------------------------------------------------------------------- */
-
-static uint32_t be32(const unsigned char *p)
-{
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-static uint32_t le32(const unsigned char *p)
-{
-    return ((uint32_t)p[3] << 24) | ((uint32_t)p[2] << 16) | ((uint32_t)p[1] << 8) | p[0];
-}
-
-static double le_f64(const unsigned char *p)
-{
-    uint64_t v = 0;
-    double d;
-
-    for (int i = 7; i >= 0; i--)
-        v = (v << 8) | p[i];
-    memcpy(&d, &v, sizeof d);
-    return d;
-}
 
 static unsigned char *slurp(const char *path, size_t *len)
 {

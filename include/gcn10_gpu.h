@@ -267,7 +267,7 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
  * of a chunk chunk_w pixels wide) is copied to dst_dev + dst_off, rows dst_stride apart.
  * status_dev[i] = 0, or the reason stream i is not a valid zlib stream (GCN10_INFLATE_E_*); a
  * stream that ends early leaves zeros, one that is longer than out_len is cut there, as the
- * host reader (tiff.c) does.  Streams must start at multiples of 16 bytes in comp_dev, and
+ * host reader (tiff_codec.c) does.  Streams must start at multiples of 16 bytes in comp_dev, and
  * comp_dev must be readable up to the next multiple of 4 past every stream's end. */
 typedef struct gcn10_inflate_tile {
     uint64_t in_off;        /* byte offset of the zlib stream in comp_dev, multiple of 16 */
@@ -283,9 +283,9 @@ typedef struct gcn10_inflate_tile {
  * in_off and only the window copy is done (no alignment rule for in_off; the host may stage only the bytes
  * from the first wanted pixel on: src_x = src_y = 0 then, chunk_w still the chunk's row pitch).
  * PREDICTOR2 = the chunk was written with TIFF Predictor 2 (horizontal differencing): every chunk row is
- * summed back, byte-wise modulo 256, from the row's first pixel while it is copied (tiff.c decode_chunk does
+ * summed back, byte-wise modulo 256, from the row's first pixel while it is copied (tiff_codec.c gcn10_tiff_decode_chunk does
  * the same on the host).
- * LZW = the chunk is a TIFF LZW stream (Compression 5: MSB-first codes, early change), decoded as tiff.c
+ * LZW = the chunk is a TIFF LZW stream (Compression 5: MSB-first codes, early change), decoded as tiff_codec.c
  * lzw_decode does (an early EOI leaves zeros, codes past out_len are ignored); same alignment rule as a zlib
  * stream.  May be combined with PREDICTOR2, not with RAW (status GCN10_INFLATE_E_HEADER).  One call may mix
  * zlib, raw and LZW tiles. */

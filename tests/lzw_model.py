@@ -1,8 +1,8 @@
 """A model of TIFF LZW decoding for the tests of the GPU LZW decoder (gcn10_lzw_decode.hip) and of the host
-reader (tiff.c lzw_decode): a reference decoder that can say what every code did, and a writer of code
+reader (tiff_codec.c lzw_decode): a reference decoder that can say what every code did, and a writer of code
 streams in which the test chooses every code.
 
-The semantics are those of tiff.c lzw_decode (TIFF 6.0 section 13 as libtiff reads it): MSB-first codes of
+The semantics are those of tiff_codec.c lzw_decode (TIFF 6.0 section 13 as libtiff reads it): MSB-first codes of
 9..12 bits with the early change of the width, ClearCode 256, EndOfInformation 257, KwKwK (code == next), a
 dictionary that stops growing at 4096 entries, `cap` bytes out: the code that reaches cap is the last one read
 and is cut there, an early EOI leaves zeros.  Three things fail, each with its own exception, which carries

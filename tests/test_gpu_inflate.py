@@ -116,7 +116,7 @@ def test_multi_block_streams_with_flushes(engine):
 def test_stream_shorter_and_longer_than_the_chunk(engine):
     raw = _data("classes", 5000, 5)
     st = _compress(raw)
-    got, status = _one(engine, st, 8192)                 # short stream: zeros follow, as tiff.c does on the host
+    got, status = _one(engine, st, 8192)                 # short stream: zeros follow, as tiff_codec.c does on the host
     assert status == 0 and np.array_equal(got[:5000], raw) and not got[5000:].any()
     out, status = engine.inflate_tiles([st], 100, [30], [(0, 0, 100, 30, 0, 0)], (30, 100))
     assert int(status[0]) == 0 and np.array_equal(out.reshape(-1), raw[:3000])     # long stream: cut
@@ -149,7 +149,7 @@ def test_many_tiles_with_windows(engine):
 def test_raw_and_predictor2_tiles_mixed_with_deflate_ones(engine):
     """Round 3 (ABI 3, gcn10_inflate_tile.flags): uncompressed chunks are untiled from the staged bytes --
     whole, or staged from the first wanted pixel on --, and chunks written with TIFF predictor 2 are summed
-    back row by row, modulo 256, from each row's first pixel (tiff.c decode_chunk is the host form).  One
+    back row by row, modulo 256, from each row's first pixel (tiff_codec.c gcn10_tiff_decode_chunk is the host form).  One
     launch holds all four kinds; chunk widths that are and are not multiples of the 1024-byte trip."""
     rng = np.random.default_rng(21)
     for tw, th in ((256, 200), (1024, 64), (1500, 9), (37, 50)):

@@ -1,5 +1,5 @@
 """GPU decoding of LZW landcover tiles (GCN10_TILE_LZW tiles of gcn10_gpu_inflate_tiles, gcn10_lzw_decode.hip),
-through the C ABI and the status words, against the host reader (tiff.c lzw_decode), PIL's libtiff and the
+through the C ABI and the status words, against the host reader (tiff_codec.c lzw_decode), PIL's libtiff and the
 reference decoder of tests/lzw_model.py; and the gcn10 program end to end on LZW landcover."""
 import os
 import zlib

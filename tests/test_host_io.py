@@ -350,7 +350,7 @@ def test_save_raster_errors(tmp_path):
         host.save_raster(_img(1, 4, 4), GT, str(tmp_path / "no_such_dir" / "x.tif"))
 
 
-# ---- read plans for the GPU decoder (csrc/host/raster.c, tiff.c) ----------------------------
+# ---- read plans for the GPU decoder (csrc/host/raster.c, tiff_window.c) ----------------------------
 
 def _assemble(plan, W, H):
     """What gcn10_gpu_inflate_tiles is asked to do with a plan, done here with stock zlib and numpy: DEFLATE

@@ -1,4 +1,4 @@
-"""Read plans of LZW landcover for the GPU decoder (host/raster.c, tiff.c: gcn10_raster_plan_window_codecs),
+"""Read plans of LZW landcover for the GPU decoder (host/raster.c, tiff_window.c: gcn10_raster_plan_window_codecs),
 and the config key gpu_inflate_lzw.  No GPU needed: the plans are carried out here with a Python LZW decoder
 and numpy, and compared with the host reader."""
 import numpy as np

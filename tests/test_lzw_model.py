@@ -1,5 +1,5 @@
 """The LZW model of tests/lzw_model.py and the crafted streams of tests/lzw_cases.py (CPU only): every family
-reaches what it is there for (stated through the reference decoder's trace), the host reader (tiff.c
+reaches what it is there for (stated through the reference decoder's trace), the host reader (tiff_codec.c
 lzw_decode) and libtiff read the streams as the model does, and every family tells the model from decoders
 that are wrong in one of the classic ways.  The GPU decoder's tests rest on this."""
 import collections

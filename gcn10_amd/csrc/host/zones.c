@@ -433,7 +433,7 @@ NO_CONTRACT static int first_index(double a, double b, int lo, int hi, double v,
 }
 
 struct edge {
-    double x1, y1, x2, y2;
+    double xl, yl, xh, yh;  /* from the endpoint of smaller y (xl, yl) to the other */
     int last;               /* last row it crosses */
     int next;               /* chain of the bucket of its first row */
 };
@@ -506,7 +506,9 @@ NO_CONTRACT static int scan_zone(const gcn10_zones *z, int zi, const double gt[6
             last = first_index(gt[3], gt[5], ry0, ry1 + 1, ylo, LT) - 1;
             if (last < first)
                 continue;
-            sc->edges[n_edges] = (struct edge){ x1, y1, x2, y2, last, sc->head[first - ry0] };
+            /* stored from the lower endpoint, so that both rings of a shared edge evaluate the same crossing */
+            sc->edges[n_edges] = y1 < y2 ? (struct edge){ x1, y1, x2, y2, last, sc->head[first - ry0] }
+                                         : (struct edge){ x2, y2, x1, y1, last, sc->head[first - ry0] };
             sc->head[first - ry0] = (int)n_edges++;
         }
     }
@@ -528,7 +530,7 @@ NO_CONTRACT static int scan_zone(const gcn10_zones *z, int zi, const double gt[6
         for (size_t a = 0; a < n_active;) {
             const struct edge *e = &sc->edges[sc->active[a]];
 
-            sc->cross[n++] = e->x1 + (py - e->y1) * (e->x2 - e->x1) / (e->y2 - e->y1);
+            sc->cross[n++] = e->xl + (py - e->yl) * (e->xh - e->xl) / (e->yh - e->yl);
             if (e->last <= y)
                 sc->active[a] = sc->active[--n_active];
             else

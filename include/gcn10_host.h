@@ -360,9 +360,14 @@ typedef struct gcn10_zone_item { uint32_t first_span, n_spans; } gcn10_zone_item
 /* Scan conversion of the zones over one block.  The block has the clipped geotransform gt (gcn10_raster_window;
  * north up: gt[1] > 0, gt[5] < 0, no rotation) and W x H pixels; pixel (x, y) has the centre
  *   px = gt[0] + (x + 0.5) * gt[1],  py = gt[3] + (y + 0.5) * gt[5]     (IEEE double, this order, no FMA).
- * Membership: an edge (x1,y1)-(x2,y2) of any ring of the zone crosses row y iff (y1 <= py) != (y2 <= py), at
- * xc = x1 + (py - y1) * (x2 - x1) / (y2 - y1); with the row's crossings sorted c0 <= c1 <= ..., the pixel is in the
- * zone iff c[2i] <= px < c[2i+1] for some i (even-odd: holes and nested parts need no special case).
+ * Membership: an edge (x1,y1)-(x2,y2) of any ring of the zone crosses row y iff (y1 <= py) != (y2 <= py).  The
+ * crossing is evaluated from the edge's lower endpoint, whichever way the ring runs: with (xl,yl) the endpoint of
+ * smaller y and (xh,yh) the other (a horizontal edge crosses no row, so one y is smaller),
+ *   xc = xl + (py - yl) * (xh - xl) / (yh - yl)                         (IEEE double, this order, no FMA);
+ * with the row's crossings sorted c0 <= c1 <= ..., the pixel is in the zone iff c[2i] <= px < c[2i+1] for some i
+ * (even-odd: holes and nested parts need no special case).  Two zones that share an edge, one ring running it P->Q
+ * and the other Q->P, compute the same double for it, so a pixel whose centre lies on the edge is in exactly one of
+ * them: zones that tile an area count each of its pixels once.
  * Ownership: only pixels with own[0] <= px < own[2] and own[1] < py <= own[3] are counted (own = the block's
  * shapefile bounding box {minx, miny, maxx, maxy}; NULL = every pixel of the window), so that blocks whose windows
  * overlap count every pixel once.

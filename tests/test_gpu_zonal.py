@@ -1,11 +1,13 @@
 """GPU: the pair histogram per zone (gcn10_gpu_zonal_pair_histogram) through the ABI face, against numpy: per zone a
 bincount over (bin of the soil code, landcover) of the pixels its spans name.  Shapes are the smallest at which the
 kernel can go wrong: widths around the 16-pixel column group, a last row that ends off a group, spans of one pixel,
-item boundaries inside a zone and inside a row, more zones than workgroups."""
+item boundaries inside a zone and inside a row, more zones than workgroups; and the spans of a real plan, a
+tessellation read from a shapefile."""
 import numpy as np
 import pytest
 
 from gcn10_amd import gpu, host
+from tests import zoneutil
 from tests.test_gpu_stats import model_histogram, soil_code
 from tests.util import ESA_NASTY, HSG_NASTY
 
@@ -164,6 +166,35 @@ def test_one_zone_over_the_strip_equals_the_pair_histogram(engine, W, rows):
             np.testing.assert_array_equal(sc.run(s2, items, 1)[0], plain)       # bin for bin
     finally:
         hist.close()
+        sc.close()
+
+
+def test_a_tessellation_planned_from_a_shapefile_counts_its_hull_once(engine, tmp_path):
+    """The kernel on a real plan: 1152 triangles with every vertex on a pixel centre (tests/test_zones_ties.py), read
+    from a shapefile and scan-converted by gcn10_zones_build_plan.  Each zone against numpy over its spans, and all
+    zones together, bin for bin, against the pair histogram of the rectangle the rule gives to the lattice's hull: a
+    pixel on a shared edge counted twice or not at all shows here.  More zones than workgroups: zones change inside
+    a workgroup."""
+    W, rows = 203, 151
+    gt = zoneutil.TIE_GTS[0]
+    rings, (x0, x1, y0, y1) = zoneutil.lattice_triangles(gt, 1, 2, 24, 24, 8, 6, seed=5)
+    zoneutil.write_zone_shapefile(str(tmp_path / "z"), [(i, [r]) for i, r in enumerate(rings)])
+    sc = Scene(engine, W, rows, 7, seed=21)
+    try:
+        hull = model_histogram(sc.esa[y0:y1, x0:x1], sc.soil[y0:y1, x0:x1])
+        assert int(hull.sum()) == (x1 - x0) * (y1 - y0) == 192 * 144
+        with host.Zones(str(tmp_path / "z.shp")) as z:
+            plans = [z.build_plan(gt, W, rows, max_span_px=s, max_item_px=i) for s, i in ((0, 0), (5, 7))]
+        assert len(plans[1]["spans"]) > len(plans[0]["spans"]) and len(plans[1]["items"]) > len(plans[0]["items"])
+        for plan in plans:
+            n_zones = len(plan["local_zone"])
+            assert n_zones == len(rings) == 1152
+            want = sc.model(plan["spans"], n_zones)
+            np.testing.assert_array_equal(want.sum(axis=1), plan["local_pixels"])
+            got = sc.run(plan["spans"], plan["items"], n_zones)
+            np.testing.assert_array_equal(got, want)
+            np.testing.assert_array_equal(got.sum(axis=0), hull)
+    finally:
         sc.close()
 
 

@@ -1,7 +1,7 @@
 """GPU: the zonal run mode end to end.  A small world -- DEFLATE landcover in 256^2 tiles at the real pixel size, LZW
 soil 25 times coarser, two adjacent blocks whose windows share a pixel column -- and a zone file; the table
 `bin/gcn10 --zones` writes against the oracle's 18 rasters of each block, masked by the numpy membership and ownership
-rules of tests/zoneutil.py."""
+rules of tests/zoneutil.py; and a second zone file, a triangulated lattice on pixel centres across both blocks."""
 import math
 import os
 import subprocess
@@ -39,15 +39,23 @@ def _run(cwd, *args):
     return subprocess.run([GCN10, *args], cwd=str(cwd), capture_output=True, text=True, timeout=300)
 
 
-def _expected(esa, soil, tables):
-    """per zone record and raster: [pixels, valid, sum, sum of squares, min, max] in Python integers"""
-    want = [[[0, 0, 0, 0, 255, 0] for _r in range(18)] for _z in ZONES]
+def _oracle_blocks(esa, soil, tables):
+    """per block: its window, clipped geotransform, box and the oracle's 18 rasters"""
+    out = []
     for _bid, *bbox in BLOCKS:
         xo, yo, W, H, gt = oc.window(ESA_GT, RX, RY, bbox)
         sxo, syo, hsx, hsy, sgt = oc.window(SOIL_GT, soil.shape[1], soil.shape[0], bbox)
         cn = oc.process_block_mem(esa[yo:yo + H, xo:xo + W], gt, soil[syo:syo + hsy, sxo:sxo + hsx], sgt, tables)
+        out.append((xo, yo, W, H, gt, bbox, cn))
+    return out
+
+
+def _expected(blocks, zones):
+    """per zone record and raster: [pixels, valid, sum, sum of squares, min, max] in Python integers"""
+    want = [[[0, 0, 0, 0, 255, 0] for _r in range(18)] for _z in zones]
+    for _xo, _yo, W, H, gt, bbox, cn in blocks:
         own = zoneutil.own_mask(gt, W, H, bbox)
-        for zi, (_id, rings) in enumerate(ZONES):
+        for zi, (_id, rings) in enumerate(zones):
             if rings is None:
                 continue
             mask = zoneutil.zone_mask(rings, gt, W, H) & own
@@ -86,7 +94,8 @@ def world(tmp_path_factory, tables):
     wins = [oc.window(ESA_GT, RX, RY, b[1:]) for b in BLOCKS]
     assert wins[0][0] + wins[0][2] == wins[1][0] + 1        # the blocks' windows share one pixel column
     out = _run(d, "-c", "config1.txt", "--zones", "zones.shp")
-    return {"dir": d, "esa": esa, "soil": soil, "want": _expected(esa, soil, tables), "run1": out}
+    blocks = _oracle_blocks(esa, soil, tables)
+    return {"dir": d, "esa": esa, "soil": soil, "blocks": blocks, "want": _expected(blocks, ZONES), "run1": out}
 
 
 def _rows(path):
@@ -95,10 +104,10 @@ def _rows(path):
     return [ln.split(",") for ln in lines[1:-1]]
 
 
-def _check_rows(rows, want, sel):
-    assert len(rows) == len(ZONES) * len(sel)
+def _check_rows(rows, want, sel, zones=ZONES):
+    assert len(rows) == len(zones) * len(sel)
     it = iter(rows)
-    for zi, (zid, _rings) in enumerate(ZONES):          # one row per zone record, file order, x selected raster
+    for zi, (zid, _rings) in enumerate(zones):          # one row per zone record, file order, x selected raster
         for r in sel:
             row = next(it)
             pixels, valid, total, sq, lo, hi = want[zi][r]
@@ -126,6 +135,37 @@ def test_the_table_equals_the_oracle_rasters_masked_by_the_zones(world):
     assert "zonal block 7: " in log and "zonal block 8: " in log and " zones, " in log and " spans" in log
     assert not [f for f in os.listdir(d) if f.startswith("cn_rasters_") or ".part" in f]
     assert not (d / "zonal_cn.csv").exists()            # zonal_output names the table
+
+
+def test_a_tessellation_across_both_blocks_counts_every_owned_pixel_of_its_hull_once(world):
+    """A second zone file: a lattice of 8 x 7 cells of 80 x 60 px with every vertex on a pixel centre of the landcover
+    grid, two triangles per cell, across the blocks' shared column 336.  Its diagonals pass through a centre every
+    (4, 3) pixels.  The table against the oracle as above; and per raster the zones' pixels add up to the hull's, which a
+    pixel on a shared edge counted by both neighbours or by neither would not."""
+    d = world["dir"]
+    rings, (x0, x1, y0, y1) = zoneutil.lattice_triangles(ESA_GT, 12, 8, 8, 7, 80, 60, seed=8)
+    zones = [(500 + i, [r]) for i, r in enumerate(rings)]
+    zoneutil.write_zone_shapefile(str(d / "lattice"), zones)
+    cfg = (d / "config1.txt").read_text().replace("table1.csv", "table4.csv").replace("logs1", "logs4")
+    (d / "config4.txt").write_text(cfg)
+    out = _run(d, "-c", "config4.txt", "--zones", "lattice.shp")
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    # the hull's owned pixels by the rule on every block's own centres; those equal the grid's at the hull's sides, so
+    # that is the rectangle of the grid (a block's clipped geotransform can put a centre an ulp off the grid's)
+    gpx, gpy = zoneutil.centres(ESA_GT, RX, RY)
+    hull = 0
+    for xo, yo, W, H, gt, bbox, _cn in world["blocks"]:
+        bpx, bpy = zoneutil.centres(gt, W, H)
+        assert all(bpx[c - xo] == gpx[c] for c in (x0, x1) if xo <= c < xo + W) and (bpy == gpy[yo:yo + H]).all()
+        hull += int((zoneutil.hull_mask(gt, W, H, rings) & zoneutil.own_mask(gt, W, H, bbox)).sum())
+    assert hull == (x1 - x0) * (y1 - y0) == 640 * 420 and x0 < 336 < x1
+    want = _expected(world["blocks"], zones)
+    assert min(w[0][0] for w in want) > 0               # every triangle has pixels
+    rows = _rows(d / "table4.csv")
+    _check_rows(rows, want, range(18), zones)
+    for r in range(18):
+        assert sum(int(row[4]) for row in rows[r::18]) == hull
+    assert "zonal: 2 blocks, %d zones, 0 without pixels, table table4.csv" % len(zones) in out.stderr
 
 
 def test_lookups_and_conditions_select_the_rows(world):

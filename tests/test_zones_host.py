@@ -1,6 +1,8 @@
 """CPU: the zone reader and the scan conversion (gcn10_amd/csrc/host/zones.c): shapefiles of a writer of its own, the
 spans against a numpy point-in-polygon over every pixel centre, ownership across two overlapping blocks, the items,
-and a stand-alone program under AddressSanitizer + UBSan over truncated and corrupted files."""
+and a stand-alone program under AddressSanitizer + UBSan over truncated and corrupted files, a tessellation on pixel
+centres and huge coordinates.  The fixtures here keep clear of pixel centres; tests/test_zones_ties.py holds the
+scan conversion to the cases where a centre lies on an edge or a vertex."""
 import os
 import shutil
 import struct
@@ -246,6 +248,22 @@ def test_sanitized_program_survives_truncated_and_corrupted_files(tmp_path):
         p = run(base + ".shp")
         assert p.returncode == 0 and p.stdout.startswith("zones %d local 8 " % len(ZONES)), p.stdout + p.stderr
         good[st] = base
+    # ties: a tessellation with every vertex on a pixel centre, which owns each pixel of its hull once; and huge
+    # coordinates: boxes around the window and triangles with one vertex up to 1.7e308 away, above, below and beside it
+    rings, (x0, x1, y0, y1) = zoneutil.lattice_triangles(GT, 1, 2, 24, 24, 8, 6, seed=5)
+    zoneutil.write_zone_shapefile(str(tmp_path / "ties"), [(i, [r]) for i, r in enumerate(rings)])
+    p = run(str(tmp_path / "ties.shp"))
+    assert p.returncode == 0 and p.stdout.startswith("zones 1152 local 1152 "), p.stdout + p.stderr
+    assert p.stdout.split()[-2:] == ["pixels", str((x1 - x0) * (y1 - y0))], p.stdout
+    far, near = [], [zoneutil.pt(GT, 20, 130), zoneutil.pt(GT, 60, 20)]
+    for d in (1e6, 1e150, 1.7e308):
+        far += [[[(-d, -d), (d, -d), (d, d), (-d, d)]], [near + [(d, d)]], [near + [(d, -d)]], [near + [(-d, near[0][1])]]]
+    zoneutil.write_zone_shapefile(str(tmp_path / "far"), [(i, r) for i, r in enumerate(far)])
+    p = run(str(tmp_path / "far.shp"))
+    with np.errstate(all="ignore"):
+        pixels = sum(int(zoneutil.zone_mask(r, GT, W, H).sum()) for r in far)
+    assert p.returncode == 0 and p.stdout.startswith("zones %d local " % len(far)), p.stdout + p.stderr
+    assert p.stdout.split()[-2:] == ["pixels", str(pixels)] and pixels >= 3 * W * H, p.stdout
     # every truncation and a few hundred single-byte corruptions of the Polygon file, in one run of the program
     # (it takes a directory and goes through its .shp files)
     shp = open(good[5] + ".shp", "rb").read()

@@ -12,12 +12,10 @@
 // malloc'd buffers, src/raster.c:169-178):
 //   esa      [rows*W]            landcover strip, read once, 16 B / lane
 //   out[r]   [rows*W]  r < 18    CN rasters, written once, 16 B / lane, nontemporal
-//   hx4      [hsy][hx_stride/16] compact soil words, one dword per 16-px column group and
-//                                coarse row (13 MB for a 36000-wide block), read by the
-//                                strips of 16-byte aligned rows
 //   codes    [hsy][codes_stride] one byte per coarse soil cell holding both remapped
 //                                soil groups, and cx[W'], the coarse column of every fine
-//                                column (2.1 MB + 144 KB): the snapshot hx is made from
+//                                column (2.1 MB + 144 KB): what the strips of 16-byte aligned
+//                                rows read, and the snapshot hx is made from
 //   hx       [hsy][hx_stride]    the same codes expanded along x, one byte per fine
 //                                column (52 MB for a 36000-wide block); made on demand
 //                                for the kernels that read soil per pixel (soil_bytes)
@@ -80,9 +78,7 @@ struct StripParams {
     uint32_t table_mask;
     uint32_t single_k;      // table index for the single-table variant
     uint32_t xcd_slabs;     // 1: each XCD streams a contiguous eighth of the strip
-    // soil tables of the prepared tile (see soil_tables_kernel); hx4 = null: not in use, hx holds the bytes
-    const uint32_t *hx4;            // compact soil words, one per 16-px column group and coarse row
-    uint32_t hx4_stride;            // dwords per coarse row
+    // soil tables of the prepared tile (see soil_tables_kernel); codes = null: not in use, hx holds the bytes
     const uint32_t *cx;             // coarse column of every fine column
     const uint8_t *codes;           // soil code of every coarse cell, codes_stride bytes per coarse row
     uint32_t codes_stride;
@@ -208,10 +204,12 @@ constexpr uint32_t kMinVectorW = kWavePx + 16u;
 
 // Where a strip kernel takes the soil codes of a lane's 16 pixels from.
 //   kSoilBytes:  the code bytes of the hx workspace (any W)
-//   kSoilWords:  W % 16 == 0, so the 16 pixels are one column group: one compact word {code a, code b, split}
+//   kSoilLanes:  W % 16 == 0, so the 16 pixels are one column group, and the lane keeps that group for the whole
+//                launch (gcn10::strip_lane_plan): its column entry {c_lo, c_hi, split} is made once, a trip loads
+//                the two codes of its coarse row from the codes table
 //   kSoilPixels: the codes table through the column map, pixel by pixel, for a tile with a group that has no
-//                compact word
-enum { kSoilBytes = 0, kSoilWords = 1, kSoilPixels = 2 };
+//                compact entry (the same lane plan)
+enum { kSoilBytes = 0, kSoilLanes = 1, kSoilPixels = 2 };
 
 // What a lane holds of one trip between issuing its loads and using them.
 template <int ILP>
@@ -220,7 +218,8 @@ struct Trip {
     uint32_t i0[ILP];
 };
 
-template <int ILP, bool NT, int SOIL>
+// The loads of one trip of a strip that reads the code bytes: chunks of 4096 px dealt by first_chunk.
+template <int ILP, bool NT>
 __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, uint32_t lane_off,
                                            uint32_t wave_off, Trip<ILP> &tr)
 {
@@ -248,29 +247,6 @@ __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, 
         const bool wrap = xl >= p.W;
         xl = wrap ? xl - p.W : xl;
         const uint32_t row = p.soil.clamp(wrap ? r1[u] : r0[u]);
-        if (SOIL == kSoilWords) {
-            tr.c16[u] = u32x4{ p.hx4[(size_t)row * p.hx4_stride + (xl >> 4)], 0u, 0u, 0u };
-            continue;
-        }
-        if (SOIL == kSoilPixels) {
-            // rare (a tile with fewer than 8 columns per soil cell, a map that is not monotone): asked to be right,
-            // not fast -- a rolled loop, so that it adds nothing to the registers of the kernel
-            const uint8_t *cr = p.codes + (size_t)row * p.codes_stride;
-            const u32x4 *pc = reinterpret_cast<const u32x4 *>(p.cx + xl);   // W % 16 == 0: xl is a multiple of 16
-            u32x4 a = { 0u, 0u, 0u, 0u };
-#pragma unroll 1
-            for (int j = 0; j < 4; j++) {
-                const u32x4 c4 = pc[j];
-                const uint32_t w = (uint32_t)cr[c4[0]] | (uint32_t)cr[c4[1]] << 8 | (uint32_t)cr[c4[2]] << 16 |
-                                   (uint32_t)cr[c4[3]] << 24;
-                a[0] = j == 0 ? w : a[0];
-                a[1] = j == 1 ? w : a[1];
-                a[2] = j == 2 ? w : a[2];
-                a[3] = j == 3 ? w : a[3];
-            }
-            tr.c16[u] = a;
-            continue;
-        }
         const uint8_t *pa = p.soil.at(row, xl);
         u32x4 a = load16_any(pa);
         if (p.W & 15u) {
@@ -293,31 +269,152 @@ __device__ __forceinline__ void issue_trip(const StripParams &p, uint32_t trip, 
     }
 }
 
-// Table gathers and stores of one trip.
-// Soil code bytes of a lane's 16 pixels from the compact word {code a, code b, split, -}: pixels [0, split)
-// have code a, the rest code b.
-__device__ __forceinline__ u32x4 expand_soil_word(uint32_t w)
+// ---- strips that read the soil tables: one column group per lane (gcn10::strip_lane_plan) ----
+// What such a lane keeps for the whole launch.
+struct LaneSoil {
+    uint32_t base;          // pixel index of the lane's vector in sub-trip 0
+    uint32_t lim;           // end of the lane's piece in pixels; 0 for a lane without a column group
+    uint32_t sub_px;        // pixels per sub-trip (B rows), wave-uniform
+    uint32_t y_first;       // strip row of the wave's first lane in sub-trip 0, wave-uniform
+    uint32_t B;
+    bool wrap;              // the lane is behind the row end inside its wave: one row further than the first lane
+    uint32_t x;             // first fine column of the group
+    uint32_t c_lo, c_hi;    // coarse columns of the group's first and last pixel
+    int32_t split;          // pixels [0, split) of the 16 take the code of c_lo, the rest that of c_hi
+    uint32_t mask[4];       // the same as byte masks of the four dwords (single-table kernel: see mix_lane_codes)
+    bool pair;              // wave-uniform: c_hi is c_lo or c_lo + 1 in every lane, one 2-byte load fetches both codes
+};
+
+// byte mask of dword j of a lane's 16 pixels: the bytes of the pixels below `split`
+__device__ __forceinline__ uint32_t split_mask(int32_t split, int j)
 {
-    const uint32_t a = (w & 0xffu) * 0x01010101u, b = ((w >> 8) & 0xffu) * 0x01010101u;
-    const int32_t split = (int32_t)((w >> 16) & 0xffu);
+    const int32_t m = split - 4 * j;
+    return m >= 4 ? 0xffffffffu : (m <= 0 ? 0u : (1u << (8 * m)) - 1u);
+}
+
+template <int SOIL>
+__device__ __forceinline__ void lane_prologue(const StripParams &p, const gcn10::StripLanePlan &pl, LaneSoil &ls)
+{
+    const uint32_t g_first = __builtin_amdgcn_readfirstlane(pl.g);
+    ls.base = (pl.row_lo * pl.G + pl.t) * (uint32_t)kPxPerLane;
+    ls.lim = pl.active ? pl.row_hi * p.W : 0u;
+    ls.sub_px = pl.B * p.W;
+    ls.y_first = pl.row_lo + __builtin_amdgcn_readfirstlane(pl.rho);
+    ls.B = pl.B;
+    ls.wrap = pl.g < g_first;
+    ls.x = pl.g * (uint32_t)kPxPerLane;
+    ls.c_lo = ls.c_hi = 0u;
+    ls.split = 16;
+    ls.pair = true;
+    if (SOIL == kSoilLanes) {
+        // the column entry, by the rule of soil_tables_kernel: a run of c_lo, then c_hi (cx is already clamped)
+        uint32_t cx[16];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const u32x4 c4 = *reinterpret_cast<const u32x4 *>(p.cx + ls.x + 4 * j);
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                cx[4 * j + q] = c4[q];
+        }
+        ls.c_lo = cx[0];
+        ls.c_hi = cx[15];
+        uint32_t split = 0;
+#pragma unroll
+        for (int q = 0; q < 16; q++)
+            split += cx[q] == ls.c_lo && split == (uint32_t)q ? 1u : 0u;
+        ls.split = (int32_t)split;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            ls.mask[j] = split_mask(ls.split, j);
+        // (a row of codes ends with a padding code: the byte behind c_lo exists)
+        ls.pair = __builtin_amdgcn_ballot_w64(ls.c_hi - ls.c_lo > 1u) == 0ull;
+    }
+}
+
+template <int ILP, bool NT, int SOIL>
+__device__ __forceinline__ void issue_lane_trip(const StripParams &p, const LaneSoil &ls, uint32_t trip,
+                                                Trip<ILP> &tr)
+{
+    // ---- wave-uniform part: the strip row of the wave's first lane, its coarse row and the next row's through the
+    // scalar cache (s_load, own counter), as offsets into the codes table ----
+    uint32_t o0[ILP], o1[ILP];
+#pragma unroll
+    for (int u = 0; u < ILP; u++) {
+        const uint32_t y = ls.y_first + (trip * ILP + u) * ls.B;
+        const uint32_t ya = y < p.rows ? y : p.rows - 1u;       // a wave past the end only needs valid addresses
+        const uint32_t yb = y + 1u < p.rows ? y + 1u : p.rows - 1u;
+        o0[u] = p.soil.clamp((uint32_t)scalar_load_i32(p.soil.cj, ya)) * p.codes_stride;
+        o1[u] = p.soil.clamp((uint32_t)scalar_load_i32(p.soil.cj, yb)) * p.codes_stride;
+    }
+#pragma unroll
+    for (int u = 0; u < ILP; u++) {
+        const uint32_t i0 = ls.base + (trip * ILP + u) * ls.sub_px;
+        const bool live = i0 < ls.lim;
+        tr.i0[u] = live ? i0 : 0xffffffffu;                     // (finish_trip: not below nvec16, no store)
+        const uint8_t *pe = p.esa + (live ? i0 : 0u);
+        tr.e16[u] = NT ? load16_aligned_nt(pe) : load16_aligned(pe);
+    }
+#pragma unroll
+    for (int u = 0; u < ILP; u++) {
+        const uint32_t off = ls.wrap ? o1[u] : o0[u];
+        if (SOIL == kSoilLanes) {
+            typedef uint16_t u16_u __attribute__((aligned(1)));
+            tr.c16[u][0] = *reinterpret_cast<const u16_u *>(p.codes + (off + ls.c_lo));
+            if (!ls.pair)
+                tr.c16[u][1] = p.codes[off + ls.c_hi];
+        }
+        else {
+            // rare (a tile with fewer than 8 columns per soil cell, a map that is not monotone): asked to be right,
+            // not fast -- a rolled loop, so that it adds nothing to the registers of the kernel
+            const uint8_t *cr = p.codes + off;
+            const u32x4 *pc = reinterpret_cast<const u32x4 *>(p.cx + ls.x);
+            u32x4 a = { 0u, 0u, 0u, 0u };
+#pragma unroll 1
+            for (int j = 0; j < 4; j++) {
+                const u32x4 c4 = pc[j];
+                const uint32_t w = (uint32_t)cr[c4[0]] | (uint32_t)cr[c4[1]] << 8 | (uint32_t)cr[c4[2]] << 16 |
+                                   (uint32_t)cr[c4[3]] << 24;
+                a[0] = j == 0 ? w : a[0];
+                a[1] = j == 1 ? w : a[1];
+                a[2] = j == 2 ? w : a[2];
+                a[3] = j == 3 ? w : a[3];
+            }
+            tr.c16[u] = a;
+        }
+    }
+}
+
+// Soil code bytes of a lane's 16 pixels from the two codes of its column entry: pixels [0, split) have the code of
+// c_lo, the rest the code of c_hi.  KEEP_MASKS: the four byte masks are registers of the whole launch (the
+// single-table kernel has them to spare).  Else they are made again from `split` for every vector, and the compiler
+// is kept from hoisting them: with the masks loop-invariant it also hoists what the all-tables gather derives from
+// them, 20 to 30 VGPRs and a wave per SIMD in the pipelined variants.
+template <bool KEEP_MASKS>
+__device__ __forceinline__ u32x4 mix_lane_codes(const LaneSoil &ls, const u32x4 &c)
+{
+    const uint32_t a = (c[0] & 0xffu) * 0x01010101u;
+    const uint32_t b = (ls.pair ? (c[0] >> 8) & 0xffu : c[1] & 0xffu) * 0x01010101u;
     u32x4 cd;
+    int32_t split = ls.split;
+    if (!KEEP_MASKS)
+        asm volatile("" : "+v"(split));
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const int32_t m = split - 4 * j;        // bytes of dword j that hold code a
-        const uint32_t mask = m >= 4 ? 0xffffffffu : (m <= 0 ? 0u : (1u << (8 * m)) - 1u);
+        const uint32_t mask = KEEP_MASKS ? ls.mask[j] : split_mask(split, j);
         cd[j] = (a & mask) | (b & ~mask);
     }
     return cd;
 }
 
+// Table gathers and stores of one trip.
 template <int KIND, int COND_MASK, int ILP, bool NT, int SOIL>
 __device__ __forceinline__ void finish_trip(const StripParams &p, const uint8_t *lut, uint32_t tmask,
-                                            const Trip<ILP> &tr)
+                                            const Trip<ILP> &tr, const LaneSoil &ls)
 {
 #pragma unroll
     for (int u = 0; u < ILP; u++) {
         const bool live = tr.i0[u] < p.nvec16;
-        const u32x4 c16 = SOIL == kSoilWords ? expand_soil_word(tr.c16[u][0]) : tr.c16[u];
+        const u32x4 c16 = SOIL == kSoilLanes ? mix_lane_codes<KIND == kLut1>(ls, tr.c16[u]) : tr.c16[u];
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             if (!(COND_MASK & (1 << c)))
@@ -358,41 +455,60 @@ __device__ __forceinline__ void finish_trip(const StripParams &p, const uint8_t 
     }
 }
 
-// The trip loop of cn_strip_kernel.
+// The trip loop of cn_strip_kernel.  SOIL == kSoilBytes: trips are groups of ILP chunks of 4096 px, dealt by
+// first_chunk (p.nchunks counts them).  Else: the trips of the lane plan, every lane in its column group.
 template <int KIND, int COND_MASK, int ILP, bool NT, bool PF, int SOIL>
-__device__ __forceinline__ void strip_loop(const StripParams &p, const uint8_t *lut, uint32_t tmask,
-                                           uint32_t lane_off, uint32_t wave_off)
+__device__ __forceinline__ void strip_loop(const StripParams &p, const uint8_t *lut, uint32_t tmask)
 {
-    // p.nchunks counts trips (groups of ILP chunks of 4096 px) here
-    uint32_t step, end;
-    uint32_t trip = first_chunk(p.nchunks, step, end, p.xcd_slabs != 0);
+    uint32_t step = 1u, end, trip = 0u, lane_off = 0u, wave_off = 0u;
+    LaneSoil ls = {};
+    if (SOIL == kSoilBytes) {
+        lane_off = (threadIdx.x & 63u) * kPxPerLane;
+        wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kWavePx;
+        trip = first_chunk(p.nchunks, step, end, p.xcd_slabs != 0);
+    }
+    else {
+        const gcn10::StripLanePlan pl = gcn10::strip_lane_plan(p.W, p.rows, gridDim.x, blockIdx.x, threadIdx.x,
+                                                               p.xcd_slabs != 0, (uint32_t)ILP);
+        end = __builtin_amdgcn_readfirstlane(pl.trips);
+        // (lane numbers rise within a wave: its first lane has a column group or none has)
+        if (!__builtin_amdgcn_readfirstlane((uint32_t)pl.active))
+            return;
+        lane_prologue<SOIL>(p, pl, ls);
+    }
     if (trip >= end)
         return;
+    auto issue = [&](uint32_t t, Trip<ILP> &tr) {
+        if (SOIL == kSoilBytes)
+            issue_trip<ILP, NT>(p, t, lane_off, wave_off, tr);
+        else
+            issue_lane_trip<ILP, NT, SOIL>(p, ls, t, tr);
+    };
     if (!PF) {
         for (; trip < end; trip += step) {
             Trip<ILP> tr;
-            issue_trip<ILP, NT, SOIL>(p, trip, lane_off, wave_off, tr);
-            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tr);
+            issue(trip, tr);
+            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tr, ls);
         }
     }
     else {
         Trip<ILP> ta, tb;       // used alternately: a copy would wait for the loads it copies
-        issue_trip<ILP, NT, SOIL>(p, trip, lane_off, wave_off, ta);
+        issue(trip, ta);
         for (;;) {
             trip += step;
             if (trip >= end) {
-                finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, ta);
+                finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, ta, ls);
                 break;
             }
-            issue_trip<ILP, NT, SOIL>(p, trip, lane_off, wave_off, tb);
-            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, ta);
+            issue(trip, tb);
+            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, ta, ls);
             trip += step;
             if (trip >= end) {
-                finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tb);
+                finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tb, ls);
                 break;
             }
-            issue_trip<ILP, NT, SOIL>(p, trip, lane_off, wave_off, ta);
-            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tb);
+            issue(trip, ta);
+            finish_trip<KIND, COND_MASK, ILP, NT, SOIL>(p, lut, tmask, tb, ls);
         }
     }
 }
@@ -414,18 +530,16 @@ __global__ __launch_bounds__(kThreads) void cn_strip_kernel(const StripParams p)
     }
     __syncthreads();
 
-    const uint32_t lane_off = (threadIdx.x & 63u) * kPxPerLane;
-    const uint32_t wave_off = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) * kWavePx;
     const uint32_t tmask = ALL_TABLES ? 0x1ffu : p.table_mask;
 
-    // the soil tables when the host offers them: compact words, or the codes table pixel by pixel when some group
-    // of this tile is complex (wave-uniform: the flag comes through the scalar cache); else the code bytes
-    if (!p.hx4)
-        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilBytes>(p, lut, tmask, lane_off, wave_off);
+    // the soil tables when the host offers them: a column entry per lane, or the codes table pixel by pixel when some
+    // group of this tile is complex (wave-uniform: the flag comes through the scalar cache); else the code bytes
+    if (!p.codes)
+        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilBytes>(p, lut, tmask);
     else if ((uint32_t)scalar_load_i32(reinterpret_cast<const int32_t *>(p.soil_complex), 0u) != p.soil_gen)
-        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilWords>(p, lut, tmask, lane_off, wave_off);
+        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilLanes>(p, lut, tmask);
     else
-        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilPixels>(p, lut, tmask, lane_off, wave_off);
+        strip_loop<KIND, COND_MASK, ILP, NT, PF, kSoilPixels>(p, lut, tmask);
 
     // the last npix % 16 pixels, one per thread
     if (blockIdx.x == 0 && threadIdx.x < p.npix - p.nvec16) {
@@ -513,31 +627,27 @@ __global__ __launch_bounds__(kThreads) void cn_strip_bytes(const StripParams p,
 //   codes[r][c]  = soil_code(coarse[r][c]) for c < hsx, the "invalid" code for hsx <= c < codes_stride
 //   cx[x]        = ci[x] clamped to the window, whatever its value; hsx (a column of padding codes) for the
 //                  columns [W, hx_stride) right of the raster
-//   hx4[r][g]    = one COMPACT WORD per 16-px column group g and coarse row r: code a | code b << 8 | split << 16,
-//                  meaning pixels [0, split) of the group have code a and the rest code b.  At the usual ratio
-//                  (25 fine columns per coarse cell) every group has that form, and the strip kernels of 16-byte
-//                  aligned rows load one dword per lane.
-// A group that has no such form (three cells under 16 columns, a map that is not monotone) gets split = 0xff and
-// stores this tile's generation number in *complex (no reset between tiles needed); the strip kernels compare that
-// word with the generation they were launched for and go through codes and cx pixel by pixel for the whole tile
-// when it matches.
+// A 16-px column group g is COMPACT when its columns are a run of c_lo = cx[16g] followed by a run of
+// c_hi = cx[16g + 15]: pixels [0, split) have the code of c_lo and the rest the code of c_hi.  At the usual ratio
+// (25 fine columns per coarse cell) every group has that form, and a lane of a strip kernel of 16-byte aligned rows,
+// which stays in one column group, makes {c_lo, c_hi, split} from cx once and loads two code bytes per trip.
+// A group that has no such form (three cells under 16 columns, a map that is not monotone) stores this tile's
+// generation number in *complex (no reset between tiles needed); the strip kernels compare that word with the
+// generation they were launched for and go through codes and cx pixel by pixel for the whole tile when it matches.
 // codes and cx are a snapshot: the code bytes of the tile (expand_code_bytes) are made from them on demand, and the
 // caller's coarse and ci are not read after this kernel.
 // ------------------------------------------------------------------------
-constexpr uint32_t kWordRows = 8;       // coarse rows per thread of the words part
-
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void soil_tables_kernel(const uint8_t *coarse, uint32_t hsx, uint32_t hsy,
                                                                const int32_t *ci, uint32_t W, uint32_t hx_stride,
-                                                               uint32_t word_chunks, uint8_t *codes,
-                                                               uint32_t codes_stride, uint32_t *cx_out, uint32_t *hx4,
-                                                               uint32_t *complex, uint32_t gen)
+                                                               uint8_t *codes, uint32_t codes_stride,
+                                                               uint32_t *cx_out, uint32_t *complex, uint32_t gen)
 {
     const uint32_t pad = (uint32_t)(kInvalidPlane | (kInvalidPlane << 4));
-    if (blockIdx.y >= word_chunks) {
+    if (blockIdx.y >= 1u) {
         // ---- codes: one thread = 16 consecutive cells of one coarse row ----
         const uint32_t per_row = codes_stride / 16u;
-        const uint32_t t = ((blockIdx.y - word_chunks) * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
+        const uint32_t t = ((blockIdx.y - 1u) * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x;
         const uint32_t r = t / per_row;
         if (r >= hsy)
             return;
@@ -567,10 +677,9 @@ __global__ __launch_bounds__(kThreads) void soil_tables_kernel(const uint8_t *co
         *reinterpret_cast<u32x4 *>(codes + (size_t)r * codes_stride + c0) = o;
         return;
     }
-    // ---- column map and compact words: one thread = 16 consecutive fine columns of kWordRows coarse rows ----
+    // ---- column map and the complex-tile word: one thread = 16 consecutive fine columns ----
     const uint32_t x = (blockIdx.x * blockDim.x + threadIdx.x) * 16u;
-    const uint32_t r0 = blockIdx.y * kWordRows;
-    if (x >= hx_stride || r0 >= hsy)
+    if (x >= hx_stride)
         return;
     uint32_t cx[16];
     if (VEC && x + 16u <= W) {
@@ -603,22 +712,12 @@ __global__ __launch_bounds__(kThreads) void soil_tables_kernel(const uint8_t *co
         compact = compact && (lo ? split == (uint32_t)q : cx[q] == c_hi);
         split += lo && split == (uint32_t)q ? 1u : 0u;
     }
-    if (blockIdx.y == 0) {
 #pragma unroll
-        for (int j = 0; j < 4; j++)
-            *reinterpret_cast<u32x4 *>(cx_out + x + 4 * j) =
-                u32x4{ cx[4 * j], cx[4 * j + 1], cx[4 * j + 2], cx[4 * j + 3] };
-        if (x < W && !compact && *reinterpret_cast<volatile uint32_t *>(complex) != gen)
-            *reinterpret_cast<volatile uint32_t *>(complex) = gen;      // every writer stores the same value
-    }
-    const uint32_t r1 = r0 + kWordRows < hsy ? r0 + kWordRows : hsy;
-    for (uint32_t r = r0; r < r1; r++) {
-        const uint8_t *row = coarse + (size_t)r * hsx;
-        // (hsx names the padding right of the raster: not a cell of the window)
-        const uint32_t a = c_lo < hsx ? soil_code(row[c_lo]) : pad, b = c_hi < hsx ? soil_code(row[c_hi]) : pad;
-        __builtin_nontemporal_store(compact ? a | (b << 8) | (split << 16) : 0x00ff0000u,
-                                    hx4 + (size_t)r * (hx_stride / 16u) + x / 16u);
-    }
+    for (int j = 0; j < 4; j++)
+        *reinterpret_cast<u32x4 *>(cx_out + x + 4 * j) =
+            u32x4{ cx[4 * j], cx[4 * j + 1], cx[4 * j + 2], cx[4 * j + 3] };
+    if (x < W && !compact && *reinterpret_cast<volatile uint32_t *>(complex) != gen)
+        *reinterpret_cast<volatile uint32_t *>(complex) = gen;      // every writer stores the same value
 }
 
 // ------------------------------------------------------------------------
@@ -1509,11 +1608,10 @@ int gcn10_gpu_prepare_tile(gcn10_gpu_ctx *ctx, const uint8_t *coarse, int hsx, i
     // read starting below W stays inside the row
     const uint32_t stride = (((uint32_t)W + 15u) & ~15u) + 16u;
     const size_t need_hx = ((size_t)stride * (size_t)hsy + 63) & ~(size_t)63;
-    // behind the code bytes: compact words, cx, codes (a row of codes ends with at least one padding code, which is
-    // what cx names for the columns right of the raster)
+    // behind the code bytes: cx, codes (a row of codes ends with at least one padding code, which is what cx names
+    // for the columns right of the raster, and what lets a strip lane load the two bytes at c_lo)
     const uint32_t codes_stride = (((uint32_t)hsx + 1u) + 15u) & ~15u;
-    const size_t off_words = need_hx;
-    const size_t off_cx = (off_words + (size_t)(stride / 16u) * 4u * (size_t)hsy + 15) & ~(size_t)15;
+    const size_t off_cx = (need_hx + 15) & ~(size_t)15;
     const size_t off_codes = (off_cx + (size_t)stride * 4u + 15) & ~(size_t)15;
     const size_t need = off_codes + (size_t)codes_stride * (size_t)hsy;
     if (need > ctx->hx_capacity) {
@@ -1532,7 +1630,6 @@ int gcn10_gpu_prepare_tile(gcn10_gpu_ctx *ctx, const uint8_t *coarse, int hsx, i
         ctx->d_hx = ctx->d_hx_alloc + 16;
         ctx->hx_capacity = need;
     }
-    ctx->d_hx4 = reinterpret_cast<uint32_t *>(ctx->d_hx + off_words);
     ctx->d_cx = reinterpret_cast<uint32_t *>(ctx->d_hx + off_cx);
     ctx->d_codes = ctx->d_hx + off_codes;
     ctx->codes_stride = codes_stride;
@@ -1544,13 +1641,12 @@ int gcn10_gpu_prepare_tile(gcn10_gpu_ctx *ctx, const uint8_t *coarse, int hsx, i
     ctx->hx_rows = (uint32_t)hsy;
     hipStream_t s = as_stream(ctx, stream);
     const uint32_t group_blocks = (stride / 16u + kThreads - 1) / kThreads;
-    const uint32_t word_chunks = ((uint32_t)hsy + kWordRows - 1) / kWordRows;
     const size_t code_threads = (size_t)(codes_stride / 16u) * (size_t)hsy;
     const uint32_t code_chunks = (uint32_t)((code_threads + (size_t)group_blocks * kThreads - 1) / ((size_t)group_blocks * kThreads));
     auto fn = aligned16(ci) ? soil_tables_kernel<true> : soil_tables_kernel<false>;
-    hipLaunchKernelGGL(fn, dim3(group_blocks, word_chunks + code_chunks), dim3(kThreads), 0, s, coarse, (uint32_t)hsx,
-                       (uint32_t)hsy, ci, (uint32_t)W, stride, word_chunks, ctx->d_codes, codes_stride, ctx->d_cx,
-                       ctx->d_hx4, ctx->d_soil_complex, ctx->soil_gen);
+    hipLaunchKernelGGL(fn, dim3(group_blocks, 1u + code_chunks), dim3(kThreads), 0, s, coarse, (uint32_t)hsx,
+                       (uint32_t)hsy, ci, (uint32_t)W, stride, ctx->d_codes, codes_stride, ctx->d_cx,
+                       ctx->d_soil_complex, ctx->soil_gen);
     HIP_TRY(hipGetLastError());
     // a tile whose strips are certain to read the bytes gets them now, behind the tables on the same stream
     if (!ctx->compact_soil || (W & 15)) {
@@ -1607,11 +1703,22 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
     // the vector kernel wants a wave's 1024-px span to cross at most one row end
     if (p.npix < 16u || p.W < kMinVectorW)
         all_aligned = false;
-    if (all_aligned && ctx->compact_soil && (p.W & 15u) == 0u) {
-        // rows are 16-byte aligned: a lane's 16 pixels are one column group of the compact soil words
+    // the launch shape of the vector kernel (needed here: whether a strip can read the soil tables depends on it)
+    const bool single = popcount(table_mask) == 1;
+    const bool tuned = single && ctx->single.set;
+    // 0 = by the number of store streams: two chunks per trip up to nine rasters, one beyond
+    const int n_streams = popcount(cond_mask) * popcount(table_mask);
+    const int ilp = tuned ? ctx->single.ilp
+                          : single ? ctx->ilp1 : (ctx->ilp16 > 0 ? ctx->ilp16 : (n_streams > 9 ? 1 : 2));
+    p.nchunks = (p.nchunks + (uint32_t)ilp - 1) / (uint32_t)ilp;    // groups of ILP sub-chunks
+    const uint32_t grid = stream_grid(ctx, p.nchunks, tuned ? ctx->single.grid_blocks_per_cu : 0);
+    if (tuned)
+        p.xcd_slabs = (uint32_t)ctx->single.xcd_slabs;
+    // rows are 16-byte aligned: a lane's 16 pixels are one column group, and the lane plan keeps it there -- unless
+    // a row has more column groups than the grid has threads (a very wide strip on a small grid: the code bytes)
+    if (all_aligned && ctx->compact_soil && (p.W & 15u) == 0u &&
+        gcn10::strip_lane_plan(p.W, p.rows, grid, 0u, 0u, p.xcd_slabs != 0, (uint32_t)ilp).B > 0u) {
         p.soil = SoilView{ nullptr, cj, ctx->hx_stride, ctx->hx_rows };
-        p.hx4 = ctx->d_hx4;
-        p.hx4_stride = ctx->hx_stride / 16u;
         p.cx = ctx->d_cx;
         p.codes = ctx->d_codes;
         p.codes_stride = ctx->codes_stride;
@@ -1631,13 +1738,7 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
         ctx->last_kernel = "cn_strip_bytes";
     }
     else {
-        const bool single = popcount(table_mask) == 1;
         const bool all = table_mask == 0x1ffu;
-        // 0 = by the number of store streams: two chunks per trip up to nine rasters, one beyond
-        const int n_streams = popcount(cond_mask) * popcount(table_mask);
-        const bool tuned = single && ctx->single.set;
-        const int ilp = tuned ? ctx->single.ilp
-                              : single ? ctx->ilp1 : (ctx->ilp16 > 0 ? ctx->ilp16 : (n_streams > 9 ? 1 : 2));
         const bool nt = ctx->nontemporal != 0;
         if (single) {
             p.single_k = (uint32_t)__builtin_ctz(table_mask);
@@ -1647,10 +1748,6 @@ int gcn10_gpu_cn_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
             p.lut = ctx->d_lut16;
         }
         const bool pf = (tuned ? ctx->single.prefetch : ctx->prefetch) != 0 && ilp <= 2;
-        p.nchunks = (p.nchunks + (uint32_t)ilp - 1) / (uint32_t)ilp;    // groups of ILP sub-chunks
-        const uint32_t grid = stream_grid(ctx, p.nchunks, tuned ? ctx->single.grid_blocks_per_cu : 0);
-        if (tuned)
-            p.xcd_slabs = (uint32_t)ctx->single.xcd_slabs;
         strip_kernel_t fn = pick_strip_kernel(single, cond_mask, all, ilp, nt, pf);
         if (!fn)
             return fail(GCN10_E_INVAL, "gcn10_gpu_cn_strip: no kernel for ilp=%d", ilp);

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "gcn10_gpu.h"
+#include "gcn10_strip_lanes.hpp"
 
 namespace gcn10 {
 
@@ -80,13 +81,12 @@ struct gcn10_gpu_ctx {
     // Soil workspace of the prepared tile (one allocation, grown by gcn10_gpu_prepare_tile):
     //   d_hx      [hx_rows][hx_stride]      soil code bytes, one per fine column.  Allocated with the tile, FILLED ON
     //                                        DEMAND: every reader gets them as a gcn10::SoilView from bind_soil()
-    //   d_hx4     [hx_rows][hx_stride / 16] compact soil words, one per 16-px column group and coarse row
     //   d_cx      [hx_stride]               clamped coarse column of every fine column; hsx = padding
     //   d_codes   [hx_rows][codes_stride]   soil code of every coarse cell; columns >= hsx hold the padding code
-    // d_cx and d_codes are a snapshot of the caller's `coarse` and `ci`: nothing reads those after prepare_tile.
+    // d_cx and d_codes are a snapshot of the caller's `coarse` and `ci`: nothing reads those after prepare_tile.  The
+    // strips of 16-byte aligned rows read them directly (one column group per lane), the other readers the bytes.
     uint8_t *d_hx = nullptr;        // row 0 of the soil-code bytes (= d_hx_alloc + 16)
     uint8_t *d_hx_alloc = nullptr;
-    uint32_t *d_hx4 = nullptr;
     uint32_t *d_cx = nullptr;
     uint8_t *d_codes = nullptr;
     uint32_t codes_stride = 0;

@@ -16,7 +16,7 @@ namespace gcn10 {
 // caller's strip to its coarse row.  cj comes from the caller (host-built, already clamped as src/cn.c:229 does); the
 // clamp here only keeps a bad map from reading outside the workspace.
 struct SoilView {
-    const uint8_t *hx;      // null in a strip that reads the compact soil words instead
+    const uint8_t *hx;      // null in a strip that reads the soil tables (codes, cx) instead
     const int32_t *cj;
     uint32_t stride, rows;
 

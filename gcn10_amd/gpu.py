@@ -324,7 +324,7 @@ class Engine:
         self._chk(lib().gcn10_gpu_stream_copy(self._ctx, src, dst, int(nbytes), stream), "gcn10_gpu_stream_copy")
 
     def soil_words_state(self, stream=None) -> int:
-        """What aligned strips of the prepared tile read: 0 = code bytes (option off), 1 = compact words,
+        """What aligned strips of the prepared tile read: 0 = code bytes (option off), 1 = one column entry per lane,
         2 = the cell codes through the column map, pixel by pixel (a column group of the tile spans more than two soil cells); see
         include/gcn10_gpu.h."""
         rc = lib().gcn10_gpu_soil_words_state(self._ctx, stream)

@@ -157,17 +157,22 @@ int gcn10_gpu_calculate_cn(gcn10_gpu_ctx *ctx, const uint8_t *esa,
  *
  * gcn10_gpu_prepare_tile: once per block.  Takes a snapshot of the soil of
  * the block into memory owned by the context -- the x half of
- * src/cn.c:218-232: the soil code of every coarse cell (hsx * hsy bytes),
+ * src/cn.c:218-232: the soil code of every coarse cell (hsx * hsy bytes) and
  * the clamped coarse column of every fine column (ci[x] < 0 or >= hsx names
- * column hsx - 1), and one compact word per 16-pixel column group and coarse
- * row (two codes and the position where the second begins).  `coarse` and
- * `ci` are not read after the kernel this call launches: the caller may
+ * column hsx - 1); it also notes whether every 16-pixel column group of the
+ * tile is compact, i.e. a run of one coarse column followed by a run of
+ * another.  Nothing is written per coarse row and column group.  `coarse`
+ * and `ci` are not read after the kernel this call launches: the caller may
  * reuse them once `stream` has passed it.
- * Strips whose width is a multiple of 16 read the compact words when every
- * group of the tile has that form, and otherwise the code of every pixel
- * from the cell codes through the column map
+ * Strips whose width is a multiple of 16 read that snapshot directly: every
+ * lane of the strip kernel stays in one column group for the whole launch,
+ * makes the group's two coarse columns and the position where the second
+ * begins from the column map once, and loads the two cell codes of its
+ * coarse row per 16 pixels.  When some group of the tile is not compact they
+ * take the code of every pixel from the cell codes through the column map
  * (gcn10_gpu_soil_words_state).  Everything else that needs soil -- strips of
- * other widths or of unaligned rasters, strips with "compact_soil" off, the
+ * other widths or of unaligned rasters, strips with "compact_soil" off,
+ * strips with more column groups in a row than the launch has threads, the
  * fused encoder, verify, the pair histograms, the average overviews, the
  * area means of gcn10_gpu_aggregate -- reads one code byte per fine column
  * and coarse row from a workspace (hsy rows of W bytes) that is allocated here and filled from the tables by the first
@@ -422,7 +427,7 @@ int gcn10_gpu_verify_buffers(gcn10_gpu_ctx *ctx, const uint8_t *const want[GCN10
 /* Launch-shape knobs of the strip kernels, for tuning runs; results never
  * depend on them.  Names: "grid_blocks_per_cu" (1..64), "ilp16" (0 = by raster count | 1 | 2),
  * "ilp1" (1|2|4), "nontemporal" (0|1), "xcd_slabs" (0|1), "prefetch" (software pipeline of the strip kernels: -1 = default = on | 0 | 1), "compact_soil" (0|1: strips of
- * 16-byte aligned rows read the compact soil words of the prepared tile, not its code bytes; takes effect with the next
+ * 16-byte aligned rows read the cell codes and the column map of the prepared tile, not its code bytes; takes effect with the next
  * strip, no new gcn10_gpu_prepare_tile needed; default 1), "deflate_wave_codes" (0|1: code
  * construction of the tile encoder by one thread or one wave per tile), "defaults" (value
  * ignored: every knob back to its built-in default).
@@ -468,9 +473,13 @@ int gcn10_gpu_tune_single_raster(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, 
 
 /* What the strips of the tile last prepared on this context read their soil codes from (synchronises
  * `stream`, on which gcn10_gpu_prepare_tile ran): 0 = code bytes (tables switched off with
- * gcn10_gpu_set_option("compact_soil", 0)), 1 = compact words -- one dword per 16-pixel column group, used by strips
- * whose width is a multiple of 16 --, 2 = the cell codes through the column map, pixel by pixel, because some column
- * group of this tile spans more than two soil cells.  <0 on error.  A diagnostic: nothing needs to call it. */
+ * gcn10_gpu_set_option("compact_soil", 0)), 1 = one column entry per lane -- every 16-pixel column group of the tile
+ * is a run of one soil column followed by a run of another, and a lane of a strip whose width is a multiple of 16
+ * keeps its group's entry for the whole launch and loads two cell codes per 16 pixels --, 2 = the cell codes through
+ * the column map, pixel by pixel, because some column group of this tile has no such form (more than two soil cells,
+ * a map that is not monotone).  The answer describes the tile, as before: a strip of another width, or one with
+ * more column groups in a row than its launch has threads, reads the code bytes whatever it says.  <0 on error.  A
+ * diagnostic: nothing needs to call it. */
 int gcn10_gpu_soil_words_state(gcn10_gpu_ctx *ctx, gcn10_stream_t stream);
 
 /* Name of the variant of the strip kernel the last cn_strip call launched

@@ -1539,7 +1539,7 @@ namespace gcn10 {
 int deflate_launch_codes(gcn10_gpu_ctx *ctx, const TileJob &job, uint32_t nblocks, hipStream_t s, bool place)
 {
     static_assert(sizeof(Work) * kBuildThreads <= 160 * 1024, "code construction slices must fit LDS");
-    if (ctx->deflate_wave_codes) {
+    if (ctx->opt.deflate_wave_codes) {
         const uint32_t per_raster = job.across * job.down;
         hipLaunchKernelGGL(deflate_codes_wave_kernel, dim3((per_raster + kWavesPerBlock - 1) / kWavesPerBlock, nblocks / per_raster),
                            dim3(64 * kWavesPerBlock), 0, s, job);
@@ -1562,7 +1562,7 @@ int deflate_launch_codes(gcn10_gpu_ctx *ctx, const TileJob &job, uint32_t nblock
 int deflate_launch_place(gcn10_gpu_ctx *ctx, const TileJob &job, hipStream_t s)
 {
     hipLaunchKernelGGL(deflate_place_kernel, dim3(1), dim3(kPlaceThreads), 0, s, job, job.across * job.down,
-                       (uint32_t)ctx->arena_segment_align);
+                       (uint32_t)ctx->opt.arena_segment_align);
     HIP_TRY(hipGetLastError());
     return GCN10_OK;
 }
@@ -1620,11 +1620,11 @@ int gcn10_gpu_deflate_strip(gcn10_gpu_ctx *ctx, const uint8_t *const *rasters_de
 
     // per-tile statistics and code books: workspace owned by the context
     const size_t need = (size_t)nblocks * ((size_t)kHistWords * 4 + (size_t)kBookBytes);
-    rc = gcn10::grow_workspace(&ctx->deflate_ws, &ctx->deflate_ws_cap, need);
+    rc = gcn10::grow_workspace(&ctx->ws.deflate, &ctx->ws.deflate_cap, need);
     if (rc)
         return rc;
-    job.hist = reinterpret_cast<uint32_t *>(ctx->deflate_ws);
-    job.books = reinterpret_cast<uint8_t *>(ctx->deflate_ws) + (size_t)nblocks * kHistWords * 4;
+    job.hist = reinterpret_cast<uint32_t *>(ctx->ws.deflate);
+    job.books = reinterpret_cast<uint8_t *>(ctx->ws.deflate) + (size_t)nblocks * kHistWords * 4;
 
     static_assert(sizeof(SharedC<false>) <= 160 * 1024, "tile + output image must fit the CU's 160 KiB of LDS");
     static_assert(sizeof(SharedC<true>) <= 80 * 1024, "two small-stream workgroups must fit one CU");

@@ -1558,7 +1558,7 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
 
     job.esa = esa;
     job.class_of = ctx->d_class_of;
-    job.seg_align = (uint32_t)ctx->arena_segment_align;
+    job.seg_align = (uint32_t)ctx->opt.arena_segment_align;
     for (int r = 0; r < GCN10_N_RASTERS; r++)
         if (gcn10::selected(r, cond_mask, table_mask))
             job.sel[job.n_sel++] = (uint8_t)r;
@@ -1587,18 +1587,18 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
     const size_t tok_bytes = (size_t)positions * kTokStride * sizeof(uint16_t);
     const size_t ntok_bytes = ((size_t)positions * sizeof(uint32_t) + 15) & ~(size_t)15;
     const size_t need = stats_bytes + tok_bytes + ntok_bytes + (size_t)nblocks * 8 + (size_t)job.n_sel * ((positions + 63u) / 64u) * 4;
-    rc = gcn10::grow_workspace(&ctx->deflate_ws, &ctx->deflate_ws_cap, need);
+    rc = gcn10::grow_workspace(&ctx->ws.deflate, &ctx->ws.deflate_cap, need);
     if (rc)
         return rc;
-    job.t.hist = reinterpret_cast<uint32_t *>(ctx->deflate_ws);
-    job.t.books = reinterpret_cast<uint8_t *>(ctx->deflate_ws) + (size_t)nblocks * kHistWords * 4;
-    job.tok = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(ctx->deflate_ws) + stats_bytes);
-    job.n_tok = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->deflate_ws) + stats_bytes + tok_bytes);
+    job.t.hist = reinterpret_cast<uint32_t *>(ctx->ws.deflate);
+    job.t.books = reinterpret_cast<uint8_t *>(ctx->ws.deflate) + (size_t)nblocks * kHistWords * 4;
+    job.tok = reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(ctx->ws.deflate) + stats_bytes);
+    job.n_tok = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->ws.deflate) + stats_bytes + tok_bytes);
     // the wave-independent pass F-C places the streams itself, every workgroup from all the sizes: those must not be
     // the table the workgroups write the offsets to
     job.t.sizes = table_dev;
-    if (ctx->fused_emit != 0) {
-        job.t.sizes = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->deflate_ws) + stats_bytes + tok_bytes + ntok_bytes);
+    if (ctx->opt.fused_emit != 0) {
+        job.t.sizes = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(ctx->ws.deflate) + stats_bytes + tok_bytes + ntok_bytes);
         job.t.chunk_tot = job.t.sizes + (size_t)nblocks * 2;        // zeroed by pass F-A, added to by pass B
         job.t.n_chunks = (positions + 63u) / 64u;
     }
@@ -1618,16 +1618,16 @@ int gcn10_gpu_deflate_fused_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(SharedFC)));
         ctx->fused_ready = true;
     }
-    if (ctx->fused_parse == 0)
+    if (ctx->opt.fused_parse == 0)
         hipLaunchKernelGGL(fused_stats_kernel, dim3(positions), dim3(kTile), sizeof(SharedFA), s, job);
     else
         hipLaunchKernelGGL(fused_stats_seg_kernel, dim3(positions), dim3(kFA2Threads), sizeof(SharedFA2), s, job);
     // (pass B' as a launch of its own only for the lock-step form of pass F-C: the wave-independent form places its streams itself)
-    rc = gcn10::deflate_launch_codes(ctx, job.t, (uint32_t)nblocks, s, ctx->fused_emit == 0);
+    rc = gcn10::deflate_launch_codes(ctx, job.t, (uint32_t)nblocks, s, ctx->opt.fused_emit == 0);
     if (rc)
         return rc;
     const uint32_t groups = (job.n_sel + kGroup - 1) / kGroup;
-    if (ctx->fused_emit == 0)
+    if (ctx->opt.fused_emit == 0)
         hipLaunchKernelGGL(fused_emit_kernel, dim3(positions, groups), dim3(kTile), sizeof(SharedFC), s, job);
     else
         hipLaunchKernelGGL(fused_emit_wave_kernel, dim3(positions, groups), dim3(kTile), sizeof(SharedFC2), s, job);

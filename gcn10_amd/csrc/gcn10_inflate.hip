@@ -1476,13 +1476,13 @@ int gcn10_gpu_inflate_tiles(gcn10_gpu_ctx *ctx, const uint8_t *comp_dev, const g
         return fail(GCN10_E_INVAL, "gcn10_gpu_inflate_tiles: compressed bytes must be 16-byte aligned");
     const uint32_t slot = (chunk_bytes + 255u) & ~255u;
     const size_t need = (size_t)slot * (size_t)n_tiles;
-    rc = gcn10::grow_workspace(&ctx->inflate_ws, &ctx->inflate_ws_cap, need);
+    rc = gcn10::grow_workspace(&ctx->ws.inflate, &ctx->ws.inflate_cap, need);
     if (rc)
         return rc;
     static_assert(kWindow / 2 + kWindow / 4 + 258 <= kWindow && (kWindow & (kWindow - 1)) == 0 && kWindow >= 4096, "window invariant");
     static_assert(sizeof(Shared) <= 16 * 1024, "ten streams per CU of 160 KiB LDS");
     hipStream_t s = as_stream(ctx, stream);
-    uint8_t *scratch = reinterpret_cast<uint8_t *>(ctx->inflate_ws);
+    uint8_t *scratch = reinterpret_cast<uint8_t *>(ctx->ws.inflate);
     hipLaunchKernelGGL(inflate_kernel, dim3((uint32_t)n_tiles), dim3(128), sizeof(Shared), s, comp_dev,
                        reinterpret_cast<const TileIn *>(tiles_dev), (uint32_t)n_tiles, scratch, slot, status_dev,
                        dst_dev, (unsigned long long)dst_stride);

@@ -300,10 +300,10 @@ int gcn10_gpu_lzw_strip(gcn10_gpu_ctx *ctx, const uint8_t *const *rasters_dev, i
     lj.n_tiles = (uint32_t)n_tiles;
 
     const size_t need = (size_t)n_tiles * kSegs * (kSegWords + 1u) * 4u;
-    rc = gcn10::grow_workspace(&ctx->lzw_ws, &ctx->lzw_ws_cap, need);
+    rc = gcn10::grow_workspace(&ctx->ws.lzw, &ctx->ws.lzw_cap, need);
     if (rc)
         return rc;
-    lj.seg_words = reinterpret_cast<uint32_t *>(ctx->lzw_ws);
+    lj.seg_words = reinterpret_cast<uint32_t *>(ctx->ws.lzw);
     lj.seg_bits = lj.seg_words + (size_t)n_tiles * kSegs * kSegWords;
 
     TileJob pj = {};

@@ -1,6 +1,6 @@
 // gcn10_soil_readers.hpp -- what every kernel that reads the soil of a prepared tile together with the landcover
 // shares: the soil view, the all-tables lookup image, the 16-pixel gather and the raster selection test.  Readers:
-// the strip kernels (gcn10_gpu.hip), the fused encoder (gcn10_deflate_fused.hip), verify_strip (gcn10_verify.hip),
+// the strip kernels (gcn10_strip.hip), the fused encoder (gcn10_deflate_fused.hip), verify_strip (gcn10_verify.hip),
 // the pair histograms (gcn10_stats.hip, gcn10_zonal.hip), the average overviews (gcn10_overview.hip) and the area
 // means (gcn10_aggregate.hip).  Their host side is gcn10::bind_soil / check_masks / grid_cap of
 // gcn10_gpu_internal.hpp.
@@ -35,6 +35,10 @@ struct SoilView {
 constexpr int kPlanes = 6;
 constexpr int kLut16Plane = 256 * 16 + 16;
 constexpr int kLut16Bytes = kPlanes * kLut16Plane;
+// The image of a single table k (gcn10_gpu_ctx::d_lut1 + k * kLut1Bytes): the same planes of one byte per landcover.
+// LDS plane stride for the single-table byte LUT (+4 B pad: next bank).
+constexpr int kPlane1 = 256 + 4;
+constexpr int kLut1Bytes = kPlanes * kPlane1;
 
 // the image into LDS, 16 bytes per thread and step (both 16-byte aligned); the caller synchronises
 template <int THREADS>

@@ -6,7 +6,7 @@
 // exact histogram of all 18 rasters on the host, and no CN raster has to exist for it: the kernel reads the same
 // inputs as cn_strip and the fused encoder, a landcover strip and the block's x-expanded soil codes.
 //
-// Only nine soil codes can occur (soil_code() of gcn10_gpu.hip: planes 0..4 or 5 = invalid, drained = 4 for the
+// Only nine soil codes can occur (soil_code() of gcn10_device_util.hpp: planes 0..4 or 5 = invalid, drained = 4 for the
 // dual classes), so the codes are mapped to a dense bin and a workgroup's private histogram is 16 x 256 dwords
 // = 16 KiB of LDS.  Contention: in patchy landcover whole waves hit one bin, and 64 lanes adding to one LDS
 // address serialise.  So every lane folds the runs of equal pairs of its 16 consecutive pixels in registers and

@@ -3,7 +3,7 @@
 //
 // gcn10_gpu_verify_strip: one pass over a landcover strip.  Every lane takes 16 consecutive pixels of one row, forms
 // their soil codes and the up to 18 table values with the all-tables strip kernel's own gather -- gcn10::gather16 of
-// gcn10_soil_readers.hpp over the same LDS image, which finish_trip of gcn10_gpu.hip calls too (one 16-byte LDS row
+// gcn10_soil_readers.hpp over the same LDS image, which finish_trip of gcn10_strip.hip calls too (one 16-byte LDS row
 // per pixel and drainage condition, 4x4 byte transposes) -- and XORs them with the 16 bytes of each selected file
 // raster.  The kernel only loads: 19 bytes per pixel with all rasters selected, all of a lane's loads issued before
 // the first is used.  The expected rasters never exist in memory.

@@ -1,6 +1,6 @@
 // Host check of gcn10::strip_lane_plan (gcn10_amd/csrc/gcn10_strip_lanes.hpp), the lane-to-pixel mapping of the strip
 // kernels that read the soil tables.  Arguments: groups of W rows grid slabs ilp.  For every group, every thread of
-// the grid is walked through its trips with the arithmetic the kernel uses (issue_lane_trip of gcn10_gpu.hip):
+// the grid is walked through its trips with the arithmetic the kernel uses (issue_lane_trip of gcn10_strip.hip):
 //   * every 16-byte vector of the strip is visited exactly once,
 //   * a thread never leaves its column group,
 //   * the pieces begin at row boundaries and tile the strip,

@@ -21,7 +21,7 @@ LC_CLASSES = np.array([0, 10, 20, 30, 40, 50, 60, 70, 80, 90, 95, 100, 1, 33, 20
 
 
 def soil_code(h):
-    """soil_code() of gcn10_gpu.hip: drained plane | undrained plane << 4, plane 5 = invalid."""
+    """soil_code() of gcn10_device_util.hpp: drained plane | undrained plane << 4, plane 5 = invalid."""
     h = np.asarray(h, np.int64)
     dual = (h >= 11) & (h <= 14)
     plain = np.where(h < 5, h, 5)

@@ -1,6 +1,6 @@
 // strip_lab.hip -- same-box A/B bench of single-raster CN strip kernel variants (BASELINE config 2)
 // next to plain copy kernels of the same launch shape.  Diagnostic only: the winner is ported into
-// gcn10_amd/csrc/gcn10_gpu.hip, where the parity tests check it against the oracle.  Every variant's
+// gcn10_amd/csrc/gcn10_strip.hip, where the parity tests check it against the oracle.  Every variant's
 // raster is compared on the device with a byte-per-thread kernel of the plain formula.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/strip_lab tools/strip_lab.hip

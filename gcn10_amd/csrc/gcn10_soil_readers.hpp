@@ -1,8 +1,8 @@
 // gcn10_soil_readers.hpp -- what every kernel that reads the soil of a prepared tile together with the landcover
 // shares: the soil view, the all-tables lookup image, the 16-pixel gather and the raster selection test.  Readers:
 // the strip kernels (gcn10_strip.hip), the fused encoder (gcn10_deflate_fused.hip), verify_strip (gcn10_verify.hip),
-// the pair histograms (gcn10_stats.hip, gcn10_zonal.hip), the average overviews (gcn10_overview.hip) and the area
-// means (gcn10_aggregate.hip).  Their host side is gcn10::bind_soil / check_masks / grid_cap of
+// the pair histograms (gcn10_stats.hip, gcn10_zonal.hip), the average overviews (gcn10_overview.hip), the area
+// means (gcn10_aggregate.hip) and the sums on a model grid (gcn10_grid.hip).  Their host side is gcn10::bind_soil / check_masks / grid_cap of
 // gcn10_gpu_internal.hpp.
 #ifndef GCN10_SOIL_READERS_HPP
 #define GCN10_SOIL_READERS_HPP

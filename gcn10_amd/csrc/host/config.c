@@ -309,6 +309,17 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             gcn10_config_free(cfg);
             return -3;
         }
+        else if (!strcmp(key, "grid")) {
+            gcn10_grid g;
+
+            if (gcn10_parse_grid(val, &g) != 0) {
+                fclose(f);
+                snprintf(err, errcap, "bad value for grid: '%s' (xmin,ymax,dx,dy,nx,ny)", val);
+                gcn10_config_free(cfg);
+                return -3;
+            }
+            rc = set_str(&cfg->grid, val);
+        }
         else if (!strcmp(key, "zones_shp_path"))
             rc = set_str(&cfg->zones_shp_path, val);
         else if (!strcmp(key, "zonal_output"))
@@ -365,5 +376,6 @@ void gcn10_config_free(gcn10_config *cfg)
     free(cfg->zones_shp_path);
     free(cfg->zones_id_field);
     free(cfg->zonal_output);
+    free(cfg->grid);
     memset(cfg, 0, sizeof *cfg);
 }

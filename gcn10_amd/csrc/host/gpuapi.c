@@ -98,6 +98,9 @@ static void load_once(void)
     *(void **)(&g_api.zonal_pair_histogram) = dlsym(h, "gcn10_gpu_zonal_pair_histogram");
     /* the area means on a coarser grid: needed by aggregate=<f> runs only, which check for it */
     *(void **)(&g_api.aggregate) = dlsym(h, "gcn10_gpu_aggregate");
+    /* the sums and means on a model grid: needed by grid=... runs only, which check for them */
+    *(void **)(&g_api.grid_sums) = dlsym(h, "gcn10_gpu_grid_sums");
+    *(void **)(&g_api.grid_finish) = dlsym(h, "gcn10_gpu_grid_finish");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -168,6 +168,11 @@ struct gcn10_gpu_api {
     /* optional: NULL when the library has none (needed by aggregate=<f> only) */
     int (*aggregate)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, int, int, int, unsigned, unsigned,
                      uint8_t *const *, size_t, gcn10_stream_t);
+    /* optional: NULL when the library has none (needed by grid=... only) */
+    int (*grid_sums)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const int32_t *, const int32_t *, int,
+                     int, unsigned, unsigned, unsigned long long *, gcn10_stream_t);
+    int (*grid_finish)(gcn10_gpu_ctx *, const unsigned long long *, int, size_t, uint8_t *, const uint32_t *, uint32_t,
+                       unsigned long long *, gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -7,7 +7,8 @@
  * --conditions to produce a subset of the 18 rasters (BASELINE config 3: "single lookup"), and --compress to
  * write LZW instead of DEFLATE GeoTIFFs, --stats / --nodata for GDAL band statistics and a NoData tag, and --verify
  * to check the rasters a run has written instead of writing them, and --zonal / --zones for the composite curve
- * numbers of the polygons of a shapefile instead of rasters, and --aggregate for area-mean rasters on a coarser grid.
+ * numbers of the polygons of a shapefile instead of rasters, and --aggregate for area-mean rasters on a coarser grid,
+ * and --grid for mean rasters on a model grid that spans the blocks.
  * No mpirun: one process drives every GPU of the node.
  */
 #include "gcn10_host.h"
@@ -25,6 +26,7 @@ static void usage(FILE *fp)
             "        [--lookups <names>] [--conditions drained|undrained|both] [--compress deflate|lzw]\n"
             "        [--cog] [--overview-resampling nearest|average] [--stats] [--nodata none|<0..255>]\n"
             "        [--verify] [--zonal] [--zones <zones.shp>] [--aggregate <f>]\n"
+            "        [--grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -50,6 +52,12 @@ static void usage(FILE *fp)
             "  --aggregate <f>\twrite no 10 m raster but, under cn_rasters_<cond>_x<f>/, the mean of every selected\n"
             "\t\t\traster over cells of f x f landcover pixels (f = 2..256), reduced on the GPU (config key\n"
             "\t\t\taggregate=<f>); not with --verify or --zonal\n"
+            "  --grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>\n"
+            "\t\t\twrite no 10 m raster but, under cn_grid_<cond>/, ONE raster per selected raster on a\n"
+            "\t\t\tmodel grid in the landcover's CRS: nx x ny cells of dx x dy units (8 landcover pixels or\n"
+            "\t\t\tmore) from the upper-left corner (xmin, ymax), each the mean over its pixels of all\n"
+            "\t\t\tprocessed blocks, reduced on the GPU (config key grid=...); not with --verify, --zonal,\n"
+            "\t\t\t--aggregate, --overwrite or --compress lzw\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -102,6 +110,8 @@ int main(int argc, char **argv)
             opt.verify = true;
         else if (!strcmp(argv[i], "--aggregate") && i + 1 < argc)
             opt.aggregate = argv[++i];
+        else if (!strcmp(argv[i], "--grid") && i + 1 < argc)
+            opt.grid = argv[++i];
         else if (!strcmp(argv[i], "--zonal"))
             opt.zonal = true;
         else if (!strcmp(argv[i], "--zones") && i + 1 < argc) {

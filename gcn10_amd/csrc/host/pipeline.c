@@ -485,6 +485,7 @@ static void worker_teardown(struct worker *w)
         g->device_sync(w->ctx);
         gcn10_verify_teardown(w);
         gcn10_zonal_teardown(w);
+        gcn10_grid_teardown(w);
         gcn10_sink_free_buffers(w);
         for (int i = 0; i < w->run->nbuf; i++) {
             struct strip_buf *b = &w->buf[i];
@@ -656,8 +657,11 @@ void *gcn10_worker_main(void *arg)
             gcn10_verify_block_unreadable(w, in->block_id);
         if (r->zonal && in->outcome == 1)
             gcn10_zonal_block_unreadable(w, in->block_id);
+        if (r->grid_on && in->outcome == 1)
+            gcn10_grid_block_unreadable(w, in->block_id);
         if (in->outcome == 0 && !atomic_load(&r->fatal) &&
-            (r->verify ? gcn10_verify_block(w, in) : r->zonal ? gcn10_zonal_block(w, in) : encode_block(w, in)) != 0)
+            (r->verify ? gcn10_verify_block(w, in) : r->zonal ? gcn10_zonal_block(w, in)
+             : r->grid_on ? gcn10_grid_block(w, in) : encode_block(w, in)) != 0)
             atomic_store(&r->fatal, 1);     /* where the reference calls MPI_Abort */
         gcn10_abort_outputs(in);            /* files of a block that was not encoded after all (a no-op otherwise) */
         w->busy_seconds += now_seconds() - t0;

@@ -264,11 +264,13 @@ static int fill_block(struct worker *w, struct block_in *in, int block_id)
     /* the block's 18 files, while the copies and the decoder run (the reference creates each raster's file
      * inside save_raster, after computing it: src/raster.c:204; an existing raster of that name is untouched
      * until this one is complete either way: files are written as <name>.part) */
-    if (r->verify || r->zonal) {
-        memset(in->tifs, 0, sizeof in->tifs);       /* a verify run and a zonal run write no raster */
+    if (r->verify || r->zonal || r->grid_on) {
+        /* a verify run and a zonal run write no raster, a grid run none per block */
+        memset(in->tifs, 0, sizeof in->tifs);
         in->tifs_ok = false;
-        /* the zones over this block, here on the input side: it overlaps the block before */
-        if (r->zonal && gcn10_zonal_plan_block(w, in, r->blocks.bbox[bi]) != 0) {
+        /* the zones, or the grid's cells, over this block, here on the input side: it overlaps the block before */
+        if ((r->zonal && gcn10_zonal_plan_block(w, in, r->blocks.bbox[bi]) != 0) ||
+            (r->grid_on && gcn10_grid_plan_input(w, in, r->blocks.bbox[bi]) != 0)) {
             g->stream_sync(w->in_ctx, w->s_in);
             gcn10_stager_idle(&w->ring);
             return -1;
@@ -425,6 +427,7 @@ void gcn10_input_teardown(struct worker *w)
 
             gcn10_abort_outputs(in);        /* a staged block the worker never took */
             gcn10_zone_plan_free(&in->zplan);
+            gcn10_grid_plan_free(&in->gplan);
             if (in->h_coarse) g->host_free(w->in_ctx, in->h_coarse);
             if (in->h_ci) g->host_free(w->in_ctx, in->h_ci);
             if (in->h_cj) g->host_free(w->in_ctx, in->h_cj);

@@ -1,6 +1,6 @@
 /* pipeline_internal.h -- the worker and run state shared by run.c (the run's steps), pipeline.c (workers, a block's
  * strips), sink.c (strip buffers, sink jobs), pipeline_input.c (landcover input through the GPU decoder), launcher.c,
- * verify.c, zonal.c and aggregate.c, and what the writer and the verifier have in common: the chunk stager (stage.c)
+ * verify.c, zonal.c, aggregate.c and grid.c, and what the writer and the verifier have in common: the chunk stager (stage.c)
  * and the overview levels (levels.c). */
 #ifndef GCN10_PIPELINE_INTERNAL_H
 #define GCN10_PIPELINE_INTERNAL_H
@@ -21,6 +21,8 @@ struct worker;
 struct gcn10_verify_state;
 struct gcn10_zonal_state;
 struct gcn10_zonal_table;
+struct gcn10_grid_state;
+struct gcn10_grid_result;
 
 /* ---- stage.c: chunks as they lie in the files -> pinned ring -> device, for gcn10_gpu_inflate_tiles ---- */
 
@@ -140,6 +142,7 @@ struct block_in {
     bool tifs_ok;                           /* all of the run's rasters have their file */
     gcn10_zone_plan zplan;                  /* zonal=1: the zones' spans and items over this block (zones.c) */
     gcn10_aggregate_geom agg;               /* aggregate=<f>: the block's owned pixels and its grid of cells (aggregate.c) */
+    gcn10_grid_plan gplan;                  /* grid=...: the block's cell rectangle, maps and shared cells (grid.c) */
 };
 
 struct worker {
@@ -196,6 +199,7 @@ struct worker {
     size_t d_hist_cap, h_hist_cap;
     struct gcn10_verify_state *verify;      /* verify=1: the worker's decode buffers and counters (verify.c) */
     struct gcn10_zonal_state *zonal;        /* zonal=1: the worker's span, item and histogram buffers (zonal.c) */
+    struct gcn10_grid_state *gridst;        /* grid=...: the worker's map, sum and mean buffers (grid.c) */
     double t_zone_plan, t_zone_accum;       /* ... seconds of the input side building spans, of the worker adding up */
     long n_win_gpu, n_win_gpu_lzw, n_win_host;  /* landcover windows through the GPU decoder (of them with LZW chunks),
                                                    through the host reader */
@@ -255,6 +259,12 @@ struct run {
     atomic_int zonal_incomplete;            /* a block's inputs could not be read: the table lacks it, exit code 1 */
     /* aggregate=<f>: no 10 m raster is written but every selected raster's area means over f x f pixels (aggregate.c) */
     int aggregate;
+    /* grid=...: no 10 m raster is written but every selected raster's means on one model grid, merged over all blocks
+     * and written after the last one (grid.c) */
+    bool grid_on;
+    gcn10_grid grid;
+    struct gcn10_grid_result *grid_result;
+    atomic_int grid_incomplete;             /* a block's inputs could not be read: the rasters lack it, exit code 1 */
 };
 
 double gcn10_now_seconds(void);
@@ -350,6 +360,17 @@ int gcn10_zonal_plan_block(struct worker *w, struct block_in *in, const double o
 int gcn10_zonal_block(struct worker *w, struct block_in *in);
 void gcn10_zonal_block_unreadable(struct worker *w, int block_id);
 void gcn10_zonal_teardown(struct worker *w);
+/* grid.c: the refused combinations, the landcover's pixel size against the cells and the result of the run (start:
+ * before any GPU is opened; finish: the rasters and the closing line, after the workers are joined; end: frees it);
+ * the cells of a staged block, made by the input side; a staged block summed and merged (0, or -1 for errors that end
+ * the run); a block whose inputs could not be staged; the worker's grid buffers */
+int gcn10_grid_start(struct run *r);
+int gcn10_grid_finish(struct run *r, gcn10_log *log0);
+void gcn10_grid_end(struct run *r);
+int gcn10_grid_plan_input(struct worker *w, struct block_in *in, const double own[4]);
+int gcn10_grid_block(struct worker *w, struct block_in *in);
+void gcn10_grid_block_unreadable(struct worker *w, int block_id);
+void gcn10_grid_teardown(struct worker *w);
 int gcn10_input_setup(struct worker *w);
 void gcn10_input_teardown(struct worker *w);
 int gcn10_input_start(struct worker *w);

@@ -106,6 +106,14 @@ static int resolve(struct run *r)
     r->aggregate = r->cfg.aggregate;
     if (r->aggregate && gcn10_aggregate_start(r) != 0)
         return 1;
+    /* a grid run: the grid, the refused combinations, the result of the run */
+    if (opt->grid) {
+        free(r->cfg.grid);
+        r->cfg.grid = strdup(opt->grid);
+    }
+    r->grid_on = r->cfg.grid != NULL;
+    if (r->grid_on && gcn10_grid_start(r) != 0)
+        return 1;
     r->null_sink = sink && strcmp(sink, "null") == 0;
     /* Rows per strip.  Rounds 2 and 3 ran 768 rows (three tile rows of a 36000-px block = 423 tile positions, one round
      * of the fused statistics pass's 512 workgroup slots); larger strips lost end to end to the coarser hand-over between
@@ -132,6 +140,8 @@ static int resolve(struct run *r)
         r->gpu_deflate = true;
         r->cog = r->stats = false;
     }
+    if (r->grid_on)
+        r->cog = r->stats = false;      /* the grid rasters are encoded on the host and carry neither */
     r->gpu_inflate = r->cfg.gpu_inflate != 0;
     r->direct_io = r->cfg.direct_io != 0 || (getenv("GCN10_DIRECT_IO") && atoi(getenv("GCN10_DIRECT_IO")) != 0);
     r->prefetch = r->cfg.prefetch_blocks != 0 && !(getenv("GCN10_PREFETCH_BLOCKS") && atoi(getenv("GCN10_PREFETCH_BLOCKS")) == 0);
@@ -156,7 +166,7 @@ static int resolve(struct run *r)
 static int require(struct run *r)
 {
     const struct gcn10_gpu_api *g;
-    char err[2048] = "", agg[48];
+    char err[2048] = "", agg[48], grid[600];
 
     r->gpu = g = gcn10_gpu_api_get(err, sizeof err);
     if (!g) {
@@ -164,6 +174,7 @@ static int require(struct run *r)
         return 1;
     }
     snprintf(agg, sizeof agg, "aggregate=%d", r->aggregate);
+    snprintf(grid, sizeof grid, "grid=%s", r->grid_on ? r->cfg.grid : "");
     {
         /* the pair histogram's soil codes are asked for where a mode counts pairs, and must be as many as its bins */
         const bool pairs = (r->stats || r->zonal) && g->pair_histogram_codes &&
@@ -173,6 +184,7 @@ static int require(struct run *r)
             { r->stats, g->pair_histogram && pairs, "gcn10_gpu_pair_histogram", "stats=1" },
             { r->zonal, g->zonal_pair_histogram && pairs, "gcn10_gpu_zonal_pair_histogram", "zonal=1" },
             { r->aggregate != 0, g->aggregate != NULL, "gcn10_gpu_aggregate", agg },
+            { r->grid_on, g->grid_sums && g->grid_finish, "gcn10_gpu_grid_sums", grid },
             { r->verify, g->verify_strip && g->verify_buffers, "gcn10_gpu_verify_strip", "verify=1" },
             { r->lzw, g->lzw_strip && g->lzw_arena_bound, "gcn10_gpu_lzw_strip", "compress=lzw" },
         };
@@ -548,8 +560,11 @@ int gcn10_run(const gcn10_run_options *opt)
         gcn10_aggregate_finish(r, log0);
     if (r->zonal && gcn10_zonal_finish(r, log0) != 0)
         atomic_store(&r->fatal, 1);
+    if (r->grid_on && gcn10_grid_finish(r, log0) != 0)
+        atomic_store(&r->fatal, 1);
     report(r, t_start);
-    exit_code = atomic_load(&r->fatal) || atomic_load(&r->zonal_incomplete) ? 1 : (verify_found > 0 ? 2 : 0);
+    exit_code = atomic_load(&r->fatal) || atomic_load(&r->zonal_incomplete) || atomic_load(&r->grid_incomplete)
+                    ? 1 : (verify_found > 0 ? 2 : 0);
 
 done:
     gcn10_pool_destroy(r->pool);
@@ -559,6 +574,7 @@ done:
     free(r->workers);
     free(r->verify_failed);
     gcn10_zonal_end(r);
+    gcn10_grid_end(r);
     free(r->block_ids);
     gcn10_blocks_free(&r->blocks);
     gcn10_config_free(&r->cfg);

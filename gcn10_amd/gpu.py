@@ -46,7 +46,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_inflate_codecs", "gcn10_gpu_overview_nearest", "gcn10_gpu_overview_average",
     "gcn10_gpu_pair_histogram_codes", "gcn10_gpu_pair_histogram",
     "gcn10_gpu_verify_strip", "gcn10_gpu_verify_buffers", "gcn10_gpu_zonal_pair_histogram",
-    "gcn10_gpu_aggregate",
+    "gcn10_gpu_aggregate", "gcn10_gpu_grid_sums", "gcn10_gpu_grid_finish",
 )
 
 
@@ -144,6 +144,8 @@ def lib():
             "gcn10_gpu_verify_buffers": (i, [vp, vp, sz, vp, sz, i, i, i, C.c_uint, vp, vp]),
             "gcn10_gpu_zonal_pair_histogram": (i, [vp, vp, i, i, vp, vp, vp, sz, i, vp, vp]),
             "gcn10_gpu_aggregate": (i, [vp, vp, i, i, vp, i, i, i, u, u, C.POINTER(vp), sz, vp]),
+            "gcn10_gpu_grid_sums": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp]),
+            "gcn10_gpu_grid_finish": (i, [vp, vp, i, sz, vp, vp, C.c_uint32, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -438,6 +440,24 @@ class Engine:
         arr = (C.c_void_p * max(len(out_ptrs), 1))(*[int(p) if p else None for p in out_ptrs])
         self._chk(lib().gcn10_gpu_aggregate(self._ctx, esa_ptr, W, rows, cj_ptr, x0, x1, factor, cond_mask, table_mask,
                                             arr, out_stride, stream), "gcn10_gpu_aggregate")
+
+    def grid_sums(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, cellx_ptr: int, celly_ptr: int, ncx: int,
+                  ncy: int, cond_mask: int, table_mask: int, acc_ptr: int, stream=None):
+        """ADDS the sum and the count of the values != 255 of every selected raster to acc[q][celly[y]][cellx[x]] =
+        {s, n} (uint64 pairs on the device, [n_sel][ncy][ncx][2]) over a W x rows device strip, with the soil of the
+        last prepare_tile (gcn10_gpu_grid_sums).  cellx_ptr / celly_ptr: int32[W] / int32[rows] on the device, the
+        cell column and row of every pixel column and strip row, -1 = in none (host.grid_plan_block makes them).
+        Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_sums(self._ctx, esa_ptr, W, rows, cj_ptr, cellx_ptr, celly_ptr, ncx, ncy,
+                                            cond_mask, table_mask, acc_ptr, stream), "gcn10_gpu_grid_sums")
+
+    def grid_finish(self, acc_ptr: int, n_sel: int, n_cells: int, means_ptr: int, shared_idx_ptr, n_shared: int,
+                    shared_ptr, stream=None):
+        """means[q][c] = n ? (2 s + n) // (2 n) : 255 of the n_sel * n_cells pairs of acc, and the pairs of the n_shared
+        cells shared_idx (uint32 on the device) names, packed into shared[q][i] (gcn10_gpu_grid_finish).  Asynchronous
+        on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_finish(self._ctx, acc_ptr, n_sel, n_cells, means_ptr, shared_idx_ptr or None,
+                                              n_shared, shared_ptr or None, stream), "gcn10_gpu_grid_finish")
 
     def zonal_pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans, items, n_zones: int,
                              hist_ptr: int, stream=None):

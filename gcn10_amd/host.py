@@ -127,6 +127,12 @@ def lib():
         L.gcn10_zone_plan_free.restype = None
         L.gcn10_aggregate_geometry.argtypes = [C.c_int, C.c_int, _f64p, vp, C.c_int, C.POINTER(AggregateGeom)]
         L.gcn10_aggregate_geometry.restype = C.c_int
+        L.gcn10_parse_grid.argtypes = [cp, C.POINTER(Grid)]
+        L.gcn10_parse_grid.restype = C.c_int
+        L.gcn10_grid_plan_block.argtypes = [C.POINTER(Grid), C.c_int, C.c_int, _f64p, vp, C.POINTER(GridPlan)]
+        L.gcn10_grid_plan_block.restype = C.c_int
+        L.gcn10_grid_plan_free.argtypes = [C.POINTER(GridPlan)]
+        L.gcn10_grid_plan_free.restype = None
         L.gcn10_zone_items_build.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(ZonePlan)]
         L.gcn10_zone_items_build.restype = C.c_int
         L.gcn10_tiff_abort.argtypes = [vp]
@@ -160,6 +166,12 @@ class ConfigFull(Config):
                 ("zones_id_field", C.c_char_p), ("zonal_output", C.c_char_p), ("aggregate", C.c_int)]
 
 
+class ConfigGrid(ConfigFull):
+    """``gcn10_config`` with the key of the model grid, appended behind ``ConfigFull`` (whose field list is pinned by
+    the tests of the aggregate key) as the C struct appends it; the pointer lies behind the padding of ``aggregate``."""
+    _fields_ = [("grid", C.c_char_p)]
+
+
 assert C.sizeof(Config) % 8 == 0
 
 
@@ -190,6 +202,20 @@ class AggregateGeom(C.Structure):
     """``gcn10_aggregate_geom`` of include/gcn10_host.h."""
     _fields_ = [("x0", C.c_int), ("x1", C.c_int), ("y0", C.c_int), ("y1", C.c_int), ("Wa", C.c_int), ("Ha", C.c_int),
                 ("gt", C.c_double * 6)]
+
+
+class Grid(C.Structure):
+    """``gcn10_grid`` of include/gcn10_host.h."""
+    _fields_ = [("xmin", C.c_double), ("ymax", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("nx", C.c_int),
+                ("ny", C.c_int)]
+
+
+class GridPlan(C.Structure):
+    """``gcn10_grid_plan`` of include/gcn10_host.h."""
+    _fields_ = [("x0", C.c_int), ("x1", C.c_int), ("y0", C.c_int), ("y1", C.c_int), ("cx0", C.c_int), ("cx1", C.c_int),
+                ("cy0", C.c_int), ("cy1", C.c_int), ("cellx", C.POINTER(C.c_int32)), ("celly", C.POINTER(C.c_int32)),
+                ("complete_x", C.POINTER(C.c_uint8)), ("complete_y", C.POINTER(C.c_uint8)),
+                ("shared", C.POINTER(C.c_uint32)), ("n_shared", C.c_size_t)]
 
 
 # struct gcn10_zone_span / gcn10_zone_item (include/gcn10_host.h, include/gcn10_gpu.h)
@@ -298,15 +324,52 @@ def aggregate_geometry(W: int, H: int, gt, own, f: int) -> dict:
     return out
 
 
+def _grid(grid) -> Grid:
+    if isinstance(grid, dict):
+        return Grid(*[grid[k] for k in ("xmin", "ymax", "dx", "dy", "nx", "ny")])
+    return Grid(*grid)
+
+
+def parse_grid(text: str) -> dict:
+    """"<xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>" -> dict of the six (``gcn10_parse_grid``); raises HostError for any other
+    text."""
+    g = Grid()
+    if lib().gcn10_parse_grid(text.encode(), C.byref(g)) != 0:
+        raise HostError("bad value for grid: '%s' (xmin,ymax,dx,dy,nx,ny)" % text)
+    return {name: getattr(g, name) for name, _t in Grid._fields_}
+
+
+def grid_plan_block(grid, W: int, H: int, gt, own=None) -> dict:
+    """A W x H block on a model grid (``gcn10_grid_plan_block``).  grid: the dict of parse_grid or the six values; own:
+    the block's box {minx, miny, maxx, maxy}, None = every pixel.  x0, x1, y0, y1 (the owned pixels), cx0, cx1, cy0,
+    cy1 (the block's cells), cellx (int32[W]) and celly (int32[H]) (local cell column / row, -1 = none; empty when the
+    block has no cell), complete_x, complete_y (bool per local cell column / row) and shared (uint32 local indices)."""
+    plan = GridPlan()
+    g = _grid(grid)
+    o = None if own is None else _f(own, 4)
+    if lib().gcn10_grid_plan_block(C.byref(g), int(W), int(H), _f(gt, 6), None if o is None else o.ctypes.data,
+                                   C.byref(plan)) != 0:
+        raise HostError("gcn10_grid_plan_block: a bad size, a block that is not north up, or out of memory")
+    out = {name: getattr(plan, name) for name in ("x0", "x1", "y0", "y1", "cx0", "cx1", "cy0", "cy1")}
+    ncx, ncy = plan.cx1 - plan.cx0, plan.cy1 - plan.cy0
+    out["cellx"] = _copy(plan.cellx, W if plan.cellx else 0, np.int32)
+    out["celly"] = _copy(plan.celly, H if plan.celly else 0, np.int32)
+    out["complete_x"] = _copy(plan.complete_x, ncx, np.uint8).astype(bool)
+    out["complete_y"] = _copy(plan.complete_y, ncy, np.uint8).astype(bool)
+    out["shared"] = _copy(plan.shared, plan.n_shared, np.uint32)
+    lib().gcn10_grid_plan_free(C.byref(plan))
+    return out
+
+
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = ConfigFull()
+    cfg = ConfigGrid()
     err = C.create_string_buffer(1024)
     rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
     out = {}
-    for name, _t in Config._fields_ + ConfigFull._fields_:
+    for name, _t in Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_:
         v = getattr(cfg, name)
         out[name] = v.decode() if isinstance(v, bytes) else v
     lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))

@@ -41,7 +41,7 @@ extern "C" {
  *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*); the pair histogram
  *    of the band statistics (gcn10_gpu_pair_histogram*); the raster verifier (gcn10_gpu_verify_*); the pair histogram
  *    per zone of the zonal composites (gcn10_gpu_zonal_pair_histogram); the area means on a coarser grid
- *    (gcn10_gpu_aggregate).
+ *    (gcn10_gpu_aggregate); the sums and means on a model grid (gcn10_gpu_grid_sums, gcn10_gpu_grid_finish).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -395,6 +395,34 @@ int gcn10_gpu_zonal_pair_histogram(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W
 int gcn10_gpu_aggregate(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
                         int x0, int x1, int factor, unsigned cond_mask, unsigned table_mask,
                         uint8_t *const *out, size_t out_stride, gcn10_stream_t stream);
+
+/* Mean-CN rasters on a model grid (config key grid=...).  Added in ABI 3 without a version change; the host looks them
+ * up for grid runs only.
+ *
+ * gcn10_gpu_grid_sums: `esa`, W, rows, `cj` and the soil prepared by gcn10_gpu_prepare_tile are those of
+ *   gcn10_gpu_pair_histogram.  cellx_dev[W] and celly_dev[rows] give the cell column of every pixel column and the
+ *   cell row of every strip row, in 0 .. ncx - 1 and 0 .. ncy - 1, anything else (-1) meaning "in no cell"
+ *   (gcn10_grid_plan_block of gcn10_host.h makes them).  Their entries that name a cell never decrease, and any 16
+ *   columns from a multiple of 16 on name at most three cell columns (cells of 8 pixels or more): pixels of a fourth
+ *   one are left out.  ADDS, for every selected raster q (ascending raster order) and every pixel (x, y) with
+ *   cellx[x] and celly[y] naming a cell and value v != 255 -- v what gcn10_gpu_cn_strip writes for that raster at that
+ *   pixel --, v to acc[q][celly[y]][cellx[x]][0] and 1 to ...[1].  Integers only: the pairs do not depend on the
+ *   launch shape, on how a caller cuts the rows into calls, or on order.  Any W, any alignment of esa; nothing at or
+ *   beyond W is read; nothing outside acc's n_sel * ncy * ncx pairs is written.
+ * gcn10_gpu_grid_finish: means[q * n_cells + c] = n ? (2 s + n) / (2 n) : 255 (the rule of gcn10_gpu_aggregate) for
+ *   the pair {s, n} = acc[q * n_cells + c] of every raster q < n_sel and cell c < n_cells, and the pairs of the
+ *   n_shared cells shared_idx_dev names, packed: shared[q * n_shared + i] = acc[q * n_cells + shared_idx[i]]
+ *   (shared_idx[i] < n_cells is the caller's to guarantee; n_shared == 0: both pointers may be NULL).
+ * GCN10_E_INVAL: the masks, W, rows, ncx or ncy <= 0, a null pointer (grid_sums); n_sel outside 1..18, n_cells == 0 or
+ *   >= 2^32, a null pointer (grid_finish).  GCN10_E_STATE: grid_sums without tables or without a tile prepared for
+ *   width W, as gcn10_gpu_aggregate (grid_finish reads no tile).  Asynchronous on `stream`. */
+int gcn10_gpu_grid_sums(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                        const int32_t *cellx_dev, const int32_t *celly_dev, int ncx, int ncy,
+                        unsigned cond_mask, unsigned table_mask,
+                        unsigned long long *acc /* [n_sel][ncy][ncx][2] = {s, n} */, gcn10_stream_t stream);
+int gcn10_gpu_grid_finish(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells, uint8_t *means,
+                          const uint32_t *shared_idx_dev, uint32_t n_shared, unsigned long long *shared,
+                          gcn10_stream_t stream);
 
 /* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
  * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.

@@ -134,6 +134,9 @@ typedef struct gcn10_config {
     char *zonal_output;     /* "zonal_output": the table's path, relative to the CWD as the rasters are (absent = zonal_cn.csv) */
     int aggregate;          /* "aggregate": f = 2..256: no 10 m raster is written but the area mean of every selected raster
                                over cells of f x f landcover pixels, reduced on the GPU (aggregate.c); 0 (default) = off */
+    char *grid;             /* "grid": <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny> (gcn10_parse_grid): no 10 m raster is written but
+                               one raster per selected raster on that grid, the mean over each cell's pixels of all
+                               blocks, reduced on the GPU (grid.c); absent (default) = off */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -157,7 +160,7 @@ int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or
 int gcn10_parse_aggregate(const char *text, int *factor);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -415,6 +418,48 @@ typedef struct gcn10_aggregate_geom {
 int gcn10_aggregate_geometry(int W, int H, const double gt[6], const double own[4], int f, gcn10_aggregate_geom *out);
 
 /* ------------------------------------------------------------------------ */
+/* model grid (config key "grid", --grid): no counterpart in the reference                                  */
+/* ------------------------------------------------------------------------ */
+
+/* A grid of nx x ny cells of dx x dy CRS units in the landcover's CRS; (xmin, ymax) is the outer upper-left corner of
+ * cell (0, 0).  Cell edges, in IEEE double, this order, no FMA:
+ *   ex(k) = xmin + (double)k * dx,   ey(k) = ymax - (double)k * dy.
+ * A pixel with centre (px, py) -- the centres of gcn10_zones_build_plan -- is in cell column k iff ex(k) <= px < ex(k+1)
+ * and in cell row k iff ey(k+1) < py <= ey(k): the half-open sides of the ownership rule, so a centre on an edge is in
+ * exactly one cell; outside [0, nx) x [0, ny) it is in none. */
+typedef struct gcn10_grid {
+    double xmin, ymax, dx, dy;
+    int nx, ny;
+} gcn10_grid;
+#define GCN10_GRID_MAX_CELLS (1 << 26)
+/* "<xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>": four doubles (strtod) and two integers, nothing else; all finite, dx, dy > 0,
+ * nx, ny >= 1, nx * ny <= GCN10_GRID_MAX_CELLS.  0, or -1 for another text. */
+int gcn10_parse_grid(const char *text, gcn10_grid *out);
+
+/* One block on the grid.  The block has W x H pixels and the clipped geotransform gt (north up, no rotation); own = its
+ * shapefile bounding box {minx, miny, maxx, maxy} (NULL: every pixel of the window is owned, and no cell is known to
+ * be complete).  [x0, x1) x [y0, y1) is the owned pixel rectangle (gcn10_owned_window's); [cx0, cx1) x [cy0, cy1) the
+ * cells that hold an owned pixel, empty (cx0 == cx1 == cy0 == cy1 == 0, no arrays) when there is none.  cellx[W] and
+ * celly[H]: the LOCAL cell column k - cx0 and row k - cy0 of every pixel column and row, -1 for one that is not owned
+ * or lies outside the grid; the non-negative entries never decrease.  The index k is found by a division and then
+ * corrected with the rule's own comparisons: the comparisons decide.  complete_x[cx1 - cx0]: own[0] <= ex(k) and
+ * ex(k+1) <= own[2]; complete_y[cy1 - cy0]: own[1] <= ey(k+1) and ey(k) <= own[3] -- every centre the cell column or
+ * row can hold is owned by this block.  A cell is complete iff its column and its row are; the others are shared
+ * (another block may add to them), and shared[n_shared] lists their local indices (cy - cy0) * (cx1 - cx0) + cx - cx0,
+ * ascending.  0; -1 for a bad size, a block that is not north up, or out of memory. */
+typedef struct gcn10_grid_plan {
+    int x0, x1, y0, y1;
+    int cx0, cx1, cy0, cy1;
+    int32_t *cellx, *celly;
+    uint8_t *complete_x, *complete_y;
+    uint32_t *shared;
+    size_t n_shared;
+} gcn10_grid_plan;
+int gcn10_grid_plan_block(const gcn10_grid *g, int W, int H, const double gt[6], const double own[4],
+                          gcn10_grid_plan *out);
+void gcn10_grid_plan_free(gcn10_grid_plan *p);
+
+/* ------------------------------------------------------------------------ */
 /* the run: src/main.c:58-203 + process_block, src/cn.c:134-384              */
 /* ------------------------------------------------------------------------ */
 
@@ -434,6 +479,7 @@ typedef struct gcn10_run_options {
     bool zonal;                 /* --zonal: composite curve numbers per zone instead of rasters (sets the config key "zonal") */
     const char *zones;          /* --zones <file.shp>: overrides the config key "zones_shp_path" and implies --zonal */
     const char *aggregate;      /* --aggregate <f>: overrides the config key "aggregate" */
+    const char *grid;           /* --grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>: overrides the config key "grid" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -469,7 +515,9 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * run (opt->zonal / "zonal=1") writes no raster either, only its table: exit codes as for a write run, and 1 as well
  * when a block's inputs could not be read (the table is written, but lacks that block).  An aggregate run
  * (opt->aggregate / "aggregate=<f>") writes cn_rasters_<cond>_x<f>/ instead of the 10 m rasters: exit codes as for a
- * write run. */
+ * write run.  A grid run (opt->grid / "grid=...") writes cn_grid_<cond>/cn_<hc>_<arc>.tif, one raster per selected
+ * raster on the model grid, after the last block: exit codes as for a zonal run (1 as well when a block's inputs could
+ * not be read: the rasters are written, but lack that block). */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

@@ -91,6 +91,12 @@ struct gcn10_gpu_ctx {
     uint8_t *d_class_of = nullptr;  // [36][256] pixel class of (soil code, landcover), then [18][256] values
     int n_classes = 0;              // 0: not available (set_tables not called, or > 256 classes)
 
+    // ---- the weights of the weighted grid sums (gcn10_grid.hip: gcn10_gpu_set_weights) ----
+    uint8_t *d_wlut = nullptr;      // two images of the all-tables layout, the low and the high bytes of w[cn] (0 where
+                                    // d_lut16 holds 255), then w[256] itself
+    bool weights_set = false;       // ... are those of the loaded tables (gcn10_gpu_set_tables clears it)
+    bool weights_rising = false;    // w[1..100] never decrease
+
     // ---- the prepared tile (gcn10_soil_tile.hip) ----
     struct Tile {
         // Soil workspace of the prepared tile (one allocation, grown by gcn10_gpu_prepare_tile):

@@ -24,9 +24,19 @@
 // Nothing at or beyond W is read (the last group of a row is read byte by byte, as in the area means); map entries
 // outside [0, ncx) and [0, ncy) count as -1, and a cell column beyond the kMaxCells a chunk's LDS words hold is left
 // out, so no map makes the kernel write outside acc.
+//
+// Weighted sums (gcn10_gpu_grid_sums_weighted, DESIGN.md "Runoff-weighted composites"): a third word per (raster,
+// cell), the sum of w[v] over the same pixels for a table w of 256 16-bit weights.  w o table is a function of (soil
+// plane, landcover, table) like the value itself, so gcn10_gpu_set_weights folds w into two more images of the
+// all-tables layout, the low and the high bytes of w[cn], zero where the CN image holds 255; against such an image the
+// same gather, masks and dot products give the sum of the low and of the high bytes, and sw = lo + 256 hi.  In a
+// weight plane 255 is a number: a plane pass makes no 255 test and no count.  A workgroup keeps its shape and gets a
+// role besides its condition -- the CN image (words 0 and 1, exactly the unweighted kernel's), the low plane (word 2)
+// or the high plane (word 2, shifted by 8) --, and the up to six workgroups of an item are dealt to one XCD.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 
 #include "gcn10_gpu_internal.hpp"
 #include "gcn10_soil_readers.hpp"
@@ -47,14 +57,21 @@ constexpr uint32_t kNoCell = 0xffffffffu;
 struct GridParams {
     const uint8_t *esa;         // strip, W x rows, row major
     SoilView soil;              // soil code bytes, soil row of every strip row
-    const uint8_t *lut16;
+    const uint8_t *lut[3];      // the CN image; the low and the high plane of the weights (weighted sums only)
     const int32_t *cellx, *celly;
     uint32_t W, rows, ncx, ncy;
     uint32_t chunks, band_rows;
     uint32_t items;             // chunks x bands
     uint32_t sel;               // bit r: raster r is selected
     uint32_t n_conds, conds[2]; // the selected conditions
-    unsigned long long *acc;    // [n_sel][ncy][ncx][2]
+    unsigned long long *acc;    // [n_sel][ncy][ncx][2], or [3] with weights
+};
+
+// the LDS of a workgroup: 62.3 KiB
+struct GridLds {
+    __attribute__((aligned(16))) uint8_t lut[kLut16Bytes];
+    uint32_t sum[9 * kMaxCells], n255[9 * kMaxCells], area[kMaxCells];
+    uint32_t cell_lo, cell_hi;
 };
 
 typedef u32x4 u32x4_u __attribute__((aligned(1)));
@@ -96,7 +113,8 @@ __device__ __forceinline__ void load_group(const GridParams &p, uint32_t y, uint
 
 // The sums of one row: the nine rasters' four dwords against the masks of the lane's first cell, and of its second
 // (has_b) and third (has_c) where some lane of the wave has one: straight-line code per case, no branch per dword.
-template <bool has_b, bool has_c>
+// PLANE: the image is a weight plane -- every byte is a number, nothing is counted.
+template <bool PLANE, bool has_b, bool has_c>
 __device__ __forceinline__ void add_row(const uint8_t *lut, const u32x4 &e, const u32x4 &c, uint32_t cond,
                                         uint32_t sel9, const uint32_t (&m)[3][4], uint32_t (&s)[3][9],
                                         uint32_t (&n)[3][9])
@@ -109,44 +127,39 @@ __device__ __forceinline__ void add_row(const uint8_t *lut, const u32x4 &e, cons
             continue;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const uint32_t v = acc[t][j], ff = ff_bytes(v);
+            const uint32_t v = acc[t][j], ff = PLANE ? 0u : ff_bytes(v);
             s[0][t] = __builtin_amdgcn_udot4(v, m[0][j], s[0][t], false);
-            n[0][t] = __builtin_amdgcn_udot4(ff, m[0][j], n[0][t], false);
+            if (!PLANE)
+                n[0][t] = __builtin_amdgcn_udot4(ff, m[0][j], n[0][t], false);
             if (has_b) {
                 s[1][t] = __builtin_amdgcn_udot4(v, m[1][j], s[1][t], false);
-                n[1][t] = __builtin_amdgcn_udot4(ff, m[1][j], n[1][t], false);
+                if (!PLANE)
+                    n[1][t] = __builtin_amdgcn_udot4(ff, m[1][j], n[1][t], false);
             }
             if (has_c) {
                 s[2][t] = __builtin_amdgcn_udot4(v, m[2][j], s[2][t], false);
-                n[2][t] = __builtin_amdgcn_udot4(ff, m[2][j], n[2][t], false);
+                if (!PLANE)
+                    n[2][t] = __builtin_amdgcn_udot4(ff, m[2][j], n[2][t], false);
             }
         }
     }
 }
 
-__global__ __launch_bounds__(kThreads) void grid_sums_kernel(const GridParams p)
+// One workgroup's item (chunk, band) for condition `cond`.  PLANE = false: against the CN image, words 0 and 1 of
+// WORDS per (raster, cell).  PLANE = true: against the weight plane `image`, its sums shifted by `shift` into word 2.
+template <bool PLANE, uint32_t WORDS>
+__device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, const uint32_t item, const uint32_t cond,
+                                         const uint8_t *image, const uint32_t shift)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lut[kLut16Bytes];
-    __shared__ uint32_t sum[9 * kMaxCells], n255[9 * kMaxCells], area[kMaxCells];
-    __shared__ uint32_t cell_lo, cell_hi;
-
-    // With both conditions, workgroups j and j + 8 of every 16 take the two conditions of one item (chunk, band):
-    // consecutive workgroups go to the eight XCDs in turn, so the two that read the same landcover and soil run on the
-    // same XCD at about the same time, and its L2 has what the second one reads.
-    uint32_t item = blockIdx.x, which = 0u;
-    if (p.n_conds == 2u) {
-        item = (blockIdx.x >> 4) * 8u + (blockIdx.x & 7u);
-        which = (blockIdx.x >> 3) & 1u;
-        if (item >= p.items)
-            return;             // the last sixteen, padded (the same for the whole workgroup)
-    }
-    const uint32_t cond = p.conds[which];
+    uint8_t *const lut = lds.lut;
+    uint32_t *const sum = lds.sum, *const n255 = lds.n255, *const area = lds.area;
+    uint32_t &cell_lo = lds.cell_lo, &cell_hi = lds.cell_hi;
     const uint32_t sel9 = (p.sel >> (9u * cond)) & 0x1ffu;
     const uint32_t band = item / p.chunks;
     const uint32_t gx = (item - band * p.chunks) * kChunkPx + threadIdx.x * kPxPerLane;
     const uint32_t y_lo = band * p.band_rows, y_hi = min(y_lo + p.band_rows, p.rows);
 
-    stage_lut16<kThreads>(lut, p.lut16);
+    stage_lut16<kThreads>(lut, image);
     for (uint32_t i = threadIdx.x; i < 9u * kMaxCells; i += kThreads)
         sum[i] = n255[i] = 0u;
     for (uint32_t i = threadIdx.x; i < kMaxCells; i += kThreads)
@@ -227,36 +240,55 @@ __global__ __launch_bounds__(kThreads) void grid_sums_kernel(const GridParams p)
                 for (uint32_t k = 0; k < 3; k++) {
                     if (cell[k] == kNoCell)
                         continue;
-                    atomicAdd(&area[cell[k]], px[k] * seg_rows);
+                    if (!PLANE)
+                        atomicAdd(&area[cell[k]], px[k] * seg_rows);
 #pragma unroll
                     for (uint32_t t = 0; t < 9; t++) {
                         if (!(sel9 & (1u << t)))
                             continue;
                         atomicAdd(&sum[t * kMaxCells + cell[k]], s[k][t]);
-                        if (n[k][t])
+                        if (!PLANE && n[k][t])
                             atomicAdd(&n255[t * kMaxCells + cell[k]], n[k][t] >> 7);
                         s[k][t] = n[k][t] = 0u;
                     }
                 }
             }
             __syncthreads();
-            // lanes 2i and 2i + 1 add s and n of cell i: a wave's adds are 512 contiguous bytes
-            for (uint32_t i = threadIdx.x; i < 2u * n_cells; i += kThreads) {
-                const uint32_t lc = i >> 1, word = i & 1u;
-                const uint32_t a = area[lc];
-                for (uint32_t t = 0; t < 9; t++) {
-                    if (!(sel9 & (1u << t)))
-                        continue;
-                    const uint32_t q = __popc(p.sel & ((1u << (9u * cond + t)) - 1u));
-                    const uint32_t nff = n255[t * kMaxCells + lc];
-                    const uint32_t sv = sum[t * kMaxCells + lc] - 255u * nff, nv = a - nff;
-                    sum[t * kMaxCells + lc] = 0u;
-                    n255[t * kMaxCells + lc] = 0u;
-                    if (nv)
-                        atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * 2u + word),
-                                  (unsigned long long)(word ? nv : sv));
+            if (PLANE) {
+                // one lane per cell: the plane's sum of every raster, shifted, to word 2
+                for (uint32_t lc = threadIdx.x; lc < n_cells; lc += kThreads) {
+                    for (uint32_t t = 0; t < 9; t++) {
+                        if (!(sel9 & (1u << t)))
+                            continue;
+                        const uint32_t q = __popc(p.sel & ((1u << (9u * cond + t)) - 1u));
+                        const uint32_t sv = sum[t * kMaxCells + lc];
+                        sum[t * kMaxCells + lc] = 0u;
+                        if (sv)
+                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * WORDS + 2u),
+                                      (unsigned long long)sv << shift);
+                    }
                 }
-                area[lc] = 0u;
+            }
+            else {
+                // lanes 2i and 2i + 1 add s and n of cell i: a wave's adds are 512 contiguous bytes (with weights: two
+                // words of every three)
+                for (uint32_t i = threadIdx.x; i < 2u * n_cells; i += kThreads) {
+                    const uint32_t lc = i >> 1, word = i & 1u;
+                    const uint32_t a = area[lc];
+                    for (uint32_t t = 0; t < 9; t++) {
+                        if (!(sel9 & (1u << t)))
+                            continue;
+                        const uint32_t q = __popc(p.sel & ((1u << (9u * cond + t)) - 1u));
+                        const uint32_t nff = n255[t * kMaxCells + lc];
+                        const uint32_t sv = sum[t * kMaxCells + lc] - 255u * nff, nv = a - nff;
+                        sum[t * kMaxCells + lc] = 0u;
+                        n255[t * kMaxCells + lc] = 0u;
+                        if (nv)
+                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * WORDS + word),
+                                      (unsigned long long)(word ? nv : sv));
+                    }
+                    area[lc] = 0u;
+                }
             }
             __syncthreads();
             seg_rows = 0u;
@@ -269,11 +301,11 @@ __global__ __launch_bounds__(kThreads) void grid_sums_kernel(const GridParams p)
             load_group(p, min(y + 1u, y_hi - 1u), gx, e_next, c_next);
             if (cy != kNoCell) {
                 if (has_c)
-                    add_row<true, true>(lut, e, c, cond, sel9, m, s, n);
+                    add_row<PLANE, true, true>(lut, e, c, cond, sel9, m, s, n);
                 else if (has_b)
-                    add_row<true, false>(lut, e, c, cond, sel9, m, s, n);
+                    add_row<PLANE, true, false>(lut, e, c, cond, sel9, m, s, n);
                 else
-                    add_row<false, false>(lut, e, c, cond, sel9, m, s, n);
+                    add_row<PLANE, false, false>(lut, e, c, cond, sel9, m, s, n);
             }
             e = e_next;
             c = c_next;
@@ -282,54 +314,135 @@ __global__ __launch_bounds__(kThreads) void grid_sums_kernel(const GridParams p)
     }
 }
 
+// With R roles per item -- the conditions, times three with weights -- workgroups j, j + 8, ..., j + 8 (R - 1) of
+// every 8 R take the roles of one item (chunk, band): consecutive workgroups go to the eight XCDs in turn, so the
+// workgroups that read the same landcover and soil run on the same XCD at about the same time, and its L2 has what
+// the later ones read.  The last 8 R are padded.
+__device__ __forceinline__ bool deal_item(const GridParams &p, uint32_t roles, uint32_t &item, uint32_t &role)
+{
+    item = blockIdx.x;
+    role = 0u;
+    if (roles > 1u) {
+        const uint32_t group = blockIdx.x / (8u * roles), in = blockIdx.x - group * (8u * roles);
+        item = group * 8u + (in & 7u);
+        role = in >> 3;
+    }
+    return item < p.items;      // the same for the whole workgroup
+}
+
+__global__ __launch_bounds__(kThreads) void grid_sums_kernel(const GridParams p)
+{
+    __shared__ GridLds lds;
+    uint32_t item, which;
+    if (!deal_item(p, p.n_conds, item, which))
+        return;
+    sum_item<false, 2u>(p, lds, item, p.conds[which], p.lut[0], 0u);
+}
+
+// roles of an item: (condition, image), the three images of a condition next to each other
+__global__ __launch_bounds__(kThreads) void grid_sums_weighted_kernel(const GridParams p)
+{
+    __shared__ GridLds lds;
+    uint32_t item, role;
+    if (!deal_item(p, 3u * p.n_conds, item, role))
+        return;
+    const uint32_t cond = p.conds[role / 3u], image = role % 3u;
+    if (image == 0u)
+        sum_item<false, 3u>(p, lds, item, cond, p.lut[0], 0u);
+    else
+        sum_item<true, 3u>(p, lds, item, cond, p.lut[image], image == 2u ? 8u : 0u);
+}
+
 struct FinishParams {
     const unsigned long long *acc;
     size_t n_cells, total;      // cells per raster, and over all rasters
-    uint8_t *means;
+    uint8_t *means, *cnq;
     const uint32_t *shared_idx;
     uint32_t n_shared, n_sel;
     unsigned long long *shared;
+    const uint16_t *weights;    // the context's, on the device (weighted finish only)
+    uint32_t rising;            // weights[1..100] never decrease: bisection finds the smallest c
 };
 
+// the rule of gcn10_runoff_cn (include/gcn10_host.h), with w[0..100] in LDS
+template <bool RISING>
+__device__ __forceinline__ uint8_t runoff_cn(const uint32_t *w, unsigned long long s, unsigned long long n,
+                                             unsigned long long sw)
+{
+    if (n == 0)
+        return (uint8_t)GCN10_NODATA;
+    if (sw == 0)
+        return (uint8_t)((2ull * s + n) / (2ull * n));
+    uint32_t lo = 1u, hi = 100u;
+    if (RISING) {
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (n * w[mid] >= sw)
+                hi = mid;
+            else
+                lo = mid + 1u;
+        }
+    }
+    else {
+        while (lo < hi && n * w[lo] < sw)
+            lo++;
+    }
+    return (uint8_t)lo;
+}
+
+// WORDS = 2: the means and the shared pairs.  WORDS = 3: the means, the runoff-equivalent bytes and the shared triples.
+template <uint32_t WORDS>
 __global__ __launch_bounds__(kThreads) void grid_finish_kernel(const FinishParams p)
 {
+    __shared__ uint32_t w[101];
+    if (WORDS == 3u) {
+        for (uint32_t i = threadIdx.x; i < 101u; i += kThreads)
+            w[i] = p.weights[i];
+        __syncthreads();
+    }
     const size_t stride = (size_t)gridDim.x * kThreads;
     for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < p.total; i += stride) {
-        const unsigned long long s = p.acc[2u * i], n = p.acc[2u * i + 1u];
+        const unsigned long long s = p.acc[WORDS * i], n = p.acc[WORDS * i + 1u];
         p.means[i] = n == 0 ? (uint8_t)GCN10_NODATA : (uint8_t)((2ull * s + n) / (2ull * n));
+        if (WORDS == 3u) {
+            const unsigned long long sw = p.acc[WORDS * i + 2u];
+            p.cnq[i] = p.rising ? runoff_cn<true>(w, s, n, sw) : runoff_cn<false>(w, s, n, sw);
+        }
     }
-    const size_t pairs = (size_t)p.n_sel * p.n_shared;
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < pairs; i += stride) {
+    const size_t packed = (size_t)p.n_sel * p.n_shared;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < packed; i += stride) {
         const size_t q = i / p.n_shared, k = i - q * p.n_shared;
         const size_t at = q * p.n_cells + p.shared_idx[k];
-        p.shared[2u * i] = p.acc[2u * at];
-        p.shared[2u * i + 1u] = p.acc[2u * at + 1u];
+#pragma unroll
+        for (uint32_t word = 0; word < WORDS; word++)
+            p.shared[WORDS * i + word] = p.acc[WORDS * at + word];
     }
 }
 
-}  // namespace
-
-extern "C" {
-
-int gcn10_gpu_grid_sums(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
-                        const int32_t *cellx, const int32_t *celly, int ncx, int ncy, unsigned cond_mask,
-                        unsigned table_mask, unsigned long long *acc, gcn10_stream_t stream)
+int launch_sums(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const uint8_t *esa, int W, int rows,
+                const int32_t *cj, const int32_t *cellx, const int32_t *celly, int ncx, int ncy, unsigned cond_mask,
+                unsigned table_mask, unsigned long long *acc, gcn10_stream_t stream)
 {
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    const char *const who = "gcn10_gpu_grid_sums";
     hipStream_t s = as_stream(ctx, stream);
     GridParams p = {};
-    if ((rc = check_tables(ctx, who)) != GCN10_OK || (rc = bind_soil(ctx, who, W, s, cj, &p.soil)) != GCN10_OK)
+    if ((rc = check_tables(ctx, who)) != GCN10_OK)
+        return rc;
+    if (weighted && !ctx->weights_set)
+        return fail(GCN10_E_STATE, "%s: call gcn10_gpu_set_weights first (after gcn10_gpu_set_tables)", who);
+    if ((rc = bind_soil(ctx, who, W, s, cj, &p.soil)) != GCN10_OK)
         return rc;
     if (!esa || !cj || !cellx || !celly || !acc || W <= 0 || rows <= 0 || ncx <= 0 || ncy <= 0)
-        return fail(GCN10_E_INVAL, "gcn10_gpu_grid_sums: bad arguments W=%d rows=%d cells %d x %d (all > 0, no null "
-                    "pointer)", W, rows, ncx, ncy);
+        return fail(GCN10_E_INVAL, "%s: bad arguments W=%d rows=%d cells %d x %d (all > 0, no null pointer)", who, W,
+                    rows, ncx, ncy);
     if ((rc = check_masks(ctx, who, cond_mask, table_mask)) != GCN10_OK)
         return rc;
     p.esa = esa;
-    p.lut16 = ctx->d_lut16;
+    p.lut[0] = ctx->d_lut16;
+    p.lut[1] = weighted ? ctx->d_wlut : nullptr;
+    p.lut[2] = weighted ? ctx->d_wlut + kLut16Bytes : nullptr;
     p.cellx = cellx;
     p.celly = celly;
     p.W = (uint32_t)W;
@@ -344,47 +457,126 @@ int gcn10_gpu_grid_sums(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
     for (uint32_t cnd = 0; cnd < 2; cnd++)
         if ((p.sel >> (9u * cnd)) & 0x1ffu)
             p.conds[n_conds++] = cnd;
+    const uint32_t roles = weighted ? 3u * n_conds : n_conds;
     p.chunks = (p.W + kChunkPx - 1u) / kChunkPx;
     // bands of at most kMaxBandRows rows, and shorter ones when the strip would not fill the device with them
-    const uint32_t want = grid_cap(ctx, 8) / (p.chunks * n_conds) + 1u;
+    const uint32_t want = grid_cap(ctx, 8) / (p.chunks * roles) + 1u;
     p.band_rows = min(max((p.rows + want - 1u) / want, 16u), kMaxBandRows);
     const uint64_t items = (uint64_t)((p.rows + p.band_rows - 1u) / p.band_rows) * p.chunks;
-    const uint64_t grid = n_conds == 2u ? (items + 7u) / 8u * 16u : items;
+    const uint64_t grid = roles > 1u ? (items + 7u) / 8u * (8u * roles) : items;
     if (grid > 0x7fffffffull)
-        return fail(GCN10_E_INVAL, "gcn10_gpu_grid_sums: %llu workgroups; cut the strip into bands",
-                    (unsigned long long)grid);
+        return fail(GCN10_E_INVAL, "%s: %llu workgroups; cut the strip into bands", who, (unsigned long long)grid);
     p.items = (uint32_t)items;
     p.n_conds = n_conds;
-    hipLaunchKernelGGL(grid_sums_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, p);
+    if (weighted)
+        hipLaunchKernelGGL(grid_sums_weighted_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, p);
+    else
+        hipLaunchKernelGGL(grid_sums_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, p);
     HIP_TRY(hipGetLastError());
     return GCN10_OK;
+}
+
+int launch_finish(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const unsigned long long *acc, int n_sel,
+                  size_t n_cells, uint8_t *means, uint8_t *cnq, const uint32_t *shared_idx, uint32_t n_shared,
+                  unsigned long long *shared, gcn10_stream_t stream)
+{
+    int rc = use_device(ctx);
+    if (rc)
+        return rc;
+    hipStream_t s = as_stream(ctx, stream);
+    if (weighted && !ctx->weights_set)
+        return fail(GCN10_E_STATE, "%s: call gcn10_gpu_set_weights first (after gcn10_gpu_set_tables)", who);
+    if (!acc || !means || (weighted && !cnq) || n_sel <= 0 || n_sel > GCN10_N_RASTERS || n_cells == 0 ||
+        n_cells > 0xffffffffull || (n_shared && (!shared_idx || !shared)))
+        return fail(GCN10_E_INVAL, "%s: bad arguments n_sel=%d n_cells=%zu n_shared=%u (1..%d rasters, 1..2^32-1 "
+                    "cells, no null pointer)", who, n_sel, n_cells, n_shared, GCN10_N_RASTERS);
+    FinishParams p = {};
+    p.acc = acc;
+    p.n_cells = n_cells;
+    p.total = n_cells * (size_t)n_sel;
+    p.means = means;
+    p.cnq = cnq;
+    p.shared_idx = shared_idx;
+    p.n_shared = n_shared;
+    p.n_sel = (uint32_t)n_sel;
+    p.shared = shared;
+    p.weights = weighted ? reinterpret_cast<const uint16_t *>(ctx->d_wlut + 2 * kLut16Bytes) : nullptr;
+    p.rising = ctx->weights_rising ? 1u : 0u;
+    const uint32_t grid = stream_grid(ctx, (p.total + kThreads - 1u) / kThreads);
+    if (weighted)
+        hipLaunchKernelGGL(grid_finish_kernel<3u>, dim3(grid), dim3(kThreads), 0, s, p);
+    else
+        hipLaunchKernelGGL(grid_finish_kernel<2u>, dim3(grid), dim3(kThreads), 0, s, p);
+    HIP_TRY(hipGetLastError());
+    return GCN10_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gcn10_gpu_grid_sums(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                        const int32_t *cellx, const int32_t *celly, int ncx, int ncy, unsigned cond_mask,
+                        unsigned table_mask, unsigned long long *acc, gcn10_stream_t stream)
+{
+    return launch_sums(ctx, "gcn10_gpu_grid_sums", false, esa, W, rows, cj, cellx, celly, ncx, ncy, cond_mask,
+                       table_mask, acc, stream);
 }
 
 int gcn10_gpu_grid_finish(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells,
                           uint8_t *means, const uint32_t *shared_idx, uint32_t n_shared, unsigned long long *shared,
                           gcn10_stream_t stream)
 {
+    return launch_finish(ctx, "gcn10_gpu_grid_finish", false, acc, n_sel, n_cells, means, nullptr, shared_idx,
+                         n_shared, shared, stream);
+}
+
+int gcn10_gpu_set_weights(gcn10_gpu_ctx *ctx, const uint16_t *w)
+{
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    hipStream_t s = as_stream(ctx, stream);
-    if (!acc || !means || n_sel <= 0 || n_sel > GCN10_N_RASTERS || n_cells == 0 || n_cells > 0xffffffffull ||
-        (n_shared && (!shared_idx || !shared)))
-        return fail(GCN10_E_INVAL, "gcn10_gpu_grid_finish: bad arguments n_sel=%d n_cells=%zu n_shared=%u (1..%d "
-                    "rasters, 1..2^32-1 cells, no null pointer)", n_sel, n_cells, n_shared, GCN10_N_RASTERS);
-    FinishParams p = {};
-    p.acc = acc;
-    p.n_cells = n_cells;
-    p.total = n_cells * (size_t)n_sel;
-    p.means = means;
-    p.shared_idx = shared_idx;
-    p.n_shared = n_shared;
-    p.n_sel = (uint32_t)n_sel;
-    p.shared = shared;
-    const uint32_t grid = stream_grid(ctx, (p.total + kThreads - 1u) / kThreads);
-    hipLaunchKernelGGL(grid_finish_kernel, dim3(grid), dim3(kThreads), 0, s, p);
-    HIP_TRY(hipGetLastError());
+    const char *const who = "gcn10_gpu_set_weights";
+    if ((rc = check_tables(ctx, who)) != GCN10_OK)
+        return rc;
+    if (!w)
+        return fail(GCN10_E_INVAL, "%s: null weights", who);
+    // the CN image as the device holds it, folded: a byte of 255 (no value, padding, a table not loaded) weighs 0
+    static thread_local uint8_t img[kLut16Bytes], planes[2 * kLut16Bytes + 256 * sizeof(uint16_t)];
+    ctx->weights_set = false;
+    HIP_TRY(hipMemcpy(img, ctx->d_lut16, sizeof img, hipMemcpyDeviceToHost));
+    for (int i = 0; i < kLut16Bytes; i++) {
+        const uint32_t v = img[i] == GCN10_NODATA ? 0u : w[img[i]];
+        planes[i] = (uint8_t)(v & 0xffu);
+        planes[kLut16Bytes + i] = (uint8_t)(v >> 8);
+    }
+    memcpy(planes + 2 * kLut16Bytes, w, 256 * sizeof(uint16_t));
+    if (!ctx->d_wlut)
+        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_wlut), sizeof planes));
+    // synchronous, as the images of set_tables: once per run, read by every later weighted call on any stream
+    HIP_TRY(hipMemcpy(ctx->d_wlut, planes, sizeof planes, hipMemcpyHostToDevice));
+    ctx->weights_rising = true;
+    for (int c = 2; c <= 100; c++)
+        if (w[c] < w[c - 1])
+            ctx->weights_rising = false;
+    ctx->weights_set = true;
     return GCN10_OK;
+}
+
+int gcn10_gpu_grid_sums_weighted(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                                 const int32_t *cellx, const int32_t *celly, int ncx, int ncy, unsigned cond_mask,
+                                 unsigned table_mask, unsigned long long *acc, gcn10_stream_t stream)
+{
+    return launch_sums(ctx, "gcn10_gpu_grid_sums_weighted", true, esa, W, rows, cj, cellx, celly, ncx, ncy, cond_mask,
+                       table_mask, acc, stream);
+}
+
+int gcn10_gpu_grid_finish_weighted(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells,
+                                   uint8_t *means, uint8_t *cnq, const uint32_t *shared_idx, uint32_t n_shared,
+                                   unsigned long long *shared, gcn10_stream_t stream)
+{
+    return launch_finish(ctx, "gcn10_gpu_grid_finish_weighted", true, acc, n_sel, n_cells, means, cnq, shared_idx,
+                         n_shared, shared, stream);
 }
 
 }  // extern "C"

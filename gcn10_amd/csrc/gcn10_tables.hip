@@ -139,6 +139,7 @@ int gcn10_gpu_set_tables(gcn10_gpu_ctx *ctx, const int *tables, int n_tables)
     if ((rc = upload_lut_images(ctx, tables, n_tables, img16)) != GCN10_OK)
         return rc;
     ctx->n_tables = n_tables;
+    ctx->weights_set = false;       // the weight planes were folded from the tables before
     return upload_pixel_classes(ctx, n_tables, img16);
 }
 

@@ -320,6 +320,15 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             }
             rc = set_str(&cfg->grid, val);
         }
+        else if (!strcmp(key, "storm")) {
+            if (gcn10_parse_storm(val, &cfg->storm_p, &cfg->storm_lambda) != 0) {
+                fclose(f);
+                snprintf(err, errcap, "bad value for storm: '%s' (P[,lambda]: 0 < P <= 650 mm, 0 <= lambda < 1)", val);
+                gcn10_config_free(cfg);
+                return -3;
+            }
+            rc = set_str(&cfg->storm, val);
+        }
         else if (!strcmp(key, "zones_shp_path"))
             rc = set_str(&cfg->zones_shp_path, val);
         else if (!strcmp(key, "zonal_output"))
@@ -377,5 +386,6 @@ void gcn10_config_free(gcn10_config *cfg)
     free(cfg->zones_id_field);
     free(cfg->zonal_output);
     free(cfg->grid);
+    free(cfg->storm);
     memset(cfg, 0, sizeof *cfg);
 }

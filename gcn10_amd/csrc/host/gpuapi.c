@@ -101,6 +101,10 @@ static void load_once(void)
     /* the sums and means on a model grid: needed by grid=... runs only, which check for them */
     *(void **)(&g_api.grid_sums) = dlsym(h, "gcn10_gpu_grid_sums");
     *(void **)(&g_api.grid_finish) = dlsym(h, "gcn10_gpu_grid_finish");
+    /* their weighted forms: needed by storm=... runs on a grid only, which check for them */
+    *(void **)(&g_api.set_weights) = dlsym(h, "gcn10_gpu_set_weights");
+    *(void **)(&g_api.grid_sums_weighted) = dlsym(h, "gcn10_gpu_grid_sums_weighted");
+    *(void **)(&g_api.grid_finish_weighted) = dlsym(h, "gcn10_gpu_grid_finish_weighted");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -15,6 +15,11 @@
  * shared cells are added up in a table of the whole process whose size follows the number of shared cells, and become
  * bytes after the last block.  All of it is integers, so the rasters do not depend on the order in which the workers of
  * all GPUs get there.  The rasters are written by the I/O pool through the host tile encoder: at most 64 Mpx each.
+ *
+ * With a design storm (config key "storm", runoff.c) the sums are triples {sum, count, sum of q[value]}: the worker hands
+ * the storm's runoff table to its context once (gcn10_gpu_set_weights) and runs the weighted pair of calls, which also
+ * gives the runoff-equivalent byte of every cell (gcn10_runoff_cn); the shared cells carry triples, and every selected
+ * raster is written twice, its mean as without a storm and cnq_<hc>_<arc>_p<N>.tif beside it.
  */
 #include "pipeline_internal.h"
 
@@ -232,10 +237,11 @@ NO_CONTRACT int gcn10_grid_plan_block(const gcn10_grid *g, int W, int H, const d
 struct gcn10_grid_result {
     pthread_mutex_t mu;
     uint8_t *raster;            /* [n_sel][ny][nx] */
+    uint8_t *cnq;               /* the same, runoff-equivalent (storm only) */
     uint32_t *key;              /* [cap]; NO_KEY: free */
-    uint64_t *pair;             /* [cap][n_sel][2] = {s, n} */
+    uint64_t *pair;             /* [cap][n_sel][words] = {s, n} or, with a storm, {s, n, sw} */
     size_t cap, used;
-    int n_sel;
+    int n_sel, words;
     int blocks;                 /* blocks summed */
     gcn10_raster *esa;          /* the landcover, for its pixel size and its geo tags */
 };
@@ -244,8 +250,9 @@ struct gcn10_grid_result {
 struct gcn10_grid_state {
     void *h_up, *d_up;                      /* cellx | celly | shared indices; h_* pinned */
     unsigned long long *d_acc, *d_shared, *h_shared;
-    uint8_t *d_means, *h_means;
+    uint8_t *d_means, *h_means;             /* the means, and with a storm the runoff-equivalent bytes behind them */
     size_t h_up_cap, d_up_cap, d_acc_cap, d_shared_cap, h_shared_cap, d_means_cap, h_means_cap;
+    bool weights_set;                       /* the context has the storm's runoff table */
 };
 
 static size_t slot_of(const struct gcn10_grid_result *t, uint32_t key)
@@ -261,7 +268,7 @@ static size_t slot_of(const struct gcn10_grid_result *t, uint32_t key)
 static int table_reserve(struct gcn10_grid_result *t, size_t more)
 {
     size_t cap = t->cap ? t->cap : 1024;
-    const size_t width = (size_t)t->n_sel * 2;
+    const size_t width = (size_t)t->n_sel * (size_t)t->words;
     uint32_t *okey = t->key;
     uint64_t *opair = t->pair;
     const size_t ocap = t->cap;
@@ -336,6 +343,7 @@ int gcn10_grid_start(struct run *r)
     r->grid_result = t;
     pthread_mutex_init(&t->mu, NULL);
     t->n_sel = r->n_sel > 0 ? r->n_sel : 1;
+    t->words = r->storm_on ? 3 : 2;
     /* the landcover's pixel size: below 8 pixels per cell the 10 m raster is the product (and a 16-pixel column group
      * of the kernel would meet more than three cell columns).  A landcover that does not open is the workers' to
      * report, block by block, as in every run. */
@@ -353,11 +361,15 @@ int gcn10_grid_start(struct run *r)
     }
     bytes = (size_t)t->n_sel * (size_t)r->grid.nx * (size_t)r->grid.ny;
     t->raster = malloc(bytes);
-    if (!t->raster || table_reserve(t, 0) != 0) {
-        fprintf(stderr, "[rank 0] out of memory for the grid rasters (%zu bytes)\n", bytes);
+    if (r->storm_on)
+        t->cnq = malloc(bytes);
+    if (!t->raster || (r->storm_on && !t->cnq) || table_reserve(t, 0) != 0) {
+        fprintf(stderr, "[rank 0] out of memory for the grid rasters (%zu bytes)\n", r->storm_on ? 2 * bytes : bytes);
         return -1;
     }
     memset(t->raster, GCN10_NODATA, bytes);
+    if (t->cnq)
+        memset(t->cnq, GCN10_NODATA, bytes);
     return 0;
 }
 
@@ -370,6 +382,7 @@ void gcn10_grid_end(struct run *r)
     gcn10_raster_close(t->esa);
     pthread_mutex_destroy(&t->mu);
     free(t->raster);
+    free(t->cnq);
     free(t->key);
     free(t->pair);
     free(t);
@@ -415,13 +428,15 @@ int gcn10_grid_plan_input(struct worker *w, struct block_in *in, const double ow
     return 0;
 }
 
-/* the block's bytes and pairs into the result of the run */
-static int merge_block(struct run *r, const gcn10_grid_plan *p, const uint8_t *means, const uint64_t *shared)
+/* the block's bytes (cnq: the runoff-equivalent ones, NULL without a storm) and pairs or triples into the result of
+ * the run */
+static int merge_block(struct run *r, const gcn10_grid_plan *p, const uint8_t *means, const uint8_t *cnq,
+                       const uint64_t *shared)
 {
     struct gcn10_grid_result *t = r->grid_result;
     const int ncx = p->cx1 - p->cx0, ncy = p->cy1 - p->cy0, nx = r->grid.nx;
     const size_t n_cells = (size_t)ncx * (size_t)ncy, plane = (size_t)nx * (size_t)r->grid.ny;
-    const size_t width = (size_t)t->n_sel * 2;
+    const size_t words = (size_t)t->words, width = (size_t)t->n_sel * words;
     int a = 0, b;
     int rc = 0;
 
@@ -433,9 +448,14 @@ static int merge_block(struct run *r, const gcn10_grid_plan *p, const uint8_t *m
     pthread_mutex_lock(&t->mu);
     for (int q = 0; q < t->n_sel && b > a; q++)
         for (int cy = 0; cy < ncy; cy++)
-            if (p->complete_y[cy])
-                memcpy(t->raster + (size_t)q * plane + (size_t)(p->cy0 + cy) * (size_t)nx + (size_t)(p->cx0 + a),
-                       means + (size_t)q * n_cells + (size_t)cy * (size_t)ncx + (size_t)a, (size_t)(b - a));
+            if (p->complete_y[cy]) {
+                const size_t to = (size_t)q * plane + (size_t)(p->cy0 + cy) * (size_t)nx + (size_t)(p->cx0 + a);
+                const size_t from = (size_t)q * n_cells + (size_t)cy * (size_t)ncx + (size_t)a;
+
+                memcpy(t->raster + to, means + from, (size_t)(b - a));
+                if (cnq)
+                    memcpy(t->cnq + to, cnq + from, (size_t)(b - a));
+            }
     if (table_reserve(t, p->n_shared) != 0)
         rc = -1;
     for (size_t i = 0; rc == 0 && i < p->n_shared; i++) {
@@ -448,10 +468,9 @@ static int merge_block(struct run *r, const gcn10_grid_plan *p, const uint8_t *m
             t->key[at] = key;
             t->used++;
         }
-        for (int q = 0; q < t->n_sel; q++) {
-            t->pair[at * width + 2 * (size_t)q] += shared[2 * ((size_t)q * p->n_shared + i)];
-            t->pair[at * width + 2 * (size_t)q + 1] += shared[2 * ((size_t)q * p->n_shared + i) + 1];
-        }
+        for (int q = 0; q < t->n_sel; q++)
+            for (size_t k = 0; k < words; k++)
+                t->pair[at * width + words * (size_t)q + k] += shared[words * ((size_t)q * p->n_shared + i) + k];
     }
     if (rc == 0)
         t->blocks++;
@@ -468,6 +487,8 @@ int gcn10_grid_block(struct worker *w, struct block_in *in)
     const size_t n_cells = (size_t)ncx * (size_t)ncy, n_sel = (size_t)r->n_sel;
     const size_t maps = ((size_t)in->W + (size_t)in->H) * sizeof(int32_t);
     const size_t up = maps + p->n_shared * sizeof(uint32_t);
+    const bool storm = r->storm_on;
+    const size_t words = storm ? 3 : 2, bytes = (storm ? 2 : 1) * n_sel * n_cells;  /* per cell: sums, and bytes back */
     struct gcn10_grid_state *s;
     int32_t *d_cellx, *d_celly;
     uint32_t *d_idx;
@@ -502,15 +523,20 @@ int gcn10_grid_block(struct worker *w, struct block_in *in)
         return 0;
     }
     if (gcn10_ensure_pinned_on(w, w->ctx, &s->h_up, &s->h_up_cap, up) != 0 ||
-        gcn10_ensure_pinned_on(w, w->ctx, (void **)&s->h_means, &s->h_means_cap, n_sel * n_cells) != 0 ||
+        gcn10_ensure_pinned_on(w, w->ctx, (void **)&s->h_means, &s->h_means_cap, bytes) != 0 ||
         gcn10_ensure_pinned_on(w, w->ctx, (void **)&s->h_shared, &s->h_shared_cap,
-                               (n_sel * p->n_shared + 1) * 2 * sizeof *s->h_shared) != 0 ||
+                               (n_sel * p->n_shared + 1) * words * sizeof *s->h_shared) != 0 ||
         gcn10_ensure_dev_on(w, w->ctx, &s->d_up, &s->d_up_cap, up) != 0 ||
-        gcn10_ensure_dev_on(w, w->ctx, (void **)&s->d_acc, &s->d_acc_cap, n_sel * n_cells * 2 * sizeof *s->d_acc) != 0 ||
-        gcn10_ensure_dev_on(w, w->ctx, (void **)&s->d_means, &s->d_means_cap, n_sel * n_cells) != 0 ||
+        gcn10_ensure_dev_on(w, w->ctx, (void **)&s->d_acc, &s->d_acc_cap, n_sel * n_cells * words * sizeof *s->d_acc) != 0 ||
+        gcn10_ensure_dev_on(w, w->ctx, (void **)&s->d_means, &s->d_means_cap, bytes) != 0 ||
         gcn10_ensure_dev_on(w, w->ctx, (void **)&s->d_shared, &s->d_shared_cap,
-                            (n_sel * p->n_shared + 1) * 2 * sizeof *s->d_shared) != 0)
+                            (n_sel * p->n_shared + 1) * words * sizeof *s->d_shared) != 0)
         return -1;
+    if (storm && !s->weights_set) {         /* once per context: the tables are set before the first block */
+        if (g->set_weights(w->ctx, r->runoff_q) != 0)
+            goto gpu_fail;
+        s->weights_set = true;
+    }
     memcpy(s->h_up, p->cellx, (size_t)in->W * sizeof(int32_t));
     memcpy((char *)s->h_up + (size_t)in->W * sizeof(int32_t), p->celly, (size_t)in->H * sizeof(int32_t));
     if (p->n_shared)
@@ -519,15 +545,19 @@ int gcn10_grid_block(struct worker *w, struct block_in *in)
     d_celly = d_cellx + in->W;
     d_idx = (uint32_t *)((char *)s->d_up + maps);
     if (g->memcpy_h2d(w->ctx, s->d_up, s->h_up, up, w->s_kernel) != 0 ||
-        g->memset(w->ctx, s->d_acc, 0, n_sel * n_cells * 2 * sizeof *s->d_acc, w->s_kernel) != 0 ||
+        g->memset(w->ctx, s->d_acc, 0, n_sel * n_cells * words * sizeof *s->d_acc, w->s_kernel) != 0 ||
         g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, in->W, w->s_kernel) != 0 ||
-        g->grid_sums(w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0, in->d_cj + p->y0,
-                     d_cellx, d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask, s->d_acc, w->s_kernel) != 0 ||
-        g->grid_finish(w->ctx, s->d_acc, r->n_sel, n_cells, s->d_means, p->n_shared ? d_idx : NULL,
-                       (uint32_t)p->n_shared, p->n_shared ? s->d_shared : NULL, w->s_kernel) != 0 ||
-        g->memcpy_d2h(w->ctx, s->h_means, s->d_means, n_sel * n_cells, w->s_kernel) != 0 ||
-        (p->n_shared && g->memcpy_d2h(w->ctx, s->h_shared, s->d_shared, n_sel * p->n_shared * 2 * sizeof *s->h_shared,
-                                      w->s_kernel) != 0))
+        (storm ? g->grid_sums_weighted : g->grid_sums)(
+            w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0, in->d_cj + p->y0, d_cellx,
+            d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask, s->d_acc, w->s_kernel) != 0 ||
+        (storm ? g->grid_finish_weighted(w->ctx, s->d_acc, r->n_sel, n_cells, s->d_means, s->d_means + n_sel * n_cells,
+                                         p->n_shared ? d_idx : NULL, (uint32_t)p->n_shared,
+                                         p->n_shared ? s->d_shared : NULL, w->s_kernel)
+               : g->grid_finish(w->ctx, s->d_acc, r->n_sel, n_cells, s->d_means, p->n_shared ? d_idx : NULL,
+                                (uint32_t)p->n_shared, p->n_shared ? s->d_shared : NULL, w->s_kernel)) != 0 ||
+        g->memcpy_d2h(w->ctx, s->h_means, s->d_means, bytes, w->s_kernel) != 0 ||
+        (p->n_shared && g->memcpy_d2h(w->ctx, s->h_shared, s->d_shared,
+                                      n_sel * p->n_shared * words * sizeof *s->h_shared, w->s_kernel) != 0))
         goto gpu_fail;
     {
         const double t0 = gcn10_now_seconds();
@@ -536,7 +566,7 @@ int gcn10_grid_block(struct worker *w, struct block_in *in)
             goto gpu_fail;
         w->t_gpu_wait += gcn10_now_seconds() - t0;
     }
-    if (merge_block(r, p, s->h_means, (const uint64_t *)s->h_shared) != 0) {
+    if (merge_block(r, p, s->h_means, storm ? s->h_means + n_sel * n_cells : NULL, (const uint64_t *)s->h_shared) != 0) {
         wlog(w, "ERROR", true, "out of memory for the shared cells of block %d", in->block_id);
         return -1;
     }
@@ -592,10 +622,11 @@ int gcn10_grid_finish(struct run *r, gcn10_log *log0)
 {
     struct gcn10_grid_result *t = r->grid_result;
     const gcn10_grid *gr = &r->grid;
-    const size_t plane = (size_t)gr->nx * (size_t)gr->ny, width = (size_t)t->n_sel * 2;
+    const size_t plane = (size_t)gr->nx * (size_t)gr->ny, words = (size_t)t->words, width = (size_t)t->n_sel * words;
+    const int per = r->storm_on ? 2 : 1, n_files = per * r->n_sel;      /* files per selected raster, and of the run */
     const double gt[6] = { gr->xmin, gr->dx, 0.0, gr->ymax, 0.0, -gr->dy };
     const int down = (gr->ny + TILE - 1) / TILE;
-    struct grid_file files[GCN10_N_RASTERS];
+    struct grid_file files[2 * GCN10_N_RASTERS];    /* file 2 q + 1 (storm only): the runoff-equivalent raster of q */
     struct grid_tile_job *jobs;
     struct gcn10_job_group group;
     char msg[PATH_MAX + 256], err[PATH_MAX + 256] = "";
@@ -605,9 +636,13 @@ int gcn10_grid_finish(struct run *r, gcn10_log *log0)
     /* the shared cells' sums become bytes by the rule of the kernels */
     for (size_t i = 0; i < t->cap; i++)
         if (t->key[i] != NO_KEY)
-            for (int q = 0; q < r->n_sel; q++)
-                t->raster[(size_t)q * plane + t->key[i]] = mean_of(t->pair[i * width + 2 * (size_t)q],
-                                                                   t->pair[i * width + 2 * (size_t)q + 1]);
+            for (int q = 0; q < r->n_sel; q++) {
+                const uint64_t *v = &t->pair[i * width + words * (size_t)q];
+
+                t->raster[(size_t)q * plane + t->key[i]] = mean_of(v[0], v[1]);
+                if (t->cnq)
+                    t->cnq[(size_t)q * plane + t->key[i]] = (uint8_t)gcn10_runoff_cn(v[0], v[1], v[2], r->runoff_q);
+            }
     for (size_t c = 0; c < plane; c++) {
         int q = 0;
 
@@ -627,37 +662,41 @@ int gcn10_grid_finish(struct run *r, gcn10_log *log0)
             return -1;
         }
     }
-    jobs = calloc((size_t)r->n_sel * (size_t)down, sizeof *jobs);
+    jobs = calloc((size_t)n_files * (size_t)down, sizeof *jobs);
     if (!jobs) {
         gcn10_log_message(log0, "ERROR", "grid: out of memory for the tile jobs", true);
         return -1;
     }
     memset(files, 0, sizeof files);
     gcn10_job_group_init(&group);
-    for (int q = 0; q < r->n_sel; q++) {
-        const int k = r->sel[q];
+    for (int fi = 0; fi < n_files; fi++) {
+        const int q = fi / per, k = r->sel[q];
         char path[PATH_MAX];
 
-        snprintf(path, sizeof path, "cn_grid_%s/cn_%s_%s.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
-                 gcn10_arcs[k % 3]);
-        files[q].data = t->raster + (size_t)q * plane;
-        files[q].tif = gcn10_tiff_create(path, gr->nx, gr->ny, gt, t->esa ? gcn10_raster_georef(t->esa) : NULL, err,
-                                         sizeof err);
-        if (files[q].tif && r->nodata >= 0 && gcn10_tiff_set_nodata(files[q].tif, r->nodata) != 0) {
+        if (fi % per == 0)
+            snprintf(path, sizeof path, "cn_grid_%s/cn_%s_%s.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
+                     gcn10_arcs[k % 3]);
+        else
+            snprintf(path, sizeof path, "cn_grid_%s/cnq_%s_%s_p%u.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
+                     gcn10_arcs[k % 3], (unsigned)r->runoff_q[100]);
+        files[fi].data = (fi % per == 0 ? t->raster : t->cnq) + (size_t)q * plane;
+        files[fi].tif = gcn10_tiff_create(path, gr->nx, gr->ny, gt, t->esa ? gcn10_raster_georef(t->esa) : NULL, err,
+                                          sizeof err);
+        if (files[fi].tif && r->nodata >= 0 && gcn10_tiff_set_nodata(files[fi].tif, r->nodata) != 0) {
             snprintf(err, sizeof err, "write error: cannot place the GDAL tags of %s", path);
-            gcn10_tiff_abort(files[q].tif);
-            files[q].tif = NULL;
+            gcn10_tiff_abort(files[fi].tif);
+            files[fi].tif = NULL;
         }
-        if (!files[q].tif) {
+        if (!files[fi].tif) {
             gcn10_log_message(log0, "ERROR", err, true);
             rc = -1;
             continue;
         }
         for (int ty = 0; ty < down; ty++) {
-            struct grid_tile_job *j = &jobs[(size_t)q * (size_t)down + (size_t)ty];
+            struct grid_tile_job *j = &jobs[(size_t)fi * (size_t)down + (size_t)ty];
 
             j->run = r;
-            j->file = &files[q];
+            j->file = &files[fi];
             j->group = &group;
             j->ty = ty;
             gcn10_job_group_add(&group, 1);
@@ -667,14 +706,15 @@ int gcn10_grid_finish(struct run *r, gcn10_log *log0)
     gcn10_job_group_wait(&group);
     gcn10_job_group_destroy(&group);
     free(jobs);
-    for (int q = 0; q < r->n_sel; q++) {
-        if (!files[q].tif)
+    for (int fi = 0; fi < n_files; fi++) {
+        if (!files[fi].tif)
             continue;
-        if (atomic_load(&files[q].failed)) {
-            gcn10_tiff_abort(files[q].tif);
-            snprintf(err, sizeof err, "write error: a tile of raster %d of the grid could not be written", r->sel[q]);
+        if (atomic_load(&files[fi].failed)) {
+            gcn10_tiff_abort(files[fi].tif);
+            snprintf(err, sizeof err, "write error: a tile of raster %d of the grid could not be written",
+                     r->sel[fi / per]);
         }
-        else if (gcn10_tiff_finish(files[q].tif, err, sizeof err) == 0) {
+        else if (gcn10_tiff_finish(files[fi].tif, err, sizeof err) == 0) {
             continue;
         }
         gcn10_log_message(log0, "ERROR", err, true);
@@ -684,8 +724,13 @@ int gcn10_grid_finish(struct run *r, gcn10_log *log0)
         gcn10_log_message(log0, "ERROR", "grid: the rasters could not be written", true);
         return -1;
     }
-    snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
-             "cn_grid_<cond>/", t->blocks, r->n_sel, gr->nx, gr->ny, empty);
+    if (r->storm_on)
+        snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
+                 "cn_grid_<cond>/: cn_<hc>_<arc>.tif (mean) and cnq_<hc>_<arc>_p%u.tif (runoff-equivalent)", t->blocks,
+                 r->n_sel, gr->nx, gr->ny, empty, (unsigned)r->runoff_q[100]);
+    else
+        snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
+                 "cn_grid_<cond>/", t->blocks, r->n_sel, gr->nx, gr->ny, empty);
     gcn10_log_message(log0, "INFO", msg, true);
     return 0;
 }

@@ -8,7 +8,8 @@
  * write LZW instead of DEFLATE GeoTIFFs, --stats / --nodata for GDAL band statistics and a NoData tag, and --verify
  * to check the rasters a run has written instead of writing them, and --zonal / --zones for the composite curve
  * numbers of the polygons of a shapefile instead of rasters, and --aggregate for area-mean rasters on a coarser grid,
- * and --grid for mean rasters on a model grid that spans the blocks.
+ * and --grid for mean rasters on a model grid that spans the blocks, and --storm for the runoff-weighted composites of
+ * a design storm beside the means of --grid and --zones.
  * No mpirun: one process drives every GPU of the node.
  */
 #include "gcn10_host.h"
@@ -26,7 +27,7 @@ static void usage(FILE *fp)
             "        [--lookups <names>] [--conditions drained|undrained|both] [--compress deflate|lzw]\n"
             "        [--cog] [--overview-resampling nearest|average] [--stats] [--nodata none|<0..255>]\n"
             "        [--verify] [--zonal] [--zones <zones.shp>] [--aggregate <f>]\n"
-            "        [--grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>]\n"
+            "        [--grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>] [--storm <P>[,<lambda>]]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -58,6 +59,12 @@ static void usage(FILE *fp)
             "\t\t\tmore) from the upper-left corner (xmin, ymax), each the mean over its pixels of all\n"
             "\t\t\tprocessed blocks, reduced on the GPU (config key grid=...); not with --verify, --zonal,\n"
             "\t\t\t--aggregate, --overwrite or --compress lzw\n"
+            "  --storm <P>[,<lambda>]\ta design storm: P mm of rain (0 < P <= 650) and the initial-abstraction ratio\n"
+            "\t\t\t(0 <= lambda < 1, default 0.2).  With --grid, a second raster per selected raster,\n"
+            "\t\t\tcn_grid_<cond>/cnq_<hc>_<arc>_p<100 P>.tif: the runoff-equivalent CN of every cell, the\n"
+            "\t\t\tcurve number that yields the cell's mean runoff depth for that storm, summed on the GPU;\n"
+            "\t\t\twith --zones, the columns runoff_mm,cn_runoff (config key storm=...); needs --grid or\n"
+            "\t\t\t--zones, not with --aggregate or --verify\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -112,6 +119,8 @@ int main(int argc, char **argv)
             opt.aggregate = argv[++i];
         else if (!strcmp(argv[i], "--grid") && i + 1 < argc)
             opt.grid = argv[++i];
+        else if (!strcmp(argv[i], "--storm") && i + 1 < argc)
+            opt.storm = argv[++i];
         else if (!strcmp(argv[i], "--zonal"))
             opt.zonal = true;
         else if (!strcmp(argv[i], "--zones") && i + 1 < argc) {

@@ -265,6 +265,9 @@ struct run {
     gcn10_grid grid;
     struct gcn10_grid_result *grid_result;
     atomic_int grid_incomplete;             /* a block's inputs could not be read: the rasters lack it, exit code 1 */
+    /* storm=...: the runoff-weighted composites beside the means of a grid or zonal run (runoff.c) */
+    bool storm_on;
+    uint16_t runoff_q[256];                 /* gcn10_runoff_table of the storm */
 };
 
 double gcn10_now_seconds(void);

@@ -104,6 +104,30 @@ static int resolve(struct run *r)
         return 1;
     }
     r->aggregate = r->cfg.aggregate;
+    /* a design storm: its runoff table, and the runs it cannot go with */
+    if (opt->storm) {
+        if (gcn10_parse_storm(opt->storm, &r->cfg.storm_p, &r->cfg.storm_lambda) != 0) {
+            fprintf(stderr, "[rank 0] bad value for storm: '%s' (P[,lambda]: 0 < P <= 650 mm, 0 <= lambda < 1)\n",
+                    opt->storm);
+            return 1;
+        }
+        free(r->cfg.storm);
+        r->cfg.storm = strdup(opt->storm);
+    }
+    r->storm_on = r->cfg.storm != NULL;
+    if (r->storm_on) {
+        if (r->verify)
+            why = "storm cannot be combined with --verify";
+        else if (r->aggregate)
+            why = "storm cannot be combined with aggregate (use --grid with cells of f pixels)";
+        else if (!r->zonal && !opt->grid && !r->cfg.grid)
+            why = "storm needs --grid or --zones";
+        if (why) {
+            fprintf(stderr, "[rank 0] %s\n", why);
+            return 1;
+        }
+        gcn10_runoff_table(r->cfg.storm_p, r->cfg.storm_lambda, r->runoff_q);
+    }
     if (r->aggregate && gcn10_aggregate_start(r) != 0)
         return 1;
     /* a grid run: the grid, the refused combinations, the result of the run */
@@ -166,7 +190,7 @@ static int resolve(struct run *r)
 static int require(struct run *r)
 {
     const struct gcn10_gpu_api *g;
-    char err[2048] = "", agg[48], grid[600];
+    char err[2048] = "", agg[48], grid[600], storm[600];
 
     r->gpu = g = gcn10_gpu_api_get(err, sizeof err);
     if (!g) {
@@ -175,6 +199,7 @@ static int require(struct run *r)
     }
     snprintf(agg, sizeof agg, "aggregate=%d", r->aggregate);
     snprintf(grid, sizeof grid, "grid=%s", r->grid_on ? r->cfg.grid : "");
+    snprintf(storm, sizeof storm, "storm=%s", r->storm_on ? r->cfg.storm : "");
     {
         /* the pair histogram's soil codes are asked for where a mode counts pairs, and must be as many as its bins */
         const bool pairs = (r->stats || r->zonal) && g->pair_histogram_codes &&
@@ -184,6 +209,8 @@ static int require(struct run *r)
             { r->stats, g->pair_histogram && pairs, "gcn10_gpu_pair_histogram", "stats=1" },
             { r->zonal, g->zonal_pair_histogram && pairs, "gcn10_gpu_zonal_pair_histogram", "zonal=1" },
             { r->aggregate != 0, g->aggregate != NULL, "gcn10_gpu_aggregate", agg },
+            { r->grid_on && r->storm_on, g->set_weights && g->grid_sums_weighted && g->grid_finish_weighted,
+              "gcn10_gpu_grid_sums_weighted", storm },
             { r->grid_on, g->grid_sums && g->grid_finish, "gcn10_gpu_grid_sums", grid },
             { r->verify, g->verify_strip && g->verify_buffers, "gcn10_gpu_verify_strip", "verify=1" },
             { r->lzw, g->lzw_strip && g->lzw_arena_bound, "gcn10_gpu_lzw_strip", "compress=lzw" },
@@ -353,6 +380,14 @@ static int load(struct run *r)
 
     log0_line(r, "INFO", true, "processing %d blocks %s", r->n_blocks,
               opt->blocks_file ? "from list file" : "from shapefile");      /* src/main.c:165-167 */
+    if (r->storm_on) {
+        int threshold = 1;
+
+        while (threshold < 100 && r->runoff_q[threshold] == 0)
+            threshold++;
+        log0_line(r, "INFO", true, "storm: P = %.17g mm, lambda = %.17g, threshold CN %d (the smallest curve number that "
+                  "sheds water)", r->cfg.storm_p, r->cfg.storm_lambda, threshold);
+    }
     if (r->n_workers > r->n_blocks) {       /* no worker (and no pinned memory) without a block */
         for (int i = r->n_blocks > 0 ? r->n_blocks : 1; i < r->n_workers; i++) {
             gcn10_log_close(r->workers[i].log);

@@ -1,0 +1,81 @@
+/* runoff.c -- the design storm of the runoff-weighted composites (config key "storm", --storm): no counterpart in the
+ * reference.
+ *
+ * A storm is a rainfall depth P in mm and an initial-abstraction ratio lambda.  The SCS runoff depth of a curve number
+ * is a table of 256 16-bit values in units of 0.01 mm, made here in plain IEEE double (this file is built with
+ * -ffp-contract=off, as geo.c is) in the operation order stated in include/gcn10_host.h; everything after the table is
+ * integers: a cell's or a zone's sum of table values, and the smallest curve number whose runoff over the whole cell
+ * reaches that sum.
+ */
+#include "gcn10_host.h"
+
+#include <errno.h>
+#include <math.h>
+#include <stdlib.h>
+
+#if defined(__GNUC__) && !defined(__clang__)
+#define NO_CONTRACT __attribute__((optimize("fp-contract=off")))
+#else
+#define NO_CONTRACT
+#pragma STDC FP_CONTRACT OFF
+#endif
+
+int gcn10_parse_storm(const char *text, double *P, double *lambda)
+{
+    double d[2] = { 0.0, 0.2 };
+    const char *p = text;
+    char *end;
+
+    if (!text)
+        return -1;
+    for (int i = 0; i < 2; i++) {
+        /* strtod skips leading white space and takes "inf" and "nan": a field starts with a sign, a digit or a point,
+         * and the values are checked below */
+        if (!(*p == '-' || *p == '+' || *p == '.' || (*p >= '0' && *p <= '9')))
+            return -1;
+        errno = 0;
+        d[i] = strtod(p, &end);
+        if (end == p || errno != 0 || (*end != '\0' && !(i == 0 && *end == ',')))
+            return -1;
+        if (*end == '\0')
+            break;
+        p = end + 1;
+    }
+    if (!isfinite(d[0]) || !isfinite(d[1]) || !(d[0] > 0.0) || !(d[0] <= 650.0) || !(d[1] >= 0.0) || !(d[1] < 1.0))
+        return -1;
+    *P = d[0];
+    *lambda = d[1];
+    return 0;
+}
+
+NO_CONTRACT void gcn10_runoff_table(double P, double lambda, uint16_t q[256])
+{
+    q[0] = q[255] = 0;
+    for (int v = 1; v < 255; v++) {
+        const double c = v < 100 ? (double)v : 100.0;
+        const double S = 25400.0 / c - 254.0;
+        const double Ia = lambda * S;
+
+        if (!(P > Ia)) {
+            q[v] = 0;
+        }
+        else {
+            const double e = P - Ia;
+            const double r = floor(e * e / (e + S) * 100.0 + 0.5);
+
+            q[v] = (uint16_t)(r < 0.0 ? 0.0 : (r > 65535.0 ? 65535.0 : r));     /* 0 < P <= 650: r <= 65000 */
+        }
+    }
+}
+
+int gcn10_runoff_cn(uint64_t s, uint64_t n, uint64_t sw, const uint16_t q[256])
+{
+    if (n == 0)
+        return 255;                         /* no value, as in every raster */
+    if (sw == 0)
+        return (int)((2 * s + n) / (2 * n));
+    for (int c = 1; c < 100; c++)
+        if (n * (uint64_t)q[c] >= sw)
+            return c;
+    return 100;
+}

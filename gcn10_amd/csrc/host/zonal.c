@@ -7,7 +7,9 @@
  * stay bounded whatever the shapefile holds.  The host turns a zone's pair histogram into the selected rasters'
  * histograms (gcn10_raster_histogram) and adds pixels, valid pixels (value != 255, whatever "nodata" says: 255 is
  * never a curve number), sum, sum of squares, min and max into one table of the whole process.  All of it is
- * integers, so the table does not depend on the order in which the workers of all GPUs add to it.
+ * integers, so the table does not depend on the order in which the workers of all GPUs add to it.  With a design storm
+ * (config key "storm", runoff.c) the sum of the storm's runoff table over the valid pixels is added up as well, from the
+ * same histograms, and the table gets the columns runoff_mm,cn_runoff.
  */
 #include "pipeline_internal.h"
 
@@ -30,6 +32,7 @@ enum { ZONE_BATCH = 1024, SPAN_BATCH = 1 << 20 };
 
 struct zcell {
     uint64_t pixels, valid, sum, sum2;
+    uint64_t runoff;            /* sum of runoff_q[value] over the valid pixels (storm only) */
     int min, max;
 };
 
@@ -136,7 +139,7 @@ static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *ce
         uint64_t hist[256];
 
         gcn10_raster_histogram_sparse(at, n, m, r->hist_codes, r->tables[k % 9], k / 9 == 0, hist);
-        c->pixels = c->valid = c->sum = c->sum2 = 0;
+        c->pixels = c->valid = c->sum = c->sum2 = c->runoff = 0;
         c->min = 255;
         c->max = 0;
         for (int v = 0; v < 256; v++) {
@@ -148,6 +151,8 @@ static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *ce
             c->valid += hist[v];
             c->sum += hist[v] * (uint64_t)v;
             c->sum2 += hist[v] * (uint64_t)(v * v);
+            if (r->storm_on)
+                c->runoff += hist[v] * (uint64_t)r->runoff_q[v];
             if (v < c->min)
                 c->min = v;
             if (v > c->max)
@@ -261,6 +266,7 @@ int gcn10_zonal_block(struct worker *w, struct block_in *in)
                     dst[q].valid += src[q].valid;
                     dst[q].sum += src[q].sum;
                     dst[q].sum2 += src[q].sum2;
+                    dst[q].runoff += src[q].runoff;
                     if (src[q].valid && src[q].min < dst[q].min)
                         dst[q].min = src[q].min;
                     if (src[q].valid && src[q].max > dst[q].max)
@@ -296,7 +302,8 @@ int gcn10_zonal_finish(struct run *r, gcn10_log *log0)
     snprintf(tmp, sizeof tmp, "%s.part.%ld", path, (long)getpid());
     f = fopen(tmp, "w");
     if (f) {
-        fprintf(f, "zone_id,condition,hc,arc,pixels,valid,sum,mean,min,max,stddev\n");
+        fprintf(f, "zone_id,condition,hc,arc,pixels,valid,sum,mean,min,max,stddev%s\n",
+                r->storm_on ? ",runoff_mm,cn_runoff" : "");
         for (int i = 0; i < r->zones.n; i++) {
             if (r->n_sel > 0 && t->cell[(size_t)i * (size_t)r->n_sel].pixels == 0)
                 without++;
@@ -311,11 +318,15 @@ int gcn10_zonal_finish(struct run *r, gcn10_log *log0)
                     /* the mean and the population standard deviation as gcn10_band_stats_of forms them */
                     const unsigned __int128 var = (unsigned __int128)c->sum2 * c->valid - (unsigned __int128)c->sum * c->sum;
 
-                    fprintf(f, "%.14g,%d,%d,%.14g\n", (double)c->sum / (double)c->valid, c->min, c->max,
+                    fprintf(f, "%.14g,%d,%d,%.14g", (double)c->sum / (double)c->valid, c->min, c->max,
                             sqrt((double)var) / (double)c->valid);
+                    if (r->storm_on)        /* the zone's mean runoff depth, and the curve number that yields it */
+                        fprintf(f, ",%.14g,%d", (double)c->runoff / (double)c->valid / 100.0,
+                                gcn10_runoff_cn(c->sum, c->valid, c->runoff, r->runoff_q));
+                    fprintf(f, "\n");
                 }
                 else {
-                    fprintf(f, ",,,\n");
+                    fprintf(f, r->storm_on ? ",,,,,\n" : ",,,\n");
                 }
             }
         }

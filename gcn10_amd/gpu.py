@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_pair_histogram_codes", "gcn10_gpu_pair_histogram",
     "gcn10_gpu_verify_strip", "gcn10_gpu_verify_buffers", "gcn10_gpu_zonal_pair_histogram",
     "gcn10_gpu_aggregate", "gcn10_gpu_grid_sums", "gcn10_gpu_grid_finish",
+    "gcn10_gpu_set_weights", "gcn10_gpu_grid_sums_weighted", "gcn10_gpu_grid_finish_weighted",
 )
 
 
@@ -146,6 +147,9 @@ def lib():
             "gcn10_gpu_aggregate": (i, [vp, vp, i, i, vp, i, i, i, u, u, C.POINTER(vp), sz, vp]),
             "gcn10_gpu_grid_sums": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp]),
             "gcn10_gpu_grid_finish": (i, [vp, vp, i, sz, vp, vp, C.c_uint32, vp, vp]),
+            "gcn10_gpu_set_weights": (i, [vp, vp]),
+            "gcn10_gpu_grid_sums_weighted": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp]),
+            "gcn10_gpu_grid_finish_weighted": (i, [vp, vp, i, sz, vp, vp, vp, C.c_uint32, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -458,6 +462,30 @@ class Engine:
         on `stream`."""
         self._chk(lib().gcn10_gpu_grid_finish(self._ctx, acc_ptr, n_sel, n_cells, means_ptr, shared_idx_ptr or None,
                                               n_shared, shared_ptr or None, stream), "gcn10_gpu_grid_finish")
+
+    def set_weights(self, w):
+        """The 256 16-bit weights of the weighted grid sums, folded into the loaded tables (gcn10_gpu_set_weights):
+        after set_tables, and again after every later set_tables.  Synchronous."""
+        a = np.ascontiguousarray(w, dtype=np.uint16).reshape(256)
+        self._chk(lib().gcn10_gpu_set_weights(self._ctx, a.ctypes.data), "gcn10_gpu_set_weights")
+
+    def grid_sums_weighted(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, cellx_ptr: int, celly_ptr: int, ncx: int,
+                           ncy: int, cond_mask: int, table_mask: int, acc_ptr: int, stream=None):
+        """grid_sums with triples: ADDS {s, n, sw} to acc[q][celly[y]][cellx[x]] (uint64 on the device,
+        [n_sel][ncy][ncx][3]), s and n exactly as grid_sums, sw the sum of w[v] over the same pixels for the weights of
+        set_weights (gcn10_gpu_grid_sums_weighted).  Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_sums_weighted(self._ctx, esa_ptr, W, rows, cj_ptr, cellx_ptr, celly_ptr, ncx, ncy,
+                                                     cond_mask, table_mask, acc_ptr, stream),
+                  "gcn10_gpu_grid_sums_weighted")
+
+    def grid_finish_weighted(self, acc_ptr: int, n_sel: int, n_cells: int, means_ptr: int, cnq_ptr: int, shared_idx_ptr,
+                             n_shared: int, shared_ptr, stream=None):
+        """means[q][c] as grid_finish, cnq[q][c] = host.runoff_cn of the triple with the weights of set_weights, and the
+        triples of the n_shared cells shared_idx names, packed into shared[q][i]
+        (gcn10_gpu_grid_finish_weighted).  Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_finish_weighted(self._ctx, acc_ptr, n_sel, n_cells, means_ptr, cnq_ptr,
+                                                       shared_idx_ptr or None, n_shared, shared_ptr or None, stream),
+                  "gcn10_gpu_grid_finish_weighted")
 
     def zonal_pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans, items, n_zones: int,
                              hist_ptr: int, stream=None):

@@ -133,6 +133,14 @@ def lib():
         L.gcn10_grid_plan_block.restype = C.c_int
         L.gcn10_grid_plan_free.argtypes = [C.POINTER(GridPlan)]
         L.gcn10_grid_plan_free.restype = None
+        L.gcn10_parse_storm.argtypes = [cp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.gcn10_parse_storm.restype = C.c_int
+        L.gcn10_runoff_table.argtypes = [C.c_double, C.c_double, np.ctypeslib.ndpointer(dtype=np.uint16,
+                                                                                       flags="C_CONTIGUOUS")]
+        L.gcn10_runoff_table.restype = None
+        L.gcn10_runoff_cn.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64,
+                                      np.ctypeslib.ndpointer(dtype=np.uint16, flags="C_CONTIGUOUS")]
+        L.gcn10_runoff_cn.restype = C.c_int
         L.gcn10_zone_items_build.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(ZonePlan)]
         L.gcn10_zone_items_build.restype = C.c_int
         L.gcn10_tiff_abort.argtypes = [vp]
@@ -170,6 +178,11 @@ class ConfigGrid(ConfigFull):
     """``gcn10_config`` with the key of the model grid, appended behind ``ConfigFull`` (whose field list is pinned by
     the tests of the aggregate key) as the C struct appends it; the pointer lies behind the padding of ``aggregate``."""
     _fields_ = [("grid", C.c_char_p)]
+
+
+class ConfigStorm(ConfigGrid):
+    """``gcn10_config`` with the key of the design storm, appended behind ``ConfigGrid`` as the C struct appends it."""
+    _fields_ = [("storm", C.c_char_p), ("storm_p", C.c_double), ("storm_lambda", C.c_double)]
 
 
 assert C.sizeof(Config) % 8 == 0
@@ -361,15 +374,38 @@ def grid_plan_block(grid, W: int, H: int, gt, own=None) -> dict:
     return out
 
 
+def parse_storm(text: str):
+    """"<P>[,<lambda>]" -> (P, lambda) (``gcn10_parse_storm``; lambda 0.2 when absent); raises HostError for any other
+    text."""
+    p, lam = C.c_double(), C.c_double()
+    if lib().gcn10_parse_storm(text.encode(), C.byref(p), C.byref(lam)) != 0:
+        raise HostError("bad value for storm: '%s' (P[,lambda]: 0 < P <= 650 mm, 0 <= lambda < 1)" % text)
+    return p.value, lam.value
+
+
+def runoff_table(P: float, lam: float = 0.2) -> np.ndarray:
+    """The runoff depth of every raster value for a storm of P mm and initial-abstraction ratio lam, uint16[256] in units
+    of 0.01 mm (``gcn10_runoff_table``)."""
+    q = np.zeros(256, np.uint16)
+    lib().gcn10_runoff_table(float(P), float(lam), q)
+    return q
+
+
+def runoff_cn(s: int, n: int, sw: int, q) -> int:
+    """The runoff-equivalent curve number of a cell with sum s, count n and sum of q[value] sw
+    (``gcn10_runoff_cn``)."""
+    return int(lib().gcn10_runoff_cn(int(s), int(n), int(sw), np.ascontiguousarray(q, dtype=np.uint16).reshape(256)))
+
+
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = ConfigGrid()
+    cfg = ConfigStorm()
     err = C.create_string_buffer(1024)
     rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
     out = {}
-    for name, _t in Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_:
+    for name, _t in Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_ + ConfigStorm._fields_:
         v = getattr(cfg, name)
         out[name] = v.decode() if isinstance(v, bytes) else v
     lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))

@@ -41,7 +41,8 @@ extern "C" {
  *    and gcn10_gpu_inflate_codecs; the overview kernels of the COG output (gcn10_gpu_overview_*); the pair histogram
  *    of the band statistics (gcn10_gpu_pair_histogram*); the raster verifier (gcn10_gpu_verify_*); the pair histogram
  *    per zone of the zonal composites (gcn10_gpu_zonal_pair_histogram); the area means on a coarser grid
- *    (gcn10_gpu_aggregate); the sums and means on a model grid (gcn10_gpu_grid_sums, gcn10_gpu_grid_finish).
+ *    (gcn10_gpu_aggregate); the sums and means on a model grid (gcn10_gpu_grid_sums, gcn10_gpu_grid_finish) and their
+ *    weighted forms (gcn10_gpu_set_weights, gcn10_gpu_grid_sums_weighted, gcn10_gpu_grid_finish_weighted).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -423,6 +424,33 @@ int gcn10_gpu_grid_sums(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
 int gcn10_gpu_grid_finish(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells, uint8_t *means,
                           const uint32_t *shared_idx_dev, uint32_t n_shared, unsigned long long *shared,
                           gcn10_stream_t stream);
+
+/* Weighted sums on a model grid (config key storm=...: the runoff-weighted composites).  Added in ABI 3 without a
+ * version change; the host looks them up for storm runs on a grid only.
+ *
+ * gcn10_gpu_set_weights: w[256], a 16-bit weight per raster value (host memory; w[255] is never read).  Called after
+ *   gcn10_gpu_set_tables, with no weighted call in flight: it folds w into two images of the loaded tables (the low
+ *   and the high bytes of w[value], zero where there is no value) and keeps w for gcn10_gpu_grid_finish_weighted.
+ *   Synchronous.  A later gcn10_gpu_set_tables invalidates the weights: the two weighted calls then answer
+ *   GCN10_E_STATE ("call gcn10_gpu_set_weights first") until it is called again.
+ * gcn10_gpu_grid_sums_weighted: every word of gcn10_gpu_grid_sums -- the maps, the -1 rule, three cell columns per
+ *   group of 16, ADD semantics, nothing read at or beyond W, nothing written outside acc whatever the maps hold --
+ *   with triples {s, n, sw} instead of pairs: words 0 and 1 are exactly what gcn10_gpu_grid_sums adds, word 2 gets the
+ *   sum of w[v] over the same pixels (v != 255).  Integers only: the triples do not depend on bands, chunks or order.
+ * gcn10_gpu_grid_finish_weighted: means[] as gcn10_gpu_grid_finish writes it; cnq[q * n_cells + c] = the
+ *   runoff-equivalent value of the triple by the rule of gcn10_runoff_cn (gcn10_host.h) with the context's weights:
+ *   255 when n = 0, the mean byte when sw = 0, else the smallest c in 1..100 with n * w[c] >= sw (100 when there is
+ *   none); and the triples of the shared cells, packed: shared[q * n_shared + i] = acc[q * n_cells + shared_idx[i]].
+ * Errors as the unweighted calls', cnq among the pointers. */
+int gcn10_gpu_set_weights(gcn10_gpu_ctx *ctx, const uint16_t *w /* [256] */);
+int gcn10_gpu_grid_sums_weighted(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                                 const int32_t *cellx_dev, const int32_t *celly_dev, int ncx, int ncy,
+                                 unsigned cond_mask, unsigned table_mask,
+                                 unsigned long long *acc /* [n_sel][ncy][ncx][3] = {s, n, sw} */,
+                                 gcn10_stream_t stream);
+int gcn10_gpu_grid_finish_weighted(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells,
+                                   uint8_t *means, uint8_t *cnq, const uint32_t *shared_idx_dev, uint32_t n_shared,
+                                   unsigned long long *shared, gcn10_stream_t stream);
 
 /* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
  * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.

@@ -137,6 +137,10 @@ typedef struct gcn10_config {
     char *grid;             /* "grid": <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny> (gcn10_parse_grid): no 10 m raster is written but
                                one raster per selected raster on that grid, the mean over each cell's pixels of all
                                blocks, reduced on the GPU (grid.c); absent (default) = off */
+    char *storm;            /* "storm": <P>[,<lambda>] (gcn10_parse_storm): the design storm of the runoff-weighted
+                               composites -- with grid, a second raster per selected raster, the runoff-equivalent CN of
+                               every cell; with zonal, two more columns of the table; absent (default) = off */
+    double storm_p, storm_lambda;   /* ... its rainfall depth in mm and its initial-abstraction ratio */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -160,7 +164,7 @@ int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or
 int gcn10_parse_aggregate(const char *text, int *factor);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -460,6 +464,26 @@ int gcn10_grid_plan_block(const gcn10_grid *g, int W, int H, const double gt[6],
 void gcn10_grid_plan_free(gcn10_grid_plan *p);
 
 /* ------------------------------------------------------------------------ */
+/* runoff-weighted composites (config key "storm", --storm): no counterpart in the reference                */
+/* ------------------------------------------------------------------------ */
+
+/* "<P>[,<lambda>]": the rainfall depth of a design storm in mm and its initial-abstraction ratio (absent: 0.2), read
+ * with strtod, nothing else in the text; 0 < P <= 650 and 0 <= lambda < 1.  0, or -1 for another text. */
+int gcn10_parse_storm(const char *text, double *P, double *lambda);
+/* The runoff depth of every raster value for that storm, in units of 0.01 mm.  q[0] = q[255] = 0; for v in 1..254, in
+ * IEEE double, this order, no FMA:
+ *   c = min(v, 100);  S = 25400.0 / c - 254.0;  Ia = lambda * S;
+ *   !(P > Ia): q[v] = 0;  else  e = P - Ia,  q[v] = floor(e * e / (e + S) * 100.0 + 0.5).
+ * Table values above 100 count as 100; q[100] = round(100 P) <= 65000 is the maximum of the table. */
+void gcn10_runoff_table(double P, double lambda, uint16_t q[256]);
+/* The runoff-equivalent curve number of a cell (or zone): over its pixels with value v != 255, s = the sum of v, n
+ * their count, sw = the sum of q[v].  n == 0: 255.  sw == 0: the mean byte (2 s + n) / (2 n) -- no pixel sheds water,
+ * every CN up to the storm's threshold is "equivalent", and the mean is one of them.  Otherwise the smallest c in
+ * 1..100 with n * q[c] >= sw, in 64-bit integers (100 when there is none, which cannot happen with a table of
+ * gcn10_runoff_table: q[100] is its maximum). */
+int gcn10_runoff_cn(uint64_t s, uint64_t n, uint64_t sw, const uint16_t q[256]);
+
+/* ------------------------------------------------------------------------ */
 /* the run: src/main.c:58-203 + process_block, src/cn.c:134-384              */
 /* ------------------------------------------------------------------------ */
 
@@ -480,6 +504,7 @@ typedef struct gcn10_run_options {
     const char *zones;          /* --zones <file.shp>: overrides the config key "zones_shp_path" and implies --zonal */
     const char *aggregate;      /* --aggregate <f>: overrides the config key "aggregate" */
     const char *grid;           /* --grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>: overrides the config key "grid" */
+    const char *storm;          /* --storm <P>[,<lambda>]: overrides the config key "storm" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -517,7 +542,8 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * (opt->aggregate / "aggregate=<f>") writes cn_rasters_<cond>_x<f>/ instead of the 10 m rasters: exit codes as for a
  * write run.  A grid run (opt->grid / "grid=...") writes cn_grid_<cond>/cn_<hc>_<arc>.tif, one raster per selected
  * raster on the model grid, after the last block: exit codes as for a zonal run (1 as well when a block's inputs could
- * not be read: the rasters are written, but lack that block). */
+ * not be read: the rasters are written, but lack that block).  A storm (opt->storm / "storm=<P>[,<lambda>]") adds
+ * cn_grid_<cond>/cnq_<hc>_<arc>_p<N>.tif to a grid run and the columns runoff_mm,cn_runoff to a zonal run's table. */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

@@ -59,20 +59,26 @@ int gcn10_aggregate_start(struct run *r)
         fprintf(stderr, "[rank 0] %s\n", why);
         return -1;
     }
+    snprintf(r->out_suffix, sizeof r->out_suffix, "_x%d", r->aggregate);
     return 0;
 }
 
-int gcn10_aggregate_plan_block(struct worker *w, struct block_in *in, const double own[4])
+/* the input side: the block's grid of cells, which is what its files hold */
+static int aggregate_plan_block(struct worker *w, struct block_in *in, const double own[4])
 {
     if (gcn10_aggregate_geometry(in->W, in->H, in->gt, own, w->run->aggregate, &in->agg) != 0) {
         wlog(w, "ERROR", true, "aggregate block %d: the %d x %d window owns no pixel of its block, or is not north up",
              in->block_id, in->W, in->H);
         return 1;
     }
+    in->out_W = in->agg.Wa;
+    in->out_H = in->agg.Ha;
+    memcpy(in->out_gt, in->agg.gt, sizeof in->out_gt);
     return 0;
 }
 
-int gcn10_aggregate_block(struct worker *w, struct block_in *in, gcn10_tiff_writer *tifs[GCN10_N_RASTERS])
+/* the block reduced into the worker's overview buffers and handed to the encoder and the sink as premade rasters */
+static int aggregate_strips(struct worker *w, struct block_in *in, gcn10_tiff_writer *tifs[GCN10_N_RASTERS])
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
@@ -117,7 +123,7 @@ int gcn10_aggregate_block(struct worker *w, struct block_in *in, gcn10_tiff_writ
     return gcn10_run_strips(w, a->Wa, a->Ha, NULL, NULL, (const uint8_t *const *)w->d_ov_ptrs, NULL, tifs);
 }
 
-void gcn10_aggregate_finish(struct run *r, gcn10_log *log0)
+static int aggregate_finish(struct run *r, gcn10_log *log0)
 {
     char msg[256];
     int blocks = 0;
@@ -127,4 +133,11 @@ void gcn10_aggregate_finish(struct run *r, gcn10_log *log0)
     snprintf(msg, sizeof msg, "aggregate: %d blocks, %d rasters each, cells of %d x %d px, under cn_rasters_<cond>_x%d/",
              blocks, r->n_sel, r->aggregate, r->aggregate, r->aggregate);
     gcn10_log_message(log0, "INFO", msg, true);
+    return 0;
 }
+
+/* the write path with premade rasters: a block that cannot be planned or read is given up as a write run gives it up */
+const struct gcn10_mode gcn10_mode_aggregate = {
+    .writes_block_files = true, .plan_block = aggregate_plan_block, .block = gcn10_encode_block, .strips = aggregate_strips,
+    .finish = aggregate_finish,
+};

@@ -305,6 +305,22 @@ static uint8_t mean_of(uint64_t s, uint64_t n)
     return n == 0 ? (uint8_t)GCN10_NODATA : (uint8_t)((2 * s + n) / (2 * n));
 }
 
+static void grid_end(struct run *r)
+{
+    struct gcn10_grid_result *t = r->grid_result;
+
+    if (!t)
+        return;
+    gcn10_raster_close(t->esa);
+    pthread_mutex_destroy(&t->mu);
+    free(t->raster);
+    free(t->cnq);
+    free(t->key);
+    free(t->pair);
+    free(t);
+    r->grid_result = NULL;
+}
+
 int gcn10_grid_start(struct run *r)
 {
     const gcn10_run_options *opt = &r->opt;
@@ -356,6 +372,7 @@ int gcn10_grid_start(struct run *r)
         if (r->grid.dx < 8.0 * fabs(gt[1]) || r->grid.dy < 8.0 * fabs(gt[5])) {
             fprintf(stderr, "[rank 0] bad value for grid: '%s' (cells under 8 landcover pixels of %.17g x %.17g)\n",
                     r->cfg.grid, fabs(gt[1]), fabs(gt[5]));
+            grid_end(r);
             return -1;
         }
     }
@@ -365,6 +382,7 @@ int gcn10_grid_start(struct run *r)
         t->cnq = malloc(bytes);
     if (!t->raster || (r->storm_on && !t->cnq) || table_reserve(t, 0) != 0) {
         fprintf(stderr, "[rank 0] out of memory for the grid rasters (%zu bytes)\n", r->storm_on ? 2 * bytes : bytes);
+        grid_end(r);
         return -1;
     }
     memset(t->raster, GCN10_NODATA, bytes);
@@ -373,23 +391,7 @@ int gcn10_grid_start(struct run *r)
     return 0;
 }
 
-void gcn10_grid_end(struct run *r)
-{
-    struct gcn10_grid_result *t = r->grid_result;
-
-    if (!t)
-        return;
-    gcn10_raster_close(t->esa);
-    pthread_mutex_destroy(&t->mu);
-    free(t->raster);
-    free(t->cnq);
-    free(t->key);
-    free(t->pair);
-    free(t);
-    r->grid_result = NULL;
-}
-
-void gcn10_grid_teardown(struct worker *w)
+static void grid_teardown(struct worker *w)
 {
     const struct gcn10_gpu_api *g = w->run->gpu;
     struct gcn10_grid_state *s = w->gridst;
@@ -409,15 +411,15 @@ void gcn10_grid_teardown(struct worker *w)
     w->gridst = NULL;
 }
 
-void gcn10_grid_block_unreadable(struct worker *w, int block_id)
+static void grid_block_unreadable(struct worker *w, int block_id)
 {
     wlog(w, "ERROR", true, "grid block %d: its landcover or soil window could not be read; the rasters lack this block",
          block_id);
-    atomic_store(&w->run->grid_incomplete, 1);
+    atomic_store(&w->run->incomplete, 1);
 }
 
 /* the input side: the grid over the staged block, while the block before is summed */
-int gcn10_grid_plan_input(struct worker *w, struct block_in *in, const double own[4])
+static int grid_plan_input(struct worker *w, struct block_in *in, const double own[4])
 {
     gcn10_grid_plan_free(&in->gplan);
     if (gcn10_grid_plan_block(&w->run->grid, in->W, in->H, in->gt, own, &in->gplan) != 0) {
@@ -478,7 +480,7 @@ static int merge_block(struct run *r, const gcn10_grid_plan *p, const uint8_t *m
     return rc;
 }
 
-int gcn10_grid_block(struct worker *w, struct block_in *in)
+static int grid_block(struct worker *w, struct block_in *in)
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
@@ -500,19 +502,12 @@ int gcn10_grid_block(struct worker *w, struct block_in *in)
     s = w->gridst;
 
     /* the block on the device, as for a write run */
-    if (g->stream_wait_event(w->ctx, w->s_kernel, in->ev_ready) != 0)
+    switch (gcn10_block_take(w, in)) {
+    case GCN10_BLOCK_DEVICE_ERROR:
         goto gpu_fail;
-    if (in->n_inflate > 0) {
-        if (g->event_sync(w->ctx, in->ev_ready) != 0)
-            goto gpu_fail;
-        for (size_t i = 0; i < in->n_inflate; i++)
-            if (in->jl.h_status[i] != 0) {
-                wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
-                                       "(stream %zu, reason %u)", in->xoff, in->yoff, in->W, in->H, i, in->jl.h_status[i]);
-                wlog(w, "ERROR", true, "esa load failed for block %d", in->block_id);
-                gcn10_grid_block_unreadable(w, in->block_id);
-                return 0;
-            }
+    case GCN10_BLOCK_UNREADABLE:
+        grid_block_unreadable(w, in->block_id);
+        return 0;
     }
     wlog(w, "INFO", false, "grid block %d: cells [%d, %d) x [%d, %d), %zu shared with other blocks", in->block_id,
          p->cx0, p->cx1, p->cy0, p->cy1, p->n_shared);
@@ -616,9 +611,9 @@ static void grid_tile_row(void *arg)
     gcn10_job_group_done(j->group);
 }
 
-/* The rasters, each through a temporary name and rename (the writer's), and the closing console line.  0, or -1 when a
- * raster could not be written. */
-int gcn10_grid_finish(struct run *r, gcn10_log *log0)
+/* The rasters, each through a temporary name and rename (the writer's), and the closing console line.  The exit code: 0,
+ * or 1 when a raster could not be written. */
+static int grid_finish(struct run *r, gcn10_log *log0)
 {
     struct gcn10_grid_result *t = r->grid_result;
     const gcn10_grid *gr = &r->grid;
@@ -659,13 +654,13 @@ int gcn10_grid_finish(struct run *r, gcn10_log *log0)
         if (mkdir(dir, 0755) != 0 && errno != EEXIST) {
             snprintf(msg, sizeof msg, "failed to create output directory %s", dir);
             gcn10_log_message(log0, "ERROR", msg, true);
-            return -1;
+            return 1;
         }
     }
     jobs = calloc((size_t)n_files * (size_t)down, sizeof *jobs);
     if (!jobs) {
         gcn10_log_message(log0, "ERROR", "grid: out of memory for the tile jobs", true);
-        return -1;
+        return 1;
     }
     memset(files, 0, sizeof files);
     gcn10_job_group_init(&group);
@@ -722,7 +717,7 @@ int gcn10_grid_finish(struct run *r, gcn10_log *log0)
     }
     if (rc != 0) {
         gcn10_log_message(log0, "ERROR", "grid: the rasters could not be written", true);
-        return -1;
+        return 1;
     }
     if (r->storm_on)
         snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
@@ -734,3 +729,14 @@ int gcn10_grid_finish(struct run *r, gcn10_log *log0)
     gcn10_log_message(log0, "INFO", msg, true);
     return 0;
 }
+
+static void grid_plan_free(struct block_in *in)
+{
+    gcn10_grid_plan_free(&in->gplan);
+}
+
+const struct gcn10_mode gcn10_mode_grid = {
+    .plan_block = grid_plan_input, .plan_free = grid_plan_free, .block = grid_block,
+    .block_unreadable = grid_block_unreadable, .worker_teardown = grid_teardown,
+    .finish = grid_finish, .end = grid_end,
+};

@@ -87,15 +87,7 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
     struct run *r = w->run;
     char err[1024] = "";
     double t_mark = now_seconds();
-    /* an aggregate run: the block's grid of cells instead of its window, under cn_rasters_<cond>_x<f> */
-    const int OW = r->aggregate ? in->agg.Wa : in->W, OH = r->aggregate ? in->agg.Ha : in->H;
-    const double *ogt = r->aggregate ? in->agg.gt : in->gt;
-    char suffix[16] = "";
 
-    if (r->aggregate)
-        snprintf(suffix, sizeof suffix, "_x%d", r->aggregate);
-    memset(in->tifs, 0, sizeof in->tifs);
-    in->tifs_ok = false;
     if (r->null_sink) {
         in->tifs_ok = true;
         return 0;
@@ -105,7 +97,7 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
 
         if (!(r->cond_mask & (1u << c)))
             continue;
-        snprintf(dir, sizeof dir, "cn_rasters_%s%s", gcn10_conds[c], suffix);
+        snprintf(dir, sizeof dir, "cn_rasters_%s%s", gcn10_conds[c], r->out_suffix);
         if (mkdir(dir, 0755) != 0 && errno != EEXIST) {
             wlog(w, "ERROR", true, "failed to create output directory %s", dir);       /* src/cn.c:250 */
             return -1;
@@ -115,13 +107,14 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
         const int k = r->sel[q];
         char path[PATH_MAX];
 
-        output_path(path, sizeof path, gcn10_conds[k / 9], suffix, gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3],
+        output_path(path, sizeof path, gcn10_conds[k / 9], r->out_suffix, gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3],
                     in->block_id, r->opt.overwrite);
         if (r->cog)
             in->tifs[k] = gcn10_tiff_create_cog(path, in->W, in->H, in->gt, gcn10_raster_georef(w->esa),
                                                 cog_levels_of(in->W, in->H), err, sizeof err);
         else
-            in->tifs[k] = gcn10_tiff_create(path, OW, OH, ogt, gcn10_raster_georef(w->esa), err, sizeof err);
+            in->tifs[k] = gcn10_tiff_create(path, in->out_W, in->out_H, in->out_gt, gcn10_raster_georef(w->esa), err,
+                                            sizeof err);
         if (!in->tifs[k]) {
             wlog(w, "ERROR", true, "%s", err);          /* save_raster logs and goes on, src/raster.c:220-223 */
             gcn10_abort_outputs(in);
@@ -338,10 +331,34 @@ static int encode_overviews(struct worker *w, struct block_in *in, gcn10_tiff_wr
     return 0;
 }
 
+int gcn10_block_statuses(struct worker *w, const struct block_in *in)
+{
+    if (in->n_inflate == 0)
+        return GCN10_BLOCK_READY;
+    /* every landcover chunk must have been a valid one (the statuses came back behind ev_ready) */
+    if (w->run->gpu->event_sync(w->ctx, in->ev_ready) != 0)
+        return GCN10_BLOCK_DEVICE_ERROR;
+    for (size_t i = 0; i < in->n_inflate; i++)
+        if (in->jl.h_status[i] != 0) {
+            wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
+                                   "(stream %zu, reason %u)", in->xoff, in->yoff, in->W, in->H, i, in->jl.h_status[i]);
+            wlog(w, "ERROR", true, "esa load failed for block %d", in->block_id);
+            return GCN10_BLOCK_UNREADABLE;
+        }
+    return GCN10_BLOCK_READY;
+}
+
+int gcn10_block_take(struct worker *w, const struct block_in *in)
+{
+    if (w->run->gpu->stream_wait_event(w->ctx, w->s_kernel, in->ev_ready) != 0)
+        return GCN10_BLOCK_DEVICE_ERROR;
+    return gcn10_block_statuses(w, in);
+}
+
 /* The back half of process_block (src/cn.c:236-384) for a block whose input the input side has put on its
  * way to HBM.  Returns 0 (done, or skipped like the reference skips) or -1 for errors the
  * reference answers with MPI_Abort */
-static int encode_block(struct worker *w, struct block_in *in)
+int gcn10_encode_block(struct worker *w, struct block_in *in)
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
@@ -369,7 +386,7 @@ static int encode_block(struct worker *w, struct block_in *in)
 
     /* device side of the block: the encoder waits (on the device) for the input side's copies and kernels */
     w->strip_rows = r->strip_rows;
-    if (gcn10_sink_ensure_buffers(w, r->aggregate ? in->agg.Wa : W) != 0) {
+    if (gcn10_sink_ensure_buffers(w, in->out_W) != 0) {
         rc = -1;
         goto out;
     }
@@ -409,8 +426,7 @@ static int encode_block(struct worker *w, struct block_in *in)
     }
     if (r->stats && g->memset(w->ctx, w->d_hist, 0, GCN10_PAIR_HIST_SIZE * sizeof *w->d_hist, w->s_kernel) != 0)
         goto gpu_fail;
-    if ((r->aggregate ? gcn10_aggregate_block(w, in, tifs)
-                      : gcn10_run_strips(w, W, H, in->d_block, in->d_cj, NULL, r->stats ? w->d_hist : NULL, tifs)) != 0) {
+    if (r->mode->strips(w, in, tifs) != 0) {
         rc = -1;
         goto out;
     }
@@ -419,18 +435,12 @@ static int encode_block(struct worker *w, struct block_in *in)
          g->stream_sync(w->ctx, w->s_kernel) != 0))
         goto gpu_fail;
     ok = !atomic_load(&w->failed);
-    if (in->n_inflate > 0) {
-        /* every landcover chunk must have been a valid one (the statuses came back behind ev_ready) */
-        if (g->event_sync(w->ctx, in->ev_ready) != 0)
-            goto gpu_fail;
-        for (size_t i = 0; i < in->n_inflate; i++)
-            if (in->jl.h_status[i] != 0) {
-                wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
-                                       "(stream %zu, reason %u)", in->xoff, in->yoff, W, H, i, in->jl.h_status[i]);
-                wlog(w, "ERROR", true, "esa load failed for block %d", block_id);
-                ok = false;
-                break;
-            }
+    /* the statuses here, behind the strips, so that decode and encode overlap */
+    switch (gcn10_block_statuses(w, in)) {
+    case GCN10_BLOCK_DEVICE_ERROR:
+        goto gpu_fail;
+    case GCN10_BLOCK_UNREADABLE:
+        ok = false;
     }
     goto out;
 
@@ -472,6 +482,15 @@ out:
     return rc;
 }
 
+/* the write run: the block's own strips, counted for the statistics on their way */
+static int write_strips(struct worker *w, struct block_in *in, gcn10_tiff_writer *tifs[GCN10_N_RASTERS])
+{
+    return gcn10_run_strips(w, in->W, in->H, in->d_block, in->d_cj, NULL, w->run->stats ? w->d_hist : NULL, tifs);
+}
+
+const struct gcn10_mode gcn10_mode_write = { .writes_block_files = true, .block = gcn10_encode_block,
+                                             .strips = write_strips };
+
 /* ------------------------------------------------------------------------ */
 /* workers: the ranks of src/main.c:58-203                                   */
 /* ------------------------------------------------------------------------ */
@@ -483,9 +502,8 @@ static void worker_teardown(struct worker *w)
     gcn10_input_teardown(w);
     if (w->ctx) {
         g->device_sync(w->ctx);
-        gcn10_verify_teardown(w);
-        gcn10_zonal_teardown(w);
-        gcn10_grid_teardown(w);
+        if (w->run->mode->worker_teardown)
+            w->run->mode->worker_teardown(w);
         gcn10_sink_free_buffers(w);
         for (int i = 0; i < w->run->nbuf; i++) {
             struct strip_buf *b = &w->buf[i];
@@ -653,15 +671,9 @@ void *gcn10_worker_main(void *arg)
         if (!in)
             break;
         t0 = now_seconds();
-        if (r->verify && in->outcome == 1)
-            gcn10_verify_block_unreadable(w, in->block_id);
-        if (r->zonal && in->outcome == 1)
-            gcn10_zonal_block_unreadable(w, in->block_id);
-        if (r->grid_on && in->outcome == 1)
-            gcn10_grid_block_unreadable(w, in->block_id);
-        if (in->outcome == 0 && !atomic_load(&r->fatal) &&
-            (r->verify ? gcn10_verify_block(w, in) : r->zonal ? gcn10_zonal_block(w, in)
-             : r->grid_on ? gcn10_grid_block(w, in) : encode_block(w, in)) != 0)
+        if (in->outcome == 1 && r->mode->block_unreadable)
+            r->mode->block_unreadable(w, in->block_id);
+        if (in->outcome == 0 && !atomic_load(&r->fatal) && r->mode->block(w, in) != 0)
             atomic_store(&r->fatal, 1);     /* where the reference calls MPI_Abort */
         gcn10_abort_outputs(in);            /* files of a block that was not encoded after all (a no-op otherwise) */
         w->busy_seconds += now_seconds() - t0;

@@ -261,31 +261,25 @@ static int fill_block(struct worker *w, struct block_in *in, int block_id)
         gcn10_stager_idle(&w->ring);
         return rc == -2 ? -1 : 1;
     }
+    /* no file yet, and rasters of the window's size unless the mode's plan says otherwise */
+    memset(in->tifs, 0, sizeof in->tifs);
+    in->tifs_ok = false;
+    in->out_W = in->W;
+    in->out_H = in->H;
+    memcpy(in->out_gt, in->gt, sizeof in->out_gt);
+    /* what the mode makes of the block on the host (the zones or the grid's cells over it, its grid of aggregated
+     * cells), here on the input side: it overlaps the block before */
+    if (r->mode->plan_block && (rc = r->mode->plan_block(w, in, r->blocks.bbox[bi])) != 0) {
+        g->stream_sync(w->in_ctx, w->s_in);
+        gcn10_stager_idle(&w->ring);
+        return rc;
+    }
+    if (!r->mode->writes_block_files)
+        return 0;
     /* the block's 18 files, while the copies and the decoder run (the reference creates each raster's file
      * inside save_raster, after computing it: src/raster.c:204; an existing raster of that name is untouched
      * until this one is complete either way: files are written as <name>.part) */
-    if (r->verify || r->zonal || r->grid_on) {
-        /* a verify run and a zonal run write no raster, a grid run none per block */
-        memset(in->tifs, 0, sizeof in->tifs);
-        in->tifs_ok = false;
-        /* the zones, or the grid's cells, over this block, here on the input side: it overlaps the block before */
-        if ((r->zonal && gcn10_zonal_plan_block(w, in, r->blocks.bbox[bi]) != 0) ||
-            (r->grid_on && gcn10_grid_plan_input(w, in, r->blocks.bbox[bi]) != 0)) {
-            g->stream_sync(w->in_ctx, w->s_in);
-            gcn10_stager_idle(&w->ring);
-            return -1;
-        }
-        return 0;
-    }
-    if (r->aggregate && gcn10_aggregate_plan_block(w, in, r->blocks.bbox[bi]) != 0) {
-        g->stream_sync(w->in_ctx, w->s_in);
-        gcn10_stager_idle(&w->ring);
-        return 1;
-    }
-    rc = gcn10_create_outputs(w, in);
-    if (rc < 0)
-        return -1;
-    return 0;               /* (rc == 1: logged; the worker finds tifs_ok false and gives the block up) */
+    return gcn10_create_outputs(w, in) < 0 ? -1 : 0;    /* (1: logged; the worker finds tifs_ok false and gives it up) */
 }
 
 /* takes the next block of the queue and fills slot `in` with it; false at the end of the queue */
@@ -426,8 +420,8 @@ void gcn10_input_teardown(struct worker *w)
             struct block_in *in = &w->in[k];
 
             gcn10_abort_outputs(in);        /* a staged block the worker never took */
-            gcn10_zone_plan_free(&in->zplan);
-            gcn10_grid_plan_free(&in->gplan);
+            if (w->run->mode->plan_free)
+                w->run->mode->plan_free(in);
             if (in->h_coarse) g->host_free(w->in_ctx, in->h_coarse);
             if (in->h_ci) g->host_free(w->in_ctx, in->h_ci);
             if (in->h_cj) g->host_free(w->in_ctx, in->h_cj);

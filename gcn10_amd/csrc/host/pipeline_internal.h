@@ -1,7 +1,9 @@
 /* pipeline_internal.h -- the worker and run state shared by run.c (the run's steps), pipeline.c (workers, a block's
- * strips), sink.c (strip buffers, sink jobs), pipeline_input.c (landcover input through the GPU decoder), launcher.c,
- * verify.c, zonal.c, aggregate.c and grid.c, and what the writer and the verifier have in common: the chunk stager (stage.c)
- * and the overview levels (levels.c). */
+ * strips), sink.c (strip buffers, sink jobs), pipeline_input.c (landcover input through the GPU decoder), launcher.c and
+ * the kinds of run, and what the writer and the verifier have in common: the chunk stager (stage.c) and the overview
+ * levels (levels.c).  A run is of one kind -- write (pipeline.c), aggregate.c, verify.c, zonal.c or grid.c -- and each
+ * is a struct gcn10_mode beside its code; resolve() (run.c) leaves the run's in run.mode and the driver calls through
+ * it.  Every kind takes a staged block over with gcn10_block_take, the one reader of the decoder's status words. */
 #ifndef GCN10_PIPELINE_INTERNAL_H
 #define GCN10_PIPELINE_INTERNAL_H
 
@@ -140,9 +142,13 @@ struct block_in {
      * the input side while the block before is encoded: 18 open + truncate calls are 5-10 ms per block */
     gcn10_tiff_writer *tifs[GCN10_N_RASTERS];
     bool tifs_ok;                           /* all of the run's rasters have their file */
-    gcn10_zone_plan zplan;                  /* zonal=1: the zones' spans and items over this block (zones.c) */
-    gcn10_aggregate_geom agg;               /* aggregate=<f>: the block's owned pixels and its grid of cells (aggregate.c) */
-    gcn10_grid_plan gplan;                  /* grid=...: the block's cell rectangle, maps and shared cells (grid.c) */
+    int out_W, out_H;                       /* the rasters in them: the window's, unless the mode's plan_block says */
+    double out_gt[6];                       /* otherwise (aggregate.c: the block's grid of cells) */
+    /* the mode's plan of the block (plan_block, plan_free): the zones' spans and items over it (zonal.c, zones.c), its
+     * owned pixels and grid of cells (aggregate.c), its cell rectangle, maps and shared cells (grid.c) */
+    gcn10_zone_plan zplan;
+    gcn10_aggregate_geom agg;
+    gcn10_grid_plan gplan;
 };
 
 struct worker {
@@ -197,10 +203,12 @@ struct worker {
     /* band statistics (stats=1): the block's pair histogram on the device, and its copy */
     unsigned long long *d_hist, *h_hist;    /* GCN10_PAIR_HIST_SIZE counters; h_hist pinned */
     size_t d_hist_cap, h_hist_cap;
-    struct gcn10_verify_state *verify;      /* verify=1: the worker's decode buffers and counters (verify.c) */
-    struct gcn10_zonal_state *zonal;        /* zonal=1: the worker's span, item and histogram buffers (zonal.c) */
-    struct gcn10_grid_state *gridst;        /* grid=...: the worker's map, sum and mean buffers (grid.c) */
-    double t_zone_plan, t_zone_accum;       /* ... seconds of the input side building spans, of the worker adding up */
+    /* the mode's buffers of this worker, made with its first block, freed by worker_teardown: decode buffers and
+     * counters (verify.c), span, item and histogram buffers (zonal.c), map, sum and mean buffers (grid.c) */
+    struct gcn10_verify_state *verify;
+    struct gcn10_zonal_state *zonal;
+    struct gcn10_grid_state *gridst;
+    double t_zone_plan, t_zone_accum;       /* zonal: seconds of the input side building spans, of the worker adding up */
     long n_win_gpu, n_win_gpu_lzw, n_win_host;  /* landcover windows through the GPU decoder (of them with LZW chunks),
                                                    through the host reader */
 };
@@ -246,25 +254,27 @@ struct run {
     unsigned cond_mask, table_mask;         /* the rasters this run produces ("conditions" / "lookups") */
     int n_sel;                              /* how many: popcount(cond_mask) * popcount(table_mask) */
     int sel[GCN10_N_RASTERS];               /* their raster indices cond*9 + hc*3 + arc, ascending */
+    /* the kind of run, which the driver calls through; and what the config says, for resolve()'s refusals, require()'s
+     * table, the modes themselves and sink.c (an aggregate run has no full-resolution strips) */
+    const struct gcn10_mode *mode;
+    bool verify, zonal, grid_on;
+    int aggregate;                          /* the factor f, 0 = none */
+    atomic_int incomplete;                  /* a block could not be read and the run's one result lacks it: exit code 1 */
     /* verify=1: nothing is written; what the workers found */
-    bool verify;
     atomic_int verify_n_ok, verify_n_bad, verify_n_missing, verify_n_unchecked;    /* files; overview levels */
     pthread_mutex_t verify_mu;
     int *verify_failed;                     /* ids of the blocks with a bad or missing file, in the order found */
     int verify_n_failed, verify_failed_cap;
     /* zonal=1: nothing is written but the table of composite curve numbers per zone (zonal.c) */
-    bool zonal;
     gcn10_zones zones;
     struct gcn10_zonal_table *zonal_table;
-    atomic_int zonal_incomplete;            /* a block's inputs could not be read: the table lacks it, exit code 1 */
-    /* aggregate=<f>: no 10 m raster is written but every selected raster's area means over f x f pixels (aggregate.c) */
-    int aggregate;
+    /* aggregate=<f>: no 10 m raster is written but every selected raster's area means over f x f pixels, under
+     * cn_rasters_<cond><out_suffix> (aggregate.c) */
+    char out_suffix[16];
     /* grid=...: no 10 m raster is written but every selected raster's means on one model grid, merged over all blocks
      * and written after the last one (grid.c) */
-    bool grid_on;
     gcn10_grid grid;
     struct gcn10_grid_result *grid_result;
-    atomic_int grid_incomplete;             /* a block's inputs could not be read: the rasters lack it, exit code 1 */
     /* storm=...: the runoff-weighted composites beside the means of a grid or zonal run (runoff.c) */
     bool storm_on;
     uint16_t runoff_q[256];                 /* gcn10_runoff_table of the storm */
@@ -336,44 +346,39 @@ void gcn10_abort_outputs(struct block_in *in);
  * the aggregated rasters as `premade` ones */
 int gcn10_run_strips(struct worker *w, int W, int H, const uint8_t *d_block, const int32_t *d_cj,
                      const uint8_t *const *premade, unsigned long long *hist, gcn10_tiff_writer *tifs[GCN10_N_RASTERS]);
-/* aggregate.c: the refused combinations (before any GPU is opened; 0, or -1 with a line on stderr); the grid of a
- * staged block, made by the input side (0, or 1: logged, the block is given up); a staged block reduced into the
- * worker's overview buffers and handed to the encoder and the sink (0, or -1 for errors that end the run); the closing
- * console line.  The worker's buffers are those of the overview phase, which an aggregate run does not have, so there
- * is nothing of its own to tear down. */
+/* pipeline.c: a staged block taken over by the worker.  gcn10_block_take: s_kernel waits for the input side's event,
+ * then the statuses.  gcn10_block_statuses: where chunks went through the decoder, waits for that event on the host and
+ * looks at every status word; the first bad one is logged with the two lines of a failed load_raster.  (The write path
+ * calls the second alone, behind its strips: a host wait before them would serialise decode and encode.) */
+enum { GCN10_BLOCK_READY = 0, GCN10_BLOCK_UNREADABLE = 1, GCN10_BLOCK_DEVICE_ERROR = -1 };   /* (the last: not logged) */
+int gcn10_block_take(struct worker *w, const struct block_in *in);
+int gcn10_block_statuses(struct worker *w, const struct block_in *in);
+/* pipeline.c: the back half of process_block for the modes that write the block's files: the staged block through the
+ * mode's strips, the encoder and the sink (0, also for a block given up as the reference gives it up, or -1) */
+int gcn10_encode_block(struct worker *w, struct block_in *in);
+
+/* One kind of run.  A member that is NULL is a step the kind does not have. */
+struct gcn10_mode {
+    bool writes_block_files;                /* the input side creates the block's files (gcn10_create_outputs) */
+    /* input side, behind the staging of a block (own: the block's box): 0, or it is logged and the block's outcome is
+     * what it returns (1: given up, -1: the run ends); plan_free: what it left in the slot */
+    int (*plan_block)(struct worker *w, struct block_in *in, const double own[4]);
+    void (*plan_free)(struct block_in *in);
+    int (*block)(struct worker *w, struct block_in *in);    /* a staged block: 0, or -1 for errors that end the run */
+    int (*strips)(struct worker *w, struct block_in *in, gcn10_tiff_writer *tifs[GCN10_N_RASTERS]); /* (encode_block's) */
+    void (*block_unreadable)(struct worker *w, int block_id);   /* one not staged (NULL: skipped as the reference skips) */
+    void (*worker_teardown)(struct worker *w);              /* the worker's buffers of the mode */
+    void (*leave_part)(struct run *r);                      /* under a launcher, before the closing barrier */
+    int (*finish)(struct run *r, gcn10_log *log0);          /* result and closing line; the exit code: 0, 1, 2 (verify) */
+    void (*end)(struct run *r);                             /* frees what its start made */
+};
+extern const struct gcn10_mode gcn10_mode_write, gcn10_mode_aggregate, gcn10_mode_verify, gcn10_mode_zonal,
+    gcn10_mode_grid;
+/* run.c's resolve() before it chooses the mode, no GPU opened yet: the refused combinations, the zones, the grid's
+ * result; 0, or -1 with a line on stderr and nothing left behind */
 int gcn10_aggregate_start(struct run *r);
-int gcn10_aggregate_plan_block(struct worker *w, struct block_in *in, const double own[4]);
-int gcn10_aggregate_block(struct worker *w, struct block_in *in, gcn10_tiff_writer *tifs[GCN10_N_RASTERS]);
-void gcn10_aggregate_finish(struct run *r, gcn10_log *log0);
-/* verify.c: a staged block's files against the values computed now (0, or -1 for errors that end the run); a block
- * whose inputs could not be staged; the worker's verify buffers; the end of the run -- this process's counts left for
- * launcher rank 0, then the closing line and verify_failed_blocks.txt (returns the bad + missing files it knows of) */
-int gcn10_verify_block(struct worker *w, struct block_in *in);
-void gcn10_verify_block_unreadable(struct worker *w, int block_id);
-void gcn10_verify_teardown(struct worker *w);
-void gcn10_verify_leave_part(struct run *r);
-int gcn10_verify_summary(struct run *r, gcn10_log *log0);
-/* zonal.c: the zones and the table of the run (start: before any GPU is opened; finish: the table and the closing
- * line; end: frees both); the spans of a staged block, made by the input side; a staged block counted (0, or -1 for
- * errors that end the run); a block whose inputs could not be staged; the worker's zonal buffers */
 int gcn10_zonal_start(struct run *r);
-int gcn10_zonal_finish(struct run *r, gcn10_log *log0);
-void gcn10_zonal_end(struct run *r);
-int gcn10_zonal_plan_block(struct worker *w, struct block_in *in, const double own[4]);
-int gcn10_zonal_block(struct worker *w, struct block_in *in);
-void gcn10_zonal_block_unreadable(struct worker *w, int block_id);
-void gcn10_zonal_teardown(struct worker *w);
-/* grid.c: the refused combinations, the landcover's pixel size against the cells and the result of the run (start:
- * before any GPU is opened; finish: the rasters and the closing line, after the workers are joined; end: frees it);
- * the cells of a staged block, made by the input side; a staged block summed and merged (0, or -1 for errors that end
- * the run); a block whose inputs could not be staged; the worker's grid buffers */
 int gcn10_grid_start(struct run *r);
-int gcn10_grid_finish(struct run *r, gcn10_log *log0);
-void gcn10_grid_end(struct run *r);
-int gcn10_grid_plan_input(struct worker *w, struct block_in *in, const double own[4]);
-int gcn10_grid_block(struct worker *w, struct block_in *in);
-void gcn10_grid_block_unreadable(struct worker *w, int block_id);
-void gcn10_grid_teardown(struct worker *w);
 int gcn10_input_setup(struct worker *w);
 void gcn10_input_teardown(struct worker *w);
 int gcn10_input_start(struct worker *w);

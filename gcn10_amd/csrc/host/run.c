@@ -13,7 +13,8 @@
 
 #define now_seconds gcn10_now_seconds
 
-/* What the config and the command line ask for, and every combination that is refused, before any GPU is opened. */
+/* What the config and the command line ask for, and every combination that is refused, before any GPU is opened.  A
+ * write run unless verify, zonal, aggregate or grid is asked for: they refuse each other, so r->mode is set once. */
 static int resolve(struct run *r)
 {
     const gcn10_run_options *opt = &r->opt;
@@ -21,6 +22,7 @@ static int resolve(struct run *r)
     const char *why = NULL;
     char err[2048] = "";
 
+    r->mode = &gcn10_mode_write;
     if (!opt->config_path) {
         fprintf(stderr, "[rank 0] missing -c/--config <file>; see 'gcn10 -h' for usage.\n");   /* src/main.c:103-106 */
         return 1;
@@ -67,6 +69,8 @@ static int resolve(struct run *r)
         fprintf(stderr, "[rank 0] --verify writes nothing and cannot be combined with --overwrite\n");
         return 1;
     }
+    if (r->verify)
+        r->mode = &gcn10_mode_verify;
     if (r->cfg.cog && r->cfg.gpu_deflate == 0) {
         fprintf(stderr, "[rank 0] bad value for cog: '1' with gpu_deflate=0 (overviews are built and encoded on the GPU "
                         "only; there is no host fallback)\n");
@@ -97,6 +101,7 @@ static int resolve(struct run *r)
             fprintf(stderr, "[rank 0] %s\n", why);
         if (why || gcn10_zonal_start(r) != 0)
             return 1;
+        r->mode = &gcn10_mode_zonal;
     }
     /* an aggregate run: the factor, and the refused combinations */
     if (opt->aggregate && gcn10_parse_aggregate(opt->aggregate, &r->cfg.aggregate) != 0) {
@@ -128,16 +133,22 @@ static int resolve(struct run *r)
         }
         gcn10_runoff_table(r->cfg.storm_p, r->cfg.storm_lambda, r->runoff_q);
     }
-    if (r->aggregate && gcn10_aggregate_start(r) != 0)
-        return 1;
+    if (r->aggregate) {
+        if (gcn10_aggregate_start(r) != 0)
+            return 1;
+        r->mode = &gcn10_mode_aggregate;
+    }
     /* a grid run: the grid, the refused combinations, the result of the run */
     if (opt->grid) {
         free(r->cfg.grid);
         r->cfg.grid = strdup(opt->grid);
     }
     r->grid_on = r->cfg.grid != NULL;
-    if (r->grid_on && gcn10_grid_start(r) != 0)
-        return 1;
+    if (r->grid_on) {
+        if (gcn10_grid_start(r) != 0)
+            return 1;
+        r->mode = &gcn10_mode_grid;
+    }
     r->null_sink = sink && strcmp(sink, "null") == 0;
     /* Rows per strip.  Rounds 2 and 3 ran 768 rows (three tile rows of a 36000-px block = 423 tile positions, one round
      * of the fused statistics pass's 512 workgroup slots); larger strips lost end to end to the coarser hand-over between
@@ -557,7 +568,7 @@ int gcn10_run(const gcn10_run_options *opt)
 {
     struct run *r = calloc(1, sizeof *r);
     gcn10_log *log0 = NULL;
-    int exit_code = 1, verify_found = 0, loaded;
+    int exit_code = 1, loaded;
     const double t_start = now_seconds();
 
     if (!r) {
@@ -585,21 +596,16 @@ int gcn10_run(const gcn10_run_options *opt)
         pthread_join(r->workers[i].thread, NULL);      /* MPI_Barrier, src/main.c:187 */
 
     log0_line(r, "INFO", true, "processed %d blocks on %d ranks", r->n_blocks, r->n_workers);  /* src/main.c:191 */
-    if (r->verify && r->outer_size > 1)
-        gcn10_verify_leave_part(r);
-    if (r->outer_size > 1)
+    if (r->outer_size > 1) {
+        if (r->mode->leave_part)
+            r->mode->leave_part(r);
         gcn10_closing_barrier(r, log0);     /* MPI_Barrier + rank 0's summary, src/main.c:187-194 */
-    if (r->verify)
-        verify_found = gcn10_verify_summary(r, log0);
-    if (r->aggregate)
-        gcn10_aggregate_finish(r, log0);
-    if (r->zonal && gcn10_zonal_finish(r, log0) != 0)
-        atomic_store(&r->fatal, 1);
-    if (r->grid_on && gcn10_grid_finish(r, log0) != 0)
-        atomic_store(&r->fatal, 1);
+    }
+    /* the mode's result, closing line and exit code; an error that ended the run or a result that lacks a block is 1 */
+    exit_code = r->mode->finish ? r->mode->finish(r, log0) : 0;
     report(r, t_start);
-    exit_code = atomic_load(&r->fatal) || atomic_load(&r->zonal_incomplete) || atomic_load(&r->grid_incomplete)
-                    ? 1 : (verify_found > 0 ? 2 : 0);
+    if (atomic_load(&r->fatal) || atomic_load(&r->incomplete))
+        exit_code = 1;
 
 done:
     gcn10_pool_destroy(r->pool);
@@ -608,8 +614,8 @@ done:
     gcn10_log_close(log0);                              /* finalize_logging, src/main.c:197 */
     free(r->workers);
     free(r->verify_failed);
-    gcn10_zonal_end(r);
-    gcn10_grid_end(r);
+    if (r->mode->end)
+        r->mode->end(r);
     free(r->block_ids);
     gcn10_blocks_free(&r->blocks);
     gcn10_config_free(&r->cfg);

@@ -189,7 +189,7 @@ static int state_setup(struct worker *w)
     return 0;
 }
 
-void gcn10_verify_teardown(struct worker *w)
+static void verify_teardown(struct worker *w)
 {
     const struct gcn10_gpu_api *g = w->run->gpu;
     struct gcn10_verify_state *v = w->verify;
@@ -466,7 +466,7 @@ static void block_failed(struct run *r, int block_id)
     pthread_mutex_unlock(&r->verify_mu);
 }
 
-void gcn10_verify_block_unreadable(struct worker *w, int block_id)
+static void verify_block_unreadable(struct worker *w, int block_id)
 {
     struct run *r = w->run;
 
@@ -476,7 +476,7 @@ void gcn10_verify_block_unreadable(struct worker *w, int block_id)
     block_failed(r, block_id);
 }
 
-int gcn10_verify_block(struct worker *w, struct block_in *in)
+static int verify_block(struct worker *w, struct block_in *in)
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
@@ -484,7 +484,7 @@ int gcn10_verify_block(struct worker *w, struct block_in *in)
     struct vfile files[GCN10_N_RASTERS];
     struct gcn10_verify_state *v;
     int L = 0, rc = -1, n_beyond_total = 0;
-    bool any_failed = false, inputs_ok = true;
+    bool any_failed = false;
 
     memset(files, 0, sizeof files);
     if (state_setup(w) != 0)
@@ -514,21 +514,11 @@ int gcn10_verify_block(struct worker *w, struct block_in *in)
     }
 
     /* 2. the block on the device, as for a write run */
-    if (g->stream_wait_event(w->ctx, w->s_kernel, in->ev_ready) != 0)
+    switch (gcn10_block_take(w, in)) {
+    case GCN10_BLOCK_DEVICE_ERROR:
         goto gpu_fail;
-    if (in->n_inflate > 0) {
-        if (g->event_sync(w->ctx, in->ev_ready) != 0)
-            goto gpu_fail;
-        for (size_t i = 0; i < in->n_inflate && inputs_ok; i++)
-            if (in->jl.h_status[i] != 0) {
-                wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
-                                       "(stream %zu, reason %u)", in->xoff, in->yoff, W, H, i, in->jl.h_status[i]);
-                wlog(w, "ERROR", true, "esa load failed for block %d", block_id);
-                inputs_ok = false;
-            }
-    }
-    if (!inputs_ok) {
-        gcn10_verify_block_unreadable(w, block_id);
+    case GCN10_BLOCK_UNREADABLE:
+        verify_block_unreadable(w, block_id);
         rc = 0;
         goto out;
     }
@@ -624,8 +614,8 @@ static int by_int(const void *a, const void *b)
 /* The end of a verify run: the closing console line and <log_dir>/verify_failed_blocks.txt, the ids of the blocks
  * with a bad or missing file, ascending, one per line (what -l reads).  Under an MPI launcher every process leaves
  * its counts and ids in "<log_dir>/.verify_<job>_<rank>" BEFORE the closing barrier, and launcher rank 0 merges
- * them behind it, the way it prints the run's totals.  Returns the number of bad + missing files it knows of. */
-void gcn10_verify_leave_part(struct run *r)
+ * them behind it, the way it prints the run's totals.  Returns the exit code: 2 when it knows of a bad or missing file. */
+static void verify_leave_part(struct run *r)
 {
     char job[96], path[PATH_MAX];
     FILE *f;
@@ -642,12 +632,11 @@ void gcn10_verify_leave_part(struct run *r)
     fclose(f);
 }
 
-int gcn10_verify_summary(struct run *r, gcn10_log *log0)
+static int verify_summary(struct run *r, gcn10_log *log0)
 {
     int blocks = r->n_blocks, ok = atomic_load(&r->verify_n_ok), bad = atomic_load(&r->verify_n_bad);
     int missing = atomic_load(&r->verify_n_missing), unchecked = atomic_load(&r->verify_n_unchecked);
     int *ids = r->verify_failed, n_ids = r->verify_n_failed;
-    const int mine = bad + missing;
     char path[PATH_MAX], msg[PATH_MAX + 64];
     FILE *f;
 
@@ -655,7 +644,7 @@ int gcn10_verify_summary(struct run *r, gcn10_log *log0)
         char job[96];
 
         if (r->outer_rank != 0)
-            return mine;
+            return bad + missing > 0 ? 2 : 0;
         gcn10_job_tag(job);
         for (int p = 1; p < r->outer_size; p++) {
             int b, o, x, m, u, n;
@@ -705,5 +694,10 @@ int gcn10_verify_summary(struct run *r, gcn10_log *log0)
     gcn10_log_message(log0, bad + missing ? "ERROR" : "INFO", msg, true);
     if (ids != r->verify_failed)
         free(ids);
-    return bad + missing > mine ? bad + missing : mine;
+    return bad + missing > 0 ? 2 : 0;
 }
+
+const struct gcn10_mode gcn10_mode_verify = {
+    .block = verify_block, .block_unreadable = verify_block_unreadable, .worker_teardown = verify_teardown,
+    .leave_part = verify_leave_part, .finish = verify_summary,
+};

@@ -77,7 +77,7 @@ int gcn10_zonal_start(struct run *r)
     return 0;
 }
 
-void gcn10_zonal_teardown(struct worker *w)
+static void zonal_teardown(struct worker *w)
 {
     const struct gcn10_gpu_api *g = w->run->gpu;
     struct gcn10_zonal_state *z = w->zonal;
@@ -97,15 +97,15 @@ void gcn10_zonal_teardown(struct worker *w)
     w->zonal = NULL;
 }
 
-void gcn10_zonal_block_unreadable(struct worker *w, int block_id)
+static void zonal_block_unreadable(struct worker *w, int block_id)
 {
     wlog(w, "ERROR", true, "zonal block %d: its landcover or soil window could not be read; the table lacks this block",
          block_id);
-    atomic_store(&w->run->zonal_incomplete, 1);
+    atomic_store(&w->run->incomplete, 1);
 }
 
 /* the input side: the zones over the staged block, while the block before is counted */
-int gcn10_zonal_plan_block(struct worker *w, struct block_in *in, const double own[4])
+static int zonal_plan_block(struct worker *w, struct block_in *in, const double own[4])
 {
     struct run *r = w->run;
     char err[1024] = "";
@@ -161,7 +161,7 @@ static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *ce
     }
 }
 
-int gcn10_zonal_block(struct worker *w, struct block_in *in)
+static int zonal_block(struct worker *w, struct block_in *in)
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
@@ -183,19 +183,12 @@ int gcn10_zonal_block(struct worker *w, struct block_in *in)
     z = w->zonal;
 
     /* the block on the device, as for a write run */
-    if (g->stream_wait_event(w->ctx, w->s_kernel, in->ev_ready) != 0)
+    switch (gcn10_block_take(w, in)) {
+    case GCN10_BLOCK_DEVICE_ERROR:
         goto gpu_fail;
-    if (in->n_inflate > 0) {
-        if (g->event_sync(w->ctx, in->ev_ready) != 0)
-            goto gpu_fail;
-        for (size_t i = 0; i < in->n_inflate; i++)
-            if (in->jl.h_status[i] != 0) {
-                wlog(w, "ERROR", true, "gdalrasterio error: cannot decode a tile of the window %d,%d %dx%d "
-                                       "(stream %zu, reason %u)", in->xoff, in->yoff, in->W, in->H, i, in->jl.h_status[i]);
-                wlog(w, "ERROR", true, "esa load failed for block %d", in->block_id);
-                gcn10_zonal_block_unreadable(w, in->block_id);
-                return 0;
-            }
+    case GCN10_BLOCK_UNREADABLE:
+        zonal_block_unreadable(w, in->block_id);
+        return 0;
     }
     wlog(w, "INFO", false, "zonal block %d: %d zones, %zu spans", in->block_id, p->n_local, p->n_spans);
 
@@ -290,8 +283,9 @@ gpu_fail:
     return -1;
 }
 
-/* The table, through a temporary name and rename, and the closing console line.  0, or -1 when it could not be written. */
-int gcn10_zonal_finish(struct run *r, gcn10_log *log0)
+/* The table, through a temporary name and rename, and the closing console line.  The exit code: 0, or 1
+ * when it could not be written. */
+static int zonal_finish(struct run *r, gcn10_log *log0)
 {
     struct gcn10_zonal_table *t = r->zonal_table;
     const char *path = r->cfg.zonal_output && *r->cfg.zonal_output ? r->cfg.zonal_output : "zonal_cn.csv";
@@ -342,14 +336,14 @@ int gcn10_zonal_finish(struct run *r, gcn10_log *log0)
     if (rc != 0) {
         snprintf(msg, sizeof msg, "zonal: cannot write the table %s", path);
         gcn10_log_message(log0, "ERROR", msg, true);
-        return -1;
+        return 1;
     }
     snprintf(msg, sizeof msg, "zonal: %d blocks, %d zones, %d without pixels, table %s", t->blocks, r->zones.n, without, path);
     gcn10_log_message(log0, "INFO", msg, true);
     return 0;
 }
 
-void gcn10_zonal_end(struct run *r)
+static void zonal_end(struct run *r)
 {
     if (r->zonal_table) {
         pthread_mutex_destroy(&r->zonal_table->mu);
@@ -359,3 +353,14 @@ void gcn10_zonal_end(struct run *r)
     }
     gcn10_zones_free(&r->zones);
 }
+
+static void zonal_plan_free(struct block_in *in)
+{
+    gcn10_zone_plan_free(&in->zplan);
+}
+
+const struct gcn10_mode gcn10_mode_zonal = {
+    .plan_block = zonal_plan_block, .plan_free = zonal_plan_free, .block = zonal_block,
+    .block_unreadable = zonal_block_unreadable, .worker_teardown = zonal_teardown,
+    .finish = zonal_finish, .end = zonal_end,
+};

@@ -1,8 +1,13 @@
-// gcn10_deflate_internal.hpp -- shared by the two tile encoders of libgcn10_gpu.so:
-// gcn10_deflate.hip (one zlib stream per tile of a CN raster held in HBM) and
-// gcn10_deflate_fused.hip (the 18 streams of a tile position straight from landcover + soil).
-// Constants, the hand-over structures between the passes, the match-candidate bit masks, and
-// the launch of pass B (code construction), which both encoders use unchanged.
+// gcn10_deflate_internal.hpp -- shared by the three tile encoders of libgcn10_gpu.so and the passes they have in
+// common:
+//   gcn10_deflate.hip        one zlib stream per tile of a CN raster held in HBM (passes A and C)
+//   gcn10_deflate_fused.hip  the 18 streams of a tile position straight from landcover + soil (passes F-A and F-C)
+//   gcn10_lzw.hip            one TIFF LZW stream per tile of a CN raster held in HBM
+//   gcn10_deflate_codes.hip  pass B, code construction, which both DEFLATE encoders use unchanged
+//   gcn10_arena_place.hip    pass B', where every stream goes in the arena, and the arena / table / cursor contract
+//                            of all three: the job setup and the arena bound
+// Constants, the hand-over structures between the passes, the match-candidate bit masks of the DEFLATE passes, and
+// the declarations of what the last two files give the encoders.
 #ifndef GCN10_DEFLATE_INTERNAL_HPP
 #define GCN10_DEFLATE_INTERNAL_HPP
 
@@ -12,6 +17,7 @@
 
 #include "gcn10_gpu.h"
 #include "gcn10_gpu_internal.hpp"
+#include "gcn10_wave.hpp"
 
 namespace gcn10_deflate {
 
@@ -183,35 +189,40 @@ __device__ __forceinline__ int next_candidate(const RowMasks &m, int x)
     return kTile;
 }
 
-
-// Inclusive prefix sum over the 64 lanes with DPP adds (no LDS traffic): three shifted adds of
-// the input give sums over 4 lanes, row_shr:4 / row_shr:8 complete the rows of 16, row_bcast:15
-// and row_bcast:31 carry the row totals on.
-__device__ __forceinline__ uint32_t wave_scan_dpp(uint32_t x)
-{
-    uint32_t r = x;
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);     // row_shr:1
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);     // row_shr:2
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x113, 0xf, 0xf, false);     // row_shr:3
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x114, 0xf, 0xe, false);     // row_shr:4, lanes 4..15
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x118, 0xf, 0xc, false);     // row_shr:8, lanes 8..15
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x142, 0xa, 0xf, false);     // row_bcast:15 -> rows 1, 3
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x143, 0xc, 0xf, false);     // row_bcast:31 -> rows 2, 3
-    return r;
-}
-
-
 }  // namespace gcn10_deflate
 
 namespace gcn10 {
 using gcn10_deflate::TileJob;
 
+// ---- gcn10_arena_place.hip: the arena / table / cursor contract of the three encoders ----
+// The arguments every encoder entry point takes, checked, and the strip's tile grid worked out: `streams` is the
+// number of streams per tile position (the rasters).  GCN10_E_INVAL ("<who>: ...") unless W > 0, rows >= 0 and
+// 1 <= streams <= GCN10_N_RASTERS.  rows == 0 is an empty strip: GCN10_OK with job->n_tiles == 0 whatever the
+// pointers are, and the caller returns without touching *cursor.  Otherwise GCN10_E_INVAL for a null arena, table or
+// cursor, an arena that is not 16-byte aligned, an arena_cap that does not fit the 32-bit offsets of the table, and
+// for 2^31 tiles or more.  On success *job holds arena, arena_cap, table, sizes (= table: pass B' places in the
+// table itself), cursor, W, rows, across, down and n_tiles; everything else is zero, for the encoder to fill.
+int tile_job_setup(const char *who, int W, int rows, int streams, uint8_t *arena, size_t arena_cap, uint32_t *table,
+                   unsigned long long *cursor, TileJob *job);
+// the arena that holds n_rasters strips of W x rows whatever their content: streams of at most max_stream bytes
+size_t arena_bound(int W, int rows, int n_rasters, size_t max_stream);
+// Pass B' (deflate_place_kernel): lays out the streams whose sizes lie in job.sizes (= job.table: { alias mark or 0,
+// bytes } per stream), writes their offsets to job.table and the bytes used to *job.cursor.
+int launch_arena_place(gcn10_gpu_ctx *ctx, const TileJob &job, hipStream_t s);
+
+// ---- gcn10_deflate_codes.hip ----
 // Pass B for `nblocks` (raster, tile) pairs whose statistics are in job.hist: code books to job.books,
-// sizes to job.table; with `place`, pass B' (deflate_place_kernel) behind it lays the streams out in the arena.
+// sizes to job.sizes; with `place`, pass B' behind it lays the streams out in the arena.
 int deflate_launch_codes(gcn10_gpu_ctx *ctx, const TileJob &job, uint32_t nblocks, hipStream_t s, bool place = true);
-// pass B' alone: places streams whose sizes lie in job.sizes (= job.table: { 0, bytes } per stream) -- the LZW
-// encoder (gcn10_lzw.hip) lays its streams out exactly as the tile encoders do
-int deflate_launch_place(gcn10_gpu_ctx *ctx, const TileJob &job, hipStream_t s);
+
+// More than 64 KiB of dynamic LDS per workgroup has to be asked for, once per kernel and device: the launch function
+// of the file that owns the kernel does, behind a flag of the context.
+template <typename Kernel>
+inline hipError_t allow_dynamic_lds(Kernel *kernel, size_t bytes)
+{
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)bytes);
+}
 
 }  // namespace gcn10
 

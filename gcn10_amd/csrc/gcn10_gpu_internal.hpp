@@ -149,9 +149,11 @@ struct gcn10_gpu_ctx {
 
     const char *last_kernel = "";   // of the last strip (a string of the strip-kernel table)
     hipEvent_t time_start = nullptr, time_stop = nullptr;  // one-shot: bracket the next strip kernel
-    bool fused_ready = false;
-    bool codes_ready = false;       // LDS attribute of the per-thread code construction set
-    bool deflate_ready = false;     // LDS attributes of the tile encoder set on this device
+    // dynamic-LDS attributes set on this device (gcn10::allow_dynamic_lds), each by the file that owns the kernels
+    bool deflate_ready = false;         // passes A and C (gcn10_deflate.hip)
+    bool codes_ready = false;           // the per-thread form of pass B (gcn10_deflate_codes.hip)
+    bool fused_stats_ready = false;     // pass F-A (gcn10_deflate_fused_stats.hpp)
+    bool fused_emit_ready = false;      // pass F-C (gcn10_deflate_fused_emit.hpp)
 
     // ---- device workspaces of the codecs, grown by gcn10::grow_workspace ----
     struct Workspaces {

@@ -35,11 +35,15 @@
 
 #include "gcn10_gpu.h"
 #include "gcn10_gpu_internal.hpp"
+#include "gcn10_wave.hpp"
 
 using gcn10::as_stream;
 using gcn10::fail;
 using gcn10::u32x4;
+using gcn10::uniform;
 using gcn10::use_device;
+using gcn10::wave_scan;
+using gcn10::wave_total;
 
 namespace {
 
@@ -182,39 +186,6 @@ __device__ __forceinline__ uint32_t take_bits(Reader &r, uint32_t n)
 __device__ __forceinline__ uint32_t reader_byte_pos(const Reader &r)
 {
     return r.ip * 4u - r.bc / 8u;
-}
-
-__device__ __forceinline__ uint32_t uniform(uint32_t v)
-{
-    return __builtin_amdgcn_readfirstlane(v);
-}
-
-// Inclusive prefix sum over the 64 lanes with DPP adds.
-__device__ __forceinline__ uint32_t wave_scan(uint32_t x)
-{
-    uint32_t r = x;
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);     // row_shr:1
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);     // row_shr:2
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x113, 0xf, 0xf, false);     // row_shr:3
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x114, 0xf, 0xe, false);     // row_shr:4, lanes 4..15
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x118, 0xf, 0xc, false);     // row_shr:8, lanes 8..15
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x142, 0xa, 0xf, false);     // row_bcast:15 -> rows 1, 3
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x143, 0xc, 0xf, false);     // row_bcast:31 -> rows 2, 3
-    return r;
-}
-
-// Sum over the 64 lanes, wave-uniform, with DPP adds (no LDS round trips): quads, rows of 16, then
-// row_bcast:15 / row_bcast:31 carry the row totals to lane 63.
-__device__ __forceinline__ uint32_t wave_total(uint32_t x)
-{
-    uint32_t r = x;
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0xb1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x4e, 0xf, 0xf, false);      // quad_perm [2,3,0,1]
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x141, 0xf, 0xf, false);     // row_half_mirror
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x140, 0xf, 0xf, false);     // row_mirror
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x142, 0xa, 0xf, false);     // row_bcast:15 -> rows 1, 3
-    r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x143, 0xc, 0xf, false);     // row_bcast:31 -> rows 2, 3
-    return (uint32_t)__builtin_amdgcn_readlane((int)r, 63);
 }
 
 // Sorts the n symbols of lens[] by (length, symbol) and derives first code / offset per

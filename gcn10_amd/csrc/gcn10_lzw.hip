@@ -4,7 +4,7 @@
 // does every GIS user who reaches for GDAL's most common option.  This is the second codec behind the arena
 // contract of gcn10_gpu_deflate_strip: every 256x256 tile of n_rasters CN strips held in HBM (edge tiles zero
 // padded) becomes one complete TIFF 6.0 section 13 LZW stream, streams are packed into the caller's arena
-// exactly as the DEFLATE tile encoders pack theirs (their placement pass, pass B', is reused), and the
+// exactly as the DEFLATE tile encoders pack theirs (the placement pass B' of gcn10_arena_place.hip), and the
 // sink, direct_io and the spill path of the host consume it unchanged.  The bytes are not libtiff's;
 // decoded pixels are the parity target (tests decode every stream with a strict decoder of their own, with
 // libtiff through PIL, and with the host reader, tiff_codec.c lzw_decode).
@@ -28,7 +28,7 @@
 //             from the strip, 16 bytes per lane ahead of use; codes go to a workspace slot of the segment.
 //             Dictionary slots carry a 4-bit generation, so a clear costs one increment (and a sweep of the
 //             segment's 1024 slots every 15th clear).
-//   pass B'   the DEFLATE encoders' placement pass: raster extents, 16-byte slots, cursor, 0xffffffff for
+//   pass B'   gcn10_arena_place.hip, as for the DEFLATE encoders: raster extents, 16-byte slots, cursor, 0xffffffff for
 //             what does not fit the arena.
 //   pass L-C  one workgroup per tile: every thread assembles whole 32-bit words of the stream from the
 //             segments' bit strings (the segment bit offsets are a 4-entry prefix sum) and stores them into
@@ -45,7 +45,6 @@
 using gcn10::as_stream;
 using gcn10::fail;
 using gcn10::use_device;
-using gcn10_deflate::kSlotAlign;
 using gcn10_deflate::kTile;
 using gcn10_deflate::TileJob;
 
@@ -260,69 +259,45 @@ extern "C" {
 
 size_t gcn10_gpu_lzw_arena_bound(int W, int rows, int n_rasters)
 {
-    if (W <= 0 || rows <= 0 || n_rasters <= 0)
-        return 0;
-    const size_t across = ((size_t)W + kTile - 1) / kTile, down = ((size_t)rows + kTile - 1) / kTile;
-    const size_t slot = ((size_t)kMaxStreamBytes + kSlotAlign - 1) / kSlotAlign * kSlotAlign;
-    // + the pads that bring every raster's extent to a multiple of the largest segment alignment (as DEFLATE)
-    return across * down * (size_t)n_rasters * slot + (size_t)n_rasters * 4096u;
+    return gcn10::arena_bound(W, rows, n_rasters, kMaxStreamBytes);
 }
 
 int gcn10_gpu_lzw_strip(gcn10_gpu_ctx *ctx, const uint8_t *const *rasters_dev, int n_rasters, int W, int rows,
                         uint8_t *arena_dev, size_t arena_cap, uint32_t *table_dev, unsigned long long *cursor_dev,
                         gcn10_stream_t stream)
 {
+    const char *const who = "gcn10_gpu_lzw_strip";
     int rc = use_device(ctx);
     if (rc)
         return rc;
-    if (n_rasters < 1 || n_rasters > GCN10_N_RASTERS || W <= 0 || rows < 0)
-        return fail(GCN10_E_INVAL, "gcn10_gpu_lzw_strip: bad shape %d rasters of %d x %d", n_rasters, W, rows);
-    if (rows == 0)
-        return GCN10_OK;
-    if (!rasters_dev || !arena_dev || !table_dev || !cursor_dev)
-        return fail(GCN10_E_INVAL, "gcn10_gpu_lzw_strip: null pointer");
-    if ((reinterpret_cast<uintptr_t>(arena_dev) & 15u) != 0)
-        return fail(GCN10_E_INVAL, "gcn10_gpu_lzw_strip: arena must be 16-byte aligned");
-    if (arena_cap >= 0xfffffffeull)
-        return fail(GCN10_E_INVAL, "gcn10_gpu_lzw_strip: an arena of %zu bytes does not fit 32-bit stream offsets "
-                                   "(use fewer rows per strip)", arena_cap);
+    TileJob pj;                 // the strip's tile grid and where pass B' places: pass L-A leaves { 0, bytes } in the table
+    rc = gcn10::tile_job_setup(who, W, rows, n_rasters, arena_dev, arena_cap, table_dev, cursor_dev, &pj);
+    if (rc || pj.n_tiles == 0)
+        return rc;              // refused, or an empty strip
+    if (!rasters_dev)
+        return fail(GCN10_E_INVAL, "%s: null pointer", who);
     LzwJob lj;
     lj.rasters = rasters_dev;
     lj.table = table_dev;
     lj.arena = arena_dev;
-    lj.W = (uint32_t)W;
-    lj.rows = (uint32_t)rows;
-    lj.across = ((uint32_t)W + kTile - 1) / kTile;
-    lj.down = ((uint32_t)rows + kTile - 1) / kTile;
-    const uint64_t n_tiles = (uint64_t)lj.across * lj.down * (uint64_t)n_rasters;
-    if (n_tiles > 0x7fffffffull)
-        return fail(GCN10_E_INVAL, "gcn10_gpu_lzw_strip: too many tiles");
-    lj.n_tiles = (uint32_t)n_tiles;
+    lj.W = pj.W;
+    lj.rows = pj.rows;
+    lj.across = pj.across;
+    lj.down = pj.down;
+    lj.n_tiles = pj.n_tiles;
 
-    const size_t need = (size_t)n_tiles * kSegs * (kSegWords + 1u) * 4u;
+    const size_t need = (size_t)lj.n_tiles * kSegs * (kSegWords + 1u) * 4u;
     rc = gcn10::grow_workspace(&ctx->ws.lzw, &ctx->ws.lzw_cap, need);
     if (rc)
         return rc;
     lj.seg_words = reinterpret_cast<uint32_t *>(ctx->ws.lzw);
-    lj.seg_bits = lj.seg_words + (size_t)n_tiles * kSegs * kSegWords;
-
-    TileJob pj = {};
-    pj.arena = arena_dev;
-    pj.table = table_dev;
-    pj.sizes = table_dev;
-    pj.cursor = cursor_dev;
-    pj.W = lj.W;
-    pj.rows = lj.rows;
-    pj.across = lj.across;
-    pj.down = lj.down;
-    pj.n_tiles = lj.n_tiles;
-    pj.arena_cap = arena_cap;
+    lj.seg_bits = lj.seg_words + (size_t)lj.n_tiles * kSegs * kSegWords;
 
     hipStream_t s = as_stream(ctx, stream);
     HIP_TRY(hipMemsetAsync(cursor_dev, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(lzw_encode_kernel, dim3(lj.n_tiles), dim3(kThreads), 0, s, lj);
     HIP_TRY(hipGetLastError());
-    rc = gcn10::deflate_launch_place(ctx, pj, s);
+    rc = gcn10::launch_arena_place(ctx, pj, s);
     if (rc)
         return rc;
     hipLaunchKernelGGL(lzw_pack_kernel, dim3(lj.n_tiles), dim3(256), 0, s, lj);

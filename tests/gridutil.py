@@ -1,6 +1,7 @@
 """What the tests of the model-grid run mode share: the membership rule of include/gcn10_host.h "model grid" in numpy
 on np.float64 -- the same expressions, the same comparisons --, the plan of a block by that rule, and the sums and
-means of full-resolution rasters over maps with np.add.at in int64.  Never another GPU path."""
+means of full-resolution rasters over maps with np.add.at in int64 (np.bincount from two million pixels on).  Never
+another GPU path."""
 import numpy as np
 
 from tests import zoneutil
@@ -76,9 +77,32 @@ def same_plan(got, want):
         np.testing.assert_array_equal(got[k], want[k], err_msg=k)
 
 
+BINCOUNT_FROM = 2000000      # pixels from which add_sums and runoffutil.add_triples count with np.bincount
+
+
+def add_words_bincount(acc, raster, cellx, celly, w=None):
+    """The fast path of add_sums (and, with the weights w, of runoffutil.add_triples) for rasters of millions of pixels,
+    where np.add.at takes seconds per word: np.bincount over celly[:, None] * ncx + cellx[None, :] of the pixels that
+    are in a cell and != 255.  Weighted bincounts add in float64; every term is an integer and every sum is asserted
+    to stay below 2^53, so they are exact and the int64 words are those of np.add.at."""
+    ncy, ncx = acc.shape[:2]
+    cx, cy = np.asarray(cellx, np.int64), np.asarray(celly, np.int64)
+    ys, xs = np.flatnonzero(cy >= 0), np.flatnonzero(cx >= 0)
+    v = np.asarray(raster)[np.ix_(ys, xs)]
+    cell = (cy[ys][:, None] * ncx + cx[xs][None, :]).astype(np.int32 if ncy * ncx < (1 << 31) else np.int64)
+    ok = v != 255
+    cell, v = cell[ok], v[ok]
+    words = [v.astype(np.float64), None] + ([np.asarray(w, np.float64)[v]] if w is not None else [])
+    for k, weights in enumerate(words):
+        assert weights is None or float(weights.sum()) < float(1 << 53)
+        acc[:, :, k] += np.bincount(cell, weights=weights, minlength=ncy * ncx).astype(np.int64).reshape(ncy, ncx)
+
+
 def add_sums(acc, raster, cellx, celly):
     """Adds the sum and the count of raster's values != 255 to acc[cy][cx] = {s, n} (int64[ncy][ncx][2]) over the maps
     (-1 = in no cell)."""
+    if np.asarray(raster).size >= BINCOUNT_FROM:
+        return add_words_bincount(acc, raster, cellx, celly)
     v = np.asarray(raster).astype(np.int64)
     ys, xs = np.flatnonzero(np.asarray(celly) >= 0), np.flatnonzero(np.asarray(cellx) >= 0)
     v = v[np.ix_(ys, xs)]

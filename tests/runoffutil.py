@@ -59,6 +59,8 @@ def cn_array(acc, q):
 def add_triples(acc, raster, cellx, celly, w):
     """Adds {sum, count, sum of w[value]} of raster's values != 255 to acc[cy][cx] (int64[ncy][ncx][3]) over the maps
     (-1 = in no cell): gridutil.add_sums with one more word."""
+    if np.asarray(raster).size >= gu.BINCOUNT_FROM:
+        return gu.add_words_bincount(acc, raster, cellx, celly, w)
     gu.add_sums(acc[:, :, :2], raster, cellx, celly)
     v = np.asarray(raster).astype(np.int64)
     ys, xs = np.flatnonzero(np.asarray(celly) >= 0), np.flatnonzero(np.asarray(cellx) >= 0)

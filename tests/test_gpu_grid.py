@@ -5,7 +5,8 @@ Inputs: the recipe of tests/test_gpu_aggregate.py (patchy landcover with noise, 
 a cj that repeats and goes back).  Expected values: the oracle's full-resolution rasters (tests/aggutil.py::
 oracle_rasters), accumulated in numpy int64 with np.add.at over maps this file builds itself (tests/gridutil.py::
 add_sums).  Every comparison is bit-exact, on the pairs and on the means.  Shapes are the smallest at which the kernel
-can go wrong: widths around a 16-pixel column group and above the 4096 columns of a workgroup, cells of 8 pixels (three
+can go wrong: widths around a 16-pixel column group, above the 4096 columns of a workgroup and the 36001 of a block (nine
+chunks; expected sums by np.bincount there, tests/gridutil.py), cells of 8 pixels (three
 cell columns in one group) to one cell wider than the strip, rows of less than a cell to several of them, -1 runs that
 end inside a group, landcover one byte into its allocation.
 """
@@ -26,7 +27,7 @@ OK, E_INVAL, E_STATE = 0, -1, -4
 POISON = 0xA5
 GUARD = 256
 ROWS = 60
-WIDTHS = [1, 15, 16, 17, 1039, 1041, 2064, 4200]
+WIDTHS = [1, 15, 16, 17, 1039, 1041, 2064, 4200, 36001]    # 36001: nine chunks, a last group of one pixel
 # (cell width, cell height) in pixels: every width and every height of 8, 8.5, 15.9, 16, 17.3, 25, 25.6, 100 and "wider
 # than the strip" once; heights of 100 (fewer rows than one cell), 60 (exactly one) and 24 (2.5 cell rows) as well
 CELLS = [(8, 8), (8.5, 100), (15.9, 24), (16, 60), (17.3, 17.3), (25, 25.6), (25.6, 8.5), (100, 15.9), (1e6, 16),

@@ -22,7 +22,7 @@ from tests.util import random_tables
 pytestmark = pytest.mark.gpu
 
 OK, E_INVAL, E_STATE = 0, -1, -4
-WIDTHS = [1, 15, 16, 17, 1041, 4200]
+WIDTHS = [1, 15, 16, 17, 1041, 4200, 36001]        # 36001: nine chunks, a last group of one pixel
 CELLS = [(8, 8), (25, 25.6), (17.3, 17.3), (1e6, 16)]
 Q50 = ru.table(50, 0.2)
 WEIGHTS = {

@@ -57,22 +57,6 @@ int bind_soil(gcn10_gpu_ctx *ctx, const char *who, int W, hipStream_t stream, co
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// the window of a gcn10_inflate_tile lies inside its chunk, and the chunk inside a slot of slot_bytes
-__device__ __forceinline__ bool inflate_window_ok(uint32_t out_len, uint32_t chunk_w, uint32_t src_x, uint32_t src_y,
-                                                  uint32_t copy_w, uint32_t copy_h, uint32_t slot_bytes)
-{
-    if (copy_w == 0 || copy_h == 0)
-        return true;
-    if (chunk_w == 0 || out_len > slot_bytes || src_x > chunk_w || copy_w > chunk_w - src_x)
-        return false;
-    const unsigned long long last = (unsigned long long)(src_y + copy_h - 1u) * chunk_w + src_x + copy_w;
-    return (unsigned long long)src_y + copy_h <= 0xffffffffull && last <= out_len;
-}
-
-// gcn10_lzw_decode.hip: the GCN10_TILE_LZW tiles of a gcn10_gpu_inflate_tiles call into their slots
-void launch_lzw_decode(const uint8_t *comp_dev, const gcn10_inflate_tile *tiles_dev, uint32_t n_tiles,
-                       uint8_t *scratch, uint32_t slot_bytes, uint32_t *status_dev, hipStream_t stream);
-
 // soil code byte of the hx workspace: drained plane | undrained plane << 4, planes 0..5;
 // compact index = drained * 6 + undrained
 constexpr int kClassCodes = 36;

@@ -5,7 +5,8 @@
 // program's own compress=lzw output is LZW too.  Without this kernel such windows went through the host
 // reader (tiff_codec.c lzw_decode on the I/O pool) and 1.3 GB of decoded pixels per 36000^2 block crossed PCIe.
 // Here the compressed chunks cross, as for DEFLATE, and are decoded into the same linear scratch slots
-// inflate_kernel uses, so untile_kernel does the window copy and the predictor-2 sum-back unchanged.
+// inflate_kernel uses, so untile_kernel does the window copy and the predictor-2 sum-back unchanged
+// (gcn10_inflate_internal.hpp: what a tile's flags, status, slot and wanted bytes are for the three kernels).
 //
 // Semantics are those of tiff_codec.c lzw_decode, exactly: MSB-first codes of 9..12 bits with the "early change"
 // of the width, ClearCode 256, EndOfInformation 257, KwKwK (code == next), a dictionary that stops growing
@@ -40,7 +41,7 @@
 #include <cstdint>
 
 #include "gcn10_gpu.h"
-#include "gcn10_gpu_internal.hpp"
+#include "gcn10_inflate_internal.hpp"
 
 namespace {
 

@@ -76,10 +76,11 @@ struct gcn10_gpu_ctx {
     int n_classes = 0;              // 0: not available (set_tables not called, or > 256 classes)
 
     // ---- the weights of the weighted grid sums (gcn10_grid.hip: gcn10_gpu_set_weights) ----
-    uint8_t *d_wlut = nullptr;      // two images of the all-tables layout, the low and the high bytes of w[cn] (0 where
-                                    // d_lut16 holds 255), then w[256] itself
+    uint8_t *d_wlut = nullptr;      // per table two images of the all-tables layout, the low and the high bytes of
+                                    // w[cn] (0 where d_lut16 holds 255), then the n_weights tables w[256] themselves
     bool weights_set = false;       // ... are those of the loaded tables (gcn10_gpu_set_tables clears it)
-    bool weights_rising = false;    // w[1..100] never decrease
+    int n_weights = 0;              // tables of weights: 1 (gcn10_gpu_set_weights) to GCN10_GPU_MAX_WEIGHT_TABLES
+    uint32_t weights_rising = 0;    // bit j: w_j[1..100] never decrease
 
     // ---- the prepared tile (gcn10_soil_tile.hip) ----
     struct Tile {

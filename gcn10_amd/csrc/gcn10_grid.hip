@@ -33,9 +33,17 @@
 // weight plane 255 is a number: a plane pass makes no 255 test and no count.  A workgroup keeps its shape and gets a
 // role besides its condition -- the CN image (words 0 and 1, exactly the unweighted kernel's), the low plane (word 2)
 // or the high plane (word 2, shifted by 8) --, and the up to six workgroups of an item are dealt to one XCD.
+//
+// Several tables (gcn10_gpu_set_weight_tables, gcn10_gpu_grid_sums_storms, DESIGN.md "Several storms"): k tables are 2 k
+// planes behind each other and 2 + k words per (raster, cell), word 2 + j the sum of w_j[v].  grid_sums_storms_kernel
+// has 1 + 2 k roles per condition -- the CN image, then (low, high) of table 0, 1, ... --, dealt as above; the word
+// count and a plane role's target word are run-time values of sum_item there, uniform, and enter only the addresses of
+// the flush's atomics.  A plane role stages one image, so the LDS of a workgroup is the same.  The finish pass keeps
+// k x 101 weights in LDS and decides per table between bisection and the scan from 1.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 
 #include "gcn10_gpu_internal.hpp"
@@ -147,10 +155,14 @@ __device__ __forceinline__ void add_row(const uint8_t *lut, const u32x4 &e, cons
 
 // One workgroup's item (chunk, band) for condition `cond`.  PLANE = false: against the CN image, words 0 and 1 of
 // WORDS per (raster, cell).  PLANE = true: against the weight plane `image`, its sums shifted by `shift` into word 2.
+// WORDS = 0: `words` per (raster, cell) and a plane's sums into word `plane_word`, both uniform run-time values that
+// enter the addresses of the flush's atomics only.
 template <bool PLANE, uint32_t WORDS>
 __device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, const uint32_t item, const uint32_t cond,
-                                         const uint8_t *image, const uint32_t shift)
+                                         const uint8_t *image, const uint32_t shift, const uint32_t words = WORDS,
+                                         const uint32_t plane_word = 2u)
 {
+    const uint32_t n_words = WORDS ? WORDS : words, to_word = WORDS ? 2u : plane_word;
     uint8_t *const lut = lds.lut;
     uint32_t *const sum = lds.sum, *const n255 = lds.n255, *const area = lds.area;
     uint32_t &cell_lo = lds.cell_lo, &cell_hi = lds.cell_hi;
@@ -264,7 +276,7 @@ __device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, cons
                         const uint32_t sv = sum[t * kMaxCells + lc];
                         sum[t * kMaxCells + lc] = 0u;
                         if (sv)
-                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * WORDS + 2u),
+                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * n_words + to_word),
                                       (unsigned long long)sv << shift);
                     }
                 }
@@ -284,7 +296,7 @@ __device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, cons
                         sum[t * kMaxCells + lc] = 0u;
                         n255[t * kMaxCells + lc] = 0u;
                         if (nv)
-                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * WORDS + word),
+                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * n_words + word),
                                       (unsigned long long)(word ? nv : sv));
                     }
                     area[lc] = 0u;
@@ -353,6 +365,30 @@ __global__ __launch_bounds__(kThreads) void grid_sums_weighted_kernel(const Grid
         sum_item<true, 3u>(p, lds, item, cond, p.lut[image], image == 2u ? 8u : 0u);
 }
 
+// k tables: roles of an item (condition, image), the 1 + 2 k images of a condition next to each other -- the CN image,
+// then (low, high) of table 0, 1, ...
+struct StormParams {
+    GridParams g;               // lut[1], lut[2]: not used
+    const uint8_t *planes;      // [2 k] images: the low and the high plane of table 0, of table 1, ...
+    uint32_t k;
+};
+
+__global__ __launch_bounds__(kThreads) void grid_sums_storms_kernel(const StormParams sp)
+{
+    __shared__ GridLds lds;
+    const GridParams &p = sp.g;
+    const uint32_t per = 1u + 2u * sp.k, words = 2u + sp.k;
+    uint32_t item, role;
+    if (!deal_item(p, per * p.n_conds, item, role))
+        return;
+    const uint32_t cond = p.conds[role / per], image = role % per;
+    if (image == 0u)
+        sum_item<false, 0u>(p, lds, item, cond, p.lut[0], 0u, words, 0u);
+    else
+        sum_item<true, 0u>(p, lds, item, cond, sp.planes + (size_t)(image - 1u) * kLut16Bytes,
+                           (image & 1u) ? 0u : 8u, words, 2u + ((image - 1u) >> 1));
+}
+
 struct FinishParams {
     const unsigned long long *acc;
     size_t n_cells, total;      // cells per raster, and over all rasters
@@ -419,7 +455,57 @@ __global__ __launch_bounds__(kThreads) void grid_finish_kernel(const FinishParam
     }
 }
 
-int launch_sums(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const uint8_t *esa, int W, int rows,
+// 2 + k words, k runoff-equivalent bytes per cell ([k][n_sel][n_cells]) and the shared cells' 2 + k words
+struct StormFinishParams {
+    FinishParams f;             // weights: [k][256]; rising: bit j for table j
+    uint32_t k;
+};
+
+__global__ __launch_bounds__(kThreads) void grid_finish_storms_kernel(const StormFinishParams sp)
+{
+    __shared__ uint32_t w[GCN10_GPU_MAX_WEIGHT_TABLES * 101];
+    const FinishParams &p = sp.f;
+    const uint32_t k = sp.k, words = 2u + k;
+    for (uint32_t i = threadIdx.x; i < k * 101u; i += kThreads)
+        w[i] = p.weights[(i / 101u) * 256u + i % 101u];
+    __syncthreads();
+    const size_t stride = (size_t)gridDim.x * kThreads;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < p.total; i += stride) {
+        const unsigned long long s = p.acc[words * i], n = p.acc[words * i + 1u];
+        p.means[i] = n == 0 ? (uint8_t)GCN10_NODATA : (uint8_t)((2ull * s + n) / (2ull * n));
+        for (uint32_t j = 0; j < k; j++) {
+            const unsigned long long sw = p.acc[words * i + 2u + j];
+            p.cnq[(size_t)j * p.total + i] = (p.rising >> j) & 1u ? runoff_cn<true>(w + 101u * j, s, n, sw)
+                                                                  : runoff_cn<false>(w + 101u * j, s, n, sw);
+        }
+    }
+    const size_t packed = (size_t)p.n_sel * p.n_shared;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < packed; i += stride) {
+        const size_t q = i / p.n_shared, c = i - q * p.n_shared;
+        const size_t at = q * p.n_cells + p.shared_idx[c];
+        for (uint32_t word = 0; word < words; word++)
+            p.shared[words * i + word] = p.acc[words * at + word];
+    }
+}
+
+enum SumsKind { kPlain, kWeighted, kStorms };      // pairs; triples of one table; 2 + k words of k tables
+
+// the weights a weighted or a storms call needs: E_STATE without them, and for the one-table calls with several
+int check_weights(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind)
+{
+    if (kind == kPlain)
+        return GCN10_OK;
+    if (!ctx->weights_set)
+        return fail(GCN10_E_STATE, kind == kStorms
+                    ? "%s: call gcn10_gpu_set_weight_tables (or gcn10_gpu_set_weights) first (after gcn10_gpu_set_tables)"
+                    : "%s: call gcn10_gpu_set_weights first (after gcn10_gpu_set_tables)", who);
+    if (kind == kWeighted && ctx->n_weights != 1)
+        return fail(GCN10_E_STATE, "%s: the context has %d weight tables; call %s", who, ctx->n_weights,
+                    strstr(who, "finish") ? "gcn10_gpu_grid_finish_storms" : "gcn10_gpu_grid_sums_storms");
+    return GCN10_OK;
+}
+
+int launch_sums(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind, const uint8_t *esa, int W, int rows,
                 const int32_t *cj, const int32_t *cellx, const int32_t *celly, int ncx, int ncy, unsigned cond_mask,
                 unsigned table_mask, unsigned long long *acc, gcn10_stream_t stream)
 {
@@ -430,8 +516,8 @@ int launch_sums(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const uint8_
     GridParams p = {};
     if ((rc = check_tables(ctx, who)) != GCN10_OK)
         return rc;
-    if (weighted && !ctx->weights_set)
-        return fail(GCN10_E_STATE, "%s: call gcn10_gpu_set_weights first (after gcn10_gpu_set_tables)", who);
+    if ((rc = check_weights(ctx, who, kind)) != GCN10_OK)
+        return rc;
     if ((rc = bind_soil(ctx, who, W, s, cj, &p.soil)) != GCN10_OK)
         return rc;
     if (!esa || !cj || !cellx || !celly || !acc || W <= 0 || rows <= 0 || ncx <= 0 || ncy <= 0)
@@ -441,8 +527,8 @@ int launch_sums(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const uint8_
         return rc;
     p.esa = esa;
     p.lut[0] = ctx->d_lut16;
-    p.lut[1] = weighted ? ctx->d_wlut : nullptr;
-    p.lut[2] = weighted ? ctx->d_wlut + kLut16Bytes : nullptr;
+    p.lut[1] = kind == kWeighted ? ctx->d_wlut : nullptr;
+    p.lut[2] = kind == kWeighted ? ctx->d_wlut + kLut16Bytes : nullptr;
     p.cellx = cellx;
     p.celly = celly;
     p.W = (uint32_t)W;
@@ -457,7 +543,8 @@ int launch_sums(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const uint8_
     for (uint32_t cnd = 0; cnd < 2; cnd++)
         if ((p.sel >> (9u * cnd)) & 0x1ffu)
             p.conds[n_conds++] = cnd;
-    const uint32_t roles = weighted ? 3u * n_conds : n_conds;
+    const uint32_t k = kind == kStorms ? (uint32_t)ctx->n_weights : 1u;
+    const uint32_t roles = kind == kPlain ? n_conds : (1u + 2u * k) * n_conds;
     p.chunks = (p.W + kChunkPx - 1u) / kChunkPx;
     // bands of at most kMaxBandRows rows, and shorter ones when the strip would not fill the device with them
     const uint32_t want = grid_cap(ctx, 8) / (p.chunks * roles) + 1u;
@@ -468,7 +555,14 @@ int launch_sums(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const uint8_
         return fail(GCN10_E_INVAL, "%s: %llu workgroups; cut the strip into bands", who, (unsigned long long)grid);
     p.items = (uint32_t)items;
     p.n_conds = n_conds;
-    if (weighted)
+    if (kind == kStorms) {
+        StormParams sp = {};
+        sp.g = p;
+        sp.planes = ctx->d_wlut;
+        sp.k = k;
+        hipLaunchKernelGGL(grid_sums_storms_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, sp);
+    }
+    else if (kind == kWeighted)
         hipLaunchKernelGGL(grid_sums_weighted_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, p);
     else
         hipLaunchKernelGGL(grid_sums_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, p);
@@ -476,7 +570,7 @@ int launch_sums(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const uint8_
     return GCN10_OK;
 }
 
-int launch_finish(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const unsigned long long *acc, int n_sel,
+int launch_finish(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind, const unsigned long long *acc, int n_sel,
                   size_t n_cells, uint8_t *means, uint8_t *cnq, const uint32_t *shared_idx, uint32_t n_shared,
                   unsigned long long *shared, gcn10_stream_t stream)
 {
@@ -484,8 +578,9 @@ int launch_finish(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const unsi
     if (rc)
         return rc;
     hipStream_t s = as_stream(ctx, stream);
-    if (weighted && !ctx->weights_set)
-        return fail(GCN10_E_STATE, "%s: call gcn10_gpu_set_weights first (after gcn10_gpu_set_tables)", who);
+    const bool weighted = kind != kPlain;
+    if ((rc = check_weights(ctx, who, kind)) != GCN10_OK)
+        return rc;
     if (!acc || !means || (weighted && !cnq) || n_sel <= 0 || n_sel > GCN10_N_RASTERS || n_cells == 0 ||
         n_cells > 0xffffffffull || (n_shared && (!shared_idx || !shared)))
         return fail(GCN10_E_INVAL, "%s: bad arguments n_sel=%d n_cells=%zu n_shared=%u (1..%d rasters, 1..2^32-1 "
@@ -500,14 +595,71 @@ int launch_finish(gcn10_gpu_ctx *ctx, const char *who, bool weighted, const unsi
     p.n_shared = n_shared;
     p.n_sel = (uint32_t)n_sel;
     p.shared = shared;
-    p.weights = weighted ? reinterpret_cast<const uint16_t *>(ctx->d_wlut + 2 * kLut16Bytes) : nullptr;
-    p.rising = ctx->weights_rising ? 1u : 0u;
+    p.weights = weighted ? reinterpret_cast<const uint16_t *>(ctx->d_wlut + 2 * ctx->n_weights * kLut16Bytes) : nullptr;
+    p.rising = ctx->weights_rising;
     const uint32_t grid = stream_grid(ctx, (p.total + kThreads - 1u) / kThreads);
-    if (weighted)
+    if (kind == kStorms) {
+        StormFinishParams sp = {};
+        sp.f = p;
+        sp.k = (uint32_t)ctx->n_weights;
+        hipLaunchKernelGGL(grid_finish_storms_kernel, dim3(grid), dim3(kThreads), 0, s, sp);
+    }
+    else if (weighted)
         hipLaunchKernelGGL(grid_finish_kernel<3u>, dim3(grid), dim3(kThreads), 0, s, p);
     else
         hipLaunchKernelGGL(grid_finish_kernel<2u>, dim3(grid), dim3(kThreads), 0, s, p);
     HIP_TRY(hipGetLastError());
+    return GCN10_OK;
+}
+
+// k tables of 256 weights into the context: 2 k planes of the loaded tables, then the tables themselves
+int fold_weights(gcn10_gpu_ctx *ctx, const char *who, const uint16_t *w, int k)
+{
+    int rc = use_device(ctx);
+    if (rc)
+        return rc;
+    if ((rc = check_tables(ctx, who)) != GCN10_OK)
+        return rc;
+    if (!w || k < 1 || k > GCN10_GPU_MAX_WEIGHT_TABLES)
+        return fail(GCN10_E_INVAL, "%s: bad arguments k=%d (1..%d tables, no null weights)", who, k,
+                    GCN10_GPU_MAX_WEIGHT_TABLES);
+    // the CN image as the device holds it, folded: a byte of 255 (no value, padding, a table not loaded) weighs 0
+    const size_t table_bytes = 256 * sizeof(uint16_t), planes_bytes = (size_t)k * (2 * kLut16Bytes + table_bytes);
+    uint8_t *const img = static_cast<uint8_t *>(malloc(kLut16Bytes + planes_bytes));
+    if (!img)
+        return fail(GCN10_E_INVAL, "%s: out of host memory", who);
+    uint8_t *const planes = img + kLut16Bytes;
+    ctx->weights_set = false;
+    hipError_t e = hipMemcpy(img, ctx->d_lut16, kLut16Bytes, hipMemcpyDeviceToHost);
+    for (int j = 0; j < k && e == hipSuccess; j++) {
+        const uint16_t *const wj = w + 256 * j;
+        uint8_t *const lo = planes + (size_t)(2 * j) * kLut16Bytes, *const hi = lo + kLut16Bytes;
+        for (int i = 0; i < kLut16Bytes; i++) {
+            const uint32_t v = img[i] == GCN10_NODATA ? 0u : wj[img[i]];
+            lo[i] = (uint8_t)(v & 0xffu);
+            hi[i] = (uint8_t)(v >> 8);
+        }
+    }
+    memcpy(planes + (size_t)(2 * k) * kLut16Bytes, w, k * table_bytes);
+    if (e == hipSuccess && !ctx->d_wlut)        // once, for the most tables a context takes
+        e = hipMalloc(reinterpret_cast<void **>(&ctx->d_wlut),
+                      GCN10_GPU_MAX_WEIGHT_TABLES * (2 * kLut16Bytes + table_bytes));
+    // synchronous, as the images of set_tables: once per run, read by every later weighted call on any stream
+    if (e == hipSuccess)
+        e = hipMemcpy(ctx->d_wlut, planes, planes_bytes, hipMemcpyHostToDevice);
+    free(img);
+    HIP_TRY(e);
+    ctx->weights_rising = 0u;
+    for (int j = 0; j < k; j++) {
+        bool rising = true;
+        for (int c = 2; c <= 100; c++)
+            if (w[256 * j + c] < w[256 * j + c - 1])
+                rising = false;
+        if (rising)
+            ctx->weights_rising |= 1u << j;
+    }
+    ctx->n_weights = k;
+    ctx->weights_set = true;
     return GCN10_OK;
 }
 
@@ -519,7 +671,7 @@ int gcn10_gpu_grid_sums(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
                         const int32_t *cellx, const int32_t *celly, int ncx, int ncy, unsigned cond_mask,
                         unsigned table_mask, unsigned long long *acc, gcn10_stream_t stream)
 {
-    return launch_sums(ctx, "gcn10_gpu_grid_sums", false, esa, W, rows, cj, cellx, celly, ncx, ncy, cond_mask,
+    return launch_sums(ctx, "gcn10_gpu_grid_sums", kPlain, esa, W, rows, cj, cellx, celly, ncx, ncy, cond_mask,
                        table_mask, acc, stream);
 }
 
@@ -527,47 +679,41 @@ int gcn10_gpu_grid_finish(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int
                           uint8_t *means, const uint32_t *shared_idx, uint32_t n_shared, unsigned long long *shared,
                           gcn10_stream_t stream)
 {
-    return launch_finish(ctx, "gcn10_gpu_grid_finish", false, acc, n_sel, n_cells, means, nullptr, shared_idx,
+    return launch_finish(ctx, "gcn10_gpu_grid_finish", kPlain, acc, n_sel, n_cells, means, nullptr, shared_idx,
                          n_shared, shared, stream);
 }
 
 int gcn10_gpu_set_weights(gcn10_gpu_ctx *ctx, const uint16_t *w)
 {
-    int rc = use_device(ctx);
-    if (rc)
-        return rc;
-    const char *const who = "gcn10_gpu_set_weights";
-    if ((rc = check_tables(ctx, who)) != GCN10_OK)
-        return rc;
-    if (!w)
-        return fail(GCN10_E_INVAL, "%s: null weights", who);
-    // the CN image as the device holds it, folded: a byte of 255 (no value, padding, a table not loaded) weighs 0
-    static thread_local uint8_t img[kLut16Bytes], planes[2 * kLut16Bytes + 256 * sizeof(uint16_t)];
-    ctx->weights_set = false;
-    HIP_TRY(hipMemcpy(img, ctx->d_lut16, sizeof img, hipMemcpyDeviceToHost));
-    for (int i = 0; i < kLut16Bytes; i++) {
-        const uint32_t v = img[i] == GCN10_NODATA ? 0u : w[img[i]];
-        planes[i] = (uint8_t)(v & 0xffu);
-        planes[kLut16Bytes + i] = (uint8_t)(v >> 8);
-    }
-    memcpy(planes + 2 * kLut16Bytes, w, 256 * sizeof(uint16_t));
-    if (!ctx->d_wlut)
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_wlut), sizeof planes));
-    // synchronous, as the images of set_tables: once per run, read by every later weighted call on any stream
-    HIP_TRY(hipMemcpy(ctx->d_wlut, planes, sizeof planes, hipMemcpyHostToDevice));
-    ctx->weights_rising = true;
-    for (int c = 2; c <= 100; c++)
-        if (w[c] < w[c - 1])
-            ctx->weights_rising = false;
-    ctx->weights_set = true;
-    return GCN10_OK;
+    return fold_weights(ctx, "gcn10_gpu_set_weights", w, 1);
+}
+
+int gcn10_gpu_set_weight_tables(gcn10_gpu_ctx *ctx, const uint16_t *w, int k)
+{
+    return fold_weights(ctx, "gcn10_gpu_set_weight_tables", w, k);
+}
+
+int gcn10_gpu_grid_sums_storms(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                               const int32_t *cellx, const int32_t *celly, int ncx, int ncy, unsigned cond_mask,
+                               unsigned table_mask, unsigned long long *acc, gcn10_stream_t stream)
+{
+    return launch_sums(ctx, "gcn10_gpu_grid_sums_storms", kStorms, esa, W, rows, cj, cellx, celly, ncx, ncy, cond_mask,
+                       table_mask, acc, stream);
+}
+
+int gcn10_gpu_grid_finish_storms(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells,
+                                 uint8_t *means, uint8_t *cnq, const uint32_t *shared_idx, uint32_t n_shared,
+                                 unsigned long long *shared, gcn10_stream_t stream)
+{
+    return launch_finish(ctx, "gcn10_gpu_grid_finish_storms", kStorms, acc, n_sel, n_cells, means, cnq, shared_idx,
+                         n_shared, shared, stream);
 }
 
 int gcn10_gpu_grid_sums_weighted(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
                                  const int32_t *cellx, const int32_t *celly, int ncx, int ncy, unsigned cond_mask,
                                  unsigned table_mask, unsigned long long *acc, gcn10_stream_t stream)
 {
-    return launch_sums(ctx, "gcn10_gpu_grid_sums_weighted", true, esa, W, rows, cj, cellx, celly, ncx, ncy, cond_mask,
+    return launch_sums(ctx, "gcn10_gpu_grid_sums_weighted", kWeighted, esa, W, rows, cj, cellx, celly, ncx, ncy, cond_mask,
                        table_mask, acc, stream);
 }
 
@@ -575,7 +721,7 @@ int gcn10_gpu_grid_finish_weighted(gcn10_gpu_ctx *ctx, const unsigned long long 
                                    uint8_t *means, uint8_t *cnq, const uint32_t *shared_idx, uint32_t n_shared,
                                    unsigned long long *shared, gcn10_stream_t stream)
 {
-    return launch_finish(ctx, "gcn10_gpu_grid_finish_weighted", true, acc, n_sel, n_cells, means, cnq, shared_idx,
+    return launch_finish(ctx, "gcn10_gpu_grid_finish_weighted", kWeighted, acc, n_sel, n_cells, means, cnq, shared_idx,
                          n_shared, shared, stream);
 }
 

@@ -329,6 +329,16 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             }
             rc = set_str(&cfg->storm, val);
         }
+        else if (!strcmp(key, "storms")) {
+            if (gcn10_parse_storms(val, cfg->storms_p, &cfg->n_storms, &cfg->storms_lambda) != 0) {
+                fclose(f);
+                snprintf(err, errcap, "bad value for storms: '%s' (P1[:P2...][,lambda]: 1 to 8 rising depths, 0 < P <= 650 "
+                                      "mm, 0 <= lambda < 1)", val);
+                gcn10_config_free(cfg);
+                return -3;
+            }
+            rc = set_str(&cfg->storms, val);
+        }
         else if (!strcmp(key, "zones_shp_path"))
             rc = set_str(&cfg->zones_shp_path, val);
         else if (!strcmp(key, "zonal_output"))
@@ -387,5 +397,6 @@ void gcn10_config_free(gcn10_config *cfg)
     free(cfg->zonal_output);
     free(cfg->grid);
     free(cfg->storm);
+    free(cfg->storms);
     memset(cfg, 0, sizeof *cfg);
 }

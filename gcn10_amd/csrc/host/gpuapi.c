@@ -105,6 +105,10 @@ static void load_once(void)
     *(void **)(&g_api.set_weights) = dlsym(h, "gcn10_gpu_set_weights");
     *(void **)(&g_api.grid_sums_weighted) = dlsym(h, "gcn10_gpu_grid_sums_weighted");
     *(void **)(&g_api.grid_finish_weighted) = dlsym(h, "gcn10_gpu_grid_finish_weighted");
+    /* and those for several weight tables: needed by storms=... runs on a grid only, which check for them */
+    *(void **)(&g_api.set_weight_tables) = dlsym(h, "gcn10_gpu_set_weight_tables");
+    *(void **)(&g_api.grid_sums_storms) = dlsym(h, "gcn10_gpu_grid_sums_storms");
+    *(void **)(&g_api.grid_finish_storms) = dlsym(h, "gcn10_gpu_grid_finish_storms");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -19,7 +19,10 @@
  * With a design storm (config key "storm", runoff.c) the sums are triples {sum, count, sum of q[value]}: the worker hands
  * the storm's runoff table to its context once (gcn10_gpu_set_weights) and runs the weighted pair of calls, which also
  * gives the runoff-equivalent byte of every cell (gcn10_runoff_cn); the shared cells carry triples, and every selected
- * raster is written twice, its mean as without a storm and cnq_<hc>_<arc>_p<N>.tif beside it.
+ * raster is written twice, its mean as without a storm and cnq_<hc>_<arc>_p<N>.tif beside it.  With K storms (config
+ * key "storms") the sums are 2 + K words, word 2 + k the sum of storm k's table: one set of tables per context
+ * (gcn10_gpu_set_weight_tables), the _storms pair of calls, K runoff-equivalent bytes per cell, and one
+ * cnq_<hc>_<arc>_p<N_k>.tif per storm beside the mean.
  */
 #include "pipeline_internal.h"
 
@@ -237,9 +240,9 @@ NO_CONTRACT int gcn10_grid_plan_block(const gcn10_grid *g, int W, int H, const d
 struct gcn10_grid_result {
     pthread_mutex_t mu;
     uint8_t *raster;            /* [n_sel][ny][nx] */
-    uint8_t *cnq;               /* the same, runoff-equivalent (storm only) */
+    uint8_t *cnq;               /* [n_storms][n_sel][ny][nx], runoff-equivalent (storm only) */
     uint32_t *key;              /* [cap]; NO_KEY: free */
-    uint64_t *pair;             /* [cap][n_sel][words] = {s, n} or, with a storm, {s, n, sw} */
+    uint64_t *pair;             /* [cap][n_sel][words] = {s, n} or, with storms, {s, n, sw of every storm} */
     size_t cap, used;
     int n_sel, words;
     int blocks;                 /* blocks summed */
@@ -359,7 +362,7 @@ int gcn10_grid_start(struct run *r)
     r->grid_result = t;
     pthread_mutex_init(&t->mu, NULL);
     t->n_sel = r->n_sel > 0 ? r->n_sel : 1;
-    t->words = r->storm_on ? 3 : 2;
+    t->words = 2 + (r->storm_on ? r->n_storms : 0);
     /* the landcover's pixel size: below 8 pixels per cell the 10 m raster is the product (and a 16-pixel column group
      * of the kernel would meet more than three cell columns).  A landcover that does not open is the workers' to
      * report, block by block, as in every run. */
@@ -379,15 +382,16 @@ int gcn10_grid_start(struct run *r)
     bytes = (size_t)t->n_sel * (size_t)r->grid.nx * (size_t)r->grid.ny;
     t->raster = malloc(bytes);
     if (r->storm_on)
-        t->cnq = malloc(bytes);
+        t->cnq = malloc((size_t)r->n_storms * bytes);
     if (!t->raster || (r->storm_on && !t->cnq) || table_reserve(t, 0) != 0) {
-        fprintf(stderr, "[rank 0] out of memory for the grid rasters (%zu bytes)\n", r->storm_on ? 2 * bytes : bytes);
+        fprintf(stderr, "[rank 0] out of memory for the grid rasters (%zu bytes)\n",
+                r->storm_on ? (size_t)(1 + r->n_storms) * bytes : bytes);
         grid_end(r);
         return -1;
     }
     memset(t->raster, GCN10_NODATA, bytes);
     if (t->cnq)
-        memset(t->cnq, GCN10_NODATA, bytes);
+        memset(t->cnq, GCN10_NODATA, (size_t)r->n_storms * bytes);
     return 0;
 }
 
@@ -430,8 +434,8 @@ static int grid_plan_input(struct worker *w, struct block_in *in, const double o
     return 0;
 }
 
-/* the block's bytes (cnq: the runoff-equivalent ones, NULL without a storm) and pairs or triples into the result of
- * the run */
+/* the block's bytes (cnq: the runoff-equivalent ones of every storm, NULL without a storm) and its shared cells' words
+ * into the result of the run */
 static int merge_block(struct run *r, const gcn10_grid_plan *p, const uint8_t *means, const uint8_t *cnq,
                        const uint64_t *shared)
 {
@@ -455,8 +459,9 @@ static int merge_block(struct run *r, const gcn10_grid_plan *p, const uint8_t *m
                 const size_t from = (size_t)q * n_cells + (size_t)cy * (size_t)ncx + (size_t)a;
 
                 memcpy(t->raster + to, means + from, (size_t)(b - a));
-                if (cnq)
-                    memcpy(t->cnq + to, cnq + from, (size_t)(b - a));
+                for (size_t k = 0; cnq && k < words - 2; k++)
+                    memcpy(t->cnq + k * (size_t)t->n_sel * plane + to, cnq + k * (size_t)t->n_sel * n_cells + from,
+                           (size_t)(b - a));
             }
     if (table_reserve(t, p->n_shared) != 0)
         rc = -1;
@@ -489,8 +494,9 @@ static int grid_block(struct worker *w, struct block_in *in)
     const size_t n_cells = (size_t)ncx * (size_t)ncy, n_sel = (size_t)r->n_sel;
     const size_t maps = ((size_t)in->W + (size_t)in->H) * sizeof(int32_t);
     const size_t up = maps + p->n_shared * sizeof(uint32_t);
-    const bool storm = r->storm_on;
-    const size_t words = storm ? 3 : 2, bytes = (storm ? 2 : 1) * n_sel * n_cells;  /* per cell: sums, and bytes back */
+    const bool storm = r->storm_on, ladder = r->storms_key;
+    const size_t n_storms = storm ? (size_t)r->n_storms : 0;
+    const size_t words = 2 + n_storms, bytes = (1 + n_storms) * n_sel * n_cells;    /* per cell: sums, and bytes back */
     struct gcn10_grid_state *s;
     int32_t *d_cellx, *d_celly;
     uint32_t *d_idx;
@@ -528,7 +534,8 @@ static int grid_block(struct worker *w, struct block_in *in)
                             (n_sel * p->n_shared + 1) * words * sizeof *s->d_shared) != 0)
         return -1;
     if (storm && !s->weights_set) {         /* once per context: the tables are set before the first block */
-        if (g->set_weights(w->ctx, r->runoff_q) != 0)
+        if ((ladder ? g->set_weight_tables(w->ctx, r->runoff_q[0], r->n_storms)
+                    : g->set_weights(w->ctx, r->runoff_q[0])) != 0)
             goto gpu_fail;
         s->weights_set = true;
     }
@@ -542,12 +549,12 @@ static int grid_block(struct worker *w, struct block_in *in)
     if (g->memcpy_h2d(w->ctx, s->d_up, s->h_up, up, w->s_kernel) != 0 ||
         g->memset(w->ctx, s->d_acc, 0, n_sel * n_cells * words * sizeof *s->d_acc, w->s_kernel) != 0 ||
         g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, in->W, w->s_kernel) != 0 ||
-        (storm ? g->grid_sums_weighted : g->grid_sums)(
+        (ladder ? g->grid_sums_storms : storm ? g->grid_sums_weighted : g->grid_sums)(
             w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0, in->d_cj + p->y0, d_cellx,
             d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask, s->d_acc, w->s_kernel) != 0 ||
-        (storm ? g->grid_finish_weighted(w->ctx, s->d_acc, r->n_sel, n_cells, s->d_means, s->d_means + n_sel * n_cells,
-                                         p->n_shared ? d_idx : NULL, (uint32_t)p->n_shared,
-                                         p->n_shared ? s->d_shared : NULL, w->s_kernel)
+        (storm ? (ladder ? g->grid_finish_storms : g->grid_finish_weighted)(
+                     w->ctx, s->d_acc, r->n_sel, n_cells, s->d_means, s->d_means + n_sel * n_cells,
+                     p->n_shared ? d_idx : NULL, (uint32_t)p->n_shared, p->n_shared ? s->d_shared : NULL, w->s_kernel)
                : g->grid_finish(w->ctx, s->d_acc, r->n_sel, n_cells, s->d_means, p->n_shared ? d_idx : NULL,
                                 (uint32_t)p->n_shared, p->n_shared ? s->d_shared : NULL, w->s_kernel)) != 0 ||
         g->memcpy_d2h(w->ctx, s->h_means, s->d_means, bytes, w->s_kernel) != 0 ||
@@ -618,13 +625,15 @@ static int grid_finish(struct run *r, gcn10_log *log0)
     struct gcn10_grid_result *t = r->grid_result;
     const gcn10_grid *gr = &r->grid;
     const size_t plane = (size_t)gr->nx * (size_t)gr->ny, words = (size_t)t->words, width = (size_t)t->n_sel * words;
-    const int per = r->storm_on ? 2 : 1, n_files = per * r->n_sel;      /* files per selected raster, and of the run */
+    const int n_storms = r->storm_on ? r->n_storms : 0;
+    const int per = 1 + n_storms, n_files = per * r->n_sel;             /* files per selected raster, and of the run */
     const double gt[6] = { gr->xmin, gr->dx, 0.0, gr->ymax, 0.0, -gr->dy };
     const int down = (gr->ny + TILE - 1) / TILE;
-    struct grid_file files[2 * GCN10_N_RASTERS];    /* file 2 q + 1 (storm only): the runoff-equivalent raster of q */
+    /* file per q: the mean of q; file per q + 1 + k (storms only): the runoff-equivalent raster of q for storm k */
+    struct grid_file files[(1 + GCN10_MAX_STORMS) * GCN10_N_RASTERS];
     struct grid_tile_job *jobs;
     struct gcn10_job_group group;
-    char msg[PATH_MAX + 256], err[PATH_MAX + 256] = "";
+    char msg[PATH_MAX + 256], err[PATH_MAX + 256] = "", names[GCN10_MAX_STORMS * 16 + 64];
     size_t empty = 0;
     int rc = 0;
 
@@ -635,8 +644,9 @@ static int grid_finish(struct run *r, gcn10_log *log0)
                 const uint64_t *v = &t->pair[i * width + words * (size_t)q];
 
                 t->raster[(size_t)q * plane + t->key[i]] = mean_of(v[0], v[1]);
-                if (t->cnq)
-                    t->cnq[(size_t)q * plane + t->key[i]] = (uint8_t)gcn10_runoff_cn(v[0], v[1], v[2], r->runoff_q);
+                for (int k = 0; k < n_storms; k++)
+                    t->cnq[((size_t)k * (size_t)r->n_sel + (size_t)q) * plane + t->key[i]] =
+                        (uint8_t)gcn10_runoff_cn(v[0], v[1], v[2 + k], r->runoff_q[k]);
             }
     for (size_t c = 0; c < plane; c++) {
         int q = 0;
@@ -673,8 +683,9 @@ static int grid_finish(struct run *r, gcn10_log *log0)
                      gcn10_arcs[k % 3]);
         else
             snprintf(path, sizeof path, "cn_grid_%s/cnq_%s_%s_p%u.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
-                     gcn10_arcs[k % 3], (unsigned)r->runoff_q[100]);
-        files[fi].data = (fi % per == 0 ? t->raster : t->cnq) + (size_t)q * plane;
+                     gcn10_arcs[k % 3], (unsigned)r->runoff_q[fi % per - 1][100]);
+        files[fi].data = fi % per == 0 ? t->raster + (size_t)q * plane
+                         : t->cnq + ((size_t)(fi % per - 1) * (size_t)r->n_sel + (size_t)q) * plane;
         files[fi].tif = gcn10_tiff_create(path, gr->nx, gr->ny, gt, t->esa ? gcn10_raster_georef(t->esa) : NULL, err,
                                           sizeof err);
         if (files[fi].tif && r->nodata >= 0 && gcn10_tiff_set_nodata(files[fi].tif, r->nodata) != 0) {
@@ -719,10 +730,16 @@ static int grid_finish(struct run *r, gcn10_log *log0)
         gcn10_log_message(log0, "ERROR", "grid: the rasters could not be written", true);
         return 1;
     }
-    if (r->storm_on)
+    if (r->storm_on) {
+        /* every storm's suffix: "cnq_<hc>_<arc>_p2500.tif, _p5000.tif" */
+        int at = snprintf(names, sizeof names, "cnq_<hc>_<arc>_p%u.tif", (unsigned)r->runoff_q[0][100]);
+
+        for (int k = 1; k < n_storms; k++)
+            at += snprintf(names + at, sizeof names - (size_t)at, ", _p%u.tif", (unsigned)r->runoff_q[k][100]);
         snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
-                 "cn_grid_<cond>/: cn_<hc>_<arc>.tif (mean) and cnq_<hc>_<arc>_p%u.tif (runoff-equivalent)", t->blocks,
-                 r->n_sel, gr->nx, gr->ny, empty, (unsigned)r->runoff_q[100]);
+                 "cn_grid_<cond>/: cn_<hc>_<arc>.tif (mean) and %s (runoff-equivalent)", t->blocks,
+                 r->n_sel, gr->nx, gr->ny, empty, names);
+    }
     else
         snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
                  "cn_grid_<cond>/", t->blocks, r->n_sel, gr->nx, gr->ny, empty);

@@ -9,7 +9,7 @@
  * to check the rasters a run has written instead of writing them, and --zonal / --zones for the composite curve
  * numbers of the polygons of a shapefile instead of rasters, and --aggregate for area-mean rasters on a coarser grid,
  * and --grid for mean rasters on a model grid that spans the blocks, and --storm for the runoff-weighted composites of
- * a design storm beside the means of --grid and --zones.
+ * a design storm beside the means of --grid and --zones, and --storms for a ladder of such storms in one run.
  * No mpirun: one process drives every GPU of the node.
  */
 #include "gcn10_host.h"
@@ -28,6 +28,7 @@ static void usage(FILE *fp)
             "        [--cog] [--overview-resampling nearest|average] [--stats] [--nodata none|<0..255>]\n"
             "        [--verify] [--zonal] [--zones <zones.shp>] [--aggregate <f>]\n"
             "        [--grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>] [--storm <P>[,<lambda>]]\n"
+            "        [--storms <P1>[:<P2>...][,<lambda>]]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -65,6 +66,12 @@ static void usage(FILE *fp)
             "\t\t\tcurve number that yields the cell's mean runoff depth for that storm, summed on the GPU;\n"
             "\t\t\twith --zones, the columns runoff_mm,cn_runoff (config key storm=...); needs --grid or\n"
             "\t\t\t--zones, not with --aggregate or --verify\n"
+            "  --storms <P1>[:<P2>...][,<lambda>]\n"
+            "\t\t\t1 to 8 design storms of rising depth and one ratio in ONE run: every block is read,\n"
+            "\t\t\tdecoded and summed once.  With --grid, cnq_<hc>_<arc>_p<100 P_k>.tif per storm, each the\n"
+            "\t\t\tfile --storm <P_k>,<lambda> alone writes; with --zones, the columns runoff_mm_p<100 P_k>,\n"
+            "\t\t\tcn_runoff_p<100 P_k> per storm (one depth: exactly what --storm gives; config key\n"
+            "\t\t\tstorms=...); not with --storm, otherwise as --storm\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -121,6 +128,8 @@ int main(int argc, char **argv)
             opt.grid = argv[++i];
         else if (!strcmp(argv[i], "--storm") && i + 1 < argc)
             opt.storm = argv[++i];
+        else if (!strcmp(argv[i], "--storms") && i + 1 < argc)
+            opt.storms = argv[++i];
         else if (!strcmp(argv[i], "--zonal"))
             opt.zonal = true;
         else if (!strcmp(argv[i], "--zones") && i + 1 < argc) {

@@ -275,9 +275,12 @@ struct run {
      * and written after the last one (grid.c) */
     gcn10_grid grid;
     struct gcn10_grid_result *grid_result;
-    /* storm=...: the runoff-weighted composites beside the means of a grid or zonal run (runoff.c) */
+    /* storm=... or storms=...: the runoff-weighted composites beside the means of a grid or zonal run (runoff.c) */
     bool storm_on;
-    uint16_t runoff_q[256];                 /* gcn10_runoff_table of the storm */
+    bool storms_key;                        /* they come from "storms": named per storm, summed by the _storms calls */
+    int n_storms;                           /* how many: 1 with "storm", 1 to GCN10_MAX_STORMS with "storms" */
+    double storm_p[GCN10_MAX_STORMS], storm_lambda;
+    uint16_t runoff_q[GCN10_MAX_STORMS][256];       /* gcn10_runoff_table of every storm */
 };
 
 double gcn10_now_seconds(void);

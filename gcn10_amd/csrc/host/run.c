@@ -119,19 +119,38 @@ static int resolve(struct run *r)
         free(r->cfg.storm);
         r->cfg.storm = strdup(opt->storm);
     }
-    r->storm_on = r->cfg.storm != NULL;
-    if (r->storm_on) {
-        if (r->verify)
-            why = "storm cannot be combined with --verify";
-        else if (r->aggregate)
-            why = "storm cannot be combined with aggregate (use --grid with cells of f pixels)";
-        else if (!r->zonal && !opt->grid && !r->cfg.grid)
-            why = "storm needs --grid or --zones";
-        if (why) {
-            fprintf(stderr, "[rank 0] %s\n", why);
+    if (opt->storms) {
+        if (gcn10_parse_storms(opt->storms, r->cfg.storms_p, &r->cfg.n_storms, &r->cfg.storms_lambda) != 0) {
+            fprintf(stderr, "[rank 0] bad value for storms: '%s' (P1[:P2...][,lambda]: 1 to 8 rising depths, 0 < P <= 650 "
+                            "mm, 0 <= lambda < 1)\n", opt->storms);
             return 1;
         }
-        gcn10_runoff_table(r->cfg.storm_p, r->cfg.storm_lambda, r->runoff_q);
+        free(r->cfg.storms);
+        r->cfg.storms = strdup(opt->storms);
+    }
+    r->storms_key = r->cfg.storms != NULL;
+    r->storm_on = r->cfg.storm != NULL || r->storms_key;
+    if (r->storm_on) {
+        const char *const key = r->storms_key ? "storms" : "storm";
+
+        if (r->storms_key && r->cfg.storm)
+            why = "cannot be combined with storm";
+        else if (r->verify)
+            why = "cannot be combined with --verify";
+        else if (r->aggregate)
+            why = "cannot be combined with aggregate (use --grid with cells of f pixels)";
+        else if (!r->zonal && !opt->grid && !r->cfg.grid)
+            why = "needs --grid or --zones";
+        if (why) {
+            fprintf(stderr, "[rank 0] %s %s\n", key, why);
+            return 1;
+        }
+        r->n_storms = r->storms_key ? r->cfg.n_storms : 1;
+        r->storm_lambda = r->storms_key ? r->cfg.storms_lambda : r->cfg.storm_lambda;
+        for (int k = 0; k < r->n_storms; k++) {
+            r->storm_p[k] = r->storms_key ? r->cfg.storms_p[k] : r->cfg.storm_p;
+            gcn10_runoff_table(r->storm_p[k], r->storm_lambda, r->runoff_q[k]);
+        }
     }
     if (r->aggregate) {
         if (gcn10_aggregate_start(r) != 0)
@@ -210,7 +229,8 @@ static int require(struct run *r)
     }
     snprintf(agg, sizeof agg, "aggregate=%d", r->aggregate);
     snprintf(grid, sizeof grid, "grid=%s", r->grid_on ? r->cfg.grid : "");
-    snprintf(storm, sizeof storm, "storm=%s", r->storm_on ? r->cfg.storm : "");
+    snprintf(storm, sizeof storm, "%s=%s", r->storms_key ? "storms" : "storm",
+             r->storms_key ? r->cfg.storms : r->storm_on ? r->cfg.storm : "");
     {
         /* the pair histogram's soil codes are asked for where a mode counts pairs, and must be as many as its bins */
         const bool pairs = (r->stats || r->zonal) && g->pair_histogram_codes &&
@@ -220,8 +240,10 @@ static int require(struct run *r)
             { r->stats, g->pair_histogram && pairs, "gcn10_gpu_pair_histogram", "stats=1" },
             { r->zonal, g->zonal_pair_histogram && pairs, "gcn10_gpu_zonal_pair_histogram", "zonal=1" },
             { r->aggregate != 0, g->aggregate != NULL, "gcn10_gpu_aggregate", agg },
-            { r->grid_on && r->storm_on, g->set_weights && g->grid_sums_weighted && g->grid_finish_weighted,
-              "gcn10_gpu_grid_sums_weighted", storm },
+            { r->grid_on && r->storm_on && !r->storms_key,
+              g->set_weights && g->grid_sums_weighted && g->grid_finish_weighted, "gcn10_gpu_grid_sums_weighted", storm },
+            { r->grid_on && r->storms_key, g->set_weight_tables && g->grid_sums_storms && g->grid_finish_storms,
+              "gcn10_gpu_grid_sums_storms", storm },
             { r->grid_on, g->grid_sums && g->grid_finish, "gcn10_gpu_grid_sums", grid },
             { r->verify, g->verify_strip && g->verify_buffers, "gcn10_gpu_verify_strip", "verify=1" },
             { r->lzw, g->lzw_strip && g->lzw_arena_bound, "gcn10_gpu_lzw_strip", "compress=lzw" },
@@ -391,13 +413,13 @@ static int load(struct run *r)
 
     log0_line(r, "INFO", true, "processing %d blocks %s", r->n_blocks,
               opt->blocks_file ? "from list file" : "from shapefile");      /* src/main.c:165-167 */
-    if (r->storm_on) {
+    for (int k = 0; r->storm_on && k < r->n_storms; k++) {      /* one line per storm, in the order given */
         int threshold = 1;
 
-        while (threshold < 100 && r->runoff_q[threshold] == 0)
+        while (threshold < 100 && r->runoff_q[k][threshold] == 0)
             threshold++;
         log0_line(r, "INFO", true, "storm: P = %.17g mm, lambda = %.17g, threshold CN %d (the smallest curve number that "
-                  "sheds water)", r->cfg.storm_p, r->cfg.storm_lambda, threshold);
+                  "sheds water)", r->storm_p[k], r->storm_lambda, threshold);
     }
     if (r->n_workers > r->n_blocks) {       /* no worker (and no pinned memory) without a block */
         for (int i = r->n_blocks > 0 ? r->n_blocks : 1; i < r->n_workers; i++) {

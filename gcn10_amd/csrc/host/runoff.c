@@ -1,5 +1,5 @@
-/* runoff.c -- the design storm of the runoff-weighted composites (config key "storm", --storm): no counterpart in the
- * reference.
+/* runoff.c -- the design storm of the runoff-weighted composites (config key "storm", --storm), and a ladder of them
+ * (config key "storms", --storms): no counterpart in the reference.
  *
  * A storm is a rainfall depth P in mm and an initial-abstraction ratio lambda.  The SCS runoff depth of a curve number
  * is a table of 256 16-bit values in units of 0.01 mm, made here in plain IEEE double (this file is built with
@@ -11,6 +11,7 @@
 
 #include <errno.h>
 #include <math.h>
+#include <stdbool.h>
 #include <stdlib.h>
 
 #if defined(__GNUC__) && !defined(__clang__)
@@ -45,6 +46,57 @@ int gcn10_parse_storm(const char *text, double *P, double *lambda)
         return -1;
     *P = d[0];
     *lambda = d[1];
+    return 0;
+}
+
+int gcn10_parse_storms(const char *text, double P[GCN10_MAX_STORMS], int *k, double *lambda)
+{
+    double d[GCN10_MAX_STORMS], lam = 0.2;
+    uint16_t q[256];
+    const char *p = text;
+    char *end;
+    int n = 0;
+    unsigned last = 0;
+
+    if (!text)
+        return -1;
+    for (bool ratio = false;;) {
+        double v;
+
+        /* a field as gcn10_parse_storm takes it: a sign, a digit or a point first, nothing but the number */
+        if (!(*p == '-' || *p == '+' || *p == '.' || (*p >= '0' && *p <= '9')))
+            return -1;
+        errno = 0;
+        v = strtod(p, &end);
+        if (end == p || errno != 0 || !isfinite(v))
+            return -1;
+        if (ratio) {
+            if (*end != '\0' || !(v >= 0.0) || !(v < 1.0))
+                return -1;
+            lam = v;
+            break;
+        }
+        if (n == GCN10_MAX_STORMS || !(v > 0.0) || !(v <= 650.0))
+            return -1;
+        d[n++] = v;
+        if (*end == '\0')
+            break;
+        if (*end == ',')
+            ratio = true;
+        else if (*end != ':')
+            return -1;
+        p = end + 1;
+    }
+    for (int i = 0; i < n; i++) {           /* rising in the unit of the names */
+        gcn10_runoff_table(d[i], lam, q);
+        if (i > 0 && q[100] <= last)
+            return -1;
+        last = q[100];
+    }
+    for (int i = 0; i < n; i++)
+        P[i] = d[i];
+    *k = n;
+    *lambda = lam;
     return 0;
 }
 

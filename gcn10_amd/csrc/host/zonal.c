@@ -9,7 +9,8 @@
  * never a curve number), sum, sum of squares, min and max into one table of the whole process.  All of it is
  * integers, so the table does not depend on the order in which the workers of all GPUs add to it.  With a design storm
  * (config key "storm", runoff.c) the sum of the storm's runoff table over the valid pixels is added up as well, from the
- * same histograms, and the table gets the columns runoff_mm,cn_runoff.
+ * same histograms, and the table gets the columns runoff_mm,cn_runoff; with several storms (config key "storms") one
+ * such sum and the columns runoff_mm_p<N>,cn_runoff_p<N> per storm.
  */
 #include "pipeline_internal.h"
 
@@ -32,7 +33,7 @@ enum { ZONE_BATCH = 1024, SPAN_BATCH = 1 << 20 };
 
 struct zcell {
     uint64_t pixels, valid, sum, sum2;
-    uint64_t runoff;            /* sum of runoff_q[value] over the valid pixels (storm only) */
+    uint64_t runoff[GCN10_MAX_STORMS];      /* per storm, the sum of runoff_q[value] over the valid pixels */
     int min, max;
 };
 
@@ -139,7 +140,8 @@ static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *ce
         uint64_t hist[256];
 
         gcn10_raster_histogram_sparse(at, n, m, r->hist_codes, r->tables[k % 9], k / 9 == 0, hist);
-        c->pixels = c->valid = c->sum = c->sum2 = c->runoff = 0;
+        c->pixels = c->valid = c->sum = c->sum2 = 0;
+        memset(c->runoff, 0, sizeof c->runoff);
         c->min = 255;
         c->max = 0;
         for (int v = 0; v < 256; v++) {
@@ -151,8 +153,8 @@ static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *ce
             c->valid += hist[v];
             c->sum += hist[v] * (uint64_t)v;
             c->sum2 += hist[v] * (uint64_t)(v * v);
-            if (r->storm_on)
-                c->runoff += hist[v] * (uint64_t)r->runoff_q[v];
+            for (int j = 0; r->storm_on && j < r->n_storms; j++)
+                c->runoff[j] += hist[v] * (uint64_t)r->runoff_q[j][v];
             if (v < c->min)
                 c->min = v;
             if (v > c->max)
@@ -259,7 +261,8 @@ static int zonal_block(struct worker *w, struct block_in *in)
                     dst[q].valid += src[q].valid;
                     dst[q].sum += src[q].sum;
                     dst[q].sum2 += src[q].sum2;
-                    dst[q].runoff += src[q].runoff;
+                    for (int j = 0; j < GCN10_MAX_STORMS; j++)
+                        dst[q].runoff[j] += src[q].runoff[j];
                     if (src[q].valid && src[q].min < dst[q].min)
                         dst[q].min = src[q].min;
                     if (src[q].valid && src[q].max > dst[q].max)
@@ -296,8 +299,15 @@ static int zonal_finish(struct run *r, gcn10_log *log0)
     snprintf(tmp, sizeof tmp, "%s.part.%ld", path, (long)getpid());
     f = fopen(tmp, "w");
     if (f) {
-        fprintf(f, "zone_id,condition,hc,arc,pixels,valid,sum,mean,min,max,stddev%s\n",
-                r->storm_on ? ",runoff_mm,cn_runoff" : "");
+        const int n_storms = r->storm_on ? r->n_storms : 0;
+
+        fprintf(f, "zone_id,condition,hc,arc,pixels,valid,sum,mean,min,max,stddev");
+        for (int j = 0; j < n_storms; j++)      /* one storm: the plain names; several: the names carry N */
+            if (n_storms == 1)
+                fprintf(f, ",runoff_mm,cn_runoff");
+            else
+                fprintf(f, ",runoff_mm_p%u,cn_runoff_p%u", (unsigned)r->runoff_q[j][100], (unsigned)r->runoff_q[j][100]);
+        fprintf(f, "\n");
         for (int i = 0; i < r->zones.n; i++) {
             if (r->n_sel > 0 && t->cell[(size_t)i * (size_t)r->n_sel].pixels == 0)
                 without++;
@@ -314,13 +324,16 @@ static int zonal_finish(struct run *r, gcn10_log *log0)
 
                     fprintf(f, "%.14g,%d,%d,%.14g", (double)c->sum / (double)c->valid, c->min, c->max,
                             sqrt((double)var) / (double)c->valid);
-                    if (r->storm_on)        /* the zone's mean runoff depth, and the curve number that yields it */
-                        fprintf(f, ",%.14g,%d", (double)c->runoff / (double)c->valid / 100.0,
-                                gcn10_runoff_cn(c->sum, c->valid, c->runoff, r->runoff_q));
+                    for (int j = 0; j < n_storms; j++)  /* the zone's mean runoff depth, and the curve number that yields it */
+                        fprintf(f, ",%.14g,%d", (double)c->runoff[j] / (double)c->valid / 100.0,
+                                gcn10_runoff_cn(c->sum, c->valid, c->runoff[j], r->runoff_q[j]));
                     fprintf(f, "\n");
                 }
                 else {
-                    fprintf(f, r->storm_on ? ",,,,,\n" : ",,,\n");
+                    fprintf(f, ",,,");
+                    for (int j = 0; j < n_storms; j++)
+                        fprintf(f, ",,");
+                    fprintf(f, "\n");
                 }
             }
         }

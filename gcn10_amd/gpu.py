@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_verify_strip", "gcn10_gpu_verify_buffers", "gcn10_gpu_zonal_pair_histogram",
     "gcn10_gpu_aggregate", "gcn10_gpu_grid_sums", "gcn10_gpu_grid_finish",
     "gcn10_gpu_set_weights", "gcn10_gpu_grid_sums_weighted", "gcn10_gpu_grid_finish_weighted",
+    "gcn10_gpu_set_weight_tables", "gcn10_gpu_grid_sums_storms", "gcn10_gpu_grid_finish_storms",
 )
 
 
@@ -150,6 +151,9 @@ def lib():
             "gcn10_gpu_set_weights": (i, [vp, vp]),
             "gcn10_gpu_grid_sums_weighted": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp]),
             "gcn10_gpu_grid_finish_weighted": (i, [vp, vp, i, sz, vp, vp, vp, C.c_uint32, vp, vp]),
+            "gcn10_gpu_set_weight_tables": (i, [vp, vp, i]),
+            "gcn10_gpu_grid_sums_storms": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp]),
+            "gcn10_gpu_grid_finish_storms": (i, [vp, vp, i, sz, vp, vp, vp, C.c_uint32, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -486,6 +490,31 @@ class Engine:
         self._chk(lib().gcn10_gpu_grid_finish_weighted(self._ctx, acc_ptr, n_sel, n_cells, means_ptr, cnq_ptr,
                                                        shared_idx_ptr or None, n_shared, shared_ptr or None, stream),
                   "gcn10_gpu_grid_finish_weighted")
+
+    def set_weight_tables(self, w):
+        """k tables of 256 16-bit weights ([k][256], 1 <= k <= 8), folded into the loaded tables as set_weights folds
+        one (gcn10_gpu_set_weight_tables): after set_tables, and again after every later set_tables.  Synchronous."""
+        a = np.ascontiguousarray(w, dtype=np.uint16).reshape(-1, 256)
+        self._chk(lib().gcn10_gpu_set_weight_tables(self._ctx, a.ctypes.data, a.shape[0]),
+                  "gcn10_gpu_set_weight_tables")
+
+    def grid_sums_storms(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, cellx_ptr: int, celly_ptr: int, ncx: int,
+                         ncy: int, cond_mask: int, table_mask: int, acc_ptr: int, stream=None):
+        """grid_sums with 2 + k words: ADDS {s, n, sw_0, ..., sw_(k-1)} to acc[q][celly[y]][cellx[x]] (uint64 on the
+        device, [n_sel][ncy][ncx][2 + k]), s and n exactly as grid_sums, sw_j the sum of w_j[v] over the same pixels
+        for the k tables of set_weight_tables (gcn10_gpu_grid_sums_storms).  Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_sums_storms(self._ctx, esa_ptr, W, rows, cj_ptr, cellx_ptr, celly_ptr, ncx, ncy,
+                                                   cond_mask, table_mask, acc_ptr, stream),
+                  "gcn10_gpu_grid_sums_storms")
+
+    def grid_finish_storms(self, acc_ptr: int, n_sel: int, n_cells: int, means_ptr: int, cnq_ptr: int, shared_idx_ptr,
+                           n_shared: int, shared_ptr, stream=None):
+        """means[q][c] as grid_finish, cnq[j][q][c] = host.runoff_cn of (s, n, sw_j) with table j of set_weight_tables,
+        and the 2 + k words of the n_shared cells shared_idx names, packed into shared[q][i]
+        (gcn10_gpu_grid_finish_storms).  Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_finish_storms(self._ctx, acc_ptr, n_sel, n_cells, means_ptr, cnq_ptr,
+                                                     shared_idx_ptr or None, n_shared, shared_ptr or None, stream),
+                  "gcn10_gpu_grid_finish_storms")
 
     def zonal_pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans, items, n_zones: int,
                              hist_ptr: int, stream=None):

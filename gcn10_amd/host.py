@@ -135,6 +135,8 @@ def lib():
         L.gcn10_grid_plan_free.restype = None
         L.gcn10_parse_storm.argtypes = [cp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.gcn10_parse_storm.restype = C.c_int
+        L.gcn10_parse_storms.argtypes = [cp, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.gcn10_parse_storms.restype = C.c_int
         L.gcn10_runoff_table.argtypes = [C.c_double, C.c_double, np.ctypeslib.ndpointer(dtype=np.uint16,
                                                                                        flags="C_CONTIGUOUS")]
         L.gcn10_runoff_table.restype = None
@@ -183,6 +185,16 @@ class ConfigGrid(ConfigFull):
 class ConfigStorm(ConfigGrid):
     """``gcn10_config`` with the key of the design storm, appended behind ``ConfigGrid`` as the C struct appends it."""
     _fields_ = [("storm", C.c_char_p), ("storm_p", C.c_double), ("storm_lambda", C.c_double)]
+
+
+MAX_STORMS = 8      # GCN10_MAX_STORMS
+
+
+class ConfigStorms(ConfigStorm):
+    """``gcn10_config`` with the key of several design storms, appended behind ``ConfigStorm`` as the C struct appends
+    it."""
+    _fields_ = [("storms", C.c_char_p), ("n_storms", C.c_int), ("storms_p", C.c_double * MAX_STORMS),
+                ("storms_lambda", C.c_double)]
 
 
 assert C.sizeof(Config) % 8 == 0
@@ -383,6 +395,16 @@ def parse_storm(text: str):
     return p.value, lam.value
 
 
+def parse_storms(text: str):
+    """"<P1>[:<P2>...][,<lambda>]" -> ([P1, P2, ...], lambda) (``gcn10_parse_storms``; 1 to 8 rising depths, lambda 0.2
+    when absent); raises HostError for any other text."""
+    p, k, lam = (C.c_double * MAX_STORMS)(), C.c_int(), C.c_double()
+    if lib().gcn10_parse_storms(text.encode(), p, C.byref(k), C.byref(lam)) != 0:
+        raise HostError("bad value for storms: '%s' (P1[:P2...][,lambda]: 1 to 8 rising depths, 0 < P <= 650 mm, "
+                        "0 <= lambda < 1)" % text)
+    return list(p[:k.value]), lam.value
+
+
 def runoff_table(P: float, lam: float = 0.2) -> np.ndarray:
     """The runoff depth of every raster value for a storm of P mm and initial-abstraction ratio lam, uint16[256] in units
     of 0.01 mm (``gcn10_runoff_table``)."""
@@ -399,15 +421,16 @@ def runoff_cn(s: int, n: int, sw: int, q) -> int:
 
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = ConfigStorm()
+    cfg = ConfigStorms()
     err = C.create_string_buffer(1024)
     rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
     out = {}
-    for name, _t in Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_ + ConfigStorm._fields_:
+    for name, _t in (Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_ + ConfigStorm._fields_ +
+                     ConfigStorms._fields_):
         v = getattr(cfg, name)
-        out[name] = v.decode() if isinstance(v, bytes) else v
+        out[name] = v.decode() if isinstance(v, bytes) else list(v) if isinstance(v, C.Array) else v
     lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))
     return out
 

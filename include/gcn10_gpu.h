@@ -42,7 +42,8 @@ extern "C" {
  *    of the band statistics (gcn10_gpu_pair_histogram*); the raster verifier (gcn10_gpu_verify_*); the pair histogram
  *    per zone of the zonal composites (gcn10_gpu_zonal_pair_histogram); the area means on a coarser grid
  *    (gcn10_gpu_aggregate); the sums and means on a model grid (gcn10_gpu_grid_sums, gcn10_gpu_grid_finish) and their
- *    weighted forms (gcn10_gpu_set_weights, gcn10_gpu_grid_sums_weighted, gcn10_gpu_grid_finish_weighted).
+ *    weighted forms (gcn10_gpu_set_weights, gcn10_gpu_grid_sums_weighted, gcn10_gpu_grid_finish_weighted), and those
+ *    for several weight tables (gcn10_gpu_set_weight_tables, gcn10_gpu_grid_sums_storms, gcn10_gpu_grid_finish_storms).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -451,6 +452,33 @@ int gcn10_gpu_grid_sums_weighted(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, 
 int gcn10_gpu_grid_finish_weighted(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells,
                                    uint8_t *means, uint8_t *cnq, const uint32_t *shared_idx_dev, uint32_t n_shared,
                                    unsigned long long *shared, gcn10_stream_t stream);
+
+/* Several weight tables in one pass (config key storms=...: a ladder of design storms).  Added in ABI 3 without a
+ * version change, as the weighted calls were; the host looks them up for storms runs on a grid only.
+ *
+ * gcn10_gpu_set_weight_tables: w[k][256], 1 <= k <= GCN10_GPU_MAX_WEIGHT_TABLES tables as gcn10_gpu_set_weights takes
+ *   one: every table is folded into its low and its high plane (2 k images behind each other), and the k tables and a
+ *   "never decreases" flag per table are kept for the finish pass.  gcn10_gpu_set_weights(ctx, w) equals k = 1.  A
+ *   later gcn10_gpu_set_tables invalidates all of it.
+ * gcn10_gpu_grid_sums_storms: every word of gcn10_gpu_grid_sums_weighted with 2 + k words per (raster, cell) instead of
+ *   three: words 0 and 1 are exactly what gcn10_gpu_grid_sums adds, word 2 + j gets the sum of w_j[v] over the same
+ *   pixels.  With k = 1 it adds exactly what gcn10_gpu_grid_sums_weighted adds.
+ * gcn10_gpu_grid_finish_storms: means[] as gcn10_gpu_grid_finish writes it; cnq[(j * n_sel + q) * n_cells + c] = the
+ *   value of (s, n, word 2 + j) by the rule of gcn10_runoff_cn with table j -- bisection for a table whose entries
+ *   1..100 never decrease, a scan from 1 for another, decided per table --; and the 2 + k words of the shared cells,
+ *   packed: shared[q * n_shared + i] = acc[q * n_cells + shared_idx[i]].
+ * Errors as the weighted calls'; k outside 1..8 or null weights: GCN10_E_INVAL; no weights: GCN10_E_STATE.  On a context
+ * with more than one table gcn10_gpu_grid_sums_weighted / _finish_weighted answer GCN10_E_STATE and name these calls. */
+#define GCN10_GPU_MAX_WEIGHT_TABLES 8
+int gcn10_gpu_set_weight_tables(gcn10_gpu_ctx *ctx, const uint16_t *w /* [k][256] */, int k);
+int gcn10_gpu_grid_sums_storms(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                               const int32_t *cellx_dev, const int32_t *celly_dev, int ncx, int ncy,
+                               unsigned cond_mask, unsigned table_mask,
+                               unsigned long long *acc /* [n_sel][ncy][ncx][2 + k] */, gcn10_stream_t stream);
+int gcn10_gpu_grid_finish_storms(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells,
+                                 uint8_t *means, uint8_t *cnq /* [k][n_sel][n_cells] */,
+                                 const uint32_t *shared_idx_dev, uint32_t n_shared,
+                                 unsigned long long *shared /* [n_sel][n_shared][2 + k] */, gcn10_stream_t stream);
 
 /* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
  * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.

@@ -82,6 +82,8 @@ int gcn10_raster_window(const double t[6], int rx, int ry, const double bbox[4],
  * 107-113) plus optional keys this program adds; unknown keys and lines
  * without '=' are ignored, '#' starts a comment line, lines are cut at 511
  * bytes (src/config.c:47-64). */
+#define GCN10_MAX_STORMS 8      /* design storms of one run (config key "storms") */
+
 typedef struct gcn10_config {
     char *hysogs_data_path;
     char *esa_data_path;
@@ -141,6 +143,12 @@ typedef struct gcn10_config {
                                composites -- with grid, a second raster per selected raster, the runoff-equivalent CN of
                                every cell; with zonal, two more columns of the table; absent (default) = off */
     double storm_p, storm_lambda;   /* ... its rainfall depth in mm and its initial-abstraction ratio */
+    char *storms;           /* "storms": <P1>[:<P2>...][,<lambda>] (gcn10_parse_storms): a ladder of 1 to GCN10_MAX_STORMS
+                               design storms in one grid or zonal run -- per storm what "storm" gives for one; not
+                               together with "storm"; absent (default) = off */
+    int n_storms;           /* ... how many, */
+    double storms_p[GCN10_MAX_STORMS];      /* their rainfall depths in mm, rising, */
+    double storms_lambda;   /* and the initial-abstraction ratio of all of them */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -164,7 +172,7 @@ int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or
 int gcn10_parse_aggregate(const char *text, int *factor);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -470,6 +478,11 @@ void gcn10_grid_plan_free(gcn10_grid_plan *p);
 /* "<P>[,<lambda>]": the rainfall depth of a design storm in mm and its initial-abstraction ratio (absent: 0.2), read
  * with strtod, nothing else in the text; 0 < P <= 650 and 0 <= lambda < 1.  0, or -1 for another text. */
 int gcn10_parse_storm(const char *text, double *P, double *lambda);
+/* "<P1>[:<P2>...][,<lambda>]": 1 to GCN10_MAX_STORMS rainfall depths and one ratio for all of them, every field read
+ * as gcn10_parse_storm reads its own.  The depths rise in hundredths of a millimetre: N_k = q_k[100] of
+ * gcn10_runoff_table(P_k, lambda) is strictly increasing (the file names and the columns carry N, so no two storms
+ * share a name).  0 with *k depths in P, or -1 for another text (nothing is written then). */
+int gcn10_parse_storms(const char *text, double P[GCN10_MAX_STORMS], int *k, double *lambda);
 /* The runoff depth of every raster value for that storm, in units of 0.01 mm.  q[0] = q[255] = 0; for v in 1..254, in
  * IEEE double, this order, no FMA:
  *   c = min(v, 100);  S = 25400.0 / c - 254.0;  Ia = lambda * S;
@@ -505,6 +518,7 @@ typedef struct gcn10_run_options {
     const char *aggregate;      /* --aggregate <f>: overrides the config key "aggregate" */
     const char *grid;           /* --grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>: overrides the config key "grid" */
     const char *storm;          /* --storm <P>[,<lambda>]: overrides the config key "storm" */
+    const char *storms;         /* --storms <P1>[:<P2>...][,<lambda>]: overrides the config key "storms" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -543,7 +557,9 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * write run.  A grid run (opt->grid / "grid=...") writes cn_grid_<cond>/cn_<hc>_<arc>.tif, one raster per selected
  * raster on the model grid, after the last block: exit codes as for a zonal run (1 as well when a block's inputs could
  * not be read: the rasters are written, but lack that block).  A storm (opt->storm / "storm=<P>[,<lambda>]") adds
- * cn_grid_<cond>/cnq_<hc>_<arc>_p<N>.tif to a grid run and the columns runoff_mm,cn_runoff to a zonal run's table. */
+ * cn_grid_<cond>/cnq_<hc>_<arc>_p<N>.tif to a grid run and the columns runoff_mm,cn_runoff to a zonal run's table;
+ * several storms (opt->storms / "storms=<P1>[:<P2>...][,<lambda>]") add one such raster per storm, or the columns
+ * runoff_mm_p<N>,cn_runoff_p<N> per storm (with one depth: exactly what storm adds). */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

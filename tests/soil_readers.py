@@ -2,7 +2,8 @@
 tests/test_soil_reader_references.py).
 
 A TILE is a landcover strip, a soil window and the two index maps (tests/test_gpu_soil_tables.Tile); tile_specs()
-names the ones of cases A to G.  A READER is one of the seven paths that read the code bytes of the prepared tile:
+names the ones of cases A to G.  A READER is one of the eight paths that read the code bytes of the prepared tile
+(strip, verify, histogram, zonal, overview, fused, aggregate and grid, all held to the cases A to I):
 it allocates and uploads everything it needs when it is made, launch(stream) queues its work, and check() compares
 what came back with numpy and the oracle -- never with another GPU path.
 """
@@ -12,8 +13,9 @@ import zlib
 import numpy as np
 
 from gcn10_amd import gpu, host
-from tests import aggutil
+from tests import aggutil, gridutil, stormutil
 from tests.fullblock import average_levels
+from tests.test_gpu_grid import maps
 from tests.test_gpu_soil_tables import K1, Tile, _with_complex_group, clamp_columns
 from tests.test_gpu_stats import model_histogram, soil_code
 from tests.util import ESA_NASTY, HSG_NASTY
@@ -21,7 +23,7 @@ from tests.util import ESA_NASTY, HSG_NASTY
 GUARD = 256
 HIST = 16 * 256
 NONE = gpu.VERIFY_NONE
-READERS = ("strip", "verify", "histogram", "zonal", "overview", "fused", "aggregate")
+READERS = ("strip", "verify", "histogram", "zonal", "overview", "fused", "aggregate", "grid")
 SHIFTED = (3, 1, 4, 0)      # case G: byte offsets of esa, coarse, ci and cj in their buffers (ci: not 16-byte aligned)
 SHIFTED_MAPS = (0, 1, 4, 0)     # the same with the landcover aligned, so that strips may read the compact words
 _REFERENCES = {}            # spec id -> (rasters, soils) of the oracle, computed once and shared
@@ -232,6 +234,60 @@ def reduce_strips(raster, x0, x1, f, strips):
     """uint8[sum of the strips' cell rows][cells]: every strip reduced by itself (aggutil.reduce_raster), the cell
     rows of a strip behind those of the strip before."""
     return np.vstack([aggutil.reduce_raster(raster[y0:y0 + rows], x0, x1, f) for y0, rows in strips])
+
+
+# the two weight tables of every GridReader: the low and the high byte of "random" both depend on the value (with
+# "all 65535" only whether a value is 255 would show), and "50 mm" is a real storm's
+GRID_TABLES = np.stack([stormutil.POOL["random"], stormutil.POOL["50 mm"]])
+GRID_LEAD, GRID_TRAIL = (5, 3), (3, 2)      # columns and rows of -1 before and behind the cells of the `storms` pass
+
+
+def grid_edges(W, H):
+    """(lead, trail) of the `storms` pass: -1 columns only where W >= 32, -1 rows only where H >= 8."""
+    wide, tall = W >= 32, H >= 8
+    return ((GRID_LEAD[0] * wide, GRID_LEAD[1] * tall), (GRID_TRAIL[0] * wide, GRID_TRAIL[1] * tall))
+
+
+def grid_passes(W, H, cj):
+    """The passes of GridReader over a W x H tile whose rows have the soil rows cj: dicts of the maps cellx and celly,
+    the cells ncx x ncy, the masks, the entry point `call`, the weight tables `ws` of its words beyond {s, n} and the
+    strips [(y0, rows)] of one call each, all adding into the same words.
+
+      rows    cells of 8 px of ONE row (the narrowest the kernel's three-masks rule allows), all rasters, pairs, one
+              call over the whole tile: every soil byte is at least 1/8 of a cell's sum
+      storms  cells of 25 x 25.6 px, -1 columns and rows around them (grid_edges), a subset of the rasters, 2 + 2 words
+              with GRID_TABLES, in the two strips of strips_inside_a_soil_row: the row walk across changing soil rows,
+              a strip that starts inside a soil row and inside a cell row, -1 runs that end inside a 16-px group"""
+    lead, trail = grid_edges(W, H)
+    sx, sy = maps(W, H, 25, 25.6, lead, trail)
+    passes = [dict(name="rows", cellx=(np.arange(W) // 8).astype(np.int32), celly=np.arange(H, dtype=np.int32),
+                   masks=(3, 0x1FF), call="grid_sums", ws=GRID_TABLES[:0], strips=[(0, H)]),
+              dict(name="storms", cellx=sx, celly=sy, masks=(2, 0x0A1), call="grid_sums_storms", ws=GRID_TABLES,
+                   strips=strips_inside_a_soil_row(cj))]
+    for p in passes:
+        p["sel"] = selected(*p["masks"])
+        p["ncx"], p["ncy"], p["words"] = int(p["cellx"].max()) + 1, int(p["celly"].max()) + 1, 2 + len(p["ws"])
+    return passes
+
+
+def weighted_rows_pass(W, H, cj):
+    """The `rows` pass as triples of one table, "random", for gcn10_gpu_grid_sums_weighted."""
+    p = grid_passes(W, H, cj)[0]
+    p.update(name="rows, weighted", call="grid_sums_weighted", ws=GRID_TABLES[:1], words=3)
+    return p
+
+
+def grid_words(p, rasters):
+    """int64[n_sel][ncy][ncx][words]: what the pass's calls add up to over rasters[r], strip by strip."""
+    acc = np.zeros((len(p["sel"]), p["ncy"], p["ncx"], p["words"]), np.int64)
+    for q, r in enumerate(p["sel"]):
+        for y0, rows in p["strips"]:
+            part, celly = rasters[r][y0:y0 + rows], p["celly"][y0:y0 + rows]
+            if len(p["ws"]):
+                stormutil.add_words(acc[q], part, p["cellx"], celly, p["ws"])
+            else:
+                gridutil.add_sums(acc[q], part, p["cellx"], celly)
+    return acc
 
 
 # ---- the readers -----------------------------------------------------------------------------------------------
@@ -483,14 +539,75 @@ class AggregateReader(Reader):
         assert (got[poison] == 0xA5).all(), "aggregate: a byte outside the cells was written"
 
 
+class GridReader(Reader):
+    """gcn10_gpu_grid_sums and gcn10_gpu_grid_sums_storms in the passes of grid_passes, into words that are zero
+    inside a poisoned buffer (the kernels ADD): a guard around every pass's words.  Every GridReader sets the same
+    weight tables when it is made -- set_weight_tables is synchronous, and a set_tables before has voided them -- so
+    launch() only queues work and two of them do not disturb each other."""
+    name = "grid"
+
+    def __init__(self, tile):
+        super().__init__(tile)
+        self.passes = self.set_weights_and_passes()
+        self.total = GUARD
+        for p in self.passes:
+            p["off"], p["nbytes"] = self.total, len(p["sel"]) * p["ncy"] * p["ncx"] * p["words"] * 8
+            p["dev"] = (self.upload(p["cellx"]), self.upload(p["celly"]))
+            self.total += p["nbytes"] + GUARD
+        self.out = self.alloc(self.total)
+
+    def set_weights_and_passes(self):
+        t = self.t
+        self.eng.set_weight_tables(GRID_TABLES)
+        return grid_passes(t.W, t.H, t.cj)
+
+    def launch(self, stream=None):
+        t = self.t
+        self.eng.memset(self.out.ptr, 0xA5, self.total, stream)
+        for p in self.passes:
+            self.eng.memset(self.out.at(p["off"]), 0, p["nbytes"], stream)
+            for y0, rows in p["strips"]:
+                getattr(self.eng, p["call"])(self.esa.at(y0 * t.W), t.W, rows, self.cj.at(4 * y0), p["dev"][0].ptr,
+                                             p["dev"][1].at(4 * y0), p["ncx"], p["ncy"], p["masks"][0], p["masks"][1],
+                                             self.out.at(p["off"]), stream)
+
+    def check(self):
+        t = self.t
+        got = self.eng.download(self.out.ptr, (self.total,))
+        poison = np.ones(self.total, bool)
+        for p in self.passes:
+            poison[p["off"]:p["off"] + p["nbytes"]] = False
+            words = got[p["off"]:p["off"] + p["nbytes"]].view(np.uint64).astype(np.int64)
+            want = grid_words(p, {r: t.want(r) for r in p["sel"]})
+            words = words.reshape(want.shape)
+            bad = np.argwhere(words != want).tolist()
+            at = tuple(bad[0]) if bad else None
+            assert not bad, "grid pass '%s' (%s) in %d strips: %d of %d words differ, first in raster %d at (cell row, " \
+                "cell, word) = %s: got %d, want %d" % (p["name"], p["call"], len(p["strips"]), len(bad), want.size,
+                                                      p["sel"][at[0]], at[1:], words[at], want[at])
+        assert (got[poison] == 0xA5).all(), "grid: a byte outside the words was written"
+
+
+class WeightedGridReader(GridReader):
+    """gcn10_gpu_grid_sums_weighted, the kernel of three words, over the `rows` pass with one table.  A context holds
+    either one table (set_weights) or the k of set_weight_tables, so this reader is not one of READERS: it cannot run
+    beside a GridReader."""
+    name = "grid, weighted"
+
+    def set_weights_and_passes(self):
+        t = self.t
+        self.eng.set_weights(GRID_TABLES[0])
+        return [weighted_rows_pass(t.W, t.H, t.cj)]
+
+
 READER_CLASSES = {c.name: c for c in (StripReader, VerifyReader, HistogramReader, ZonalReader, OverviewReader,
-                                      FusedReader, AggregateReader)}
+                                      FusedReader, AggregateReader, GridReader)}
 assert tuple(READER_CLASSES) == READERS
 
 
 def run_reader(tile, name, stream=None):
-    """The named reader over the tile: made, launched, awaited, checked, freed."""
-    rd = READER_CLASSES[name](tile)
+    """The named reader (or a Reader class outside READERS) over the tile: made, launched, awaited, checked, freed."""
+    rd = (READER_CLASSES[name] if isinstance(name, str) else name)(tile)
     try:
         rd.launch(stream)
         tile.eng.sync(stream)

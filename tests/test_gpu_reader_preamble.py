@@ -4,18 +4,19 @@ a refused call leaves the context fit for the next good one.  Needs an MI355X.
 
 The entry points: gcn10_gpu_cn_strip (at this width it launches the byte strip kernel; the vector kernel is behind
 the same preamble), gcn10_gpu_verify_strip, gcn10_gpu_pair_histogram, gcn10_gpu_zonal_pair_histogram,
-gcn10_gpu_overview_average, gcn10_gpu_deflate_fused_strip and gcn10_gpu_aggregate.  For each of them, on a context
-of its own, so that the call is the first one after the state it tests:
+gcn10_gpu_overview_average, gcn10_gpu_deflate_fused_strip, gcn10_gpu_aggregate and gcn10_gpu_grid_sums (its weighted
+and storms forms are behind the same preamble, after a check of the weights).  For each of them, on a context of its
+own, so that the call is the first one after the state it tests:
 
   (a) tables loaded, no tile prepared                      GCN10_E_STATE
   (b) tile prepared for W = 32, called with W = 48         GCN10_E_INVAL from gcn10_gpu_cn_strip (a bad argument
                                                            there), GCN10_E_STATE from the others
-  (c) cond_mask 0 and 4, table_mask 0 and 1 << 9           GCN10_E_INVAL (the five entries that take masks)
+  (c) cond_mask 0 and 4, table_mask 0 and 1 << 9           GCN10_E_INVAL (the six entries that take masks)
   (d) rows == 0 with null pointers                         success from cn_strip, verify_strip and deflate_fused_strip;
                                                            GCN10_E_INVAL from pair_histogram (it looks at its
                                                            pointers first; success with pointers) and from
-                                                           overview_average and aggregate (an empty strip is a bad
-                                                           strip there);
+                                                           overview_average, aggregate and grid_sums (an empty
+                                                           strip is a bad strip there);
                                                            zonal: n_items == 0 is success whatever else it is given,
                                                            even without a tile
   (e) after each of these, the same context runs the reader of tests/soil_readers.py for that entry point, whose
@@ -23,7 +24,8 @@ of its own, so that the call is the first one after the state it tests:
 
 The codes of the first six are those of the code before the preamble was shared
 (profiles/soil_view/preamble_on_parent.txt: this module run against that library); gcn10_gpu_aggregate came after
-it, and its codes are the ones tests/test_gpu_aggregate.py::test_errors pins.  Shapes: the smallest that reach every
+it, and its codes are the ones tests/test_gpu_aggregate.py::test_errors pins, as gcn10_gpu_grid_sums has those of
+tests/test_gpu_grid.py::test_errors.  Shapes: the smallest that reach every
 check -- a tile of 32 x 2 pixels over a 2 x 2 soil window, one strip of 2 rows.
 """
 import ctypes as C
@@ -40,10 +42,10 @@ OK, E_INVAL, E_STATE = 0, -1, -4
 W, H, HS = 32, 2, 2
 OTHER_W = 48
 SLOT = 256
-WITH_MASKS = ("strip", "verify", "overview", "fused", "aggregate")
+WITH_MASKS = ("strip", "verify", "overview", "fused", "aggregate", "grid")
 NAMES = {"strip": "gcn10_gpu_cn_strip", "verify": "gcn10_gpu_verify_strip", "histogram": "gcn10_gpu_pair_histogram",
          "zonal": "gcn10_gpu_zonal_pair_histogram", "overview": "gcn10_gpu_overview_average",
-         "fused": "gcn10_gpu_deflate_fused_strip", "aggregate": "gcn10_gpu_aggregate"}
+         "fused": "gcn10_gpu_deflate_fused_strip", "aggregate": "gcn10_gpu_aggregate", "grid": "gcn10_gpu_grid_sums"}
 
 
 @pytest.fixture
@@ -80,8 +82,10 @@ def call(reader, eng, tile, scratch, w=W, rows=H, cond=3, table=0x1FF, null=Fals
         return L.gcn10_gpu_overview_average(c, esa, w, rows, 0, rows, cj, cond, table, 1, ptrs, None)
     if reader == "fused":
         return L.gcn10_gpu_deflate_fused_strip(c, esa, w, rows, cj, cond, table, at(0), 16 * SLOT, at(17), at(18), None)
-    assert reader == "aggregate"      # cells of 2 x 2 px over all columns: one row of w / 2 cells in a slot
-    return L.gcn10_gpu_aggregate(c, esa, w, rows, cj, 0, w, 2, cond, table, ptrs, SLOT, None)
+    if reader == "aggregate":           # cells of 2 x 2 px over all columns: one row of w / 2 cells in a slot
+        return L.gcn10_gpu_aggregate(c, esa, w, rows, cj, 0, w, 2, cond, table, ptrs, SLOT, None)
+    assert reader == "grid"             # one cell (the maps are the scratch's zeros), its 18 pairs in slots 2 and 3
+    return L.gcn10_gpu_grid_sums(c, esa, w, rows, cj, at(0), at(1), 1, 1, cond, table, at(2), None)
 
 
 def refused(code, reader, rc, about=None):
@@ -149,7 +153,7 @@ def test_d_an_empty_strip(ctx, reader):
         else:
             tile.prepare()
             rc = call(reader, eng, tile, scratch, rows=0, null=True)
-            if reader in ("histogram", "overview", "aggregate"):
+            if reader in ("histogram", "overview", "aggregate", "grid"):
                 refused(E_INVAL, reader, rc)
             else:
                 assert rc == OK, gpu.lib().gcn10_gpu_last_error().decode()

@@ -1,16 +1,17 @@
 """GPU: every reader of the code bytes of a prepared tile -- the byte and vector strip kernels, the fused tile
-encoder, verify_strip, the pair histogram, the zonal pair histogram, the average overviews and the area means of
-gcn10_gpu_aggregate (seven readers, tests/soil_readers.READERS) -- held to the contract of gcn10_gpu_prepare_tile
-in include/gcn10_gpu.h, on the tiles A to I where that machinery can go wrong: column maps that are not monotone
+encoder, verify_strip, the pair histogram, the zonal pair histogram, the average overviews, the area means of
+gcn10_gpu_aggregate and the sums on a model grid of gcn10_gpu_grid_sums / _storms (eight readers,
+tests/soil_readers.READERS; the three-word gcn10_gpu_grid_sums_weighted in a test of its own) -- held to the contract
+of gcn10_gpu_prepare_tile in include/gcn10_gpu.h, on the tiles A to I where that machinery can go wrong: column maps that are not monotone
 or leave the window, one complex group, one soil column or row, cells narrower than a pixel, widths around the 16-px group, two tile rows, pointers at odd offsets, the caller's buffers overwritten after
 prepare_tile, and tile after tile on one context.  On every tile every reader is the first call after a
 prepare_tile of its own, so it is the one that makes the bytes (or, where the width is no multiple of 16, waits
 for the ones prepare_tile made).  Needs an MI355X.
 
 Expected values: the oracle's calculate_cn / modify_hysogs_data over coarse[cj][:, clamp_columns(ci, hsx)] by plain
-numpy indexing, numpy pair counts, the numpy model of the average overviews and the numpy reduction of the oracle's
-rasters to cells (tests/soil_readers.py, whose references tests/test_soil_reader_references.py checks on the CPU) --
-never another GPU path.
+numpy indexing, numpy pair counts, the numpy model of the average overviews, the numpy reduction of the oracle's
+rasters to cells and their int64 sums over the maps of a model grid (tests/soil_readers.py, whose references
+tests/test_soil_reader_references.py checks on the CPU) -- never another GPU path.
 """
 import numpy as np
 import pytest
@@ -75,6 +76,27 @@ def test_g_pointers_as_the_abi_allows_them(eng9, tables, reader, name):
         aligned.close()
         if shifted is not None:
             shifted.close()
+
+
+@pytest.mark.parametrize("name", TILES_A_TO_F + TILES_G)
+def test_the_weighted_grid_sums_on_tiles_a_to_g(eng9, tables, name):
+    """gcn10_gpu_grid_sums_weighted, the kernel of three words per cell: a context holds one weight table or several,
+    so it cannot be one of READERS beside the k = 2 of the grid reader.  set_weights("random"), then the `rows` pass as
+    the first call after prepare_tile, exact against the oracle's rasters summed with one table.  G: the pointers of
+    case G, after an aligned tile of other soil as there."""
+    aligned = _other_soil(eng9, tables, name) if name in TILES_G else None
+    t = None
+    try:
+        if aligned is not None:
+            aligned.prepare()
+        t = make_tile(eng9, tables, name, offsets=sr.SHIFTED if name in TILES_G else None)
+        t.prepare()
+        run_reader(t, sr.WeightedGridReader)
+    finally:
+        eng9.sync()
+        for tile in (aligned, t):
+            if tile is not None:
+                tile.close()
 
 
 @pytest.mark.parametrize("name,state", [("G-2048", 1), ("A-decreasing", 1), ("B-runs", 1), ("A-zig-zag", 2),
@@ -172,11 +194,11 @@ def test_two_readers_on_two_streams(eng9, tables, delay, first, second, W):
     and `second` waits on the context's event for them; W = 2051: prepare_tile made them and both wait.
 
     Truly concurrent -- both launches are queued before either is awaited -- are the pairs whose FIRST reader is
-    strip, verify, histogram, zonal, overview or aggregate (cn_strip, verify_strip, pair_histogram,
-    zonal_pair_histogram_device, overview_average and aggregate return at once); with fused second, its kernels are
-    queued behind the event while the first reader may still run.  Only ordered are the seven pairs whose first reader
-    is fused: deflate_fused downloads its streams and frees its arena, so stream 1 is idle when `second` is launched --
-    those pairs show that a reader on another stream finds the bytes, not that it waits for them.
+    strip, verify, histogram, zonal, overview, aggregate or grid (cn_strip, verify_strip, pair_histogram,
+    zonal_pair_histogram_device, overview_average, aggregate and grid_sums / grid_sums_storms return at once); with
+    fused second, its kernels are queued behind the event while the first reader may still run.  Only ordered are the
+    eight pairs whose first reader is fused: deflate_fused downloads its streams and frees its arena, so stream 1 is
+    idle when `second` is launched -- those pairs show that a reader on another stream finds the bytes, not that it waits for them.
 
     Stream 1 first copies 256 MiB, so that `second` is queued on an idle stream 2 before `first` has made the
     bytes, and every pair has soil of its own, so that the bytes the test before left behind are wrong ones."""

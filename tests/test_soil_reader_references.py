@@ -103,6 +103,35 @@ def test_the_spans_and_strips_of_the_readers_have_the_shapes_the_cases_name(name
         assert passes[2]["x0"] % 16 != 0 and passes[2]["x1"] % 16 != 0
         assert passes[2]["x0"] == 1 and W - 2 <= passes[2]["x1"] <= W - 1
 
+    # the passes of the grid reader
+    rows, storms = sr.grid_passes(W, H, cj.astype(np.int32))
+    assert (rows["name"], storms["name"]) == ("rows", "storms") and (rows["words"], storms["words"]) == (2, 4)
+    for p in (rows, storms):
+        assert p["cellx"].dtype == p["celly"].dtype == np.int32 and p["cellx"].shape == (W,) and p["celly"].shape == (H,)
+        assert p["cellx"].max() == p["ncx"] - 1 and p["celly"].max() == p["ncy"] - 1
+        for m in (p["cellx"], p["celly"]):          # the cells of a map never go back, and a cell column is >= 8 px or
+            inside = m[m >= 0]                      # cut by the tile's edge: the kernel's three-masks rule
+            assert (np.diff(inside) >= 0).all() and set(inside.tolist()) == set(range(int(m.max()) + 1))
+        widths = np.bincount(p["cellx"][p["cellx"] >= 0])
+        assert (widths[1:-1] >= 8).all()
+        assert sum(n for _, n in p["strips"]) == H and p["strips"][0][0] == 0
+    assert (rows["cellx"] >= 0).all() and (rows["celly"] >= 0).all()                    # no -1 entry
+    assert np.bincount(rows["cellx"]).max() <= 8 and np.bincount(rows["celly"]).max() == 1
+    assert rows["strips"] == [(0, H)] and len(rows["sel"]) == 18 and rows["call"] == "grid_sums"
+    (lx, ly), (tx, ty) = sr.grid_edges(W, H)
+    assert (lx, tx) == ((5, 3) if W >= 32 else (0, 0)) and (ly, ty) == ((3, 2) if H >= 8 else (0, 0))
+    for m, lead, trail in ((storms["cellx"], lx, tx), (storms["celly"], ly, ty)):
+        assert np.flatnonzero(m < 0).tolist() == list(range(lead)) + list(range(len(m) - trail, len(m)))
+    if W >= 32:                                      # the leading -1 run ends inside a 16-px group
+        assert (storms["cellx"][:16] < 0).any() and (storms["cellx"][:16] >= 0).any()
+    assert storms["strips"] == strips and storms["call"] == "grid_sums_storms" and len(storms["ws"]) == 2
+    y0 = storms["strips"][1][0]
+    assert cj[y0] == cj[y0 - 1] and storms["celly"][y0] == storms["celly"][y0 - 1] >= 0    # inside a soil and a cell row
+    assert 0 < len(storms["sel"]) < 18
+    weighted = sr.weighted_rows_pass(W, H, cj.astype(np.int32))
+    assert weighted["words"] == 3 and len(weighted["ws"]) == 1 and weighted["call"] == "grid_sums_weighted"
+    assert np.array_equal(weighted["cellx"], rows["cellx"]) and weighted["strips"] == rows["strips"]
+
 
 # ---- the reference of the aggregate reader ---------------------------------------------------------------------------
 
@@ -292,6 +321,134 @@ def test_every_soil_row_is_observable_by_the_row_walk(tables, name):
     judged, unseen = rows_unseen(t, p, rasters_of(t, t.soil))
     assert unseen == []
     assert judged >= t.H // 2       # (a tile on ONE soil column, A-constant, has soil rows of the same class)
+
+
+# ---- the reference of the grid reader --------------------------------------------------------------------------------
+
+def words_by_hand(p, rasters):
+    """The words of a pass in Python integers, strip by strip and cell by cell: {s, n, sum of every table's weight} over
+    the values != 255 of the cell's pixels."""
+    cellx, celly, ws = p["cellx"].tolist(), p["celly"].tolist(), [w.tolist() for w in p["ws"]]
+    columns = [[x for x in range(len(cellx)) if cellx[x] == cx] for cx in range(p["ncx"])]
+    out = []
+    for r in p["sel"]:
+        v = np.asarray(rasters[r]).tolist()
+        acc = [[[0] * p["words"] for _cx in range(p["ncx"])] for _cy in range(p["ncy"])]
+        for y0, rows in p["strips"]:
+            for cy in range(p["ncy"]):
+                ys = [y for y in range(y0, y0 + rows) if celly[y] == cy]
+                for cx in range(p["ncx"] if ys else 0):
+                    cell = acc[cy][cx]
+                    for x in columns[cx]:
+                        for y in ys:
+                            value = v[y][x]
+                            if value != 255:
+                                cell[0] += value
+                                cell[1] += 1
+                                for j, w in enumerate(ws):
+                                    cell[2 + j] += w[value]
+        out.append(acc)
+    return out
+
+
+@pytest.mark.parametrize("name", [k for k in sr.SPECS if k[0] == "E"])
+def test_the_strip_wise_sums_equal_a_loop_over_cells(tables, name):
+    t = sr.host_tile(tables, name)
+    for p in sr.grid_passes(t.W, t.H, t.cj)[1:] + [sr.weighted_rows_pass(t.W, t.H, t.cj)]:
+        rasters = {r: t.want(r) for r in (p["sel"] if p["name"] == "storms" else p["sel"][:1])}
+        p = dict(p, sel=list(rasters))
+        got = sr.grid_words(p, rasters)
+        assert got.dtype == np.int64 and got.shape == (len(rasters), p["ncy"], p["ncx"], p["words"])
+        assert got.tolist() == words_by_hand(p, rasters), p["name"]
+        assert (got[..., 2:].reshape(-1, len(p["ws"])).max(axis=0) > 0).all()      # every table weighs something here
+
+
+def pixel_words(raster, ws):
+    """int64[H][W][2 + k]: what every pixel adds to the words of its cell."""
+    v = np.asarray(raster).astype(np.int64)
+    ok = v != 255
+    return np.stack([np.where(ok, v, 0), ok.astype(np.int64)] + [np.where(ok, w.astype(np.int64)[v], 0) for w in ws],
+                    axis=-1)
+
+
+def lines_seen(p, want, other, axis):
+    """bool[W] (axis 1) or bool[H] (axis 0): the columns or rows whose pixels, taken from `other` ALONE, change a word
+    the pass expects.  The words are sums over pixels, so per cell the change is the sum, over the line's pixels in that
+    cell, of what each adds in `other` less what it adds in `want`; a strip only cuts these sums in two."""
+    cellx, celly = p["cellx"].astype(np.int64), p["celly"].astype(np.int64)
+    ys, xs = np.flatnonzero(celly >= 0), np.flatnonzero(cellx >= 0)
+    seen = np.zeros(len(cellx) if axis else len(celly), bool)
+    for r in p["sel"]:
+        delta = pixel_words(other[r], p["ws"]) - pixel_words(want[r], p["ws"])
+        if axis:            # a column: one change per cell row
+            change = np.zeros((p["ncy"],) + delta.shape[1:], np.int64)
+            np.add.at(change, celly[ys], delta[ys])
+            seen[xs] |= (change != 0).any(axis=(0, 2))[xs]
+        else:               # a row: one change per cell column
+            change = np.zeros((p["ncx"], delta.shape[0], delta.shape[2]), np.int64)
+            np.add.at(change, cellx[xs], delta[:, xs].transpose(1, 0, 2))
+            seen[ys] |= (change != 0).any(axis=(0, 2))[ys]
+    return seen
+
+
+def other_soils(t):
+    """(soil with every column on another class, soil with every row on another class): the neighbouring soil cell's
+    and the next soil row's, or, where the window has one column or one row, each of the four classes in turn."""
+    cols = [neighbour_soil(t)] if t.hsx > 1 else [np.full_like(t.soil, hsg) for hsg in (1, 2, 3, 4)]
+    rows = [t.coarse[(t.cj + 1) % t.hsy][:, sr.clamp_columns(t.ci, t.hsx)]] if t.hsy > 1 else \
+        [np.full_like(t.soil, hsg) for hsg in (1, 2, 3, 4)]
+    return cols, rows
+
+
+@pytest.mark.parametrize("name", list(sr.SPECS))
+def test_every_soil_column_and_row_is_observable_by_the_grid_passes(tables, name):
+    """The sums are exact, but a cell adds up many pixels.  One soil column on another class changes words of the `rows`
+    pass wherever it changes a full-resolution raster, and one strip row on another soil row's soil changes words of
+    the `storms` pass wherever it changes a raster the pass selects in a column it reads."""
+    t = sr.host_tile(tables, name)
+    want = rasters_of(t, t.soil)
+    rows, storms = sr.grid_passes(t.W, t.H, t.cj)
+    cols_soil, rows_soil = other_soils(t)
+    judged = 0
+    for soil in cols_soil:
+        other = rasters_of(t, soil)
+        differ = columns_that_differ(want, other)
+        assert np.flatnonzero(differ & ~lines_seen(rows, want, other, 1)).tolist() == [], "rows pass"
+        judged = max(judged, int(differ.sum()))
+    assert judged >= t.W // 2, "hardly a column of this tile would show its soil at full resolution"
+    judged = 0
+    xs = storms["cellx"] >= 0
+    for soil in rows_soil:
+        other = rasters_of(t, soil)
+        differ = np.any([(want[r][:, xs] != other[r][:, xs]).any(axis=1) for r in storms["sel"]], axis=0)
+        differ &= storms["celly"] >= 0
+        assert np.flatnonzero(differ & ~lines_seen(storms, want, other, 0)).tolist() == [], "storms pass"
+        judged = max(judged, int(differ.sum()))
+    assert judged >= (t.H - 5) // 2     # (a tile on ONE soil column, A-constant, has soil rows of the same class)
+
+
+@pytest.mark.parametrize("name,columns,rows", [("E-5", range(5), range(3)), ("E-17", range(17), range(3)),
+                                               ("A-zig-zag", (0, 4, 5, 1039, 2044, 2047), (0, 2, 3, 20, 37, 38))])
+def test_the_per_line_change_equals_the_sums_of_the_swapped_tile(tables, name, columns, rows):
+    """lines_seen against the statement it abbreviates: the oracle over the soil with ONE column or row swapped, summed
+    by the reader's own reference."""
+    t = sr.host_tile(tables, name)
+    want = rasters_of(t, t.soil)
+    cols_soil, rows_soil = other_soils(t)
+    for axis, soil2, lines in ((1, cols_soil[0], columns), (0, rows_soil[0], rows)):
+        other = rasters_of(t, soil2)
+        passes = sr.grid_passes(t.W, t.H, t.cj)
+        seen, words = [lines_seen(p, want, other, axis) for p in passes], [sr.grid_words(p, want) for p in passes]
+        for i in lines:
+            soil = t.soil.copy()
+            if axis:
+                soil[:, i] = soil2[:, i]
+            else:
+                soil[i] = soil2[i]
+            swapped = rasters_of(t, soil)
+            for p, s, w in zip(passes, seen, words):
+                assert (sr.grid_words(p, swapped) != w).any() == bool(s[i]), (p["name"], axis, i)
+
 
 def test_the_tiles_of_case_i_differ_in_more_than_half_of_their_soil():
     soils = sr.case_i_soils()

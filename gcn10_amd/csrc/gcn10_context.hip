@@ -207,6 +207,8 @@ void gcn10_gpu_destroy(gcn10_gpu_ctx *ctx)
         (void)hipFree(ctx->d_lut1);
     if (ctx->d_wlut)
         (void)hipFree(ctx->d_wlut);
+    if (ctx->d_rain_tables)
+        (void)hipFree(ctx->d_rain_tables);
     if (ctx->tile.d_hx_alloc)
         (void)hipFree(ctx->tile.d_hx_alloc);
     if (ctx->tile.d_soil_complex)

@@ -82,6 +82,10 @@ struct gcn10_gpu_ctx {
     int n_weights = 0;              // tables of weights: 1 (gcn10_gpu_set_weights) to GCN10_GPU_MAX_WEIGHT_TABLES
     uint32_t weights_rising = 0;    // bit j: w_j[1..100] never decrease
 
+    // ---- the tables of the rain sums (gcn10_grid_rain.hip: gcn10_gpu_set_rain_tables) ----
+    uint16_t *d_rain_tables = nullptr;  // n_rain_tables tables w[256], then a byte per table: w[1..100] never decrease
+    int n_rain_tables = 0;              // 0: not set
+
     // ---- the prepared tile (gcn10_soil_tile.hip) ----
     struct Tile {
         // Soil workspace of the prepared tile (one allocation, grown by gcn10_gpu_prepare_tile):

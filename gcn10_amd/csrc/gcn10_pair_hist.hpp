@@ -76,6 +76,27 @@ __device__ __forceinline__ void count16(uint32_t *h, const u32x4 &e, const u32x4
     }
 }
 
+// pixels [a, b) of a lane's 16 (a span end of gcn10_zonal.hip, a cell edge of gcn10_grid_rain.hip): the run folding of
+// count16 over the unmasked ones
+__device__ __forceinline__ void count_masked(uint32_t *h, const u32x4 &e, const u32x4 &s, uint32_t a, uint32_t b)
+{
+    uint32_t cur = 0u, n = 0u;
+#pragma unroll
+    for (uint32_t i = 0; i < kPxPerLane; i++) {
+        if (i >= a && i < b) {
+            const uint32_t k = pair_key(e, s, i);
+            if (n && k != cur) {
+                add_run(h, cur, n);
+                n = 0u;
+            }
+            cur = k;
+            n++;
+        }
+    }
+    if (n)
+        add_run(h, cur, n);
+}
+
 // the row's last pixels (W not a multiple of 16): byte loads, nothing past the row end
 __device__ __forceinline__ void count_tail(uint32_t *h, const uint8_t *erow, const uint8_t *srow, uint32_t m)
 {

@@ -41,26 +41,6 @@ struct ZonalParams {
     uint32_t W, n_items, items_per_wg;
 };
 
-// pixels [a, b) of a lane's 16: the run folding of count16 over the unmasked ones
-__device__ __forceinline__ void count_masked(uint32_t *h, const u32x4 &e, const u32x4 &s, uint32_t a, uint32_t b)
-{
-    uint32_t cur = 0u, n = 0u;
-#pragma unroll
-    for (uint32_t i = 0; i < kPxPerLane; i++) {
-        if (i >= a && i < b) {
-            const uint32_t k = pair_key(e, s, i);
-            if (n && k != cur) {
-                add_run(h, cur, n);
-                n = 0u;
-            }
-            cur = k;
-            n++;
-        }
-    }
-    if (n)
-        add_run(h, cur, n);
-}
-
 // the workgroup's histogram to the zone's, nonzero bins only, and cleared for the next zone
 __device__ __forceinline__ void flush_zone(uint32_t *h, unsigned long long *dst)
 {

@@ -109,6 +109,10 @@ static void load_once(void)
     *(void **)(&g_api.set_weight_tables) = dlsym(h, "gcn10_gpu_set_weight_tables");
     *(void **)(&g_api.grid_sums_storms) = dlsym(h, "gcn10_gpu_grid_sums_storms");
     *(void **)(&g_api.grid_finish_storms) = dlsym(h, "gcn10_gpu_grid_finish_storms");
+    /* and those with a weight table per cell: needed by rain=... runs only, which check for them */
+    *(void **)(&g_api.set_rain_tables) = dlsym(h, "gcn10_gpu_set_rain_tables");
+    *(void **)(&g_api.grid_sums_rain) = dlsym(h, "gcn10_gpu_grid_sums_rain");
+    *(void **)(&g_api.grid_finish_rain) = dlsym(h, "gcn10_gpu_grid_finish_rain");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

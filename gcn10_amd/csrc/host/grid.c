@@ -23,6 +23,12 @@
  * key "storms") the sums are 2 + K words, word 2 + k the sum of storm k's table: one set of tables per context
  * (gcn10_gpu_set_weight_tables), the _storms pair of calls, K runoff-equivalent bytes per cell, and one
  * cnq_<hc>_<arc>_p<N_k>.tif per storm beside the mean.
+ *
+ * With a rainfall raster (config key "rain") the storm differs from cell to cell: the run holds the raster's nx x ny
+ * counts and the 256 runoff tables of gcn10_rain_tables, the worker hands the tables to its context once
+ * (gcn10_gpu_set_rain_tables), uploads the counts of the block's cell rectangle beside the maps and runs the _rain pair
+ * of calls; triples as with one storm, the shared cells finished with the table of the cell's own count, and
+ * cnq_<hc>_<arc>_rain.tif beside every mean.
  */
 #include "pipeline_internal.h"
 
@@ -232,6 +238,49 @@ NO_CONTRACT int gcn10_grid_plan_block(const gcn10_grid *g, int W, int H, const d
 }
 
 /* ---------------------------------------------------------------------------------------------------------------- */
+/* the rainfall raster                                                                                               */
+/* ---------------------------------------------------------------------------------------------------------------- */
+
+int gcn10_rain_load(const char *path, const gcn10_grid *g, uint8_t **out, char *err, size_t errcap)
+{
+    char why[1024] = "";
+    gcn10_raster *ra = gcn10_raster_open(path, NULL, why, sizeof why);
+    const double none[6] = { 0.0, 1.0, 0.0, 0.0, 0.0, 1.0 };       /* what the reader reports without georeferencing */
+    double gt[6];
+    uint8_t *bytes;
+    int w, h;
+
+    *out = NULL;
+    if (!ra) {
+        snprintf(err, errcap, "rain: cannot read '%s': %s", path, why);
+        return GCN10_RAIN_E_READ;
+    }
+    gcn10_raster_info(ra, &w, &h, gt);
+    if (w != g->nx || h != g->ny) {
+        snprintf(err, errcap, "rain: '%s' has %d x %d pixels, the grid has %d x %d cells", path, w, h, g->nx, g->ny);
+        gcn10_raster_close(ra);
+        return GCN10_RAIN_E_SIZE;
+    }
+    if (memcmp(gt, none, sizeof none) != 0 &&
+        !(gt[0] == g->xmin && gt[3] == g->ymax && gt[1] == g->dx && gt[5] == -g->dy && gt[2] == 0.0 && gt[4] == 0.0)) {
+        snprintf(err, errcap, "rain: '%s' does not lie on the grid (origin %.17g, %.17g, pixel %.17g x %.17g)", path,
+                 gt[0], gt[3], gt[1], gt[5]);
+        gcn10_raster_close(ra);
+        return GCN10_RAIN_E_GEOTRANSFORM;
+    }
+    bytes = malloc((size_t)w * (size_t)h);
+    if (!bytes || gcn10_raster_read(ra, 0, 0, w, h, bytes, why, sizeof why) != 0) {
+        snprintf(err, errcap, "rain: cannot read '%s': %s", path, bytes ? why : "out of memory");
+        free(bytes);
+        gcn10_raster_close(ra);
+        return GCN10_RAIN_E_READ;
+    }
+    gcn10_raster_close(ra);
+    *out = bytes;
+    return 0;
+}
+
+/* ---------------------------------------------------------------------------------------------------------------- */
 /* the run                                                                                                           */
 /* ---------------------------------------------------------------------------------------------------------------- */
 
@@ -240,11 +289,12 @@ NO_CONTRACT int gcn10_grid_plan_block(const gcn10_grid *g, int W, int H, const d
 struct gcn10_grid_result {
     pthread_mutex_t mu;
     uint8_t *raster;            /* [n_sel][ny][nx] */
-    uint8_t *cnq;               /* [n_storms][n_sel][ny][nx], runoff-equivalent (storm only) */
+    uint8_t *cnq;               /* [n_cnq][n_sel][ny][nx], runoff-equivalent (storm and rain only) */
     uint32_t *key;              /* [cap]; NO_KEY: free */
     uint64_t *pair;             /* [cap][n_sel][words] = {s, n} or, with storms, {s, n, sw of every storm} */
     size_t cap, used;
     int n_sel, words;
+    int n_cnq;                  /* runoff-equivalent rasters per selected raster: one per storm, one with rain */
     int blocks;                 /* blocks summed */
     gcn10_raster *esa;          /* the landcover, for its pixel size and its geo tags */
 };
@@ -255,7 +305,7 @@ struct gcn10_grid_state {
     unsigned long long *d_acc, *d_shared, *h_shared;
     uint8_t *d_means, *h_means;             /* the means, and with a storm the runoff-equivalent bytes behind them */
     size_t h_up_cap, d_up_cap, d_acc_cap, d_shared_cap, h_shared_cap, d_means_cap, h_means_cap;
-    bool weights_set;                       /* the context has the storm's runoff table */
+    bool weights_set;                       /* the context has the storm's runoff table, or the 256 of the rain */
 };
 
 static size_t slot_of(const struct gcn10_grid_result *t, uint32_t key)
@@ -321,6 +371,10 @@ static void grid_end(struct run *r)
     free(t->key);
     free(t->pair);
     free(t);
+    free(r->rain);
+    free(r->rain_q);
+    r->rain = NULL;
+    r->rain_q = NULL;
     r->grid_result = NULL;
 }
 
@@ -362,7 +416,22 @@ int gcn10_grid_start(struct run *r)
     r->grid_result = t;
     pthread_mutex_init(&t->mu, NULL);
     t->n_sel = r->n_sel > 0 ? r->n_sel : 1;
-    t->words = 2 + (r->storm_on ? r->n_storms : 0);
+    t->n_cnq = r->storm_on ? r->n_storms : (r->rain_on ? 1 : 0);
+    t->words = 2 + t->n_cnq;
+    if (r->rain_on) {           /* the raster on this grid, and the table of every count */
+        if (gcn10_rain_load(r->cfg.rain, &r->grid, &r->rain, err, sizeof err) != 0) {
+            fprintf(stderr, "[rank 0] %s\n", err);
+            grid_end(r);
+            return -1;
+        }
+        r->rain_q = malloc(256 * sizeof *r->rain_q);
+        if (!r->rain_q) {
+            fprintf(stderr, "[rank 0] out of memory for the tables of the rainfall raster\n");
+            grid_end(r);
+            return -1;
+        }
+        gcn10_rain_tables(r->rain_unit, r->rain_lambda, r->rain_q);
+    }
     /* the landcover's pixel size: below 8 pixels per cell the 10 m raster is the product (and a 16-pixel column group
      * of the kernel would meet more than three cell columns).  A landcover that does not open is the workers' to
      * report, block by block, as in every run. */
@@ -381,17 +450,16 @@ int gcn10_grid_start(struct run *r)
     }
     bytes = (size_t)t->n_sel * (size_t)r->grid.nx * (size_t)r->grid.ny;
     t->raster = malloc(bytes);
-    if (r->storm_on)
-        t->cnq = malloc((size_t)r->n_storms * bytes);
-    if (!t->raster || (r->storm_on && !t->cnq) || table_reserve(t, 0) != 0) {
-        fprintf(stderr, "[rank 0] out of memory for the grid rasters (%zu bytes)\n",
-                r->storm_on ? (size_t)(1 + r->n_storms) * bytes : bytes);
+    if (t->n_cnq)
+        t->cnq = malloc((size_t)t->n_cnq * bytes);
+    if (!t->raster || (t->n_cnq && !t->cnq) || table_reserve(t, 0) != 0) {
+        fprintf(stderr, "[rank 0] out of memory for the grid rasters (%zu bytes)\n", (size_t)(1 + t->n_cnq) * bytes);
         grid_end(r);
         return -1;
     }
     memset(t->raster, GCN10_NODATA, bytes);
     if (t->cnq)
-        memset(t->cnq, GCN10_NODATA, (size_t)r->n_storms * bytes);
+        memset(t->cnq, GCN10_NODATA, (size_t)t->n_cnq * bytes);
     return 0;
 }
 
@@ -493,13 +561,15 @@ static int grid_block(struct worker *w, struct block_in *in)
     const int ncx = p->cx1 - p->cx0, ncy = p->cy1 - p->cy0;
     const size_t n_cells = (size_t)ncx * (size_t)ncy, n_sel = (size_t)r->n_sel;
     const size_t maps = ((size_t)in->W + (size_t)in->H) * sizeof(int32_t);
-    const size_t up = maps + p->n_shared * sizeof(uint32_t);
-    const bool storm = r->storm_on, ladder = r->storms_key;
-    const size_t n_storms = storm ? (size_t)r->n_storms : 0;
+    const bool storm = r->storm_on, ladder = r->storms_key, rain = r->rain_on;
+    /* behind the maps and the shared indices, with rain: the counts of the block's cell rectangle */
+    const size_t up = maps + p->n_shared * sizeof(uint32_t) + (rain ? n_cells : 0);
+    const size_t n_storms = storm ? (size_t)r->n_storms : (rain ? 1 : 0);
     const size_t words = 2 + n_storms, bytes = (1 + n_storms) * n_sel * n_cells;    /* per cell: sums, and bytes back */
     struct gcn10_grid_state *s;
     int32_t *d_cellx, *d_celly;
     uint32_t *d_idx;
+    uint8_t *d_rain;
 
     if (!w->gridst && !(w->gridst = calloc(1, sizeof *w->gridst))) {
         wlog(w, "ERROR", true, "out of memory for the grid buffers");
@@ -539,6 +609,11 @@ static int grid_block(struct worker *w, struct block_in *in)
             goto gpu_fail;
         s->weights_set = true;
     }
+    if (rain && !s->weights_set) {
+        if (g->set_rain_tables(w->ctx, r->rain_q[0], 256) != 0)
+            goto gpu_fail;
+        s->weights_set = true;
+    }
     memcpy(s->h_up, p->cellx, (size_t)in->W * sizeof(int32_t));
     memcpy((char *)s->h_up + (size_t)in->W * sizeof(int32_t), p->celly, (size_t)in->H * sizeof(int32_t));
     if (p->n_shared)
@@ -546,13 +621,23 @@ static int grid_block(struct worker *w, struct block_in *in)
     d_cellx = s->d_up;
     d_celly = d_cellx + in->W;
     d_idx = (uint32_t *)((char *)s->d_up + maps);
+    d_rain = (uint8_t *)s->d_up + maps + p->n_shared * sizeof(uint32_t);
+    for (int cy = 0; rain && cy < ncy; cy++)
+        memcpy((uint8_t *)s->h_up + maps + p->n_shared * sizeof(uint32_t) + (size_t)cy * (size_t)ncx,
+               r->rain + (size_t)(p->cy0 + cy) * (size_t)r->grid.nx + (size_t)p->cx0, (size_t)ncx);
     if (g->memcpy_h2d(w->ctx, s->d_up, s->h_up, up, w->s_kernel) != 0 ||
         g->memset(w->ctx, s->d_acc, 0, n_sel * n_cells * words * sizeof *s->d_acc, w->s_kernel) != 0 ||
         g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, in->W, w->s_kernel) != 0 ||
-        (ladder ? g->grid_sums_storms : storm ? g->grid_sums_weighted : g->grid_sums)(
-            w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0, in->d_cj + p->y0, d_cellx,
-            d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask, s->d_acc, w->s_kernel) != 0 ||
-        (storm ? (ladder ? g->grid_finish_storms : g->grid_finish_weighted)(
+        (rain ? g->grid_sums_rain(w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0,
+                                  in->d_cj + p->y0, d_cellx, d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask,
+                                  d_rain, s->d_acc, w->s_kernel)
+              : (ladder ? g->grid_sums_storms : storm ? g->grid_sums_weighted : g->grid_sums)(
+                    w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0, in->d_cj + p->y0, d_cellx,
+                    d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask, s->d_acc, w->s_kernel)) != 0 ||
+        (rain ? g->grid_finish_rain(w->ctx, s->d_acc, r->n_sel, n_cells, d_rain, s->d_means,
+                                    s->d_means + n_sel * n_cells, p->n_shared ? d_idx : NULL, (uint32_t)p->n_shared,
+                                    p->n_shared ? s->d_shared : NULL, w->s_kernel) :
+         storm ? (ladder ? g->grid_finish_storms : g->grid_finish_weighted)(
                      w->ctx, s->d_acc, r->n_sel, n_cells, s->d_means, s->d_means + n_sel * n_cells,
                      p->n_shared ? d_idx : NULL, (uint32_t)p->n_shared, p->n_shared ? s->d_shared : NULL, w->s_kernel)
                : g->grid_finish(w->ctx, s->d_acc, r->n_sel, n_cells, s->d_means, p->n_shared ? d_idx : NULL,
@@ -568,7 +653,8 @@ static int grid_block(struct worker *w, struct block_in *in)
             goto gpu_fail;
         w->t_gpu_wait += gcn10_now_seconds() - t0;
     }
-    if (merge_block(r, p, s->h_means, storm ? s->h_means + n_sel * n_cells : NULL, (const uint64_t *)s->h_shared) != 0) {
+    if (merge_block(r, p, s->h_means, storm || rain ? s->h_means + n_sel * n_cells : NULL,
+                    (const uint64_t *)s->h_shared) != 0) {
         wlog(w, "ERROR", true, "out of memory for the shared cells of block %d", in->block_id);
         return -1;
     }
@@ -625,7 +711,7 @@ static int grid_finish(struct run *r, gcn10_log *log0)
     struct gcn10_grid_result *t = r->grid_result;
     const gcn10_grid *gr = &r->grid;
     const size_t plane = (size_t)gr->nx * (size_t)gr->ny, words = (size_t)t->words, width = (size_t)t->n_sel * words;
-    const int n_storms = r->storm_on ? r->n_storms : 0;
+    const int n_storms = t->n_cnq;
     const int per = 1 + n_storms, n_files = per * r->n_sel;             /* files per selected raster, and of the run */
     const double gt[6] = { gr->xmin, gr->dx, 0.0, gr->ymax, 0.0, -gr->dy };
     const int down = (gr->ny + TILE - 1) / TILE;
@@ -646,7 +732,8 @@ static int grid_finish(struct run *r, gcn10_log *log0)
                 t->raster[(size_t)q * plane + t->key[i]] = mean_of(v[0], v[1]);
                 for (int k = 0; k < n_storms; k++)
                     t->cnq[((size_t)k * (size_t)r->n_sel + (size_t)q) * plane + t->key[i]] =
-                        (uint8_t)gcn10_runoff_cn(v[0], v[1], v[2 + k], r->runoff_q[k]);
+                        (uint8_t)gcn10_runoff_cn(v[0], v[1], v[2 + k],
+                                                 r->rain_on ? r->rain_q[r->rain[t->key[i]]] : r->runoff_q[k]);
             }
     for (size_t c = 0; c < plane; c++) {
         int q = 0;
@@ -680,6 +767,9 @@ static int grid_finish(struct run *r, gcn10_log *log0)
 
         if (fi % per == 0)
             snprintf(path, sizeof path, "cn_grid_%s/cn_%s_%s.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
+                     gcn10_arcs[k % 3]);
+        else if (r->rain_on)
+            snprintf(path, sizeof path, "cn_grid_%s/cnq_%s_%s_rain.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
                      gcn10_arcs[k % 3]);
         else
             snprintf(path, sizeof path, "cn_grid_%s/cnq_%s_%s_p%u.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
@@ -740,6 +830,10 @@ static int grid_finish(struct run *r, gcn10_log *log0)
                  "cn_grid_<cond>/: cn_<hc>_<arc>.tif (mean) and %s (runoff-equivalent)", t->blocks,
                  r->n_sel, gr->nx, gr->ny, empty, names);
     }
+    else if (r->rain_on)
+        snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
+                 "cn_grid_<cond>/: cn_<hc>_<arc>.tif (mean) and cnq_<hc>_<arc>_rain.tif (runoff-equivalent)", t->blocks,
+                 r->n_sel, gr->nx, gr->ny, empty);
     else
         snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
                  "cn_grid_<cond>/", t->blocks, r->n_sel, gr->nx, gr->ny, empty);

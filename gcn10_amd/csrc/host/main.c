@@ -28,7 +28,7 @@ static void usage(FILE *fp)
             "        [--cog] [--overview-resampling nearest|average] [--stats] [--nodata none|<0..255>]\n"
             "        [--verify] [--zonal] [--zones <zones.shp>] [--aggregate <f>]\n"
             "        [--grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>] [--storm <P>[,<lambda>]]\n"
-            "        [--storms <P1>[:<P2>...][,<lambda>]]\n"
+            "        [--storms <P1>[:<P2>...][,<lambda>]] [--rain <file> [--rain-unit <unit>[,<lambda>]]]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -72,6 +72,14 @@ static void usage(FILE *fp)
             "\t\t\tfile --storm <P_k>,<lambda> alone writes; with --zones, the columns runoff_mm_p<100 P_k>,\n"
             "\t\t\tcn_runoff_p<100 P_k> per storm (one depth: exactly what --storm gives; config key\n"
             "\t\t\tstorms=...); not with --storm, otherwise as --storm\n"
+            "  --rain <file>\t\ta rainfall raster on the model grid: a one-band Byte GeoTIFF of nx x ny pixels, a cell\n"
+            "\t\t\twith byte b has P = b x unit mm of rain (every byte is a depth, 0 = no rain).  With --grid,\n"
+            "\t\t\tcn_grid_<cond>/cnq_<hc>_<arc>_rain.tif beside every mean: the runoff-equivalent CN of every\n"
+            "\t\t\tcell for the cell's own depth, summed on the GPU (config key rain=...); needs --grid, not\n"
+            "\t\t\twith --storm, --storms, --zonal, --aggregate or --verify\n"
+            "  --rain-unit <unit>[,<lambda>]\n"
+            "\t\t\tmillimetres per count of --rain (0 < unit, 255 unit <= 650, default 1) and the\n"
+            "\t\t\tinitial-abstraction ratio (0 <= lambda < 1, default 0.2; config key rain_unit=...)\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -130,6 +138,10 @@ int main(int argc, char **argv)
             opt.storm = argv[++i];
         else if (!strcmp(argv[i], "--storms") && i + 1 < argc)
             opt.storms = argv[++i];
+        else if (!strcmp(argv[i], "--rain") && i + 1 < argc)
+            opt.rain = argv[++i];
+        else if (!strcmp(argv[i], "--rain-unit") && i + 1 < argc)
+            opt.rain_unit = argv[++i];
         else if (!strcmp(argv[i], "--zonal"))
             opt.zonal = true;
         else if (!strcmp(argv[i], "--zones") && i + 1 < argc) {

@@ -281,6 +281,11 @@ struct run {
     int n_storms;                           /* how many: 1 with "storm", 1 to GCN10_MAX_STORMS with "storms" */
     double storm_p[GCN10_MAX_STORMS], storm_lambda;
     uint16_t runoff_q[GCN10_MAX_STORMS][256];       /* gcn10_runoff_table of every storm */
+    /* rain=...: a rainfall depth per cell of the grid, and the runoff-equivalent raster for it beside every mean */
+    bool rain_on;
+    double rain_unit, rain_lambda;
+    uint8_t *rain;                          /* [ny][nx]: the counts of the rainfall raster (gcn10_rain_load) */
+    uint16_t (*rain_q)[256];                /* [256][256]: gcn10_rain_tables */
 };
 
 double gcn10_now_seconds(void);

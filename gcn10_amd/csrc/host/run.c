@@ -4,6 +4,7 @@
  */
 #include "pipeline_internal.h"
 
+#include <limits.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -79,6 +80,50 @@ static int resolve(struct run *r)
     for (int k = 0; k < GCN10_N_RASTERS; k++)
         if ((r->cond_mask >> (k / 9)) & 1u && (r->table_mask >> (k % 9)) & 1u)
             r->sel[r->n_sel++] = k;
+    /* a rainfall raster: the runs it cannot go with, tested before any of them starts, and its unit; the raster itself
+     * is read once the grid is known (gcn10_grid_start) */
+    if (opt->rain) {
+        free(r->cfg.rain);
+        r->cfg.rain = strdup(opt->rain);
+    }
+    if (opt->rain_unit) {
+        free(r->cfg.rain_unit);
+        r->cfg.rain_unit = strdup(opt->rain_unit);
+    }
+    r->rain_on = r->cfg.rain != NULL;
+    if (r->cfg.rain_unit && !r->rain_on) {
+        fprintf(stderr, "[rank 0] rain_unit needs rain\n");
+        return 1;
+    }
+    if (r->rain_on) {
+        int factor = r->cfg.aggregate;
+
+        if (opt->aggregate && gcn10_parse_aggregate(opt->aggregate, &factor) != 0)
+            factor = 0;                     /* a bad value is reported below, as without rain */
+        if (r->verify)
+            why = "rain cannot be combined with --verify";
+        else if (factor)
+            why = "rain cannot be combined with aggregate";
+        else if (r->cfg.zonal || opt->zonal)
+            why = "rain cannot be combined with --zonal";
+        else if (opt->storm || r->cfg.storm)
+            why = "rain cannot be combined with storm";
+        else if (opt->storms || r->cfg.storms)
+            why = "rain cannot be combined with storms";
+        else if (!opt->grid && !r->cfg.grid)
+            why = "rain needs --grid";
+        if (why) {
+            fprintf(stderr, "[rank 0] %s\n", why);
+            return 1;
+        }
+        r->rain_unit = 1.0;
+        r->rain_lambda = 0.2;
+        if (r->cfg.rain_unit && gcn10_parse_rain_unit(r->cfg.rain_unit, &r->rain_unit, &r->rain_lambda) != 0) {
+            fprintf(stderr, "[rank 0] bad value for rain_unit: '%s' (unit[,lambda]: 0 < unit, 255 unit <= 650 mm, 0 <= "
+                            "lambda < 1)\n", r->cfg.rain_unit);
+            return 1;
+        }
+    }
     /* a zonal run: refused combinations and the zone file */
     if (opt->zones) {
         free(r->cfg.zones_shp_path);
@@ -220,7 +265,7 @@ static int resolve(struct run *r)
 static int require(struct run *r)
 {
     const struct gcn10_gpu_api *g;
-    char err[2048] = "", agg[48], grid[600], storm[600];
+    char err[2048] = "", agg[48], grid[600], storm[600], rain[PATH_MAX + 8];
 
     r->gpu = g = gcn10_gpu_api_get(err, sizeof err);
     if (!g) {
@@ -231,6 +276,7 @@ static int require(struct run *r)
     snprintf(grid, sizeof grid, "grid=%s", r->grid_on ? r->cfg.grid : "");
     snprintf(storm, sizeof storm, "%s=%s", r->storms_key ? "storms" : "storm",
              r->storms_key ? r->cfg.storms : r->storm_on ? r->cfg.storm : "");
+    snprintf(rain, sizeof rain, "rain=%s", r->rain_on ? r->cfg.rain : "");
     {
         /* the pair histogram's soil codes are asked for where a mode counts pairs, and must be as many as its bins */
         const bool pairs = (r->stats || r->zonal) && g->pair_histogram_codes &&
@@ -244,6 +290,8 @@ static int require(struct run *r)
               g->set_weights && g->grid_sums_weighted && g->grid_finish_weighted, "gcn10_gpu_grid_sums_weighted", storm },
             { r->grid_on && r->storms_key, g->set_weight_tables && g->grid_sums_storms && g->grid_finish_storms,
               "gcn10_gpu_grid_sums_storms", storm },
+            { r->rain_on, g->set_rain_tables && g->grid_sums_rain && g->grid_finish_rain, "gcn10_gpu_grid_sums_rain",
+              rain },
             { r->grid_on, g->grid_sums && g->grid_finish, "gcn10_gpu_grid_sums", grid },
             { r->verify, g->verify_strip && g->verify_buffers, "gcn10_gpu_verify_strip", "verify=1" },
             { r->lzw, g->lzw_strip && g->lzw_arena_bound, "gcn10_gpu_lzw_strip", "compress=lzw" },
@@ -420,6 +468,20 @@ static int load(struct run *r)
             threshold++;
         log0_line(r, "INFO", true, "storm: P = %.17g mm, lambda = %.17g, threshold CN %d (the smallest curve number that "
                   "sheds water)", r->storm_p[k], r->storm_lambda, threshold);
+    }
+    if (r->rain_on) {
+        const size_t n = (size_t)r->grid.nx * (size_t)r->grid.ny;
+        unsigned lo = 255, hi = 0;
+        size_t dry = 0;
+
+        for (size_t c = 0; c < n; c++) {
+            lo = r->rain[c] < lo ? r->rain[c] : lo;
+            hi = r->rain[c] > hi ? r->rain[c] : hi;
+            dry += r->rain[c] == 0;
+        }
+        log0_line(r, "INFO", true, "rain: %s, %d x %d cells, unit = %.17g mm, lambda = %.17g", r->cfg.rain, r->grid.nx,
+                  r->grid.ny, r->rain_unit, r->rain_lambda);
+        log0_line(r, "INFO", true, "rain: depths %u..%u counts, %zu cells without rain", lo, hi, dry);
     }
     if (r->n_workers > r->n_blocks) {       /* no worker (and no pinned memory) without a block */
         for (int i = r->n_blocks > 0 ? r->n_blocks : 1; i < r->n_workers; i++) {

@@ -6,6 +6,9 @@
  * -ffp-contract=off, as geo.c is) in the operation order stated in include/gcn10_host.h; everything after the table is
  * integers: a cell's or a zone's sum of table values, and the smallest curve number whose runoff over the whole cell
  * reaches that sum.
+ *
+ * A rainfall raster (config keys "rain" / "rain_unit") is 256 such storms, one per count of the raster's byte: the unit
+ * parser and the 256 tables are here, the raster itself is read by grid.c (gcn10_rain_load).
  */
 #include "gcn10_host.h"
 
@@ -98,6 +101,40 @@ int gcn10_parse_storms(const char *text, double P[GCN10_MAX_STORMS], int *k, dou
     *k = n;
     *lambda = lam;
     return 0;
+}
+
+int gcn10_parse_rain_unit(const char *text, double *unit, double *lambda)
+{
+    double d[2] = { 1.0, 0.2 };
+    const char *p = text;
+    char *end;
+
+    if (!text)
+        return -1;
+    for (int i = 0; i < 2; i++) {
+        /* a field as gcn10_parse_storm takes it: a sign, a digit or a point first, nothing but the number */
+        if (!(*p == '-' || *p == '+' || *p == '.' || (*p >= '0' && *p <= '9')))
+            return -1;
+        errno = 0;
+        d[i] = strtod(p, &end);
+        if (end == p || errno != 0 || (*end != '\0' && !(i == 0 && *end == ',')))
+            return -1;
+        if (*end == '\0')
+            break;
+        p = end + 1;
+    }
+    if (!isfinite(d[0]) || !isfinite(d[1]) || !(d[0] > 0.0) || !(255.0 * d[0] <= 650.0) || !(d[1] >= 0.0) ||
+        !(d[1] < 1.0))
+        return -1;
+    *unit = d[0];
+    *lambda = d[1];
+    return 0;
+}
+
+NO_CONTRACT void gcn10_rain_tables(double unit, double lambda, uint16_t q[256][256])
+{
+    for (int b = 0; b < 256; b++)
+        gcn10_runoff_table((double)b * unit, lambda, q[b]);
 }
 
 NO_CONTRACT void gcn10_runoff_table(double P, double lambda, uint16_t q[256])

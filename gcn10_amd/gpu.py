@@ -49,7 +49,18 @@ ABI_SYMBOLS = (
     "gcn10_gpu_aggregate", "gcn10_gpu_grid_sums", "gcn10_gpu_grid_finish",
     "gcn10_gpu_set_weights", "gcn10_gpu_grid_sums_weighted", "gcn10_gpu_grid_finish_weighted",
     "gcn10_gpu_set_weight_tables", "gcn10_gpu_grid_sums_storms", "gcn10_gpu_grid_finish_storms",
+    "gcn10_gpu_grid_rain_item", "gcn10_gpu_set_rain_tables", "gcn10_gpu_grid_sums_rain", "gcn10_gpu_grid_finish_rain",
 )
+
+
+def grid_rain_item():
+    """(columns, rows) of an item of the rain sums, the most a wave counts in one histogram
+    (gcn10_gpu_grid_rain_item; no device needed)."""
+    cols, rows = C.c_int(0), C.c_int(0)
+    n = lib().gcn10_gpu_grid_rain_item(C.byref(cols), C.byref(rows))
+    if n != cols.value * rows.value:
+        raise RuntimeError("gcn10_gpu_grid_rain_item returned %d" % n)
+    return cols.value, rows.value
 
 
 def pair_histogram_codes() -> np.ndarray:
@@ -154,6 +165,10 @@ def lib():
             "gcn10_gpu_set_weight_tables": (i, [vp, vp, i]),
             "gcn10_gpu_grid_sums_storms": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp]),
             "gcn10_gpu_grid_finish_storms": (i, [vp, vp, i, sz, vp, vp, vp, C.c_uint32, vp, vp]),
+            "gcn10_gpu_grid_rain_item": (i, [C.POINTER(i), C.POINTER(i)]),
+            "gcn10_gpu_set_rain_tables": (i, [vp, vp, i]),
+            "gcn10_gpu_grid_sums_rain": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp, vp]),
+            "gcn10_gpu_grid_finish_rain": (i, [vp, vp, i, sz, vp, vp, vp, vp, C.c_uint32, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -515,6 +530,30 @@ class Engine:
         self._chk(lib().gcn10_gpu_grid_finish_storms(self._ctx, acc_ptr, n_sel, n_cells, means_ptr, cnq_ptr,
                                                      shared_idx_ptr or None, n_shared, shared_ptr or None, stream),
                   "gcn10_gpu_grid_finish_storms")
+
+    def set_rain_tables(self, w):
+        """k tables of 256 16-bit weights ([k][256], 1 <= k <= 256) for the rain sums, one of them named per cell
+        (gcn10_gpu_set_rain_tables).  Independent of set_weights, set_weight_tables and set_tables.  Synchronous."""
+        a = np.ascontiguousarray(w, dtype=np.uint16).reshape(-1, 256)
+        self._chk(lib().gcn10_gpu_set_rain_tables(self._ctx, a.ctypes.data, a.shape[0]), "gcn10_gpu_set_rain_tables")
+
+    def grid_sums_rain(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, cellx_ptr: int, celly_ptr: int, ncx: int,
+                       ncy: int, cond_mask: int, table_mask: int, cell_table_ptr: int, acc_ptr: int, stream=None):
+        """grid_sums_weighted with a table per cell: ADDS {s, n, sw} to acc[q][celly[y]][cellx[x]] (uint64 on the
+        device, [n_sel][ncy][ncx][3]), sw the sum of w[cell_table[cy][cx]][v] for the tables of set_rain_tables;
+        cell_table_ptr: uint8[ncy][ncx] on the device (gcn10_gpu_grid_sums_rain).  Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_sums_rain(self._ctx, esa_ptr, W, rows, cj_ptr, cellx_ptr, celly_ptr, ncx, ncy,
+                                                 cond_mask, table_mask, cell_table_ptr, acc_ptr, stream),
+                  "gcn10_gpu_grid_sums_rain")
+
+    def grid_finish_rain(self, acc_ptr: int, n_sel: int, n_cells: int, cell_table_ptr: int, means_ptr: int,
+                         cnq_ptr: int, shared_idx_ptr, n_shared: int, shared_ptr, stream=None):
+        """means[q][c] as grid_finish, cnq[q][c] = host.runoff_cn of the triple with table cell_table[c] of
+        set_rain_tables, and the triples of the n_shared cells shared_idx names, packed into shared[q][i]
+        (gcn10_gpu_grid_finish_rain).  Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_finish_rain(self._ctx, acc_ptr, n_sel, n_cells, cell_table_ptr, means_ptr,
+                                                   cnq_ptr, shared_idx_ptr or None, n_shared, shared_ptr or None,
+                                                   stream), "gcn10_gpu_grid_finish_rain")
 
     def zonal_pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans, items, n_zones: int,
                              hist_ptr: int, stream=None):

@@ -143,6 +143,13 @@ def lib():
         L.gcn10_runoff_cn.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64,
                                       np.ctypeslib.ndpointer(dtype=np.uint16, flags="C_CONTIGUOUS")]
         L.gcn10_runoff_cn.restype = C.c_int
+        L.gcn10_parse_rain_unit.argtypes = [cp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.gcn10_parse_rain_unit.restype = C.c_int
+        L.gcn10_rain_tables.argtypes = [C.c_double, C.c_double, np.ctypeslib.ndpointer(dtype=np.uint16,
+                                                                                      flags="C_CONTIGUOUS")]
+        L.gcn10_rain_tables.restype = None
+        L.gcn10_rain_load.argtypes = [cp, C.POINTER(Grid), C.POINTER(vp), cp, C.c_size_t]
+        L.gcn10_rain_load.restype = C.c_int
         L.gcn10_zone_items_build.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(ZonePlan)]
         L.gcn10_zone_items_build.restype = C.c_int
         L.gcn10_tiff_abort.argtypes = [vp]
@@ -195,6 +202,12 @@ class ConfigStorms(ConfigStorm):
     it."""
     _fields_ = [("storms", C.c_char_p), ("n_storms", C.c_int), ("storms_p", C.c_double * MAX_STORMS),
                 ("storms_lambda", C.c_double)]
+
+
+class ConfigRain(ConfigStorms):
+    """``gcn10_config`` with the keys of the rainfall raster, appended behind ``ConfigStorms`` as the C struct appends
+    them."""
+    _fields_ = [("rain", C.c_char_p), ("rain_unit", C.c_char_p)]
 
 
 assert C.sizeof(Config) % 8 == 0
@@ -419,16 +432,51 @@ def runoff_cn(s: int, n: int, sw: int, q) -> int:
     return int(lib().gcn10_runoff_cn(int(s), int(n), int(sw), np.ascontiguousarray(q, dtype=np.uint16).reshape(256)))
 
 
+def parse_rain_unit(text: str):
+    """"<unit>[,<lambda>]" -> (unit, lambda) (``gcn10_parse_rain_unit``; lambda 0.2 when absent); raises HostError for any
+    other text."""
+    unit, lam = C.c_double(), C.c_double()
+    if lib().gcn10_parse_rain_unit(text.encode(), C.byref(unit), C.byref(lam)) != 0:
+        raise HostError("bad value for rain_unit: '%s' (unit[,lambda]: 0 < unit, 255 unit <= 650 mm, 0 <= lambda < 1)"
+                        % text)
+    return unit.value, lam.value
+
+
+def rain_tables(unit: float = 1.0, lam: float = 0.2) -> np.ndarray:
+    """uint16[256][256]: table b is ``runoff_table(b * unit, lam)`` (``gcn10_rain_tables``)."""
+    q = np.zeros((256, 256), np.uint16)
+    lib().gcn10_rain_tables(float(unit), float(lam), q)
+    return q
+
+
+def rain_load(path: str, grid) -> np.ndarray:
+    """The rainfall raster of the grid (a dict as parse_grid returns it), uint8[ny][nx] (``gcn10_rain_load``); raises
+    HostError with the run's refusal text when the file cannot be read, has another size or does not lie on the grid."""
+    g = Grid(**grid)
+    out = C.c_void_p()
+    err = C.create_string_buffer(4096 + 512)
+    rc = lib().gcn10_rain_load(os.fsencode(path), C.byref(g), C.byref(out), err, len(err))
+    if rc != 0:
+        e = HostError(err.value.decode(errors="replace"))
+        e.code = rc
+        raise e
+    try:
+        n = grid["nx"] * grid["ny"]
+        return np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), (n,)).copy().reshape(grid["ny"], grid["nx"])
+    finally:
+        lib().free_(out)
+
+
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = ConfigStorms()
+    cfg = ConfigRain()
     err = C.create_string_buffer(1024)
     rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
     out = {}
     for name, _t in (Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_ + ConfigStorm._fields_ +
-                     ConfigStorms._fields_):
+                     ConfigStorms._fields_ + ConfigRain._fields_):
         v = getattr(cfg, name)
         out[name] = v.decode() if isinstance(v, bytes) else list(v) if isinstance(v, C.Array) else v
     lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))

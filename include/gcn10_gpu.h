@@ -43,7 +43,9 @@ extern "C" {
  *    per zone of the zonal composites (gcn10_gpu_zonal_pair_histogram); the area means on a coarser grid
  *    (gcn10_gpu_aggregate); the sums and means on a model grid (gcn10_gpu_grid_sums, gcn10_gpu_grid_finish) and their
  *    weighted forms (gcn10_gpu_set_weights, gcn10_gpu_grid_sums_weighted, gcn10_gpu_grid_finish_weighted), and those
- *    for several weight tables (gcn10_gpu_set_weight_tables, gcn10_gpu_grid_sums_storms, gcn10_gpu_grid_finish_storms).
+ *    for several weight tables (gcn10_gpu_set_weight_tables, gcn10_gpu_grid_sums_storms, gcn10_gpu_grid_finish_storms);
+ *    the sums with a weight table per cell (gcn10_gpu_set_rain_tables, gcn10_gpu_grid_sums_rain,
+ *    gcn10_gpu_grid_finish_rain, gcn10_gpu_grid_rain_item).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -479,6 +481,43 @@ int gcn10_gpu_grid_finish_storms(gcn10_gpu_ctx *ctx, const unsigned long long *a
                                  uint8_t *means, uint8_t *cnq /* [k][n_sel][n_cells] */,
                                  const uint32_t *shared_idx_dev, uint32_t n_shared,
                                  unsigned long long *shared /* [n_sel][n_shared][2 + k] */, gcn10_stream_t stream);
+
+/* A weight table per cell (config key rain=...: a rainfall raster on the model grid).  Added in ABI 3 without a version
+ * change, as the storms calls were; the host looks them up for rain runs only.
+ *
+ * gcn10_gpu_set_rain_tables: w[k][256], 1 <= k <= GCN10_GPU_MAX_RAIN_TABLES tables of 16-bit weights per raster value
+ *   (host memory; w[t][255] is never read), kept on the device with a "never decreases over 1..100" flag per table.
+ *   Synchronous.  Independent of gcn10_gpu_set_weights / gcn10_gpu_set_weight_tables: neither invalidates the other,
+ *   and a later gcn10_gpu_set_tables does not invalidate the rain tables either -- they are functions of the value,
+ *   not of the lookups, and nothing is folded.
+ * gcn10_gpu_grid_sums_rain: every word of gcn10_gpu_grid_sums_weighted -- the maps, the -1 rule, ADD semantics, nothing
+ *   read at or beyond W, nothing written outside acc whatever the maps hold, cells of 8 pixels or more --: words 0 and
+ *   1 are exactly what gcn10_gpu_grid_sums adds, word 2 gets the sum of w[cell_table[cy * ncx + cx]][v] over the same
+ *   pixels of cell (cx, cy).  cell_table_dev[ncy][ncx] names the table of every cell; an entry >= k is an error of the
+ *   caller and counts as table 0.  There is no limit on the cell columns a workgroup meets, and pixels of a map whose
+ *   entries do decrease are summed all the same.  The kernel works in items of GCN10_GPU_RAIN_ITEM_COLS columns x at
+ *   most GCN10_GPU_RAIN_ITEM_ROWS rows, one wave each; a cell larger than an item gets its words from several.
+ * gcn10_gpu_grid_finish_rain: means[] as gcn10_gpu_grid_finish writes it; cnq[q * n_cells + c] = the value of the
+ *   triple by the rule of gcn10_runoff_cn with table cell_table[c] (c = cy * ncx + cx; an entry >= k counts as 0) --
+ *   bisection for a table that never decreases, a scan from 1 for one that does, the table read from device memory --;
+ *   and the triples of the shared cells, packed as gcn10_gpu_grid_finish_weighted packs them.
+ * gcn10_gpu_grid_rain_item: the columns and rows of an item (either pointer may be NULL); returns their product, the
+ *   most pixels a wave counts in 16 bits.  No device needed.
+ * Errors as the weighted calls', cell_table among the pointers; k outside 1..256 or null weights: GCN10_E_INVAL; no rain
+ * tables: GCN10_E_STATE ("call gcn10_gpu_set_rain_tables first"). */
+#define GCN10_GPU_MAX_RAIN_TABLES 256
+#define GCN10_GPU_RAIN_ITEM_COLS 512
+#define GCN10_GPU_RAIN_ITEM_ROWS 127
+int gcn10_gpu_grid_rain_item(int *cols, int *rows);
+int gcn10_gpu_set_rain_tables(gcn10_gpu_ctx *ctx, const uint16_t *w /* [k][256] */, int k);
+int gcn10_gpu_grid_sums_rain(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                             const int32_t *cellx_dev, const int32_t *celly_dev, int ncx, int ncy,
+                             unsigned cond_mask, unsigned table_mask, const uint8_t *cell_table_dev /* [ncy][ncx] */,
+                             unsigned long long *acc /* [n_sel][ncy][ncx][3] = {s, n, sw} */, gcn10_stream_t stream);
+int gcn10_gpu_grid_finish_rain(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells,
+                               const uint8_t *cell_table_dev, uint8_t *means, uint8_t *cnq,
+                               const uint32_t *shared_idx_dev, uint32_t n_shared, unsigned long long *shared,
+                               gcn10_stream_t stream);
 
 /* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
  * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.

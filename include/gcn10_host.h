@@ -149,6 +149,10 @@ typedef struct gcn10_config {
     int n_storms;           /* ... how many, */
     double storms_p[GCN10_MAX_STORMS];      /* their rainfall depths in mm, rising, */
     double storms_lambda;   /* and the initial-abstraction ratio of all of them */
+    char *rain;             /* "rain": a one-band Byte GeoTIFF of nx x ny pixels, the rainfall depth of every cell of
+                               "grid" in counts (gcn10_rain_load); not together with "storm" / "storms"; absent = off */
+    char *rain_unit;        /* "rain_unit": <unit>[,<lambda>] (gcn10_parse_rain_unit): millimetres per count (default 1)
+                               and the initial-abstraction ratio (default 0.2); needs "rain" */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -172,7 +176,7 @@ int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or
 int gcn10_parse_aggregate(const char *text, int *factor);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" / "rain_unit" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -496,6 +500,25 @@ void gcn10_runoff_table(double P, double lambda, uint16_t q[256]);
  * gcn10_runoff_table: q[100] is its maximum). */
 int gcn10_runoff_cn(uint64_t s, uint64_t n, uint64_t sw, const uint16_t q[256]);
 
+/* A rainfall raster on the model grid (config key "rain", --rain): a rainfall depth per cell instead of one per run.
+ * The raster holds one byte b per cell of the grid, and the cell's storm is P = b * unit mm: all 256 bytes are depths,
+ * there is no NoData value, and b = 0 is "no rain" (its table is all zero, so sw = 0 and the cell gets its mean byte by
+ * the rule of gcn10_runoff_cn).  cnq_<hc>_<arc>_rain.tif holds gcn10_runoff_cn(s, n, sw, q[b]) per cell, {s, n, sw} as
+ * for one storm with sw = the sum of q[b][v] over the cell's pixels. */
+/* "<unit>[,<lambda>]": millimetres per count and the initial-abstraction ratio (absent: 0.2), every field read as
+ * gcn10_parse_storm reads its own; 0 < unit, 255 * unit <= 650 and 0 <= lambda < 1.  0, or -1 for another text. */
+int gcn10_parse_rain_unit(const char *text, double *unit, double *lambda);
+/* q[b] = gcn10_runoff_table(b * unit, lambda) for b = 0..255, and nothing else: 128 KiB, made once per run. */
+void gcn10_rain_tables(double unit, double lambda, uint16_t q[256][256]);
+/* Reads the rainfall raster of grid g whole: *out = nx * ny bytes, row major (the caller frees them).  The file has
+ * exactly nx x ny pixels; if it carries a geotransform, its origin and pixel size equal xmin, ymax, dx, -dy of the grid
+ * as doubles, bit for bit, and it has no rotation; a file without georeferencing (the reader then reports the
+ * geotransform 0, 1, 0, 0, 0, 1) is taken to lie on the grid.  Returns 0, or GCN10_RAIN_E_* with the message of the
+ * run's refusal in err ("rain: cannot read '<file>': ...", "rain: '<file>' has <w> x <h> pixels, the grid has <nx> x
+ * <ny> cells", "rain: '<file>' does not lie on the grid (origin %.17g, %.17g, pixel %.17g x %.17g)"). */
+enum { GCN10_RAIN_E_READ = -1, GCN10_RAIN_E_SIZE = -2, GCN10_RAIN_E_GEOTRANSFORM = -3 };
+int gcn10_rain_load(const char *path, const gcn10_grid *g, uint8_t **out, char *err, size_t errcap);
+
 /* ------------------------------------------------------------------------ */
 /* the run: src/main.c:58-203 + process_block, src/cn.c:134-384              */
 /* ------------------------------------------------------------------------ */
@@ -519,6 +542,8 @@ typedef struct gcn10_run_options {
     const char *grid;           /* --grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>: overrides the config key "grid" */
     const char *storm;          /* --storm <P>[,<lambda>]: overrides the config key "storm" */
     const char *storms;         /* --storms <P1>[:<P2>...][,<lambda>]: overrides the config key "storms" */
+    const char *rain;           /* --rain <file>: overrides the config key "rain" */
+    const char *rain_unit;      /* --rain-unit <unit>[,<lambda>]: overrides the config key "rain_unit" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -559,7 +584,9 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * not be read: the rasters are written, but lack that block).  A storm (opt->storm / "storm=<P>[,<lambda>]") adds
  * cn_grid_<cond>/cnq_<hc>_<arc>_p<N>.tif to a grid run and the columns runoff_mm,cn_runoff to a zonal run's table;
  * several storms (opt->storms / "storms=<P1>[:<P2>...][,<lambda>]") add one such raster per storm, or the columns
- * runoff_mm_p<N>,cn_runoff_p<N> per storm (with one depth: exactly what storm adds). */
+ * runoff_mm_p<N>,cn_runoff_p<N> per storm (with one depth: exactly what storm adds).  A rainfall raster (opt->rain /
+ * "rain=<file>", with opt->rain_unit / "rain_unit=<unit>[,<lambda>]") adds cn_grid_<cond>/cnq_<hc>_<arc>_rain.tif to a
+ * grid run, every cell for its own depth; the means are byte for byte those of the run without it. */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

@@ -1,16 +1,25 @@
 """GPU: every kernel whose grid is capped by the device's size, run past its first trip.  Needs an MI355X (all tests
-but the last two, which are arithmetic and run anywhere).
+but three, which are arithmetic and numpy and run anywhere).
 
 Several kernels launch at most a multiple of the compute-unit count of workgroups; beyond that a workgroup loops over
 further work and carries state from trip to trip -- the verifier's tally in LDS and its 64-bit minimum, the pair
-histogram's LDS bins --, or strides over a flat array (grid_finish, stream_copy); in gcn10_gpu_grid_sums the device's
-size sets the rows of a band instead.  Every production call on 256 CUs is deep in that regime; the other kernel tests
-stay below the caps (one trip per workgroup, bands of the 16-row floor).  This module computes each shape from the
-device's CU count with the launch arithmetic of the sources, restated below beside the constant it mirrors, asserts
-from that arithmetic that the shape reaches the regime it names, and then compares exactly: the verifier with numpy on
-the oracle's rasters (strip form) or on random bytes (buffer form), the histogram with the numpy model of
-tests/test_gpu_stats.py, grid_finish with gridutil.means / runoffutil.cn_array and plain indexing, the weighted grid sums
-with np.bincount over the oracle's rasters, stream_copy byte for byte.  No tolerance anywhere.
+histogram's LDS bins --, or strides over a flat array (grid_finish, stream_copy); in gcn10_gpu_grid_sums and in
+gcn10_gpu_grid_sums_rain the device's size sets the rows of a band instead.  Every production call on 256 CUs is deep in
+that regime; the other kernel tests stay below the caps (one trip per workgroup, bands of the 16-row floor).  This
+module computes each shape from the device's CU count with the launch arithmetic of the sources, restated below beside
+the constant it mirrors, asserts from that arithmetic that the shape reaches the regime it names, and then compares
+exactly: the verifier with numpy on the oracle's rasters (strip form) or on random bytes (buffer form), the histogram
+with the numpy model of tests/test_gpu_stats.py, grid_finish with gridutil.means / runoffutil.cn_array and plain
+indexing, the weighted grid sums with np.bincount over the oracle's rasters, stream_copy byte for byte.  No tolerance
+anywhere.
+
+The rain sums (gcn10_grid_rain.hip, section 6): the launch is not capped, but the band height -- the rows of an item --
+is ceil(rows / (16 x CUs // chunks + 1)) held between 16 and 127, and a block's rows in one call (36 000 x 36 000 on 256 CUs)
+make every item the full 512 x 127 = 65 024 pixels, on which the kernel's 16-bit counts and 32-bit sums rest.  Bands of
+17, 127 and "128" rows (the clamp) run on a strip of 17 columns against the summed oracle of tests/test_gpu_grid_rain.py;
+items of 512 x 127 run on a strip of 528 columns whose landcover and soil are made so that one item holds ONE pair
+65 024 times and another a bin of 32 768 -- asserted from the arrays --, with a table of 65 535, so that a piece's and
+the wave's 32-bit sum is 4 261 347 840, and against a closed form that is itself held to the summed oracle on a cut-out.
 
 Not reached: bands of 256 rows (kMaxBandRows) at block width.  At the 36001 columns of a block they take about 350 Mpx
 in one call, and no short test can hold that; the 36001-wide test here reaches bands of 20 rows, the first regime above
@@ -18,6 +27,7 @@ the floor of 16, in the weighted kernel only (the unweighted launch of the same 
 stays at the floor).  Both kernels' band arithmetic up to the clamp at 256 rows is run on a strip of 17 columns, where a
 band is short -- and where a chunk's 32-bit sums stay far from the bound that 4096 columns x 256 rows come near.
 """
+import time
 import types
 
 import numpy as np
@@ -25,10 +35,15 @@ import pytest
 
 from gcn10_amd import gpu, host
 from oracle import cn_oracle_c as oc
+from tests import aggutil as au
 from tests import gridutil as gu
+from tests import rainutil as rn
 from tests import runoffutil as ru
+from tests import stormutil
 from tests.test_gpu_aggregate import Inputs, scene  # noqa: F401  (the recipe and the fixture)
 from tests.test_gpu_grid import check_sums, maps, run_finish, run_sums
+from tests.test_gpu_grid_rain import TABLES as RAIN_TABLES
+from tests.test_gpu_grid_rain import check_rain, field_for, map_of, run_rain, want_rain
 from tests.test_gpu_grid_runoff import Q50, WEIGHTS, check_weighted, run_finish_weighted
 from tests.test_gpu_stats import landcover, model_histogram
 from tests.test_gpu_verify import plant, strips_of
@@ -53,6 +68,13 @@ GRID_CHUNK = 4096           # gcn10_grid.hip kChunkPx
 BAND_FLOOR, BAND_MAX = 16, 256      # launch_sums: min(max(.., 16), kMaxBandRows)
 N_RASTERS = 18
 NARROW_BANDS = (17, 257)    # bands asked of the 17-column strips: the first above the floor, and one past kMaxBandRows
+RAIN_PER_CU = 16            # gcn10_gpu_grid_sums_rain of gcn10_grid_rain.hip: grid_cap(ctx, 16)
+RAIN_ITEM_COLS = 512        # GCN10_GPU_RAIN_ITEM_COLS (kItemCols): columns of an item, and of a chunk of the strip
+RAIN_ITEM_ROWS = 127        # GCN10_GPU_RAIN_ITEM_ROWS (kItemRows): the most rows of a band
+RAIN_FLOOR = 16             # kMinBandRows
+RAIN_NARROW_BANDS = (17, 127, 128)  # of the 17-column strips: the first above the floor, kItemRows, and one past it
+RAIN_TALL = 2 * RAIN_ITEM_ROWS + 10     # rows of a cell that at least three bands of any height add to
+LC, LC_RARE, CN, CN_RARE = 40, 41, 100, 7   # the full items' two landcover bytes and what their tables make of them
 
 
 def ceil_div(a, b):
@@ -200,6 +222,51 @@ def narrow_bands_shape(cus, weighted, band):
     return s
 
 
+def rain_band_rows(W, rows, cus):
+    """gcn10_gpu_grid_sums_rain of gcn10_grid_rain.hip: the rows of a band, and so of an item"""
+    chunks = ceil_div(W, RAIN_ITEM_COLS)
+    want = grid_cap(cus, RAIN_PER_CU) // chunks + 1
+    return min(max(ceil_div(rows, want), RAIN_FLOOR), RAIN_ITEM_ROWS)
+
+
+def rain_narrow_shape(cus, band):
+    """The rain sums over a strip of 17 columns (one chunk: a whole group and a group of one pixel): the fewest rows
+    with bands of `band` rows, or, for band = 128, rows for the clamp to kItemRows.  An item of 17 columns counts 2159
+    pixels at most: the band arithmetic alone, far from the 16-bit and 32-bit bounds (rain_full_item_shape)."""
+    s = types.SimpleNamespace(W=17)
+    want = grid_cap(cus, RAIN_PER_CU) // ceil_div(s.W, RAIN_ITEM_COLS) + 1
+    s.rows = (band - 1) * want + 1
+    s.rows += s.rows % min(band, RAIN_ITEM_ROWS) == 0           # the last band is a cut one
+    s.band_rows = rain_band_rows(s.W, s.rows, cus)
+    s.bands = ceil_div(s.rows, s.band_rows)
+    assert s.band_rows == min(band, RAIN_ITEM_ROWS) > RAIN_FLOOR and ceil_div(s.rows, want) == band
+    assert s.bands >= 2 and s.rows % s.band_rows != 0
+    if band > RAIN_ITEM_ROWS:
+        assert ceil_div(s.rows, want) > s.band_rows == RAIN_ITEM_ROWS      # the clamp applies
+    s.regime = "W=17 rows=%d: %d bands of %d rows" % (s.rows, s.bands, s.band_rows)
+    return s
+
+
+def rain_full_item_shape(cus):
+    """The rain sums over the cheapest strip whose items are 512 columns x 127 rows, the size of every item of a
+    block-sized call: two chunks (512 columns and one group of 16), the fewest rows with bands of kItemRows.  rows_clamp:
+    the fewest rows at which the arithmetic asks for 128 and the clamp holds it to 127; the bands are the same ones."""
+    s = types.SimpleNamespace(W=RAIN_ITEM_COLS + PX_PER_LANE, chunks=2)
+    s.want = grid_cap(cus, RAIN_PER_CU) // s.chunks + 1
+    s.rows = (RAIN_ITEM_ROWS - 1) * s.want + 1
+    s.rows_clamp = RAIN_ITEM_ROWS * s.want + 1
+    s.band_rows = rain_band_rows(s.W, s.rows, cus)
+    s.bands = ceil_div(s.rows, s.band_rows)
+    assert s.W == 528 and ceil_div(s.W, RAIN_ITEM_COLS) == s.chunks and s.band_rows == RAIN_ITEM_ROWS
+    assert ceil_div(s.rows, s.want) == RAIN_ITEM_ROWS and rain_band_rows(s.W, s.rows - 1, cus) == RAIN_ITEM_ROWS - 1
+    assert ceil_div(s.rows_clamp, s.want) == RAIN_ITEM_ROWS + 1 and rain_band_rows(s.W, s.rows_clamp, cus) == RAIN_ITEM_ROWS
+    assert s.bands >= 7                                         # bands 3 and 5 are whole ones
+    assert RAIN_ITEM_COLS * s.band_rows == 65024
+    s.regime = "W=%d rows=%d (%d px): %d bands of %d rows, the last of %d; and rows=%d for the clamp" % (
+        s.W, s.rows, s.W * s.rows, s.bands, s.band_rows, s.rows - (s.bands - 1) * s.band_rows, s.rows_clamp)
+    return s
+
+
 def copy_shape(cus):
     """stream_copy_kernel: trips of 512 vectors, grid = stream_grid(trips), the trips dealt in eight slabs (first_chunk of
     gcn10_device_util.hpp) when the grid is a multiple of 8 and there are trips for every workgroup"""
@@ -230,6 +297,9 @@ def regimes(cus):
             out["grid_sums%s W=17 band=%d" % ("_weighted" if weighted else "", band)] = \
                 narrow_bands_shape(cus, weighted, band).regime
     out["stream_copy"] = copy_shape(cus).regime
+    for band in RAIN_NARROW_BANDS:
+        out["grid_sums_rain W=17 band=%d" % band] = rain_narrow_shape(cus, band).regime
+    out["grid_sums_rain full items"] = rain_full_item_shape(cus).regime
     return out
 
 
@@ -673,6 +743,226 @@ def test_stream_copy_past_the_cap(engine, cus):
     assert np.array_equal(got[GUARD:-GUARD], src)
 
 
+# ---- 6. grid_sums_rain in items taller than the 16-row floor, up to the full 512 x 127 --------------------------------
+
+def rain_tall_celly(rows, band_rows):
+    """(celly, the tall cell nearest the middle): cells of 25 and 26 rows in turn with three rows of -1 behind each, and
+    after every forty of them one of RAIN_TALL rows, round and round; -1 for the first 3 rows and the last 2."""
+    m = map_of(rows, [25, 3, 26, 3] * 20 + [RAIN_TALL, 3], 3, 2)
+    celly = np.where((m >= 0) & (m % 2 == 0), m // 2, -1).astype(np.int32)     # every second run is a gap
+    sizes = np.bincount(celly[celly >= 0])
+    tall = np.flatnonzero(sizes == RAIN_TALL)
+    assert len(tall) >= 3 and set(sizes[:-1].tolist()) == {25, 26, RAIN_TALL} and (celly[3:-2] == -1).any()
+    big = int(tall[len(tall) // 2])
+    y = np.flatnonzero(celly == big)
+    assert len(y) == RAIN_TALL and y[-1] - y[0] == RAIN_TALL - 1
+    assert y[-1] // band_rows - y[0] // band_rows >= 2, "the tall cell does not span three bands"
+    return celly, big
+
+
+@on_gpu
+@pytest.mark.parametrize("band", RAIN_NARROW_BANDS)
+def test_grid_sums_rain_of_a_narrow_strip_in_tall_bands(scene, tables, cus, band):
+    """The band arithmetic of the rain sums above the floor, at kItemRows and at the clamp to it, on a strip narrow
+    enough to be short: every row of a tall band must be summed, in cells smaller than a band and in one that several
+    bands add to.  One condition, three tables: three rasters of the oracle per strip."""
+    assert gpu.grid_rain_item() == (RAIN_ITEM_COLS, RAIN_ITEM_ROWS)
+    s = rain_narrow_shape(cus, band)
+    print("grid_sums_rain narrow: %s" % s.regime)
+    t0 = time.perf_counter()
+    inp = Inputs(s.W, s.rows, 25, 29 + band, tables)
+    sc = scene(inp)
+    t_setup = time.perf_counter() - t0
+    cond_mask, table_mask = 1, 0x111
+    tall_y, big = rain_tall_celly(s.rows, s.band_rows)
+    pairs = [maps(s.W, s.rows, 8, 25.6, (0, 3), (0, 2)), maps(s.W, s.rows, 1e6, 1e6, (0, 3), (0, 2)),
+             (maps(s.W, s.rows, 8, 25.6)[0], tall_y)]
+    t0 = time.perf_counter()
+    for k, (cellx, celly) in enumerate(pairs):
+        assert cellx[-1] >= 0 and celly[0] == -1 and celly[-1] == -1
+        ncx, ncy = int(cellx.max()) + 1, int(celly.max()) + 1
+        assert ncx == (1 if k == 1 else 3) and (ncy == 1) == (k == 1)
+        field = field_for(ncx, ncy, 5 + k)
+        got = check_rain(sc, cellx, celly, field, RAIN_TABLES, cond_mask, table_mask)
+        assert got.shape == (3, ncy, ncx, 3) and got[..., 1].max() > 0 and got[..., 2].max() > 0
+    t_checks = time.perf_counter() - t0
+    # on the last maps: ADD semantics, and a cut inside a band and inside the tall cell
+    t0 = time.perf_counter()
+    twice = run_rain(sc, cellx, celly, field, RAIN_TABLES, cond_mask, table_mask, repeat=2)
+    np.testing.assert_array_equal(twice, 2 * got)
+    y = np.flatnonzero(celly == big)
+    cut = int(y[0]) + RAIN_TALL // 2
+    cut += cut % s.band_rows == 0
+    assert celly[cut - 1] == celly[cut] == big and cut % s.band_rows != 0
+    parts = run_rain(sc, cellx, celly, field, RAIN_TABLES, cond_mask, table_mask, bands=[(0, cut), (cut, s.rows - cut)])
+    np.testing.assert_array_equal(parts, got)
+    t_runs = time.perf_counter() - t0
+    print("grid_sums_rain narrow band=%d: inputs and scene %.2f s, three checks against the oracle %.2f s, two runs of "
+          "the device alone (three calls, two downloads) %.2f s; the cut: rows %d + %d in bands of %d and %d" % (
+              band, t_setup, t_checks, t_runs, cut, s.rows - cut, rain_band_rows(s.W, cut, cus),
+              rain_band_rows(s.W, s.rows - cut, cus)))
+
+
+class OnePairStrip:
+    """What Scene reads of a strip -- and want_rain, on a small one -- for a landcover array over ONE valid soil class
+    and tables with two values: CN everywhere, CN_RARE for landcover LC_RARE."""
+
+    def __init__(self, esa):
+        self.esa = np.ascontiguousarray(esa)
+        self.rows, self.W = self.esa.shape
+        self.tables = np.full((9, 256, 5), CN, np.int32)
+        self.tables[:, LC_RARE, :] = CN_RARE
+        self.hsx, self.hsy = int(self.W / 25) + 2, int(self.rows / 25) + 3
+        self.coarse = np.full((self.hsy, self.hsx), 2, np.uint8)            # a valid soil everywhere: no pixel is 255
+        gt = [0.0, 1.0 / self.W, 0.0, 1.0, 0.0, -1.0 / self.W]
+        sgt = [-0.013 * 25 / self.W, 25 / self.W, 0.0, 1.0 + 0.02 * 25 / self.W, 0.0, -25 / self.W]
+        self.ci, self.cj = host.build_index_maps(gt, sgt, self.W, self.rows, self.hsx, self.hsy)
+        self.rare = np.argwhere(self.esa == LC_RARE)                        # (y, x) of every LC_RARE pixel
+        self._want = {}
+
+    def want(self, r):
+        if r not in self._want:
+            self._want.update(au.oracle_rasters(self.esa, np.full(self.esa.shape, 2, np.uint8), self.tables, [r]))
+        return self._want[r]
+
+
+def full_item_landcover(W, rows, seed=41, n_rare=4000):
+    """uint8[rows][W]: LC everywhere, but (a) LC_RARE at n_rare random places, none in bands 3 and 5 of chunk 0, and
+    (b) LC_RARE in the upper 64 rows of band 5 of chunk 0 -- bands of RAIN_ITEM_ROWS rows, chunks of RAIN_ITEM_COLS."""
+    rng = np.random.default_rng(seed)
+    esa = np.full((rows, W), LC, np.uint8)
+    ys, xs = rng.integers(0, rows, n_rare), rng.integers(0, W, n_rare)
+    keep = ~(np.isin(ys // RAIN_ITEM_ROWS, (3, 5)) & (xs < RAIN_ITEM_COLS))
+    esa[ys[keep], xs[keep]] = LC_RARE
+    esa[5 * RAIN_ITEM_ROWS:5 * RAIN_ITEM_ROWS + 64, :RAIN_ITEM_COLS] = LC_RARE
+    return esa
+
+
+def full_item_preconditions(inp):
+    """The point of the full-item test, asserted from the arrays: the item of band 3 / chunk 0 holds one single pair
+    over all its 65 024 pixels, the one of band 5 exactly two bins, of 32 768 (bit 15 alone) and 32 256."""
+    assert (inp.coarse == 2).all()
+    item = inp.esa[3 * RAIN_ITEM_ROWS:4 * RAIN_ITEM_ROWS, :RAIN_ITEM_COLS]
+    assert item.shape == (RAIN_ITEM_ROWS, RAIN_ITEM_COLS) and item.size == 65024 and (item == LC).all()
+    item = inp.esa[5 * RAIN_ITEM_ROWS:6 * RAIN_ITEM_ROWS, :RAIN_ITEM_COLS]
+    bins = np.bincount(item.reshape(-1), minlength=256)
+    assert item.shape == (RAIN_ITEM_ROWS, RAIN_ITEM_COLS) and np.count_nonzero(bins) == 2
+    assert (bins[LC_RARE], bins[LC]) == (32768, 32256) and 32768 == 1 << 15
+    assert len(inp.rare) > 32768 + 2000                             # and the sprinkle of (a) is there
+
+
+def full_item_tables():
+    """uint16[3][256]: `a` (65535 for the common value, 1 for the rare one, else 0), the 50 mm table, a random one"""
+    a = np.zeros(256, np.uint16)
+    a[CN], a[CN_RARE] = 65535, 1
+    return np.stack([a, Q50, stormutil.POOL["random"]])
+
+
+def full_item_triples(inp, cellx, celly, field, w, n_sel):
+    """int64[n_sel][ncy][ncx][3] in closed form, no pixel visited but the LC_RARE ones: with n pixels in a cell and k of
+    them LC_RARE, s = CN (n - k) + CN_RARE k and sw = w[CN] (n - k) + w[CN_RARE] k for the table w the cell's byte names."""
+    ncy, ncx = field.shape
+    assert celly.max() == ncy - 1 and cellx.max() == ncx - 1 and len(cellx) == inp.W
+    n = np.outer(np.bincount(celly[celly >= 0], minlength=ncy), np.bincount(cellx[cellx >= 0], minlength=ncx)).astype(np.int64)
+    at = inp.rare[inp.rare[:, 0] < len(celly)]
+    cy, cx = celly[at[:, 0]], cellx[at[:, 1]]
+    k = np.zeros((ncy, ncx), np.int64)
+    np.add.at(k, (cy[(cy >= 0) & (cx >= 0)], cx[(cy >= 0) & (cx >= 0)]), 1)
+    wt = np.asarray(w, np.int64)[rn.clamp_field(field, len(w))]     # [ncy][ncx][256]
+    acc = np.stack([CN * (n - k) + CN_RARE * k, n, wt[..., CN] * (n - k) + wt[..., CN_RARE] * k], axis=-1)
+    return np.broadcast_to(acc, (n_sel,) + acc.shape)
+
+
+def rain_edge_cellx(W):
+    """cell edges at 16 k + 7 (inside a lane's 16 pixels) and at 512 (between two items), -1 columns around"""
+    assert W == RAIN_ITEM_COLS + PX_PER_LANE
+    m = np.full(W, -1, np.int32)
+    for k, (a, b) in enumerate(((7, 23), (23, 231), (231, RAIN_ITEM_COLS), (RAIN_ITEM_COLS, 519), (521, W - 2))):
+        m[a:b] = k
+    return m
+
+
+def full_item_maps(W, rows, seed=6):
+    """{name: (cellx, celly, field)}, the field's bytes naming the three tables of full_item_tables"""
+    rng = np.random.default_rng(seed)
+    out = {"one cell, table a": (np.zeros(W, np.int32), np.zeros(rows, np.int32), None),
+           "120 x 50": maps(W, rows, 120, 50, (5, 3), (3, 2)) + [None],
+           "8 columns, the whole height": maps(W, rows, 8, 1e6) + [None],
+           "edges at 16 k + 7 and at 512": (rain_edge_cellx(W), map_of(rows, (300,), 3, 2), None)}
+    for name, (cellx, celly, _) in out.items():
+        shape = (int(celly.max()) + 1, int(cellx.max()) + 1)
+        field = np.zeros(shape, np.uint8) if name.startswith("one cell") else rng.integers(0, 3, shape).astype(np.uint8)
+        assert field.size < 30 or len(np.unique(field)) == 3
+        out[name] = (cellx, celly, field)
+    return out
+
+
+def same_triples(got, want, what):
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, "%s: %d of %d words differ, first (q, cy, cx, word) = %s: got %d, want %d" % (
+        what, len(bad), want.size, tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
+
+
+def test_the_closed_form_of_the_full_items_is_the_summed_oracle(tables):
+    """No GPU: full_item_triples against want_rain (the oracle's rasters, summed) on 528 x 300 pixels cut out of the
+    recipe where it holds both landcover bytes, and what the pure item alone gives to one cell with table a."""
+    whole = OnePairStrip(full_item_landcover(528, 7 * RAIN_ITEM_ROWS + 11))
+    full_item_preconditions(whole)
+    y0 = 3 * RAIN_ITEM_ROWS + 100                       # the end of band 3, band 4, and (b) of band 5 with rows below
+    inp = OnePairStrip(whole.esa[y0:y0 + 300])
+    n_rare = len(inp.rare)
+    assert (inp.W, inp.rows) == (528, 300) and 64 * 512 + 100 < n_rare < 64 * 512 + 3000 and (inp.esa == LC).sum() == 528 * 300 - n_rare
+    w = full_item_tables()
+    assert w[0][CN] == 65535 and w[0][CN_RARE] == 1 and w[0].sum() == 65536 and len({t.tobytes() for t in w}) == 3
+    for name, (cellx, celly, field) in full_item_maps(528, 300).items():
+        want = want_rain(inp, cellx, celly, field, w, 3, 0x11)
+        assert want.shape[0] == 4 and want[..., 2].max() > 0
+        same_triples(full_item_triples(inp, cellx, celly, field, w, 4), want, name)
+    # one condition's values are the other's and a table's another's: CN and CN_RARE, nothing else
+    assert all(set(np.unique(inp.want(r)).tolist()) == {CN, CN_RARE} for r in (0, 4, 9, 13))
+    item = OnePairStrip(whole.esa[3 * RAIN_ITEM_ROWS:4 * RAIN_ITEM_ROWS, :RAIN_ITEM_COLS])
+    one = full_item_triples(item, np.zeros(512, np.int32), np.zeros(RAIN_ITEM_ROWS, np.int32), np.zeros((1, 1), np.uint8), w, 1)
+    assert one[0, 0, 0].tolist() == [6502400, 65024, 4261347840] and 4261347840 == 65024 * 65535 < 2 ** 32
+    assert 2 ** 32 - 4261347840 < 2 ** 32 // 100        # within 1 % of the bound
+
+
+@on_gpu
+def test_grid_sums_rain_of_full_items_at_the_16_and_32_bit_bounds(scene, cus):
+    """Items of 512 x 127 pixels, what every item of a block-sized call is: a count of 65 024 in one bin, one of 32 768,
+    and a 32-bit sum of 65 024 x 65 535 -- 0.8 % below 2^32 -- in a piece and in the wave's total.  Then the same
+    strip with rows for the clamp: no item may grow to 128 rows, which would carry a count into the bin field."""
+    assert gpu.grid_rain_item() == (RAIN_ITEM_COLS, RAIN_ITEM_ROWS)
+    s = rain_full_item_shape(cus)
+    print("grid_sums_rain full items: %s" % s.regime)
+    t0 = time.perf_counter()
+    inp = OnePairStrip(full_item_landcover(s.W, s.rows_clamp))
+    full_item_preconditions(inp)
+    t_host = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    sc = scene(inp)
+    sc.eng.sync()
+    t_up = time.perf_counter() - t0
+    w = full_item_tables()
+    cond_mask, table_mask = 3, 0x11
+    t_dev = t_ref = 0.0
+    cases = list(full_item_maps(s.W, s.rows).items())
+    cases.append(("one cell, table a, rows for the clamp", full_item_maps(s.W, s.rows_clamp)["one cell, table a"]))
+    for name, (cellx, celly, field) in cases:
+        t0 = time.perf_counter()
+        got = run_rain(sc, cellx, celly, field, w, cond_mask, table_mask)       # the first len(celly) rows
+        t1 = time.perf_counter()
+        want = full_item_triples(inp, cellx, celly, field, w, 4)
+        t_dev, t_ref = t_dev + t1 - t0, t_ref + time.perf_counter() - t1
+        same_triples(got, want, name)
+        if name.startswith("one cell"):
+            rows = len(celly)
+            k = int((inp.rare[:, 0] < rows).sum())
+            assert got.shape == (4, 1, 1, 3) and got[0, 0, 0, 1] == s.W * rows
+            assert got[0, 0, 0, 2] == 65535 * (s.W * rows - k) + k > 2 ** 32
+    print("grid_sums_rain full items: landcover and reference set-up %.2f s, upload and prepare %.2f s, %d runs of the "
+          "device (maps up, kernel, triples down) %.2f s, closed forms %.2f s" % (t_host, t_up, len(cases), t_dev, t_ref))
+
+
 # ---- the fast path of the expected sums (no GPU) ----------------------------------------------------------------
 
 def test_the_bincount_path_adds_what_add_at_adds(monkeypatch):
@@ -703,7 +993,7 @@ def test_the_shapes_reach_their_regimes(n_cus):
     """Every shape function asserts the regime it names; here for the MI355X's 256 CUs and two other device sizes, with
     the figures the module docstring and DESIGN.md quote for 256."""
     r = regimes(n_cus)
-    assert len(r) == 7 + 2 * len(NARROW_BANDS)
+    assert len(r) == 7 + 2 * len(NARROW_BANDS) + len(RAIN_NARROW_BANDS) + 1 == 15
     places, counts = places_for(verify_shape("A", n_cus))
     assert counts[ROLES["three"]] == 3 and counts[ROLES["two"]] == 2 and len(places[ROLES["tail"]]) == 1
     places, counts = places_for(verify_shape("B", n_cus))
@@ -721,3 +1011,16 @@ def test_the_shapes_reach_their_regimes(n_cus):
         assert [(v.rows, v.band_rows) for v in n] == [(32785, 17), (524545, 256), (10929, 17), (174849, 256)]
         # and what no short test reaches: bands of 256 rows at this width
         assert band_rows(36001, 255 * 38, 6, 256) == 255 and 36001 * (255 * 38 + 1) > 348000000
+        # the rain sums: a block's owned rows in one call (host/grid.c) are items of 127 rows, all of them, ...
+        assert ceil_div(36000, RAIN_ITEM_COLS) == 71 and grid_cap(256, RAIN_PER_CU) // 71 + 1 == 58
+        assert rain_band_rows(36000, 36000, 256) == RAIN_ITEM_ROWS
+        # ... every strip of tests/test_gpu_grid_rain.py stays at the floor, ...
+        small = ((1043, 61), (4099, 300), (301, 301), (2100, 24), (17, 17))
+        assert [rain_band_rows(w, h, 256) for w, h in small] == [RAIN_FLOOR] * 5
+        # ... and the strips of this module do not
+        n = [rain_narrow_shape(256, b) for b in RAIN_NARROW_BANDS]
+        assert [(v.rows, v.band_rows, v.bands) for v in n] == [(65553, 17, 3857), (516223, 127, 4065), (520320, 127, 4098)]
+        f = rain_full_item_shape(256)
+        assert (f.want, f.rows, f.W * f.rows, f.bands, f.rows - (f.bands - 1) * f.band_rows) == \
+            (2049, 258175, 136316400, 2033, 111)
+        assert f.rows_clamp == 260224

@@ -7,7 +7,9 @@ cell in numpy with the table the cell's byte names, and runoffutil.cn per cell (
 field also the triples and bytes of gcn10_gpu_grid_sums_weighted / _finish_weighted for the same table, a cross-check
 between two GPU paths.  Every comparison is bit for bit.  The shapes follow the kernel's items, whose size is read
 from the library (gpu.grid_rain_item): cells of 8 pixels, cells of 25 and 26 pixels in turn, cells cut by items, one
-cell over several items each way, a last column group of one pixel.
+cell over several items each way, a last column group of one pixel.  Every strip here is short enough for the launch
+to stay at its floor of 16 rows per item; items of 17 to 127 rows, the full 512 x 127 of a block-sized call among them,
+are run in tests/test_gpu_capped_grids.py ("6. grid_sums_rain").
 """
 import numpy as np
 import pytest

@@ -25,29 +25,29 @@
 // outside [0, ncx) and [0, ncy) count as -1, and a cell column beyond the kMaxCells a chunk's LDS words hold is left
 // out, so no map makes the kernel write outside acc.
 //
-// Weighted sums (gcn10_gpu_grid_sums_weighted, DESIGN.md "Runoff-weighted composites"): a third word per (raster,
-// cell), the sum of w[v] over the same pixels for a table w of 256 16-bit weights.  w o table is a function of (soil
-// plane, landcover, table) like the value itself, so gcn10_gpu_set_weights folds w into two more images of the
-// all-tables layout, the low and the high bytes of w[cn], zero where the CN image holds 255; against such an image the
-// same gather, masks and dot products give the sum of the low and of the high bytes, and sw = lo + 256 hi.  In a
-// weight plane 255 is a number: a plane pass makes no 255 test and no count.  A workgroup keeps its shape and gets a
-// role besides its condition -- the CN image (words 0 and 1, exactly the unweighted kernel's), the low plane (word 2)
-// or the high plane (word 2, shifted by 8) --, and the up to six workgroups of an item are dealt to one XCD.
-//
-// Several tables (gcn10_gpu_set_weight_tables, gcn10_gpu_grid_sums_storms, DESIGN.md "Several storms"): k tables are 2 k
-// planes behind each other and 2 + k words per (raster, cell), word 2 + j the sum of w_j[v].  grid_sums_storms_kernel
-// has 1 + 2 k roles per condition -- the CN image, then (low, high) of table 0, 1, ... --, dealt as above; the word
-// count and a plane role's target word are run-time values of sum_item there, uniform, and enter only the addresses of
-// the flush's atomics.  A plane role stages one image, so the LDS of a workgroup is the same.  The finish pass keeps
+// Weighted sums (DESIGN.md "Runoff-weighted composites", "Several storms"): with k tables w_j of 256 16-bit weights a
+// (raster, cell) has 2 + k words, word 2 + j the sum of w_j[v] over the same pixels.  w o table is a function of (soil
+// plane, landcover, table) like the value itself, so gcn10_gpu_set_weight_tables folds every w_j into two more images
+// of the all-tables layout, the low and the high bytes of w_j[cn], zero where the CN image holds 255; against such an
+// image the same gather, masks and dot products give the sum of the low and of the high bytes, and sw = lo + 256 hi.
+// In a weight plane 255 is a number: a plane pass makes no 255 test and no count.  A workgroup keeps its shape and
+// gets a role besides its condition, one of 1 + 2 k -- the CN image (words 0 and 1), then (low, high) of table 0, 1,
+// ...: word 2 + j, the high plane's sums shifted by 8 --, and the workgroups of an item are dealt to one XCD.  The word
+// count and a plane role's target word are uniform run-time values that enter only the addresses of the flush's
+// atomics; a plane role stages one image, so the LDS of a workgroup does not depend on k.  The finish pass keeps
 // k x 101 weights in LDS and decides per table between bisection and the scan from 1.
+//
+// ONE sums kernel and ONE finish kernel serve all three pairs of calls: gcn10_gpu_grid_sums / _finish are k = 0
+// whatever weights the context holds (pairs, one role, no plane and no weight is touched), the _weighted calls are
+// k = 1 (gcn10_gpu_set_weights is gcn10_gpu_set_weight_tables with one table), the _storms calls the context's k.
+// The sums kernel has two instantiations, k at run time and k = 0 at compile time, picked from k in its one launch.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 
-#include "gcn10_gpu_internal.hpp"
-#include "gcn10_soil_readers.hpp"
+#include "gcn10_grid_internal.hpp"
 
 using namespace gcn10;
 
@@ -65,14 +65,16 @@ constexpr uint32_t kNoCell = 0xffffffffu;
 struct GridParams {
     const uint8_t *esa;         // strip, W x rows, row major
     SoilView soil;              // soil code bytes, soil row of every strip row
-    const uint8_t *lut[3];      // the CN image; the low and the high plane of the weights (weighted sums only)
+    const uint8_t *image;       // the CN image
     const int32_t *cellx, *celly;
     uint32_t W, rows, ncx, ncy;
     uint32_t chunks, band_rows;
     uint32_t items;             // chunks x bands
     uint32_t sel;               // bit r: raster r is selected
     uint32_t n_conds, conds[2]; // the selected conditions
-    unsigned long long *acc;    // [n_sel][ncy][ncx][2], or [3] with weights
+    uint32_t k;                 // tables of weights, 0 to GCN10_GPU_MAX_WEIGHT_TABLES
+    unsigned long long *acc;    // [n_sel][ncy][ncx][2 + k]
+    const uint8_t *planes;      // [2 k] images: the low and the high plane of table 0, of table 1, ...
 };
 
 // the LDS of a workgroup: 62.3 KiB
@@ -81,8 +83,6 @@ struct GridLds {
     uint32_t sum[9 * kMaxCells], n255[9 * kMaxCells], area[kMaxCells];
     uint32_t cell_lo, cell_hi;
 };
-
-typedef u32x4 u32x4_u __attribute__((aligned(1)));
 
 // 0x80 in every byte of v that is 255
 __device__ __forceinline__ uint32_t ff_bytes(uint32_t v)
@@ -154,15 +154,13 @@ __device__ __forceinline__ void add_row(const uint8_t *lut, const u32x4 &e, cons
 }
 
 // One workgroup's item (chunk, band) for condition `cond`.  PLANE = false: against the CN image, words 0 and 1 of
-// WORDS per (raster, cell).  PLANE = true: against the weight plane `image`, its sums shifted by `shift` into word 2.
-// WORDS = 0: `words` per (raster, cell) and a plane's sums into word `plane_word`, both uniform run-time values that
-// enter the addresses of the flush's atomics only.
-template <bool PLANE, uint32_t WORDS>
+// `words` per (raster, cell).  PLANE = true: against the weight plane `image`, its sums shifted by `shift` into word
+// `plane_word`.  Both are uniform run-time values that enter the addresses of the flush's atomics only.
+template <bool PLANE>
 __device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, const uint32_t item, const uint32_t cond,
-                                         const uint8_t *image, const uint32_t shift, const uint32_t words = WORDS,
-                                         const uint32_t plane_word = 2u)
+                                         const uint8_t *image, const uint32_t shift, const uint32_t words,
+                                         const uint32_t plane_word)
 {
-    const uint32_t n_words = WORDS ? WORDS : words, to_word = WORDS ? 2u : plane_word;
     uint8_t *const lut = lds.lut;
     uint32_t *const sum = lds.sum, *const n255 = lds.n255, *const area = lds.area;
     uint32_t &cell_lo = lds.cell_lo, &cell_hi = lds.cell_hi;
@@ -267,7 +265,7 @@ __device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, cons
             }
             __syncthreads();
             if (PLANE) {
-                // one lane per cell: the plane's sum of every raster, shifted, to word 2
+                // one lane per cell: the plane's sum of every raster, shifted, to its word
                 for (uint32_t lc = threadIdx.x; lc < n_cells; lc += kThreads) {
                     for (uint32_t t = 0; t < 9; t++) {
                         if (!(sel9 & (1u << t)))
@@ -276,14 +274,14 @@ __device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, cons
                         const uint32_t sv = sum[t * kMaxCells + lc];
                         sum[t * kMaxCells + lc] = 0u;
                         if (sv)
-                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * n_words + to_word),
+                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * words + plane_word),
                                       (unsigned long long)sv << shift);
                     }
                 }
             }
             else {
-                // lanes 2i and 2i + 1 add s and n of cell i: a wave's adds are 512 contiguous bytes (with weights: two
-                // words of every three)
+                // lanes 2i and 2i + 1 add s and n of cell i: a wave's adds are 512 contiguous bytes (with k tables:
+                // two words of every 2 + k)
                 for (uint32_t i = threadIdx.x; i < 2u * n_cells; i += kThreads) {
                     const uint32_t lc = i >> 1, word = i & 1u;
                     const uint32_t a = area[lc];
@@ -296,7 +294,7 @@ __device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, cons
                         sum[t * kMaxCells + lc] = 0u;
                         n255[t * kMaxCells + lc] = 0u;
                         if (nv)
-                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * n_words + word),
+                            atomicAdd(p.acc + ((((size_t)q * p.ncy + cur) * p.ncx + c_lo + lc) * words + word),
                                       (unsigned long long)(word ? nv : sv));
                     }
                     area[lc] = 0u;
@@ -326,7 +324,7 @@ __device__ __forceinline__ void sum_item(const GridParams &p, GridLds &lds, cons
     }
 }
 
-// With R roles per item -- the conditions, times three with weights -- workgroups j, j + 8, ..., j + 8 (R - 1) of
+// With R roles per item -- the conditions, times 1 + 2 k with k tables -- workgroups j, j + 8, ..., j + 8 (R - 1) of
 // every 8 R take the roles of one item (chunk, band): consecutive workgroups go to the eight XCDs in turn, so the
 // workgroups that read the same landcover and soil run on the same XCD at about the same time, and its L2 has what
 // the later ones read.  The last 8 R are padded.
@@ -342,141 +340,54 @@ __device__ __forceinline__ bool deal_item(const GridParams &p, uint32_t roles, u
     return item < p.items;      // the same for the whole workgroup
 }
 
+// Roles of an item: (condition, image), the 1 + 2 k images of a condition next to each other -- the CN image, then
+// (low, high) of table 0, 1, ...  TABLES = false is the same kernel with k a compile-time 0: measured, the plain call
+// is 1.5 % slower at cells of 25 px with k = 0 at run time (DESIGN.md "Model grid").
+template <bool TABLES>
 __global__ __launch_bounds__(kThreads) void grid_sums_kernel(const GridParams p)
 {
     __shared__ GridLds lds;
-    uint32_t item, which;
-    if (!deal_item(p, p.n_conds, item, which))
-        return;
-    sum_item<false, 2u>(p, lds, item, p.conds[which], p.lut[0], 0u);
-}
-
-// roles of an item: (condition, image), the three images of a condition next to each other
-__global__ __launch_bounds__(kThreads) void grid_sums_weighted_kernel(const GridParams p)
-{
-    __shared__ GridLds lds;
-    uint32_t item, role;
-    if (!deal_item(p, 3u * p.n_conds, item, role))
-        return;
-    const uint32_t cond = p.conds[role / 3u], image = role % 3u;
-    if (image == 0u)
-        sum_item<false, 3u>(p, lds, item, cond, p.lut[0], 0u);
-    else
-        sum_item<true, 3u>(p, lds, item, cond, p.lut[image], image == 2u ? 8u : 0u);
-}
-
-// k tables: roles of an item (condition, image), the 1 + 2 k images of a condition next to each other -- the CN image,
-// then (low, high) of table 0, 1, ...
-struct StormParams {
-    GridParams g;               // lut[1], lut[2]: not used
-    const uint8_t *planes;      // [2 k] images: the low and the high plane of table 0, of table 1, ...
-    uint32_t k;
-};
-
-__global__ __launch_bounds__(kThreads) void grid_sums_storms_kernel(const StormParams sp)
-{
-    __shared__ GridLds lds;
-    const GridParams &p = sp.g;
-    const uint32_t per = 1u + 2u * sp.k, words = 2u + sp.k;
+    const uint32_t k = TABLES ? p.k : 0u, per = 1u + 2u * k, words = 2u + k;
     uint32_t item, role;
     if (!deal_item(p, per * p.n_conds, item, role))
         return;
     const uint32_t cond = p.conds[role / per], image = role % per;
     if (image == 0u)
-        sum_item<false, 0u>(p, lds, item, cond, p.lut[0], 0u, words, 0u);
+        sum_item<false>(p, lds, item, cond, p.image, 0u, words, 0u);
     else
-        sum_item<true, 0u>(p, lds, item, cond, sp.planes + (size_t)(image - 1u) * kLut16Bytes,
-                           (image & 1u) ? 0u : 8u, words, 2u + ((image - 1u) >> 1));
+        sum_item<true>(p, lds, item, cond, p.planes + (size_t)(image - 1u) * kLut16Bytes, (image & 1u) ? 0u : 8u,
+                       words, 2u + ((image - 1u) >> 1));
 }
 
 struct FinishParams {
     const unsigned long long *acc;
     size_t n_cells, total;      // cells per raster, and over all rasters
-    uint8_t *means, *cnq;
+    uint8_t *means, *cnq;       // cnq: [k][n_sel][n_cells]
     const uint32_t *shared_idx;
     uint32_t n_shared, n_sel;
     unsigned long long *shared;
-    const uint16_t *weights;    // the context's, on the device (weighted finish only)
-    uint32_t rising;            // weights[1..100] never decrease: bisection finds the smallest c
-};
-
-// the rule of gcn10_runoff_cn (include/gcn10_host.h), with w[0..100] in LDS
-template <bool RISING>
-__device__ __forceinline__ uint8_t runoff_cn(const uint32_t *w, unsigned long long s, unsigned long long n,
-                                             unsigned long long sw)
-{
-    if (n == 0)
-        return (uint8_t)GCN10_NODATA;
-    if (sw == 0)
-        return (uint8_t)((2ull * s + n) / (2ull * n));
-    uint32_t lo = 1u, hi = 100u;
-    if (RISING) {
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (n * w[mid] >= sw)
-                hi = mid;
-            else
-                lo = mid + 1u;
-        }
-    }
-    else {
-        while (lo < hi && n * w[lo] < sw)
-            lo++;
-    }
-    return (uint8_t)lo;
-}
-
-// WORDS = 2: the means and the shared pairs.  WORDS = 3: the means, the runoff-equivalent bytes and the shared triples.
-template <uint32_t WORDS>
-__global__ __launch_bounds__(kThreads) void grid_finish_kernel(const FinishParams p)
-{
-    __shared__ uint32_t w[101];
-    if (WORDS == 3u) {
-        for (uint32_t i = threadIdx.x; i < 101u; i += kThreads)
-            w[i] = p.weights[i];
-        __syncthreads();
-    }
-    const size_t stride = (size_t)gridDim.x * kThreads;
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < p.total; i += stride) {
-        const unsigned long long s = p.acc[WORDS * i], n = p.acc[WORDS * i + 1u];
-        p.means[i] = n == 0 ? (uint8_t)GCN10_NODATA : (uint8_t)((2ull * s + n) / (2ull * n));
-        if (WORDS == 3u) {
-            const unsigned long long sw = p.acc[WORDS * i + 2u];
-            p.cnq[i] = p.rising ? runoff_cn<true>(w, s, n, sw) : runoff_cn<false>(w, s, n, sw);
-        }
-    }
-    const size_t packed = (size_t)p.n_sel * p.n_shared;
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < packed; i += stride) {
-        const size_t q = i / p.n_shared, k = i - q * p.n_shared;
-        const size_t at = q * p.n_cells + p.shared_idx[k];
-#pragma unroll
-        for (uint32_t word = 0; word < WORDS; word++)
-            p.shared[WORDS * i + word] = p.acc[WORDS * at + word];
-    }
-}
-
-// 2 + k words, k runoff-equivalent bytes per cell ([k][n_sel][n_cells]) and the shared cells' 2 + k words
-struct StormFinishParams {
-    FinishParams f;             // weights: [k][256]; rising: bit j for table j
+    const uint16_t *weights;    // [k][256]: the context's, on the device
+    uint32_t rising;            // bit j: weights[j][1..100] never decrease
     uint32_t k;
 };
 
-__global__ __launch_bounds__(kThreads) void grid_finish_storms_kernel(const StormFinishParams sp)
+// 2 + k words per (raster, cell): the means, k runoff-equivalent bytes per cell and the shared cells' 2 + k words
+__global__ __launch_bounds__(kThreads) void grid_finish_kernel(const FinishParams p)
 {
     __shared__ uint32_t w[GCN10_GPU_MAX_WEIGHT_TABLES * 101];
-    const FinishParams &p = sp.f;
-    const uint32_t k = sp.k, words = 2u + k;
+    const uint32_t k = p.k, words = 2u + k;
     for (uint32_t i = threadIdx.x; i < k * 101u; i += kThreads)
         w[i] = p.weights[(i / 101u) * 256u + i % 101u];
     __syncthreads();
     const size_t stride = (size_t)gridDim.x * kThreads;
     for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < p.total; i += stride) {
         const unsigned long long s = p.acc[words * i], n = p.acc[words * i + 1u];
-        p.means[i] = n == 0 ? (uint8_t)GCN10_NODATA : (uint8_t)((2ull * s + n) / (2ull * n));
+        p.means[i] = mean_byte(s, n);
         for (uint32_t j = 0; j < k; j++) {
             const unsigned long long sw = p.acc[words * i + 2u + j];
-            p.cnq[(size_t)j * p.total + i] = (p.rising >> j) & 1u ? runoff_cn<true>(w + 101u * j, s, n, sw)
-                                                                  : runoff_cn<false>(w + 101u * j, s, n, sw);
+            // two copies of the rule: each has one of its loops only
+            p.cnq[(size_t)j * p.total + i] = (p.rising >> j) & 1u ? runoff_cn(w + 101u * j, true, s, n, sw)
+                                                                  : runoff_cn(w + 101u * j, false, s, n, sw);
         }
     }
     const size_t packed = (size_t)p.n_sel * p.n_shared;
@@ -488,7 +399,7 @@ __global__ __launch_bounds__(kThreads) void grid_finish_storms_kernel(const Stor
     }
 }
 
-enum SumsKind { kPlain, kWeighted, kStorms };      // pairs; triples of one table; 2 + k words of k tables
+enum SumsKind { kPlain, kWeighted, kStorms };      // the three pairs of calls, as check_weights words its refusals
 
 // the weights a weighted or a storms call needs: E_STATE without them, and for the one-table calls with several
 int check_weights(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind)
@@ -503,6 +414,12 @@ int check_weights(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind)
         return fail(GCN10_E_STATE, "%s: the context has %d weight tables; call %s", who, ctx->n_weights,
                     strstr(who, "finish") ? "gcn10_gpu_grid_finish_storms" : "gcn10_gpu_grid_sums_storms");
     return GCN10_OK;
+}
+
+// the tables of a call that check_weights has let through: none for the plain calls, WHATEVER the context holds
+uint32_t tables_of(const gcn10_gpu_ctx *ctx, SumsKind kind)
+{
+    return kind == kPlain ? 0u : (uint32_t)ctx->n_weights;
 }
 
 int launch_sums(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind, const uint8_t *esa, int W, int rows,
@@ -520,15 +437,14 @@ int launch_sums(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind, const uint8_
         return rc;
     if ((rc = bind_soil(ctx, who, W, s, cj, &p.soil)) != GCN10_OK)
         return rc;
-    if (!esa || !cj || !cellx || !celly || !acc || W <= 0 || rows <= 0 || ncx <= 0 || ncy <= 0)
-        return fail(GCN10_E_INVAL, "%s: bad arguments W=%d rows=%d cells %d x %d (all > 0, no null pointer)", who, W,
-                    rows, ncx, ncy);
+    if ((rc = check_sums_args(who, esa, W, rows, cj, cellx, celly, ncx, ncy, acc)) != GCN10_OK)
+        return rc;
     if ((rc = check_masks(ctx, who, cond_mask, table_mask)) != GCN10_OK)
         return rc;
     p.esa = esa;
-    p.lut[0] = ctx->d_lut16;
-    p.lut[1] = kind == kWeighted ? ctx->d_wlut : nullptr;
-    p.lut[2] = kind == kWeighted ? ctx->d_wlut + kLut16Bytes : nullptr;
+    p.image = ctx->d_lut16;
+    p.k = tables_of(ctx, kind);
+    p.planes = p.k ? ctx->d_wlut : nullptr;
     p.cellx = cellx;
     p.celly = celly;
     p.W = (uint32_t)W;
@@ -536,36 +452,17 @@ int launch_sums(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind, const uint8_
     p.ncx = (uint32_t)ncx;
     p.ncy = (uint32_t)ncy;
     p.acc = acc;
-    uint32_t n_conds = 0;
-    for (uint32_t r = 0; r < GCN10_N_RASTERS; r++)
-        if (selected(r, cond_mask, table_mask))
-            p.sel |= 1u << r;
-    for (uint32_t cnd = 0; cnd < 2; cnd++)
-        if ((p.sel >> (9u * cnd)) & 0x1ffu)
-            p.conds[n_conds++] = cnd;
-    const uint32_t k = kind == kStorms ? (uint32_t)ctx->n_weights : 1u;
-    const uint32_t roles = kind == kPlain ? n_conds : (1u + 2u * k) * n_conds;
+    p.sel = select_rasters(cond_mask, table_mask, p.conds, p.n_conds);
+    const uint32_t roles = (1u + 2u * p.k) * p.n_conds;
     p.chunks = (p.W + kChunkPx - 1u) / kChunkPx;
-    // bands of at most kMaxBandRows rows, and shorter ones when the strip would not fill the device with them
-    const uint32_t want = grid_cap(ctx, 8) / (p.chunks * roles) + 1u;
-    p.band_rows = min(max((p.rows + want - 1u) / want, 16u), kMaxBandRows);
+    p.band_rows = band_height(ctx, 8, p.chunks * roles, p.rows, 16u, kMaxBandRows);
     const uint64_t items = (uint64_t)((p.rows + p.band_rows - 1u) / p.band_rows) * p.chunks;
     const uint64_t grid = roles > 1u ? (items + 7u) / 8u * (8u * roles) : items;
     if (grid > 0x7fffffffull)
         return fail(GCN10_E_INVAL, "%s: %llu workgroups; cut the strip into bands", who, (unsigned long long)grid);
     p.items = (uint32_t)items;
-    p.n_conds = n_conds;
-    if (kind == kStorms) {
-        StormParams sp = {};
-        sp.g = p;
-        sp.planes = ctx->d_wlut;
-        sp.k = k;
-        hipLaunchKernelGGL(grid_sums_storms_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, sp);
-    }
-    else if (kind == kWeighted)
-        hipLaunchKernelGGL(grid_sums_weighted_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, p);
-    else
-        hipLaunchKernelGGL(grid_sums_kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, p);
+    const auto kernel = p.k ? grid_sums_kernel<true> : grid_sums_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)grid), dim3(kThreads), 0, s, p);
     HIP_TRY(hipGetLastError());
     return GCN10_OK;
 }
@@ -578,14 +475,13 @@ int launch_finish(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind, const unsi
     if (rc)
         return rc;
     hipStream_t s = as_stream(ctx, stream);
-    const bool weighted = kind != kPlain;
     if ((rc = check_weights(ctx, who, kind)) != GCN10_OK)
         return rc;
-    if (!acc || !means || (weighted && !cnq) || n_sel <= 0 || n_sel > GCN10_N_RASTERS || n_cells == 0 ||
-        n_cells > 0xffffffffull || (n_shared && (!shared_idx || !shared)))
-        return fail(GCN10_E_INVAL, "%s: bad arguments n_sel=%d n_cells=%zu n_shared=%u (1..%d rasters, 1..2^32-1 "
-                    "cells, no null pointer)", who, n_sel, n_cells, n_shared, GCN10_N_RASTERS);
     FinishParams p = {};
+    p.k = tables_of(ctx, kind);
+    rc = check_finish_args(who, acc, n_sel, n_cells, means, shared_idx, n_shared, shared, !p.k || cnq);
+    if (rc != GCN10_OK)
+        return rc;
     p.acc = acc;
     p.n_cells = n_cells;
     p.total = n_cells * (size_t)n_sel;
@@ -595,19 +491,10 @@ int launch_finish(gcn10_gpu_ctx *ctx, const char *who, SumsKind kind, const unsi
     p.n_shared = n_shared;
     p.n_sel = (uint32_t)n_sel;
     p.shared = shared;
-    p.weights = weighted ? reinterpret_cast<const uint16_t *>(ctx->d_wlut + 2 * ctx->n_weights * kLut16Bytes) : nullptr;
+    p.weights = p.k ? reinterpret_cast<const uint16_t *>(ctx->d_wlut + 2 * p.k * kLut16Bytes) : nullptr;
     p.rising = ctx->weights_rising;
     const uint32_t grid = stream_grid(ctx, (p.total + kThreads - 1u) / kThreads);
-    if (kind == kStorms) {
-        StormFinishParams sp = {};
-        sp.f = p;
-        sp.k = (uint32_t)ctx->n_weights;
-        hipLaunchKernelGGL(grid_finish_storms_kernel, dim3(grid), dim3(kThreads), 0, s, sp);
-    }
-    else if (weighted)
-        hipLaunchKernelGGL(grid_finish_kernel<3u>, dim3(grid), dim3(kThreads), 0, s, p);
-    else
-        hipLaunchKernelGGL(grid_finish_kernel<2u>, dim3(grid), dim3(kThreads), 0, s, p);
+    hipLaunchKernelGGL(grid_finish_kernel, dim3(grid), dim3(kThreads), 0, s, p);
     HIP_TRY(hipGetLastError());
     return GCN10_OK;
 }
@@ -650,14 +537,9 @@ int fold_weights(gcn10_gpu_ctx *ctx, const char *who, const uint16_t *w, int k)
     free(img);
     HIP_TRY(e);
     ctx->weights_rising = 0u;
-    for (int j = 0; j < k; j++) {
-        bool rising = true;
-        for (int c = 2; c <= 100; c++)
-            if (w[256 * j + c] < w[256 * j + c - 1])
-                rising = false;
-        if (rising)
+    for (int j = 0; j < k; j++)
+        if (never_decreases(w + 256 * j))
             ctx->weights_rising |= 1u << j;
-    }
     ctx->n_weights = k;
     ctx->weights_set = true;
     return GCN10_OK;

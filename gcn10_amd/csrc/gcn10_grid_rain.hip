@@ -30,9 +30,8 @@
 #include <cstdint>
 #include <cstring>
 
-#include "gcn10_gpu_internal.hpp"
+#include "gcn10_grid_internal.hpp"
 #include "gcn10_pair_hist.hpp"
-#include "gcn10_soil_readers.hpp"
 
 using namespace gcn10;
 using namespace gcn10::pair_hist;
@@ -63,8 +62,6 @@ struct RainParams {
     uint32_t n_conds, conds[2];     // the selected conditions
     unsigned long long *acc;        // [n_sel][ncy][ncx][3]
 };
-
-typedef u32x4 u32x4_u __attribute__((aligned(1)));
 
 // The run of equal entries of `map` that begins at i < end: its value, and where it ends (<= end).  Called by the whole
 // wave with the same arguments.
@@ -264,31 +261,6 @@ struct RainFinishParams {
     uint32_t n_tables;
 };
 
-// the rule of gcn10_runoff_cn (include/gcn10_host.h) against a table in global memory
-__device__ __forceinline__ uint8_t runoff_cn(const uint16_t *w, bool rising, unsigned long long s, unsigned long long n,
-                                             unsigned long long sw)
-{
-    if (n == 0)
-        return (uint8_t)GCN10_NODATA;
-    if (sw == 0)
-        return (uint8_t)((2ull * s + n) / (2ull * n));
-    uint32_t lo = 1u, hi = 100u;
-    if (rising) {
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (n * w[mid] >= sw)
-                hi = mid;
-            else
-                lo = mid + 1u;
-        }
-    }
-    else {
-        while (lo < hi && n * w[lo] < sw)
-            lo++;
-    }
-    return (uint8_t)lo;
-}
-
 // blockIdx.y: the raster; a thread: a cell, and a shared cell
 __global__ __launch_bounds__(kFinishThreads) void grid_finish_rain_kernel(const RainFinishParams p)
 {
@@ -298,7 +270,7 @@ __global__ __launch_bounds__(kFinishThreads) void grid_finish_rain_kernel(const 
         const unsigned long long s = a[0], n = a[1], sw = a[2];
         const uint32_t tb = p.cell_table[i], t = tb < p.n_tables ? tb : 0u;
         const uint8_t *const rising = reinterpret_cast<const uint8_t *>(p.tables + 256u * p.n_tables);
-        p.means[q * p.n_cells + i] = n == 0 ? (uint8_t)GCN10_NODATA : (uint8_t)((2ull * s + n) / (2ull * n));
+        p.means[q * p.n_cells + i] = mean_byte(s, n);
         p.cnq[q * p.n_cells + i] = runoff_cn(p.tables + 256u * t, rising[t] != 0, s, n, sw);
     }
     if (i < p.n_shared) {
@@ -342,12 +314,8 @@ int gcn10_gpu_set_rain_tables(gcn10_gpu_ctx *ctx, const uint16_t *w, int k)
     // the tables, then the "never decreases over 1..100" byte of each
     const size_t table_bytes = 256 * sizeof(uint16_t);
     uint8_t rising[GCN10_GPU_MAX_RAIN_TABLES];
-    for (int j = 0; j < k; j++) {
-        rising[j] = 1;
-        for (int c = 2; c <= 100; c++)
-            if (w[256 * j + c] < w[256 * j + c - 1])
-                rising[j] = 0;
-    }
+    for (int j = 0; j < k; j++)
+        rising[j] = never_decreases(w + 256 * j);
     ctx->n_rain_tables = 0;
     if (!ctx->d_rain_tables)            // once, for the most tables a context takes
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ctx->d_rain_tables),
@@ -377,9 +345,8 @@ int gcn10_gpu_grid_sums_rain(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int 
         return rc;
     if ((rc = bind_soil(ctx, who, W, s, cj, &p.soil)) != GCN10_OK)
         return rc;
-    if (!esa || !cj || !cellx || !celly || !cell_table || !acc || W <= 0 || rows <= 0 || ncx <= 0 || ncy <= 0)
-        return fail(GCN10_E_INVAL, "%s: bad arguments W=%d rows=%d cells %d x %d (all > 0, no null pointer)", who, W,
-                    rows, ncx, ncy);
+    if ((rc = check_sums_args(who, esa, W, rows, cj, cellx, celly, ncx, ncy, acc, cell_table != nullptr)) != GCN10_OK)
+        return rc;
     if ((rc = check_masks(ctx, who, cond_mask, table_mask)) != GCN10_OK)
         return rc;
     // the LDS a workgroup may take, from the device
@@ -400,16 +367,9 @@ int gcn10_gpu_grid_sums_rain(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int 
     p.ncx = (uint32_t)ncx;
     p.ncy = (uint32_t)ncy;
     p.acc = acc;
-    for (uint32_t r = 0; r < GCN10_N_RASTERS; r++)
-        if (selected(r, cond_mask, table_mask))
-            p.sel |= 1u << r;
-    for (uint32_t cnd = 0; cnd < 2; cnd++)
-        if ((p.sel >> (9u * cnd)) & 0x1ffu)
-            p.conds[p.n_conds++] = cnd;
+    p.sel = select_rasters(cond_mask, table_mask, p.conds, p.n_conds);
     p.chunks = (p.W + kItemCols - 1u) / kItemCols;
-    // bands of at most kItemRows rows, and shorter ones when the strip would not fill the device with them
-    const uint32_t want = grid_cap(ctx, 16) / p.chunks + 1u;
-    p.band_rows = min(max((p.rows + want - 1u) / want, kMinBandRows), kItemRows);
+    p.band_rows = band_height(ctx, 16, p.chunks, p.rows, kMinBandRows, kItemRows);
     const uint64_t grid = (uint64_t)((p.rows + p.band_rows - 1u) / p.band_rows) * p.chunks;
     if (grid > 0x7fffffffull)
         return fail(GCN10_E_INVAL, "%s: %llu workgroups; cut the strip into bands", who, (unsigned long long)grid);
@@ -429,10 +389,9 @@ int gcn10_gpu_grid_finish_rain(gcn10_gpu_ctx *ctx, const unsigned long long *acc
     hipStream_t s = as_stream(ctx, stream);
     if ((rc = check_rain_tables(ctx, who)) != GCN10_OK)
         return rc;
-    if (!acc || !cell_table || !means || !cnq || n_sel <= 0 || n_sel > GCN10_N_RASTERS || n_cells == 0 ||
-        n_cells > 0xffffffffull || (n_shared && (!shared_idx || !shared)))
-        return fail(GCN10_E_INVAL, "%s: bad arguments n_sel=%d n_cells=%zu n_shared=%u (1..%d rasters, 1..2^32-1 "
-                    "cells, no null pointer)", who, n_sel, n_cells, n_shared, GCN10_N_RASTERS);
+    rc = check_finish_args(who, acc, n_sel, n_cells, means, shared_idx, n_shared, shared, cell_table && cnq);
+    if (rc != GCN10_OK)
+        return rc;
     RainFinishParams p = {};
     p.acc = acc;
     p.n_cells = n_cells;

@@ -417,6 +417,8 @@ int gcn10_gpu_aggregate(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows,
  *   the pair {s, n} = acc[q * n_cells + c] of every raster q < n_sel and cell c < n_cells, and the pairs of the
  *   n_shared cells shared_idx_dev names, packed: shared[q * n_shared + i] = acc[q * n_cells + shared_idx[i]]
  *   (shared_idx[i] < n_cells is the caller's to guarantee; n_shared == 0: both pointers may be NULL).
+ * Neither reads weights: on a context that holds weight tables (below) both still work on pairs.  One sums kernel and
+ *   one finish kernel serve these two calls (no table), the _weighted calls (one) and the _storms calls (k).
  * GCN10_E_INVAL: the masks, W, rows, ncx or ncy <= 0, a null pointer (grid_sums); n_sel outside 1..18, n_cells == 0 or
  *   >= 2^32, a null pointer (grid_finish).  GCN10_E_STATE: grid_sums without tables or without a tile prepared for
  *   width W, as gcn10_gpu_aggregate (grid_finish reads no tile).  Asynchronous on `stream`. */

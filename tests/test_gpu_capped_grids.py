@@ -23,8 +23,8 @@ the wave's 32-bit sum is 4 261 347 840, and against a closed form that is itself
 
 Not reached: bands of 256 rows (kMaxBandRows) at block width.  At the 36001 columns of a block they take about 350 Mpx
 in one call, and no short test can hold that; the 36001-wide test here reaches bands of 20 rows, the first regime above
-the floor of 16, in the weighted kernel only (the unweighted launch of the same strip has a third of the roles and
-stays at the floor).  Both kernels' band arithmetic up to the clamp at 256 rows is run on a strip of 17 columns, where a
+the floor of 16, in the weighted launch only (the unweighted launch of the same strip has a third of the roles and
+stays at the floor).  Both launches' band arithmetic up to the clamp at 256 rows is run on a strip of 17 columns, where a
 band is short -- and where a chunk's 32-bit sums stay far from the bound that 4096 columns x 256 rows come near.
 """
 import time
@@ -192,7 +192,7 @@ def band_rows(W, rows, roles, cus):
 
 
 def bands_shape(cus):
-    """grid_sums_weighted_kernel over a 36001-wide strip, both conditions (6 roles): the fewest rows with bands of 20"""
+    """grid_sums_kernel, one table, over a 36001-wide strip, both conditions (6 roles): the fewest rows with bands of 20"""
     s = types.SimpleNamespace(W=36001, roles=6, chunks=ceil_div(36001, GRID_CHUNK))
     want = grid_cap(cus, GRID_PER_CU) // (s.chunks * s.roles) + 1
     s.rows = 19 * want + 1

@@ -17,9 +17,9 @@ from tests import aggutil as au
 from tests import gridutil as gu
 from tests import runoffutil as ru
 from tests import stormutil as su
-from tests.test_gpu_aggregate import Inputs, inputs, scene  # noqa: F401  (the recipe, its cache and the fixture)
+from tests.test_gpu_aggregate import Inputs, Scene, inputs, scene  # noqa: F401  (the recipe, its cache and the fixture)
 from tests.test_gpu_capped_grids import band_rows, cus, finish_shape, triple_pool  # noqa: F401  (shape rules, fixture)
-from tests.test_gpu_grid import GUARD, POISON, ROWS, WORKGROUP_PX, maps, run_sums
+from tests.test_gpu_grid import GUARD, POISON, ROWS, WORKGROUP_PX, maps, run_finish, run_sums, want_sums
 from tests.test_gpu_grid_runoff import Q50, run_weighted
 from tests.test_runoff_host import hand_made_triples
 
@@ -423,3 +423,44 @@ def test_state_and_errors(tables):
     finally:
         eng.sync()
         eng.close()
+
+
+# ---- 8. the plain calls on a context that holds tables ---------------------------------------------------------------
+
+def test_the_plain_calls_take_no_table_from_the_context(tables):
+    """One sums kernel and one finish kernel serve 0 to 8 tables through one launch each, and gcn10_gpu_grid_sums /
+    gcn10_gpu_grid_finish are k = 0 whatever the context holds: on a context with eight tables set, slot 0 all 65535,
+    they write the pairs, the means and the packed pairs of a fresh context on which no weights were ever set, and not
+    a byte around them (run_sums and run_finish hold the guards; grid_finish is given no cnq).  A call that took the
+    context's k would write 10 words per (raster, cell) and 8 bytes per cell more."""
+    inp = inputs(("grid", 1041), 1041, ROWS, 25, 70 + 1041, tables)
+    cellx, celly = maps(1041, ROWS, 8, 8, (5, 3), (3, 2))
+    ws = su.table_set(8, su.ORDER.index("all 65535"))
+    assert (ws[0] == 65535).all()
+    rng = np.random.default_rng(31)
+    n = rng.integers(1, 1 << 33, (2, 300))                  # sums beyond 32 bits, means of 0 .. 254
+    pairs = np.stack([n * rng.integers(0, 255, (2, 300)) + rng.integers(0, 1 << 33, (2, 300)) % n, n], axis=-1)
+    pairs[:, ::7, 1] = 0                                    # cells without a value
+    pairs[:, 1::7, 0] = 5 * pairs[:, 1::7, 1] // 2          # exact halves, which round up, where n is even
+    got = []
+    for with_tables in (False, True):
+        eng = gpu.Engine(0)
+        try:
+            sc = Scene(eng, inp)
+            try:
+                if with_tables:
+                    eng.set_weight_tables(ws)
+                got.append([run_sums(sc, cellx, celly)] + [run_finish(eng, pairs, idx) for idx in ([0, 299, 7, 7], [])])
+            finally:
+                sc.close()
+        finally:
+            eng.sync()
+            eng.close()
+    fresh, held = got
+    np.testing.assert_array_equal(fresh[0], want_sums(inp, cellx, celly))
+    np.testing.assert_array_equal(held[0], fresh[0])
+    for (means, shared), (means0, shared0), idx in zip(held[1:], fresh[1:], ([0, 299, 7, 7], [])):
+        np.testing.assert_array_equal(means0, gu.means(pairs))
+        np.testing.assert_array_equal(shared0, pairs[:, idx, :])
+        np.testing.assert_array_equal(means, means0)
+        np.testing.assert_array_equal(shared, shared0)

@@ -92,6 +92,14 @@ inline int check_finish_args(const char *who, const unsigned long long *acc, int
     return GCN10_OK;
 }
 
+// GCN10_E_STATE unless gcn10_gpu_set_rain_tables has run (gcn10_grid_rain.hip, gcn10_zonal_rain.hip)
+inline int check_rain_tables(gcn10_gpu_ctx *ctx, const char *who)
+{
+    if (ctx->n_rain_tables < 1)
+        return fail(GCN10_E_STATE, "%s: call gcn10_gpu_set_rain_tables first", who);
+    return GCN10_OK;
+}
+
 // Rows of a band: at most `cap`, and fewer (`floor` at least) when the strip would not fill the device -- per_cu
 // workgroups on every compute unit -- with bands that tall; n: the workgroups of one band
 inline uint32_t band_height(const gcn10_gpu_ctx *ctx, int per_cu, uint32_t n, uint32_t rows, uint32_t floor,

@@ -76,12 +76,6 @@ __device__ __forceinline__ uint32_t run_end(const int32_t *map, uint32_t i, uint
     }
 }
 
-// the soil code of a bin of the pair histogram (gcn10_gpu_pair_histogram_codes)
-__device__ __forceinline__ uint32_t bin_code(uint32_t bin)
-{
-    return bin < 6u ? bin * 0x11u : bin < 9u ? 4u | (bin - 5u) << 4 : 0x55u;
-}
-
 // a unit of a piece: the 16-column group at gx of strip row y, of which the piece has columns [a, b)
 struct Unit {
     u32x4 e, s;
@@ -280,13 +274,6 @@ __global__ __launch_bounds__(kFinishThreads) void grid_finish_rain_kernel(const 
         to[1] = a[1];
         to[2] = a[2];
     }
-}
-
-int check_rain_tables(gcn10_gpu_ctx *ctx, const char *who)
-{
-    if (ctx->n_rain_tables < 1)
-        return fail(GCN10_E_STATE, "%s: call gcn10_gpu_set_rain_tables first", who);
-    return GCN10_OK;
 }
 
 }  // namespace

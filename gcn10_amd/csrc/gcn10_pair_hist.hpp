@@ -1,5 +1,5 @@
 // gcn10_pair_hist.hpp -- the pieces the pair-histogram kernels share (gcn10_stats.hip: a whole strip;
-// gcn10_zonal.hip: the spans of zones): the bin of a soil code, the key of a pixel, and the run folding of a
+// gcn10_zonal.hip and gcn10_zonal_rain.hip: the spans of zones; gcn10_grid_rain.hip: the cells of a grid): the bin of a soil code, the key of a pixel, and the run folding of a
 // lane's 16 pixels.  Why runs are folded: header comment of gcn10_stats.hip.
 #ifndef GCN10_PAIR_HIST_HPP
 #define GCN10_PAIR_HIST_HPP
@@ -25,6 +25,12 @@ __host__ __device__ inline uint32_t code_bin(uint32_t code)
     const uint32_t d = code & 15u, u = code >> 4;
     const uint32_t b = d == u ? d : 5u + u;
     return b < (uint32_t)kBins ? b : (uint32_t)kBins - 1u;
+}
+
+// the soil code of a bin (gcn10_gpu_pair_histogram_codes): the inverse of code_bin on the bins a code maps to
+__host__ __device__ inline uint32_t bin_code(uint32_t bin)
+{
+    return bin < 6u ? bin * 0x11u : bin < 9u ? 4u | (bin - 5u) << 4 : 0x55u;
 }
 
 // key of pixel i of a lane: landcover in bits 0..7, soil code in bits 8..15

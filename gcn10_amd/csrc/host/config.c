@@ -353,6 +353,20 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             }
             rc = set_str(&cfg->rain_unit, val);
         }
+        else if (!strcmp(key, "zone_rain"))
+            rc = set_str(&cfg->zone_rain, val);
+        else if (!strcmp(key, "zone_rain_unit")) {
+            double unit, lambda;
+
+            if (gcn10_parse_rain_unit(val, &unit, &lambda) != 0) {
+                fclose(f);
+                snprintf(err, errcap, "bad value for zone_rain_unit: '%s' (unit[,lambda]: 0 < unit, 255 unit <= 650 mm, "
+                                      "0 <= lambda < 1)", val);
+                gcn10_config_free(cfg);
+                return -3;
+            }
+            rc = set_str(&cfg->zone_rain_unit, val);
+        }
         else if (!strcmp(key, "zones_shp_path"))
             rc = set_str(&cfg->zones_shp_path, val);
         else if (!strcmp(key, "zonal_output"))
@@ -414,5 +428,7 @@ void gcn10_config_free(gcn10_config *cfg)
     free(cfg->storms);
     free(cfg->rain);
     free(cfg->rain_unit);
+    free(cfg->zone_rain);
+    free(cfg->zone_rain_unit);
     memset(cfg, 0, sizeof *cfg);
 }

@@ -280,6 +280,44 @@ int gcn10_rain_load(const char *path, const gcn10_grid *g, uint8_t **out, char *
     return 0;
 }
 
+int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char *err, size_t errcap)
+{
+    char why[1024] = "";
+    gcn10_raster *ra = gcn10_raster_open(path, NULL, why, sizeof why);
+    const double none[6] = { 0.0, 1.0, 0.0, 0.0, 0.0, 1.0 };       /* what the reader reports without georeferencing */
+    double gt[6];
+    uint8_t *bytes;
+    int w, h;
+
+    *out = NULL;
+    memset(grid, 0, sizeof *grid);
+    if (!ra) {
+        snprintf(err, errcap, "zone_rain: cannot read '%s': %s", path, why);
+        return -1;
+    }
+    gcn10_raster_info(ra, &w, &h, gt);
+    if (memcmp(gt, none, sizeof none) == 0)
+        snprintf(err, errcap, "zone_rain: '%s' carries no geotransform", path);
+    else if (!(gt[1] > 0.0) || !(gt[5] < 0.0) || gt[2] != 0.0 || gt[4] != 0.0 || !isfinite(gt[0]) || !isfinite(gt[3]) ||
+             !isfinite(gt[1]) || !isfinite(gt[5]))
+        snprintf(err, errcap, "zone_rain: '%s' is rotated or not north up", path);
+    else if (w < 1 || h < 1 || (uint64_t)w * (uint64_t)h > (uint64_t)GCN10_GRID_MAX_CELLS)
+        snprintf(err, errcap, "zone_rain: '%s' has more than %d pixels", path, GCN10_GRID_MAX_CELLS);
+    else {
+        bytes = malloc((size_t)w * (size_t)h);
+        if (!bytes || gcn10_raster_read(ra, 0, 0, w, h, bytes, why, sizeof why) != 0) {
+            snprintf(err, errcap, "zone_rain: cannot read '%s': %s", path, bytes ? why : "out of memory");
+            free(bytes);
+        }
+        else {
+            *grid = (gcn10_grid){ gt[0], gt[3], gt[1], -gt[5], w, h };
+            *out = bytes;
+        }
+    }
+    gcn10_raster_close(ra);
+    return *out ? 0 : -1;
+}
+
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* the run                                                                                                           */
 /* ---------------------------------------------------------------------------------------------------------------- */

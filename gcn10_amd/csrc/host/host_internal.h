@@ -191,6 +191,10 @@ struct gcn10_gpu_api {
                           int, int, unsigned, unsigned, const uint8_t *, unsigned long long *, gcn10_stream_t);
     int (*grid_finish_rain)(gcn10_gpu_ctx *, const unsigned long long *, int, size_t, const uint8_t *, uint8_t *,
                             uint8_t *, const uint32_t *, uint32_t, unsigned long long *, gcn10_stream_t);
+    /* optional: NULL when the library has none (needed by zone_rain=... only) */
+    int (*zonal_sums_rain)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const gcn10_zone_span *,
+                           const gcn10_zone_rain_item *, size_t, int, unsigned, unsigned, unsigned long long *,
+                           gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -29,6 +29,7 @@ static void usage(FILE *fp)
             "        [--verify] [--zonal] [--zones <zones.shp>] [--aggregate <f>]\n"
             "        [--grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>] [--storm <P>[,<lambda>]]\n"
             "        [--storms <P1>[:<P2>...][,<lambda>]] [--rain <file> [--rain-unit <unit>[,<lambda>]]]\n"
+            "        [--zone-rain <file> [--zone-rain-unit <unit>[,<lambda>]]]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -80,6 +81,13 @@ static void usage(FILE *fp)
             "  --rain-unit <unit>[,<lambda>]\n"
             "\t\t\tmillimetres per count of --rain (0 < unit, 255 unit <= 650, default 1) and the\n"
             "\t\t\tinitial-abstraction ratio (0 <= lambda < 1, default 0.2; config key rain_unit=...)\n"
+            "  --zone-rain <file>\ta rainfall raster under the zones: a one-band Byte GeoTIFF with its own geotransform\n"
+            "\t\t\t(north up, the landcover's CRS), byte b = b x unit mm of rain.  With --zones, the columns\n"
+            "\t\t\train_pixels,rain_mm,rain_valid,runoff_mm_rain,cn_runoff_rain: every zone's runoff under\n"
+            "\t\t\tthe field, reduced on the GPU, and the CN that yields it with the zone's mean depth\n"
+            "\t\t\t(config key zone_rain=...); needs --zones, not with --storm or --storms\n"
+            "  --zone-rain-unit <unit>[,<lambda>]\n"
+            "\t\t\tas --rain-unit, for --zone-rain (config key zone_rain_unit=...)\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -142,6 +150,10 @@ int main(int argc, char **argv)
             opt.rain = argv[++i];
         else if (!strcmp(argv[i], "--rain-unit") && i + 1 < argc)
             opt.rain_unit = argv[++i];
+        else if (!strcmp(argv[i], "--zone-rain") && i + 1 < argc)
+            opt.zone_rain = argv[++i];
+        else if (!strcmp(argv[i], "--zone-rain-unit") && i + 1 < argc)
+            opt.zone_rain_unit = argv[++i];
         else if (!strcmp(argv[i], "--zonal"))
             opt.zonal = true;
         else if (!strcmp(argv[i], "--zones") && i + 1 < argc) {

@@ -149,6 +149,8 @@ struct block_in {
     gcn10_zone_plan zplan;
     gcn10_aggregate_geom agg;
     gcn10_grid_plan gplan;
+    gcn10_grid_plan zr_gplan;               /* zone_rain: the block on the raster's grid, */
+    gcn10_zone_rain_plan zr_cut;            /* ... and the zones' spans cut at its depth changes */
 };
 
 struct worker {
@@ -286,6 +288,12 @@ struct run {
     double rain_unit, rain_lambda;
     uint8_t *rain;                          /* [ny][nx]: the counts of the rainfall raster (gcn10_rain_load) */
     uint16_t (*rain_q)[256];                /* [256][256]: gcn10_rain_tables */
+    /* zone_rain=...: a rainfall raster under the zones of a zonal run, with its own grid (zonal.c) */
+    bool zone_rain_on;
+    double zone_rain_unit, zone_rain_lambda;
+    gcn10_grid zone_rain_grid;              /* the raster as a grid (gcn10_zone_rain_load) */
+    uint8_t *zone_rain;                     /* [ny][nx]: its counts */
+    uint16_t (*zone_rain_q)[256];           /* [256][256]: gcn10_rain_tables */
 };
 
 double gcn10_now_seconds(void);

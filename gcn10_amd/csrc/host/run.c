@@ -124,6 +124,51 @@ static int resolve(struct run *r)
             return 1;
         }
     }
+    /* a rainfall raster under the zones: what it needs and cannot go with, its unit, and the raster itself -- it carries
+     * its own grid, so it is read here, before anything starts */
+    if (opt->zone_rain) {
+        free(r->cfg.zone_rain);
+        r->cfg.zone_rain = strdup(opt->zone_rain);
+    }
+    if (opt->zone_rain_unit) {
+        free(r->cfg.zone_rain_unit);
+        r->cfg.zone_rain_unit = strdup(opt->zone_rain_unit);
+    }
+    r->zone_rain_on = r->cfg.zone_rain != NULL;
+    if (r->cfg.zone_rain_unit && !r->zone_rain_on) {
+        fprintf(stderr, "[rank 0] zone_rain_unit needs zone_rain\n");
+        return 1;
+    }
+    if (r->zone_rain_on) {
+        if (!r->cfg.zonal && !opt->zonal)
+            why = "zone_rain needs --zones";
+        else if (opt->storm || r->cfg.storm)
+            why = "zone_rain cannot be combined with storm";
+        else if (opt->storms || r->cfg.storms)
+            why = "zone_rain cannot be combined with storms";
+        if (why) {
+            fprintf(stderr, "[rank 0] %s\n", why);
+            return 1;
+        }
+        r->zone_rain_unit = 1.0;
+        r->zone_rain_lambda = 0.2;
+        if (r->cfg.zone_rain_unit &&
+            gcn10_parse_rain_unit(r->cfg.zone_rain_unit, &r->zone_rain_unit, &r->zone_rain_lambda) != 0) {
+            fprintf(stderr, "[rank 0] bad value for zone_rain_unit: '%s' (unit[,lambda]: 0 < unit, 255 unit <= 650 mm, 0 <= "
+                            "lambda < 1)\n", r->cfg.zone_rain_unit);
+            return 1;
+        }
+        if (gcn10_zone_rain_load(r->cfg.zone_rain, &r->zone_rain_grid, &r->zone_rain, err, sizeof err) != 0) {
+            fprintf(stderr, "[rank 0] %s\n", err);
+            return 1;
+        }
+        r->zone_rain_q = malloc(256 * sizeof *r->zone_rain_q);
+        if (!r->zone_rain_q) {
+            fprintf(stderr, "[rank 0] out of memory for the tables of the rainfall raster\n");
+            return 1;
+        }
+        gcn10_rain_tables(r->zone_rain_unit, r->zone_rain_lambda, r->zone_rain_q);
+    }
     /* a zonal run: refused combinations and the zone file */
     if (opt->zones) {
         free(r->cfg.zones_shp_path);
@@ -265,7 +310,7 @@ static int resolve(struct run *r)
 static int require(struct run *r)
 {
     const struct gcn10_gpu_api *g;
-    char err[2048] = "", agg[48], grid[600], storm[600], rain[PATH_MAX + 8];
+    char err[2048] = "", agg[48], grid[600], storm[600], rain[PATH_MAX + 8], zrain[PATH_MAX + 16];
 
     r->gpu = g = gcn10_gpu_api_get(err, sizeof err);
     if (!g) {
@@ -277,6 +322,7 @@ static int require(struct run *r)
     snprintf(storm, sizeof storm, "%s=%s", r->storms_key ? "storms" : "storm",
              r->storms_key ? r->cfg.storms : r->storm_on ? r->cfg.storm : "");
     snprintf(rain, sizeof rain, "rain=%s", r->rain_on ? r->cfg.rain : "");
+    snprintf(zrain, sizeof zrain, "zone_rain=%s", r->zone_rain_on ? r->cfg.zone_rain : "");
     {
         /* the pair histogram's soil codes are asked for where a mode counts pairs, and must be as many as its bins */
         const bool pairs = (r->stats || r->zonal) && g->pair_histogram_codes &&
@@ -284,6 +330,7 @@ static int require(struct run *r)
         const struct { bool on, present; const char *symbol, *needed_by; } needs[] = {
             { r->cog, g->overview_nearest && g->overview_average, "gcn10_gpu_overview_*", "cog=1" },
             { r->stats, g->pair_histogram && pairs, "gcn10_gpu_pair_histogram", "stats=1" },
+            { r->zone_rain_on, g->set_rain_tables && g->zonal_sums_rain, "gcn10_gpu_zonal_sums_rain", zrain },
             { r->zonal, g->zonal_pair_histogram && pairs, "gcn10_gpu_zonal_pair_histogram", "zonal=1" },
             { r->aggregate != 0, g->aggregate != NULL, "gcn10_gpu_aggregate", agg },
             { r->grid_on && r->storm_on && !r->storms_key,
@@ -482,6 +529,22 @@ static int load(struct run *r)
         log0_line(r, "INFO", true, "rain: %s, %d x %d cells, unit = %.17g mm, lambda = %.17g", r->cfg.rain, r->grid.nx,
                   r->grid.ny, r->rain_unit, r->rain_lambda);
         log0_line(r, "INFO", true, "rain: depths %u..%u counts, %zu cells without rain", lo, hi, dry);
+    }
+    if (r->zone_rain_on) {
+        const gcn10_grid *zg = &r->zone_rain_grid;
+        const size_t n = (size_t)zg->nx * (size_t)zg->ny;
+        unsigned lo = 255, hi = 0;
+        size_t dry = 0;
+
+        for (size_t c = 0; c < n; c++) {
+            lo = r->zone_rain[c] < lo ? r->zone_rain[c] : lo;
+            hi = r->zone_rain[c] > hi ? r->zone_rain[c] : hi;
+            dry += r->zone_rain[c] == 0;
+        }
+        log0_line(r, "INFO", true, "zone_rain: %s, %d x %d cells of %.17g x %.17g from (%.17g, %.17g), unit = %.17g mm, "
+                  "lambda = %.17g", r->cfg.zone_rain, zg->nx, zg->ny, zg->dx, zg->dy, zg->xmin, zg->ymax,
+                  r->zone_rain_unit, r->zone_rain_lambda);
+        log0_line(r, "INFO", true, "zone_rain: depths %u..%u counts, %zu cells without rain", lo, hi, dry);
     }
     if (r->n_workers > r->n_blocks) {       /* no worker (and no pinned memory) without a block */
         for (int i = r->n_blocks > 0 ? r->n_blocks : 1; i < r->n_workers; i++) {
@@ -700,6 +763,8 @@ done:
     free(r->verify_failed);
     if (r->mode->end)
         r->mode->end(r);
+    free(r->zone_rain);
+    free(r->zone_rain_q);
     free(r->block_ids);
     gcn10_blocks_free(&r->blocks);
     gcn10_config_free(&r->cfg);

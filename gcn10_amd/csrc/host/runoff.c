@@ -168,3 +168,21 @@ int gcn10_runoff_cn(uint64_t s, uint64_t n, uint64_t sw, const uint16_t q[256])
             return c;
     return 100;
 }
+
+NO_CONTRACT int gcn10_zone_rain_values(uint64_t rain_pixels, uint64_t rain_sum, double unit, double lambda, uint64_t s,
+                                       uint64_t n, uint64_t sw, double *rain_mm, double *runoff_mm, int *cn)
+{
+    uint16_t q[256];
+
+    *rain_mm = *runoff_mm = 0.0;
+    *cn = 255;
+    if (rain_pixels == 0)
+        return 0;
+    *rain_mm = ((double)rain_sum / (double)rain_pixels) * unit;
+    if (n == 0)
+        return 1;
+    *runoff_mm = (double)sw / (double)n / 100.0;
+    gcn10_runoff_table(*rain_mm, lambda, q);
+    *cn = gcn10_runoff_cn(s, n, sw, q);
+    return 3;
+}

@@ -11,6 +11,14 @@
  * (config key "storm", runoff.c) the sum of the storm's runoff table over the valid pixels is added up as well, from the
  * same histograms, and the table gets the columns runoff_mm,cn_runoff; with several storms (config key "storms") one
  * such sum and the columns runoff_mm_p<N>,cn_runoff_p<N> per storm.
+ *
+ * With a rainfall raster under the zones (config key "zone_rain", include/gcn10_host.h "A rainfall raster under the
+ * zones") the depth differs from pixel to pixel of a zone, so no histogram of the zone gives its runoff.  The input side
+ * also plans the block on the raster's grid and cuts the zones' spans where the raster's byte changes
+ * (gcn10_zone_rain_cut); after the histogram pass, which is unchanged, the worker uploads the cut spans and items in
+ * the same kind of batches, clears nz x n_sel triples, runs gcn10_gpu_zonal_sums_rain -- the reduction against the 256
+ * tables happens on the device -- and takes the triples back: 24 bytes per (zone, raster).  The table adds them, and
+ * the cutter's rain_pixels and rain_sum per zone, under its mutex: integers again.
  */
 #include "pipeline_internal.h"
 
@@ -34,12 +42,14 @@ enum { ZONE_BATCH = 1024, SPAN_BATCH = 1 << 20 };
 struct zcell {
     uint64_t pixels, valid, sum, sum2;
     uint64_t runoff[GCN10_MAX_STORMS];      /* per storm, the sum of runoff_q[value] over the valid pixels */
+    uint64_t rain[3];                       /* zone_rain: {s, n, sw} over the valid pixels that lie in a rain cell */
     int min, max;
 };
 
 struct gcn10_zonal_table {
     pthread_mutex_t mu;
     struct zcell *cell;         /* [zones.n][n_sel] */
+    uint64_t *rain_pixels, *rain_sum;       /* zone_rain: [zones.n] pixels in a rain cell, and the sum of their bytes */
     int blocks;                 /* blocks counted */
 };
 
@@ -49,6 +59,12 @@ struct gcn10_zonal_state {
     unsigned long long *h_hist, *d_hist;
     size_t h_spans_cap, d_spans_cap, h_items_cap, d_items_cap, h_hist_cap, d_hist_cap;
     struct zcell *part;                     /* [ZONE_BATCH][n_sel]: a batch, before it goes into the table */
+    /* zone_rain: the cut spans, their items and the triples of a batch */
+    gcn10_zone_span *h_rspans, *d_rspans;
+    gcn10_zone_rain_item *h_ritems, *d_ritems;
+    unsigned long long *h_acc, *d_acc;
+    size_t h_rspans_cap, d_rspans_cap, h_ritems_cap, d_ritems_cap, h_acc_cap, d_acc_cap;
+    bool rain_tables_set;                   /* this worker's context holds the 256 tables */
 };
 
 int gcn10_zonal_start(struct run *r)
@@ -63,8 +79,17 @@ int gcn10_zonal_start(struct run *r)
     t = calloc(1, sizeof *t);
     if (t)
         t->cell = calloc((size_t)(r->zones.n > 0 ? r->zones.n : 1) * (size_t)(r->n_sel > 0 ? r->n_sel : 1), sizeof *t->cell);
-    if (!t || !t->cell) {
+    if (t && t->cell && r->zone_rain_on) {
+        t->rain_pixels = calloc((size_t)(r->zones.n > 0 ? r->zones.n : 1), sizeof *t->rain_pixels);
+        t->rain_sum = calloc((size_t)(r->zones.n > 0 ? r->zones.n : 1), sizeof *t->rain_sum);
+    }
+    if (!t || !t->cell || (r->zone_rain_on && (!t->rain_pixels || !t->rain_sum))) {
         fprintf(stderr, "[rank 0] out of memory for the table of %d zones\n", r->zones.n);
+        if (t) {
+            free(t->cell);
+            free(t->rain_pixels);
+            free(t->rain_sum);
+        }
         free(t);
         gcn10_zones_free(&r->zones);
         return -1;
@@ -92,6 +117,12 @@ static void zonal_teardown(struct worker *w)
         if (z->d_spans) g->free(w->ctx, z->d_spans);
         if (z->d_items) g->free(w->ctx, z->d_items);
         if (z->d_hist) g->free(w->ctx, z->d_hist);
+        if (z->h_rspans) g->host_free(w->ctx, z->h_rspans);
+        if (z->h_ritems) g->host_free(w->ctx, z->h_ritems);
+        if (z->h_acc) g->host_free(w->ctx, z->h_acc);
+        if (z->d_rspans) g->free(w->ctx, z->d_rspans);
+        if (z->d_ritems) g->free(w->ctx, z->d_ritems);
+        if (z->d_acc) g->free(w->ctx, z->d_acc);
     }
     free(z->part);
     free(z);
@@ -116,6 +147,19 @@ static int zonal_plan_block(struct worker *w, struct block_in *in, const double 
     if (gcn10_zones_build_plan(&r->zones, in->gt, in->W, in->H, own, 0, 0, &in->zplan, err, sizeof err) != 0) {
         wlog(w, "ERROR", true, "zonal block %d: %s", in->block_id, err);
         return -1;
+    }
+    if (r->zone_rain_on) {
+        /* the block on the raster's grid -- ownership is in the spans already --, and the spans cut at its bytes */
+        const gcn10_grid *zg = &r->zone_rain_grid;
+
+        gcn10_grid_plan_free(&in->zr_gplan);
+        gcn10_zone_rain_plan_free(&in->zr_cut);
+        if (gcn10_grid_plan_block(zg, in->W, in->H, in->gt, NULL, &in->zr_gplan) != 0 ||
+            gcn10_zone_rain_cut(&in->zplan, in->W, in->H, in->zr_gplan.cellx, in->zr_gplan.celly, in->zr_gplan.cx0,
+                                in->zr_gplan.cy0, r->zone_rain, zg->nx, zg->ny, 0, 0, &in->zr_cut) != 0) {
+            wlog(w, "ERROR", true, "zonal block %d: out of memory for the spans under the rainfall raster", in->block_id);
+            return -1;
+        }
     }
     w->t_zone_plan += gcn10_now_seconds() - t0;
     return 0;
@@ -142,6 +186,7 @@ static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *ce
         gcn10_raster_histogram_sparse(at, n, m, r->hist_codes, r->tables[k % 9], k / 9 == 0, hist);
         c->pixels = c->valid = c->sum = c->sum2 = 0;
         memset(c->runoff, 0, sizeof c->runoff);
+        memset(c->rain, 0, sizeof c->rain);
         c->min = 255;
         c->max = 0;
         for (int v = 0; v < 256; v++) {
@@ -161,6 +206,95 @@ static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *ce
                 c->max = v;
         }
     }
+}
+
+/* zone_rain: the triples of the block's local zones under the rainfall raster, in batches of at most ZONE_BATCH zones
+ * and SPAN_BATCH cut spans (one item at least); the table adds them.  0, or -1: a GPU call failed (the caller logs
+ * it), or memory ran out (logged). */
+static int zonal_rain_block(struct worker *w, struct block_in *in, bool *prepared)
+{
+    struct run *r = w->run;
+    const struct gcn10_gpu_api *g = r->gpu;
+    const gcn10_zone_rain_plan *c = &in->zr_cut;
+    const gcn10_zone_plan *p = &in->zplan;
+    struct gcn10_zonal_table *t = r->zonal_table;
+    struct gcn10_zonal_state *z = w->zonal;
+    const size_t row = (size_t)r->n_sel * 3u;
+
+    if (c->n_items && !z->rain_tables_set) {
+        if (g->set_rain_tables(w->ctx, r->zone_rain_q[0], 256) != 0)
+            return -1;
+        z->rain_tables_set = true;
+    }
+    for (size_t i0 = 0; i0 < c->n_items;) {
+        const size_t s0 = c->items[i0].first_span;
+        const int zone0 = c->spans[s0].zone;
+        size_t i1 = i0, s1 = s0;
+        int nz;
+
+        while (i1 < c->n_items) {
+            const gcn10_zone_rain_item *it = &c->items[i1];
+
+            if (i1 > i0 && (c->spans[it->first_span].zone - zone0 >= ZONE_BATCH ||
+                            it->first_span + it->n_spans - s0 > SPAN_BATCH))
+                break;
+            s1 = (size_t)it->first_span + it->n_spans;
+            i1++;
+        }
+        nz = c->spans[s1 - 1].zone - zone0 + 1;
+
+        if (gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_rspans, &z->h_rspans_cap, (s1 - s0) * sizeof *z->h_rspans) != 0 ||
+            gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_ritems, &z->h_ritems_cap, (i1 - i0) * sizeof *z->h_ritems) != 0 ||
+            gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_acc, &z->h_acc_cap, (size_t)nz * row * sizeof *z->h_acc) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_rspans, &z->d_rspans_cap, (s1 - s0) * sizeof *z->d_rspans) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_ritems, &z->d_ritems_cap, (i1 - i0) * sizeof *z->d_ritems) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_acc, &z->d_acc_cap, (size_t)nz * row * sizeof *z->d_acc) != 0)
+            return -1;
+        for (size_t s = s0; s < s1; s++) {
+            z->h_rspans[s - s0] = c->spans[s];
+            z->h_rspans[s - s0].zone -= zone0;
+        }
+        for (size_t i = i0; i < i1; i++) {
+            z->h_ritems[i - i0] = c->items[i];
+            z->h_ritems[i - i0].first_span -= (uint32_t)s0;
+        }
+        if (!*prepared) {
+            if (g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, in->W, w->s_kernel) != 0)
+                return -1;
+            *prepared = true;
+        }
+        if (g->memcpy_h2d(w->ctx, z->d_rspans, z->h_rspans, (s1 - s0) * sizeof *z->h_rspans, w->s_kernel) != 0 ||
+            g->memcpy_h2d(w->ctx, z->d_ritems, z->h_ritems, (i1 - i0) * sizeof *z->h_ritems, w->s_kernel) != 0 ||
+            g->memset(w->ctx, z->d_acc, 0, (size_t)nz * row * sizeof *z->d_acc, w->s_kernel) != 0 ||
+            g->zonal_sums_rain(w->ctx, in->d_block, in->W, in->H, in->d_cj, z->d_rspans, z->d_ritems, i1 - i0, nz,
+                               r->cond_mask, r->table_mask, z->d_acc, w->s_kernel) != 0 ||
+            g->memcpy_d2h(w->ctx, z->h_acc, z->d_acc, (size_t)nz * row * sizeof *z->h_acc, w->s_kernel) != 0)
+            return -1;
+        {
+            const double t0 = gcn10_now_seconds();
+
+            if (g->stream_sync(w->ctx, w->s_kernel) != 0)
+                return -1;
+            w->t_gpu_wait += gcn10_now_seconds() - t0;
+        }
+        {
+            const double t0 = gcn10_now_seconds();
+
+            pthread_mutex_lock(&t->mu);
+            for (int k = 0; k < nz; k++) {
+                struct zcell *dst = &t->cell[(size_t)p->local_zone[zone0 + k] * (size_t)r->n_sel];
+                const unsigned long long *src = z->h_acc + (size_t)k * row;
+
+                for (int q = 0; q < r->n_sel; q++)
+                    for (int word = 0; word < 3; word++)
+                        dst[q].rain[word] += src[3 * q + word];
+            }
+            pthread_mutex_unlock(&t->mu);
+            w->t_zone_accum += gcn10_now_seconds() - t0;
+        }
+        i0 = i1;
+    }
+    return 0;
 }
 
 static int zonal_block(struct worker *w, struct block_in *in)
@@ -263,6 +397,7 @@ static int zonal_block(struct worker *w, struct block_in *in)
                     dst[q].sum2 += src[q].sum2;
                     for (int j = 0; j < GCN10_MAX_STORMS; j++)
                         dst[q].runoff[j] += src[q].runoff[j];
+                    /* (the rain triples come from the pass of their own below) */
                     if (src[q].valid && src[q].min < dst[q].min)
                         dst[q].min = src[q].min;
                     if (src[q].valid && src[q].max > dst[q].max)
@@ -274,7 +409,13 @@ static int zonal_block(struct worker *w, struct block_in *in)
         }
         i0 = i1;
     }
+    if (r->zone_rain_on && zonal_rain_block(w, in, &prepared) != 0)
+        goto gpu_fail;
     pthread_mutex_lock(&t->mu);
+    for (int k = 0; r->zone_rain_on && k < in->zr_cut.n_local; k++) {
+        t->rain_pixels[p->local_zone[k]] += in->zr_cut.rain_pixels[k];
+        t->rain_sum[p->local_zone[k]] += in->zr_cut.rain_sum[k];
+    }
     t->blocks++;
     pthread_mutex_unlock(&t->mu);
     return 0;
@@ -307,6 +448,8 @@ static int zonal_finish(struct run *r, gcn10_log *log0)
                 fprintf(f, ",runoff_mm,cn_runoff");
             else
                 fprintf(f, ",runoff_mm_p%u,cn_runoff_p%u", (unsigned)r->runoff_q[j][100], (unsigned)r->runoff_q[j][100]);
+        if (r->zone_rain_on)
+            fprintf(f, ",rain_pixels,rain_mm,rain_valid,runoff_mm_rain,cn_runoff_rain");
         fprintf(f, "\n");
         for (int i = 0; i < r->zones.n; i++) {
             if (r->n_sel > 0 && t->cell[(size_t)i * (size_t)r->n_sel].pixels == 0)
@@ -327,14 +470,29 @@ static int zonal_finish(struct run *r, gcn10_log *log0)
                     for (int j = 0; j < n_storms; j++)  /* the zone's mean runoff depth, and the curve number that yields it */
                         fprintf(f, ",%.14g,%d", (double)c->runoff[j] / (double)c->valid / 100.0,
                                 gcn10_runoff_cn(c->sum, c->valid, c->runoff[j], r->runoff_q[j]));
-                    fprintf(f, "\n");
                 }
                 else {
                     fprintf(f, ",,,");
                     for (int j = 0; j < n_storms; j++)
                         fprintf(f, ",,");
-                    fprintf(f, "\n");
                 }
+                if (r->zone_rain_on) {      /* include/gcn10_host.h "A rainfall raster under the zones" */
+                    double rain_mm, runoff_mm;
+                    int cn;
+                    const int have = gcn10_zone_rain_values(t->rain_pixels[i], t->rain_sum[i], r->zone_rain_unit,
+                                                            r->zone_rain_lambda, c->rain[0], c->rain[1], c->rain[2],
+                                                            &rain_mm, &runoff_mm, &cn);
+
+                    fprintf(f, ",%llu,", (unsigned long long)t->rain_pixels[i]);
+                    if (have & 1)
+                        fprintf(f, "%.14g", rain_mm);
+                    fprintf(f, ",%llu,", (unsigned long long)c->rain[1]);
+                    if (have & 2)
+                        fprintf(f, "%.14g,%d", runoff_mm, cn);
+                    else
+                        fprintf(f, ",");
+                }
+                fprintf(f, "\n");
             }
         }
         {
@@ -361,6 +519,8 @@ static void zonal_end(struct run *r)
     if (r->zonal_table) {
         pthread_mutex_destroy(&r->zonal_table->mu);
         free(r->zonal_table->cell);
+        free(r->zonal_table->rain_pixels);
+        free(r->zonal_table->rain_sum);
         free(r->zonal_table);
         r->zonal_table = NULL;
     }
@@ -370,6 +530,8 @@ static void zonal_end(struct run *r)
 static void zonal_plan_free(struct block_in *in)
 {
     gcn10_zone_plan_free(&in->zplan);
+    gcn10_grid_plan_free(&in->zr_gplan);
+    gcn10_zone_rain_plan_free(&in->zr_cut);
 }
 
 const struct gcn10_mode gcn10_mode_zonal = {

@@ -643,3 +643,170 @@ oom:
     free(sc.cross);
     return rc;
 }
+
+/* ---------------------------------------------------------------------------------------------------------------- */
+/* spans cut at the depth changes of a rainfall raster (config key "zone_rain")                                      */
+/* ---------------------------------------------------------------------------------------------------------------- */
+
+void gcn10_zone_rain_plan_free(gcn10_zone_rain_plan *p)
+{
+    free(p->rain_pixels);
+    free(p->rain_sum);
+    free(p->spans);
+    free(p->items);
+    memset(p, 0, sizeof *p);
+}
+
+struct rain_items {
+    gcn10_zone_rain_item *v;
+    size_t n, cap;
+};
+
+static int rain_item_push(struct rain_items *l, uint32_t first, uint32_t n, uint32_t table)
+{
+    if (l->n == l->cap) {
+        const size_t cap = l->cap ? l->cap * 2 : 256;
+        gcn10_zone_rain_item *g = realloc(l->v, cap * sizeof *g);
+
+        if (!g)
+            return -1;
+        l->v = g;
+        l->cap = cap;
+    }
+    l->v[l->n++] = (gcn10_zone_rain_item){ first, n, table, 0 };
+    return 0;
+}
+
+int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t *cellx, const int32_t *celly, int cx0,
+                        int cy0, const uint8_t *rain, int nx, int ny, uint32_t max_span_px, uint32_t max_item_px,
+                        gcn10_zone_rain_plan *out)
+{
+    struct span_list pieces = { NULL, 0, 0 }, cut = { NULL, 0, 0 };     /* a piece's `zone` is its byte */
+    struct rain_items items = { NULL, 0, 0 };
+    gcn10_zone_span *sorted = NULL;
+    size_t sorted_cap = 0;
+    int32_t *next = NULL;       /* next[x]: the first column after x whose entry of cellx differs from cellx[x] */
+    int rc = -1;
+
+    memset(out, 0, sizeof *out);
+    if (W <= 0 || H <= 0 || plan->n_local < 0 || plan->n_spans > 0xffffffffu)
+        return -1;
+    bounds_of(&max_span_px, &max_item_px);
+    out->n_local = plan->n_local;
+    out->rain_pixels = calloc((size_t)plan->n_local + 1, sizeof *out->rain_pixels);
+    out->rain_sum = calloc((size_t)plan->n_local + 1, sizeof *out->rain_sum);
+    if (!out->rain_pixels || !out->rain_sum)
+        goto done;
+    if (!cellx || !celly || !rain || nx <= 0 || ny <= 0 || plan->n_spans == 0) {
+        rc = 0;                 /* a block without rain cells, or without zones */
+        goto done;
+    }
+    next = malloc((size_t)W * sizeof *next);
+    if (!next)
+        goto done;
+    next[W - 1] = W;
+    for (int x = W - 2; x >= 0; x--)
+        next[x] = cellx[x + 1] == cellx[x] ? next[x + 1] : x + 1;
+
+    for (size_t i = 0; i < plan->n_spans;) {
+        const int32_t zone = plan->spans[i].zone;
+        size_t count[257] = { 0 }, j = i;
+
+        /* the pieces of the zone, in the order of its spans: (y, x0) */
+        pieces.n = 0;
+        for (; j < plan->n_spans && plan->spans[j].zone == zone; j++) {
+            const gcn10_zone_span *sp = &plan->spans[j];
+            const uint8_t *row;
+            int32_t run0 = 0, run1 = 0;         /* the open run [run0, run1) of byte runb; empty: none */
+            uint8_t runb = 0;
+            int64_t cy;
+
+            if (sp->y < 0 || sp->y >= H || sp->x0 < 0 || sp->x1 > W || sp->x0 >= sp->x1 || zone < 0 ||
+                zone >= plan->n_local)
+                goto done;
+            cy = (int64_t)celly[sp->y] + cy0;
+            if (celly[sp->y] < 0 || cy >= ny)
+                continue;
+            row = rain + (size_t)cy * (size_t)nx;
+            for (int32_t x = sp->x0; x <= sp->x1;) {
+                const int32_t end = x < sp->x1 ? (next[x] < sp->x1 ? next[x] : sp->x1) : x + 1;
+                const int64_t cx = x < sp->x1 ? (int64_t)cellx[x] + cx0 : -1;
+                const bool in = x < sp->x1 && cellx[x] >= 0 && cx < nx;
+
+                if (in && run1 > run0 && run1 == x && row[cx] == runb) {
+                    run1 = end;         /* a neighbouring cell of equal byte */
+                }
+                else {
+                    if (run1 > run0) {
+                        if (span_push(&pieces, sp->y, run0, run1, runb, 0x40000000u) != 0)
+                            goto done;
+                        count[runb + 1]++;
+                        out->rain_pixels[zone] += (uint64_t)(run1 - run0);
+                        out->rain_sum[zone] += (uint64_t)(run1 - run0) * runb;
+                    }
+                    run0 = run1 = 0;
+                    if (in) {
+                        run0 = x;
+                        run1 = end;
+                        runb = row[cx];
+                    }
+                }
+                x = end;
+            }
+        }
+        i = j;
+        if (pieces.n == 0)
+            continue;
+
+        /* a counting sort on the byte keeps (y, x0) within a byte */
+        if (grow((void **)&sorted, &sorted_cap, pieces.n, sizeof *sorted) != 0)
+            goto done;
+        for (int b = 0; b < 256; b++)
+            count[b + 1] += count[b];
+        for (size_t k = 0; k < pieces.n; k++)
+            sorted[count[pieces.v[k].zone]++] = pieces.v[k];
+
+        /* the zone's spans, never longer than max_span_px, and items of one byte with at most max_item_px pixels */
+        for (size_t k = 0; k < pieces.n;) {
+            const int32_t b = sorted[k].zone;
+            size_t first = cut.n;
+            uint64_t px = 0;
+
+            for (; k < pieces.n && sorted[k].zone == b; k++) {
+                const size_t before = cut.n;
+
+                if (span_push(&cut, sorted[k].y, sorted[k].x0, sorted[k].x1, zone, max_span_px) != 0)
+                    goto done;
+                for (size_t m = before; m < cut.n; m++) {
+                    const uint64_t len = (uint64_t)(cut.v[m].x1 - cut.v[m].x0);
+
+                    if (m > first && px + len > max_item_px) {
+                        if (rain_item_push(&items, (uint32_t)first, (uint32_t)(m - first), (uint32_t)b) != 0)
+                            goto done;
+                        first = m;
+                        px = 0;
+                    }
+                    px += len;
+                }
+            }
+            if (cut.n > 0xffffffffu || rain_item_push(&items, (uint32_t)first, (uint32_t)(cut.n - first), (uint32_t)b) != 0)
+                goto done;
+        }
+    }
+    out->spans = cut.v;
+    out->n_spans = cut.n;
+    out->items = items.v;
+    out->n_items = items.n;
+    cut.v = NULL;
+    items.v = NULL;
+    rc = 0;
+done:
+    if (rc != 0)
+        gcn10_zone_rain_plan_free(out);
+    free(pieces.v);
+    free(cut.v);
+    free(items.v);
+    free(sorted);
+    free(next);
+    return rc;
+}

@@ -152,6 +152,17 @@ def lib():
         L.gcn10_rain_load.restype = C.c_int
         L.gcn10_zone_items_build.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(ZonePlan)]
         L.gcn10_zone_items_build.restype = C.c_int
+        L.gcn10_zone_rain_load.argtypes = [cp, C.POINTER(Grid), C.POINTER(vp), cp, C.c_size_t]
+        L.gcn10_zone_rain_load.restype = C.c_int
+        L.gcn10_zone_rain_values.argtypes = [C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_uint64, C.c_uint64,
+                                             C.c_uint64, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_int)]
+        L.gcn10_zone_rain_values.restype = C.c_int
+        L.gcn10_zone_rain_cut.argtypes = [C.POINTER(ZonePlan), C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, C.c_int,
+                                          C.c_int, C.c_uint32, C.c_uint32, C.POINTER(ZoneRainPlan)]
+        L.gcn10_zone_rain_cut.restype = C.c_int
+        L.gcn10_zone_rain_plan_free.argtypes = [C.POINTER(ZoneRainPlan)]
+        L.gcn10_zone_rain_plan_free.restype = None
         L.gcn10_tiff_abort.argtypes = [vp]
         L.gcn10_tiff_abort.restype = None
         L.free_ = C.CDLL(None).free
@@ -210,6 +221,12 @@ class ConfigRain(ConfigStorms):
     _fields_ = [("rain", C.c_char_p), ("rain_unit", C.c_char_p)]
 
 
+class ConfigZoneRain(ConfigRain):
+    """``gcn10_config`` with the keys of the rainfall raster under zones, appended behind ``ConfigRain`` as the C struct
+    appends them."""
+    _fields_ = [("zone_rain", C.c_char_p), ("zone_rain_unit", C.c_char_p)]
+
+
 assert C.sizeof(Config) % 8 == 0
 
 
@@ -236,6 +253,12 @@ class ZonePlan(C.Structure):
                 ("n_spans", C.c_size_t), ("n_items", C.c_size_t), ("spans", C.c_void_p), ("items", C.c_void_p)]
 
 
+class ZoneRainPlan(C.Structure):
+    """``gcn10_zone_rain_plan`` of include/gcn10_host.h."""
+    _fields_ = [("n_local", C.c_int), ("rain_pixels", C.POINTER(C.c_uint64)), ("rain_sum", C.POINTER(C.c_uint64)),
+                ("n_spans", C.c_size_t), ("n_items", C.c_size_t), ("spans", C.c_void_p), ("items", C.c_void_p)]
+
+
 class AggregateGeom(C.Structure):
     """``gcn10_aggregate_geom`` of include/gcn10_host.h."""
     _fields_ = [("x0", C.c_int), ("x1", C.c_int), ("y0", C.c_int), ("y1", C.c_int), ("Wa", C.c_int), ("Ha", C.c_int),
@@ -259,6 +282,8 @@ class GridPlan(C.Structure):
 # struct gcn10_zone_span / gcn10_zone_item (include/gcn10_host.h, include/gcn10_gpu.h)
 ZONE_SPAN_DTYPE = np.dtype([("y", "<i4"), ("x0", "<i4"), ("x1", "<i4"), ("zone", "<i4")])
 ZONE_ITEM_DTYPE = np.dtype([("first_span", "<u4"), ("n_spans", "<u4")])
+# struct gcn10_zone_rain_item
+ZONE_RAIN_ITEM_DTYPE = np.dtype([("first_span", "<u4"), ("n_spans", "<u4"), ("table", "<u4"), ("reserved", "<u4")])
 
 
 class HostError(RuntimeError):
@@ -467,16 +492,74 @@ def rain_load(path: str, grid) -> np.ndarray:
         lib().free_(out)
 
 
+def zone_rain_load(path: str):
+    """The rainfall raster of a zonal run: (grid, bytes) -- the raster as a model grid (the dict of parse_grid) and
+    uint8[ny][nx] (``gcn10_zone_rain_load``); raises HostError with the run's refusal text."""
+    g = Grid()
+    out = C.c_void_p()
+    err = C.create_string_buffer(4096 + 512)
+    if lib().gcn10_zone_rain_load(os.fsencode(path), C.byref(g), C.byref(out), err, len(err)) != 0:
+        raise HostError(err.value.decode(errors="replace"))
+    try:
+        grid = {name: getattr(g, name) for name, _t in Grid._fields_}
+        n = g.nx * g.ny
+        return grid, np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), (n,)).copy().reshape(g.ny, g.nx)
+    finally:
+        lib().free_(out)
+
+
+def zone_rain_values(rain_pixels: int, rain_sum: int, unit: float, lam: float, s: int, n: int, sw: int):
+    """(rain_mm, runoff_mm_rain, cn_runoff_rain) of one row of the zonal table under a rainfall raster, None where the
+    table leaves the field empty (``gcn10_zone_rain_values``)."""
+    mm, ro, cn = C.c_double(), C.c_double(), C.c_int()
+    f = lib().gcn10_zone_rain_values(int(rain_pixels), int(rain_sum), float(unit), float(lam), int(s), int(n), int(sw),
+                                     C.byref(mm), C.byref(ro), C.byref(cn))
+    return (mm.value if f & 1 else None, ro.value if f & 2 else None, cn.value if f & 2 else None)
+
+
+def zone_rain_cut(plan: dict, W: int, H: int, gplan: dict, rain, max_span_px: int = 0, max_item_px: int = 0,
+                  n_local: int | None = None) -> dict:
+    """The spans of a block's zone plan (the dict of Zones.build_plan, or anything with ``spans``) cut where the byte of
+    the rainfall raster changes (``gcn10_zone_rain_cut``).  gplan: the dict of grid_plan_block for the block on the
+    raster's grid; rain: uint8[ny][nx].  ``spans`` (ZONE_SPAN_DTYPE, sorted by (zone, byte, y, x0)), ``items``
+    (ZONE_RAIN_ITEM_DTYPE), ``rain_pixels`` and ``rain_sum`` (uint64 per local zone)."""
+    sp = np.ascontiguousarray(plan["spans"], dtype=ZONE_SPAN_DTYPE)
+    if n_local is None:
+        n_local = len(plan["local_zone"]) if "local_zone" in plan else (int(sp["zone"].max()) + 1 if sp.size else 0)
+    zp = ZonePlan()
+    zp.n_local = int(n_local)
+    zp.n_spans = sp.size
+    zp.spans = sp.ctypes.data if sp.size else None
+    r = np.ascontiguousarray(rain, dtype=np.uint8)
+    cellx = np.ascontiguousarray(gplan["cellx"], dtype=np.int32)
+    celly = np.ascontiguousarray(gplan["celly"], dtype=np.int32)
+    if (cellx.size not in (0, W)) or (celly.size not in (0, H)) or r.ndim != 2:
+        raise ValueError("cellx / celly must have W / H entries (or none), the raster two dimensions")
+    out = ZoneRainPlan()
+    rc = lib().gcn10_zone_rain_cut(C.byref(zp), int(W), int(H), cellx.ctypes.data if cellx.size else None,
+                                   celly.ctypes.data if celly.size else None, int(gplan["cx0"]), int(gplan["cy0"]),
+                                   r.ctypes.data, r.shape[1], r.shape[0], int(max_span_px), int(max_item_px),
+                                   C.byref(out))
+    if rc != 0:
+        raise HostError("gcn10_zone_rain_cut: a span outside the block, a zone outside the plan, or out of memory")
+    res = {"spans": _copy(out.spans, out.n_spans, ZONE_SPAN_DTYPE),
+           "items": _copy(out.items, out.n_items, ZONE_RAIN_ITEM_DTYPE),
+           "rain_pixels": _copy(out.rain_pixels, out.n_local, np.uint64),
+           "rain_sum": _copy(out.rain_sum, out.n_local, np.uint64)}
+    lib().gcn10_zone_rain_plan_free(C.byref(out))
+    return res
+
+
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = ConfigRain()
+    cfg = ConfigZoneRain()
     err = C.create_string_buffer(1024)
     rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
     out = {}
     for name, _t in (Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_ + ConfigStorm._fields_ +
-                     ConfigStorms._fields_ + ConfigRain._fields_):
+                     ConfigStorms._fields_ + ConfigRain._fields_ + ConfigZoneRain._fields_):
         v = getattr(cfg, name)
         out[name] = v.decode() if isinstance(v, bytes) else list(v) if isinstance(v, C.Array) else v
     lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))

@@ -45,7 +45,8 @@ extern "C" {
  *    weighted forms (gcn10_gpu_set_weights, gcn10_gpu_grid_sums_weighted, gcn10_gpu_grid_finish_weighted), and those
  *    for several weight tables (gcn10_gpu_set_weight_tables, gcn10_gpu_grid_sums_storms, gcn10_gpu_grid_finish_storms);
  *    the sums with a weight table per cell (gcn10_gpu_set_rain_tables, gcn10_gpu_grid_sums_rain,
- *    gcn10_gpu_grid_finish_rain, gcn10_gpu_grid_rain_item).
+ *    gcn10_gpu_grid_finish_rain, gcn10_gpu_grid_rain_item); the sums per zone with a weight table per piece of a zone
+ *    (gcn10_gpu_zonal_sums_rain).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -520,6 +521,32 @@ int gcn10_gpu_grid_finish_rain(gcn10_gpu_ctx *ctx, const unsigned long long *acc
                                const uint8_t *cell_table_dev, uint8_t *means, uint8_t *cnq,
                                const uint32_t *shared_idx_dev, uint32_t n_shared, unsigned long long *shared,
                                gcn10_stream_t stream);
+
+/* A weight table per piece of a zone (config key zone_rain=...: a rainfall raster under the zones).  Added in ABI 3
+ * without a version change; the host looks it up for zone_rain runs only.
+ *
+ * gcn10_gpu_zonal_sums_rain: esa, W, rows, cj, the prepared soil, the spans and what the caller guarantees of them are
+ *   those of gcn10_gpu_zonal_pair_histogram; the tables are those of gcn10_gpu_set_rain_tables.  items_dev[i] names
+ *   n_spans consecutive spans of ONE zone from first_span on, all under table `table` (gcn10_zone_rain_cut of
+ *   gcn10_host.h makes spans and items, sorted by (zone, table)); `reserved` is not read; a table >= k is an error of
+ *   the caller and counts as table 0.  ADDS, for every selected raster q (ascending raster order), every item and every
+ *   pixel of its spans with value v != 255 -- v what gcn10_gpu_cn_strip writes for that raster at that pixel --, v to
+ *   acc[zone][q][0], 1 to ...[1] and w[table][v] to ...[2].  Integers in 64 bits throughout the reduction: the triples
+ *   do not depend on the launch shape, on how the spans are cut into items, or on order; the pixels of one (zone,
+ *   table) run of a workgroup are counted in 32-bit words, so such a run names fewer than 2^32 pixels.  Pixels named by
+ *   two spans count twice.  Any W, any alignment of esa; nothing at or beyond esa + W * rows is read; nothing outside
+ *   acc's n_zones * n_sel * 3 words is written.  n_items == 0 is a successful no-op.  A workgroup takes a contiguous
+ *   run of items; the grid is capped as gcn10_gpu_zonal_pair_histogram's.
+ * GCN10_E_INVAL: the masks, W, rows or n_zones <= 0, a null pointer, n_items >= 2^32.  GCN10_E_STATE: no tables, no tile
+ *   prepared for width W, or no rain tables ("call gcn10_gpu_set_rain_tables first").  Asynchronous on `stream`. */
+#ifndef GCN10_ZONE_RAIN_ITEM_DEFINED
+#define GCN10_ZONE_RAIN_ITEM_DEFINED
+typedef struct gcn10_zone_rain_item { uint32_t first_span, n_spans, table, reserved; } gcn10_zone_rain_item;
+#endif
+int gcn10_gpu_zonal_sums_rain(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                              const gcn10_zone_span *spans_dev, const gcn10_zone_rain_item *items_dev, size_t n_items,
+                              int n_zones, unsigned cond_mask, unsigned table_mask,
+                              unsigned long long *acc /* [n_zones][n_sel][3] = {s, n, sw} */, gcn10_stream_t stream);
 
 /* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
  * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.

@@ -153,6 +153,10 @@ typedef struct gcn10_config {
                                "grid" in counts (gcn10_rain_load); not together with "storm" / "storms"; absent = off */
     char *rain_unit;        /* "rain_unit": <unit>[,<lambda>] (gcn10_parse_rain_unit): millimetres per count (default 1)
                                and the initial-abstraction ratio (default 0.2); needs "rain" */
+    char *zone_rain;        /* "zone_rain": a one-band Byte GeoTIFF with a geotransform, the rainfall depth in counts under
+                               the zones of a zonal run (gcn10_zone_rain_load); not together with "storm" / "storms";
+                               absent = off */
+    char *zone_rain_unit;   /* "zone_rain_unit": <unit>[,<lambda>] as "rain_unit"; needs "zone_rain" */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -176,7 +180,7 @@ int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or
 int gcn10_parse_aggregate(const char *text, int *factor);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" / "rain_unit" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" / "rain_unit" / "zone_rain_unit" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -519,6 +523,64 @@ void gcn10_rain_tables(double unit, double lambda, uint16_t q[256][256]);
 enum { GCN10_RAIN_E_READ = -1, GCN10_RAIN_E_SIZE = -2, GCN10_RAIN_E_GEOTRANSFORM = -3 };
 int gcn10_rain_load(const char *path, const gcn10_grid *g, uint8_t **out, char *err, size_t errcap);
 
+/* A rainfall raster under the zones (config keys "zone_rain" and "zone_rain_unit", --zone-rain / --zone-rain-unit; needs
+ * zones): the runoff of every zone under a depth that varies across it.  "rain" stays "one byte per cell of grid" and
+ * stays refused with zones; this raster carries its own georeferencing.
+ *
+ * The raster: one Byte band WITH a geotransform, north up and without rotation (gt[1] > 0, gt[5] < 0, gt[2] == gt[4] ==
+ * 0), taken to be in the landcover's CRS, of at most GCN10_GRID_MAX_CELLS pixels.  It IS the gcn10_grid {xmin = gt[0],
+ * ymax = gt[3], dx = gt[1], dy = -gt[5], nx, ny}: a landcover pixel's rain cell is decided by that grid's rule, through
+ * gcn10_grid_plan_block(grid, W, H, gt_block, NULL, ...) (ownership is already in the zone's spans).  Byte b means P =
+ * b * unit mm with table q[b] of gcn10_rain_tables(unit, lambda); b = 0 is no rain; there is no NoData byte.  The unit
+ * is read by gcn10_parse_rain_unit (defaults 1 mm and 0.2).
+ *
+ * The sums, for zone z and selected raster r, over the pixels of z (the spans of gcn10_zones_build_plan, unchanged)
+ * that lie in a rain cell and whose value v != 255:  s = the sum of v, n = their count, sw = the sum of q[b(pixel)][v];
+ * independent of r: rain_pixels = the pixels of z that lie in a rain cell, rain_sum = the sum of b over them.  All are
+ * integers, additive across blocks and workers.
+ *
+ * zonal_cn.csv keeps its columns, byte for byte, and gains rain_pixels,rain_mm,rain_valid,runoff_mm_rain,cn_runoff_rain:
+ *   rain_mm        = ((double)rain_sum / (double)rain_pixels) * unit, in this order; empty when rain_pixels == 0
+ *   rain_valid     = n
+ *   runoff_mm_rain = (double)sw / (double)n / 100.0, printed %.14g
+ *   cn_runoff_rain = gcn10_runoff_cn(s, n, sw, T) with T = gcn10_runoff_table(rain_mm, lambda): the CN a lumped model
+ *                    needs with the basin-mean depth to reproduce the distributed runoff
+ * the last two empty when n == 0; with rain_mm == 0 the table is all zero and the rule gives the mean byte. */
+/* The derived columns of one row: bit 0 of the result: *rain_mm holds (rain_pixels > 0); bit 1: *runoff_mm and *cn hold
+ * (n > 0, which implies rain_pixels > 0).  What does not hold is 0, 0 and 255. */
+int gcn10_zone_rain_values(uint64_t rain_pixels, uint64_t rain_sum, double unit, double lambda, uint64_t s, uint64_t n,
+                           uint64_t sw, double *rain_mm, double *runoff_mm, int *cn);
+/* Reads such a raster whole: *grid as above, *out = nx * ny bytes, row major (the caller frees them).  0, or -1 with the
+ * run's refusal in err: "zone_rain: cannot read '<file>': ...", "zone_rain: '<file>' carries no geotransform" (the
+ * reader reports 0, 1, 0, 0, 0, 1 then), "zone_rain: '<file>' is rotated or not north up", "zone_rain: '<file>' has
+ * more than <GCN10_GRID_MAX_CELLS> pixels". */
+int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char *err, size_t errcap);
+/* The spans of a block's plan cut where the rainfall byte changes -- the input of gcn10_gpu_zonal_sums_rain (the same
+ * item struct as in gcn10_gpu.h).  cellx[W], celly[H], cx0, cy0: the maps of gcn10_grid_plan_block for the block on the
+ * raster's grid (column x lies in raster column cellx[x] + cx0; a negative entry: in none; both NULL: the block meets no
+ * cell); rain: the raster's nx x ny bytes.  Each cut span is a maximal run of columns of ONE source span that have
+ * cellx >= 0, in a row with celly >= 0, under one byte (neighbouring cells of equal byte merge), split at max_span_px;
+ * spans sorted by (zone, byte, y, x0), their `zone` the plan's local index; items: runs of consecutive spans of ONE
+ * zone and ONE byte (`table`), at most max_item_px pixels each (0 = the builder's own bounds; results never depend on
+ * them).  rain_pixels[n_local], rain_sum[n_local]: the pixels of each local zone in a rain cell, and the sum of their
+ * bytes.  Cost: O(W + spans + rain cells crossed), a counting sort on the byte within a zone.  0; -1 for a span outside
+ * the W x H block, a zone outside the plan, or out of memory. */
+#ifndef GCN10_ZONE_RAIN_ITEM_DEFINED
+#define GCN10_ZONE_RAIN_ITEM_DEFINED
+typedef struct gcn10_zone_rain_item { uint32_t first_span, n_spans, table, reserved; } gcn10_zone_rain_item;
+#endif
+typedef struct gcn10_zone_rain_plan {
+    int n_local;
+    uint64_t *rain_pixels, *rain_sum;   /* [n_local] */
+    size_t n_spans, n_items;
+    gcn10_zone_span *spans;
+    gcn10_zone_rain_item *items;
+} gcn10_zone_rain_plan;
+int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t *cellx, const int32_t *celly, int cx0,
+                        int cy0, const uint8_t *rain, int nx, int ny, uint32_t max_span_px, uint32_t max_item_px,
+                        gcn10_zone_rain_plan *out);
+void gcn10_zone_rain_plan_free(gcn10_zone_rain_plan *p);
+
 /* ------------------------------------------------------------------------ */
 /* the run: src/main.c:58-203 + process_block, src/cn.c:134-384              */
 /* ------------------------------------------------------------------------ */
@@ -544,6 +606,8 @@ typedef struct gcn10_run_options {
     const char *storms;         /* --storms <P1>[:<P2>...][,<lambda>]: overrides the config key "storms" */
     const char *rain;           /* --rain <file>: overrides the config key "rain" */
     const char *rain_unit;      /* --rain-unit <unit>[,<lambda>]: overrides the config key "rain_unit" */
+    const char *zone_rain;      /* --zone-rain <file>: overrides the config key "zone_rain" */
+    const char *zone_rain_unit; /* --zone-rain-unit <unit>[,<lambda>]: overrides the config key "zone_rain_unit" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -586,7 +650,10 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * several storms (opt->storms / "storms=<P1>[:<P2>...][,<lambda>]") add one such raster per storm, or the columns
  * runoff_mm_p<N>,cn_runoff_p<N> per storm (with one depth: exactly what storm adds).  A rainfall raster (opt->rain /
  * "rain=<file>", with opt->rain_unit / "rain_unit=<unit>[,<lambda>]") adds cn_grid_<cond>/cnq_<hc>_<arc>_rain.tif to a
- * grid run, every cell for its own depth; the means are byte for byte those of the run without it. */
+ * grid run, every cell for its own depth; the means are byte for byte those of the run without it.  A rainfall raster
+ * under the zones (opt->zone_rain / "zone_rain=<file>", with opt->zone_rain_unit / "zone_rain_unit=...") adds the columns
+ * rain_pixels,rain_mm,rain_valid,runoff_mm_rain,cn_runoff_rain to a zonal run's table ("A rainfall raster under the
+ * zones" above); the other columns are byte for byte those of the run without it. */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

@@ -1,6 +1,8 @@
-// gcn10_grid_internal.hpp -- what the two model-grid files of libgcn10_gpu.so share, each piece once:
-//   gcn10_grid.hip       sums with one weight table per launch, folded into image planes (0 to 8 tables)
-//   gcn10_grid_rain.hip  sums with the weight table chosen per cell, from the cells' pair histograms
+// gcn10_grid_internal.hpp -- what the model-grid files of libgcn10_gpu.so share, each piece once:
+//   gcn10_grid.hip        sums with one weight table per launch, folded into image planes (0 to 8 tables)
+//   gcn10_grid_rain.hip   sums with the weight table chosen per cell, from the cells' pair histograms
+//   gcn10_grid_rains.hip  the same with 1 to 8 tables per cell, the histograms counted once
+//                         (the counting itself: gcn10_grid_rain_piece.hpp)
 // The device side is the two byte rules of a cell; the host side is what their sums and finish calls check and size
 // alike.
 #ifndef GCN10_GRID_INTERNAL_HPP
@@ -92,7 +94,7 @@ inline int check_finish_args(const char *who, const unsigned long long *acc, int
     return GCN10_OK;
 }
 
-// GCN10_E_STATE unless gcn10_gpu_set_rain_tables has run (gcn10_grid_rain.hip, gcn10_zonal_rain.hip)
+// GCN10_E_STATE unless gcn10_gpu_set_rain_tables has run (gcn10_grid_rain.hip, gcn10_grid_rains.hip, gcn10_zonal_rain.hip)
 inline int check_rain_tables(gcn10_gpu_ctx *ctx, const char *who)
 {
     if (ctx->n_rain_tables < 1)

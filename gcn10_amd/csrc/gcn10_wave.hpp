@@ -36,9 +36,9 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t x)
     return r;
 }
 
-// Sum over the 64 lanes, wave-uniform, with DPP adds (no LDS round trips): quads, rows of 16, then
-// row_bcast:15 / row_bcast:31 carry the row totals to lane 63.
-__device__ __forceinline__ uint32_t wave_total(uint32_t x)
+// Sum over the 64 lanes with DPP adds (no LDS round trips), in every lane of the last row (48..63): quads, rows of 16,
+// then row_bcast:15 / row_bcast:31 carry the row totals on.  What the other lanes hold is a partial sum.
+__device__ __forceinline__ uint32_t wave_total_in_last_row(uint32_t x)
 {
     uint32_t r = x;
     r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0xb1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
@@ -47,7 +47,13 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t x)
     r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x140, 0xf, 0xf, false);     // row_mirror
     r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x142, 0xa, 0xf, false);     // row_bcast:15 -> rows 1, 3
     r += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)r, 0x143, 0xc, 0xf, false);     // row_bcast:31 -> rows 2, 3
-    return (uint32_t)__builtin_amdgcn_readlane((int)r, 63);
+    return r;
+}
+
+// Sum over the 64 lanes, wave-uniform
+__device__ __forceinline__ uint32_t wave_total(uint32_t x)
+{
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_total_in_last_row(x), 63);
 }
 
 }  // namespace gcn10

@@ -353,6 +353,8 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             }
             rc = set_str(&cfg->rain_unit, val);
         }
+        else if (!strcmp(key, "rains"))
+            rc = set_str(&cfg->rains, val);
         else if (!strcmp(key, "zone_rain"))
             rc = set_str(&cfg->zone_rain, val);
         else if (!strcmp(key, "zone_rain_unit")) {
@@ -430,5 +432,6 @@ void gcn10_config_free(gcn10_config *cfg)
     free(cfg->rain_unit);
     free(cfg->zone_rain);
     free(cfg->zone_rain_unit);
+    free(cfg->rains);
     memset(cfg, 0, sizeof *cfg);
 }

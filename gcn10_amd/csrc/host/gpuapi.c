@@ -113,6 +113,9 @@ static void load_once(void)
     *(void **)(&g_api.set_rain_tables) = dlsym(h, "gcn10_gpu_set_rain_tables");
     *(void **)(&g_api.grid_sums_rain) = dlsym(h, "gcn10_gpu_grid_sums_rain");
     *(void **)(&g_api.grid_finish_rain) = dlsym(h, "gcn10_gpu_grid_finish_rain");
+    /* and those with several weight tables per cell: needed by rains=... runs only, which check for them */
+    *(void **)(&g_api.grid_sums_rains) = dlsym(h, "gcn10_gpu_grid_sums_rains");
+    *(void **)(&g_api.grid_finish_rains) = dlsym(h, "gcn10_gpu_grid_finish_rains");
     /* and the zonal sums with a weight table per item: needed by zone_rain=... runs only, which check for it */
     *(void **)(&g_api.zonal_sums_rain) = dlsym(h, "gcn10_gpu_zonal_sums_rain");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {

@@ -28,7 +28,10 @@
  * counts and the 256 runoff tables of gcn10_rain_tables, the worker hands the tables to its context once
  * (gcn10_gpu_set_rain_tables), uploads the counts of the block's cell rectangle beside the maps and runs the _rain pair
  * of calls; triples as with one storm, the shared cells finished with the table of the cell's own count, and
- * cnq_<hc>_<arc>_rain.tif beside every mean.
+ * cnq_<hc>_<arc>_rain.tif beside every mean.  With K rainfall rasters (config key "rains") the run holds K such rasters
+ * and still one set of tables; the K byte rectangles of a block go up behind the maps, the _rains pair of calls counts the
+ * block once into 2 + K words, the shared cells are finished per layer with the table of the cell's byte in that layer
+ * (gcn10_rains_cell), and cnq_<hc>_<arc>_rain<j>.tif per raster stands beside every mean (one raster: _rain.tif).
  */
 #include "pipeline_internal.h"
 
@@ -280,6 +283,28 @@ int gcn10_rain_load(const char *path, const gcn10_grid *g, uint8_t **out, char *
     return 0;
 }
 
+int gcn10_rains_load(const char *const files[], int k, const gcn10_grid *g, uint8_t *out[GCN10_MAX_RAINS], char *err,
+                     size_t errcap)
+{
+    char why[PATH_MAX + 1200] = "";
+
+    for (int j = 0; j < GCN10_MAX_RAINS; j++)
+        out[j] = NULL;
+    for (int j = 0; j < k; j++) {
+        const int rc = gcn10_rain_load(files[j], g, &out[j], why, sizeof why);
+
+        if (rc != 0) {
+            for (int i = 0; i < j; i++) {
+                free(out[i]);
+                out[i] = NULL;
+            }
+            snprintf(err, errcap, "rains%s", why + strlen("rain"));     /* "rain: ..." as "rains: ..." */
+            return rc;
+        }
+    }
+    return 0;
+}
+
 int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char *err, size_t errcap)
 {
     char why[1024] = "";
@@ -409,9 +434,11 @@ static void grid_end(struct run *r)
     free(t->key);
     free(t->pair);
     free(t);
-    free(r->rain);
+    for (int j = 0; j < GCN10_MAX_RAINS; j++) {
+        free(r->rain_layer[j]);
+        r->rain_layer[j] = NULL;
+    }
     free(r->rain_q);
-    r->rain = NULL;
     r->rain_q = NULL;
     r->grid_result = NULL;
 }
@@ -421,7 +448,7 @@ int gcn10_grid_start(struct run *r)
     const gcn10_run_options *opt = &r->opt;
     const char *why = NULL;
     struct gcn10_grid_result *t;
-    char err[1024] = "";
+    char err[PATH_MAX + 1200] = "";
     size_t bytes;
 
     if (gcn10_parse_grid(r->cfg.grid, &r->grid) != 0) {
@@ -454,10 +481,11 @@ int gcn10_grid_start(struct run *r)
     r->grid_result = t;
     pthread_mutex_init(&t->mu, NULL);
     t->n_sel = r->n_sel > 0 ? r->n_sel : 1;
-    t->n_cnq = r->storm_on ? r->n_storms : (r->rain_on ? 1 : 0);
+    t->n_cnq = r->storm_on ? r->n_storms : (r->rain_on ? r->n_rains : 0);
     t->words = 2 + t->n_cnq;
-    if (r->rain_on) {           /* the raster on this grid, and the table of every count */
-        if (gcn10_rain_load(r->cfg.rain, &r->grid, &r->rain, err, sizeof err) != 0) {
+    if (r->rain_on) {           /* the rasters on this grid, and the table of every count */
+        if ((r->rains_key ? gcn10_rains_load(r->rain_file, r->n_rains, &r->grid, r->rain_layer, err, sizeof err)
+                          : gcn10_rain_load(r->cfg.rain, &r->grid, &r->rain_layer[0], err, sizeof err)) != 0) {
             fprintf(stderr, "[rank 0] %s\n", err);
             grid_end(r);
             return -1;
@@ -599,10 +627,10 @@ static int grid_block(struct worker *w, struct block_in *in)
     const int ncx = p->cx1 - p->cx0, ncy = p->cy1 - p->cy0;
     const size_t n_cells = (size_t)ncx * (size_t)ncy, n_sel = (size_t)r->n_sel;
     const size_t maps = ((size_t)in->W + (size_t)in->H) * sizeof(int32_t);
-    const bool storm = r->storm_on, ladder = r->storms_key, rain = r->rain_on;
-    /* behind the maps and the shared indices, with rain: the counts of the block's cell rectangle */
-    const size_t up = maps + p->n_shared * sizeof(uint32_t) + (rain ? n_cells : 0);
-    const size_t n_storms = storm ? (size_t)r->n_storms : (rain ? 1 : 0);
+    const bool storm = r->storm_on, ladder = r->storms_key, rain = r->rain_on, layers = r->rains_key;
+    const size_t n_storms = storm ? (size_t)r->n_storms : (rain ? (size_t)r->n_rains : 0);
+    /* behind the maps and the shared indices, with rain: the counts of the block's cell rectangle, raster by raster */
+    const size_t up = maps + p->n_shared * sizeof(uint32_t) + (rain ? n_storms * n_cells : 0);
     const size_t words = 2 + n_storms, bytes = (1 + n_storms) * n_sel * n_cells;    /* per cell: sums, and bytes back */
     struct gcn10_grid_state *s;
     int32_t *d_cellx, *d_celly;
@@ -660,19 +688,26 @@ static int grid_block(struct worker *w, struct block_in *in)
     d_celly = d_cellx + in->W;
     d_idx = (uint32_t *)((char *)s->d_up + maps);
     d_rain = (uint8_t *)s->d_up + maps + p->n_shared * sizeof(uint32_t);
-    for (int cy = 0; rain && cy < ncy; cy++)
-        memcpy((uint8_t *)s->h_up + maps + p->n_shared * sizeof(uint32_t) + (size_t)cy * (size_t)ncx,
-               r->rain + (size_t)(p->cy0 + cy) * (size_t)r->grid.nx + (size_t)p->cx0, (size_t)ncx);
+    for (size_t j = 0; rain && j < n_storms; j++)
+        for (int cy = 0; cy < ncy; cy++)
+            memcpy((uint8_t *)s->h_up + maps + p->n_shared * sizeof(uint32_t) + j * n_cells + (size_t)cy * (size_t)ncx,
+                   r->rain_layer[j] + (size_t)(p->cy0 + cy) * (size_t)r->grid.nx + (size_t)p->cx0, (size_t)ncx);
     if (g->memcpy_h2d(w->ctx, s->d_up, s->h_up, up, w->s_kernel) != 0 ||
         g->memset(w->ctx, s->d_acc, 0, n_sel * n_cells * words * sizeof *s->d_acc, w->s_kernel) != 0 ||
         g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, in->W, w->s_kernel) != 0 ||
-        (rain ? g->grid_sums_rain(w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0,
+        (layers ? g->grid_sums_rains(w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0,
+                                     in->d_cj + p->y0, d_cellx, d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask,
+                                     d_rain, r->n_rains, s->d_acc, w->s_kernel) :
+         rain ? g->grid_sums_rain(w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0,
                                   in->d_cj + p->y0, d_cellx, d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask,
                                   d_rain, s->d_acc, w->s_kernel)
               : (ladder ? g->grid_sums_storms : storm ? g->grid_sums_weighted : g->grid_sums)(
                     w->ctx, in->d_block + (size_t)p->y0 * (size_t)in->W, in->W, p->y1 - p->y0, in->d_cj + p->y0, d_cellx,
                     d_celly + p->y0, ncx, ncy, r->cond_mask, r->table_mask, s->d_acc, w->s_kernel)) != 0 ||
-        (rain ? g->grid_finish_rain(w->ctx, s->d_acc, r->n_sel, n_cells, d_rain, s->d_means,
+        (layers ? g->grid_finish_rains(w->ctx, s->d_acc, r->n_sel, n_cells, d_rain, r->n_rains, s->d_means,
+                                       s->d_means + n_sel * n_cells, p->n_shared ? d_idx : NULL, (uint32_t)p->n_shared,
+                                       p->n_shared ? s->d_shared : NULL, w->s_kernel) :
+         rain ? g->grid_finish_rain(w->ctx, s->d_acc, r->n_sel, n_cells, d_rain, s->d_means,
                                     s->d_means + n_sel * n_cells, p->n_shared ? d_idx : NULL, (uint32_t)p->n_shared,
                                     p->n_shared ? s->d_shared : NULL, w->s_kernel) :
          storm ? (ladder ? g->grid_finish_storms : g->grid_finish_weighted)(
@@ -766,12 +801,17 @@ static int grid_finish(struct run *r, gcn10_log *log0)
         if (t->key[i] != NO_KEY)
             for (int q = 0; q < r->n_sel; q++) {
                 const uint64_t *v = &t->pair[i * width + words * (size_t)q];
+                uint8_t of_layer[GCN10_MAX_RAINS], cn[GCN10_MAX_RAINS];
 
                 t->raster[(size_t)q * plane + t->key[i]] = mean_of(v[0], v[1]);
+                if (r->rain_on) {           /* per layer, with the table of the cell's own byte in it */
+                    for (int k = 0; k < n_storms; k++)
+                        of_layer[k] = r->rain_layer[k][t->key[i]];
+                    gcn10_rains_cell(v, n_storms, of_layer, r->rain_q, cn);
+                }
                 for (int k = 0; k < n_storms; k++)
                     t->cnq[((size_t)k * (size_t)r->n_sel + (size_t)q) * plane + t->key[i]] =
-                        (uint8_t)gcn10_runoff_cn(v[0], v[1], v[2 + k],
-                                                 r->rain_on ? r->rain_q[r->rain[t->key[i]]] : r->runoff_q[k]);
+                        r->rain_on ? cn[k] : (uint8_t)gcn10_runoff_cn(v[0], v[1], v[2 + k], r->runoff_q[k]);
             }
     for (size_t c = 0; c < plane; c++) {
         int q = 0;
@@ -806,9 +846,12 @@ static int grid_finish(struct run *r, gcn10_log *log0)
         if (fi % per == 0)
             snprintf(path, sizeof path, "cn_grid_%s/cn_%s_%s.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
                      gcn10_arcs[k % 3]);
-        else if (r->rain_on)
+        else if (r->rain_on && r->n_rains == 1)
             snprintf(path, sizeof path, "cn_grid_%s/cnq_%s_%s_rain.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
                      gcn10_arcs[k % 3]);
+        else if (r->rain_on)
+            snprintf(path, sizeof path, "cn_grid_%s/cnq_%s_%s_rain%d.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
+                     gcn10_arcs[k % 3], fi % per);
         else
             snprintf(path, sizeof path, "cn_grid_%s/cnq_%s_%s_p%u.tif", gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3],
                      gcn10_arcs[k % 3], (unsigned)r->runoff_q[fi % per - 1][100]);
@@ -868,10 +911,20 @@ static int grid_finish(struct run *r, gcn10_log *log0)
                  "cn_grid_<cond>/: cn_<hc>_<arc>.tif (mean) and %s (runoff-equivalent)", t->blocks,
                  r->n_sel, gr->nx, gr->ny, empty, names);
     }
-    else if (r->rain_on)
+    else if (r->rain_on && r->n_rains == 1)
         snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
                  "cn_grid_<cond>/: cn_<hc>_<arc>.tif (mean) and cnq_<hc>_<arc>_rain.tif (runoff-equivalent)", t->blocks,
                  r->n_sel, gr->nx, gr->ny, empty);
+    else if (r->rain_on) {
+        /* every raster's suffix: "cnq_<hc>_<arc>_rain1.tif, _rain2.tif" */
+        int at = snprintf(names, sizeof names, "cnq_<hc>_<arc>_rain1.tif");
+
+        for (int k = 2; k <= n_storms; k++)
+            at += snprintf(names + at, sizeof names - (size_t)at, ", _rain%d.tif", k);
+        snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
+                 "cn_grid_<cond>/: cn_<hc>_<arc>.tif (mean) and %s (runoff-equivalent)", t->blocks, r->n_sel, gr->nx,
+                 gr->ny, empty, names);
+    }
     else
         snprintf(msg, sizeof msg, "grid: %d blocks, %d rasters of %d x %d cells, %zu cells without a valid pixel, under "
                  "cn_grid_<cond>/", t->blocks, r->n_sel, gr->nx, gr->ny, empty);

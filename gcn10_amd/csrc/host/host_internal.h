@@ -191,6 +191,11 @@ struct gcn10_gpu_api {
                           int, int, unsigned, unsigned, const uint8_t *, unsigned long long *, gcn10_stream_t);
     int (*grid_finish_rain)(gcn10_gpu_ctx *, const unsigned long long *, int, size_t, const uint8_t *, uint8_t *,
                             uint8_t *, const uint32_t *, uint32_t, unsigned long long *, gcn10_stream_t);
+    /* optional: NULL when the library has none (needed by rains=... only, with set_rain_tables) */
+    int (*grid_sums_rains)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const int32_t *, const int32_t *,
+                           int, int, unsigned, unsigned, const uint8_t *, int, unsigned long long *, gcn10_stream_t);
+    int (*grid_finish_rains)(gcn10_gpu_ctx *, const unsigned long long *, int, size_t, const uint8_t *, int, uint8_t *,
+                             uint8_t *, const uint32_t *, uint32_t, unsigned long long *, gcn10_stream_t);
     /* optional: NULL when the library has none (needed by zone_rain=... only) */
     int (*zonal_sums_rain)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const gcn10_zone_span *,
                            const gcn10_zone_rain_item *, size_t, int, unsigned, unsigned, unsigned long long *,

@@ -29,7 +29,7 @@ static void usage(FILE *fp)
             "        [--verify] [--zonal] [--zones <zones.shp>] [--aggregate <f>]\n"
             "        [--grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>] [--storm <P>[,<lambda>]]\n"
             "        [--storms <P1>[:<P2>...][,<lambda>]] [--rain <file> [--rain-unit <unit>[,<lambda>]]]\n"
-            "        [--zone-rain <file> [--zone-rain-unit <unit>[,<lambda>]]]\n"
+            "        [--rains <file1>[:<file2>...]] [--zone-rain <file> [--zone-rain-unit <unit>[,<lambda>]]]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -81,6 +81,11 @@ static void usage(FILE *fp)
             "  --rain-unit <unit>[,<lambda>]\n"
             "\t\t\tmillimetres per count of --rain (0 < unit, 255 unit <= 650, default 1) and the\n"
             "\t\t\tinitial-abstraction ratio (0 <= lambda < 1, default 0.2; config key rain_unit=...)\n"
+            "  --rains <file1>[:<file2>...]\n"
+            "\t\t\t1 to 8 rainfall rasters as --rain takes one, in ONE run: every block is read, decoded\n"
+            "\t\t\tand counted once.  cnq_<hc>_<arc>_rain<j>.tif per file, each the file --rain <file_j>\n"
+            "\t\t\talone writes (one file: exactly what --rain gives; config key rains=...); --rain-unit\n"
+            "\t\t\tholds for all files; not with --rain, otherwise as --rain\n"
             "  --zone-rain <file>\ta rainfall raster under the zones: a one-band Byte GeoTIFF with its own geotransform\n"
             "\t\t\t(north up, the landcover's CRS), byte b = b x unit mm of rain.  With --zones, the columns\n"
             "\t\t\train_pixels,rain_mm,rain_valid,runoff_mm_rain,cn_runoff_rain: every zone's runoff under\n"
@@ -150,6 +155,8 @@ int main(int argc, char **argv)
             opt.rain = argv[++i];
         else if (!strcmp(argv[i], "--rain-unit") && i + 1 < argc)
             opt.rain_unit = argv[++i];
+        else if (!strcmp(argv[i], "--rains") && i + 1 < argc)
+            opt.rains = argv[++i];
         else if (!strcmp(argv[i], "--zone-rain") && i + 1 < argc)
             opt.zone_rain = argv[++i];
         else if (!strcmp(argv[i], "--zone-rain-unit") && i + 1 < argc)

@@ -283,10 +283,15 @@ struct run {
     int n_storms;                           /* how many: 1 with "storm", 1 to GCN10_MAX_STORMS with "storms" */
     double storm_p[GCN10_MAX_STORMS], storm_lambda;
     uint16_t runoff_q[GCN10_MAX_STORMS][256];       /* gcn10_runoff_table of every storm */
-    /* rain=...: a rainfall depth per cell of the grid, and the runoff-equivalent raster for it beside every mean */
+    /* rain=... / rains=...: a rainfall depth per cell of the grid, or several, and the runoff-equivalent raster for each
+     * beside every mean */
     bool rain_on;
     double rain_unit, rain_lambda;
-    uint8_t *rain;                          /* [ny][nx]: the counts of the rainfall raster (gcn10_rain_load) */
+    bool rains_key;                         /* the rasters come from "rains": summed by the _rains calls */
+    int n_rains;                            /* how many: 1 with "rain", 1 to GCN10_MAX_RAINS with "rains" */
+    char *rains_copy;                       /* gcn10_parse_rains' copy of the "rains" value */
+    const char *rain_file[GCN10_MAX_RAINS]; /* their names: cfg.rain, or pointers into rains_copy */
+    uint8_t *rain_layer[GCN10_MAX_RAINS];   /* [ny][nx] each: the counts of every rainfall raster (gcn10_rain_load) */
     uint16_t (*rain_q)[256];                /* [256][256]: gcn10_rain_tables */
     /* zone_rain=...: a rainfall raster under the zones of a zonal run, with its own grid (zonal.c) */
     bool zone_rain_on;

@@ -80,40 +80,59 @@ static int resolve(struct run *r)
     for (int k = 0; k < GCN10_N_RASTERS; k++)
         if ((r->cond_mask >> (k / 9)) & 1u && (r->table_mask >> (k % 9)) & 1u)
             r->sel[r->n_sel++] = k;
-    /* a rainfall raster: the runs it cannot go with, tested before any of them starts, and its unit; the raster itself
-     * is read once the grid is known (gcn10_grid_start) */
+    /* a rainfall raster, or several ("rains"): the runs they cannot go with, tested before any of them starts, and their
+     * unit; the rasters themselves are read once the grid is known (gcn10_grid_start) */
     if (opt->rain) {
         free(r->cfg.rain);
         r->cfg.rain = strdup(opt->rain);
+    }
+    if (opt->rains) {
+        free(r->cfg.rains);
+        r->cfg.rains = strdup(opt->rains);
     }
     if (opt->rain_unit) {
         free(r->cfg.rain_unit);
         r->cfg.rain_unit = strdup(opt->rain_unit);
     }
-    r->rain_on = r->cfg.rain != NULL;
+    r->rains_key = r->cfg.rains != NULL;
+    r->rain_on = r->cfg.rain != NULL || r->rains_key;
     if (r->cfg.rain_unit && !r->rain_on) {
         fprintf(stderr, "[rank 0] rain_unit needs rain\n");
         return 1;
     }
+    if (r->rains_key && r->cfg.rain) {
+        fprintf(stderr, "[rank 0] rains cannot be combined with rain\n");
+        return 1;
+    }
     if (r->rain_on) {
+        const char *key = r->rains_key ? "rains" : "rain";
         int factor = r->cfg.aggregate;
 
         if (opt->aggregate && gcn10_parse_aggregate(opt->aggregate, &factor) != 0)
             factor = 0;                     /* a bad value is reported below, as without rain */
         if (r->verify)
-            why = "rain cannot be combined with --verify";
+            why = "cannot be combined with --verify";
         else if (factor)
-            why = "rain cannot be combined with aggregate";
+            why = "cannot be combined with aggregate";
         else if (r->cfg.zonal || opt->zonal)
-            why = "rain cannot be combined with --zonal";
+            why = "cannot be combined with --zonal";
         else if (opt->storm || r->cfg.storm)
-            why = "rain cannot be combined with storm";
+            why = "cannot be combined with storm";
         else if (opt->storms || r->cfg.storms)
-            why = "rain cannot be combined with storms";
+            why = "cannot be combined with storms";
         else if (!opt->grid && !r->cfg.grid)
-            why = "rain needs --grid";
+            why = "needs --grid";
         if (why) {
-            fprintf(stderr, "[rank 0] %s\n", why);
+            fprintf(stderr, "[rank 0] %s %s\n", key, why);
+            return 1;
+        }
+        if (!r->rains_key) {
+            r->n_rains = 1;
+            r->rain_file[0] = r->cfg.rain;
+        }
+        else if (gcn10_parse_rains(r->cfg.rains, &r->rains_copy, r->rain_file, &r->n_rains) != 0) {
+            fprintf(stderr, "[rank 0] bad value for rains: '%s' (file1[:file2...]: 1 to %d files)\n", r->cfg.rains,
+                    GCN10_MAX_RAINS);
             return 1;
         }
         r->rain_unit = 1.0;
@@ -310,7 +329,8 @@ static int resolve(struct run *r)
 static int require(struct run *r)
 {
     const struct gcn10_gpu_api *g;
-    char err[2048] = "", agg[48], grid[600], storm[600], rain[PATH_MAX + 8], zrain[PATH_MAX + 16];
+    char err[2048] = "", agg[48], grid[600], storm[600], rain[PATH_MAX + 8], zrain[PATH_MAX + 16], *rains = NULL;
+    int rc = 0;
 
     r->gpu = g = gcn10_gpu_api_get(err, sizeof err);
     if (!g) {
@@ -321,7 +341,16 @@ static int require(struct run *r)
     snprintf(grid, sizeof grid, "grid=%s", r->grid_on ? r->cfg.grid : "");
     snprintf(storm, sizeof storm, "%s=%s", r->storms_key ? "storms" : "storm",
              r->storms_key ? r->cfg.storms : r->storm_on ? r->cfg.storm : "");
-    snprintf(rain, sizeof rain, "rain=%s", r->rain_on ? r->cfg.rain : "");
+    snprintf(rain, sizeof rain, "rain=%s", r->rain_on && !r->rains_key ? r->cfg.rain : "");
+    if (r->rains_key) {                     /* up to eight paths: as long as the key's value */
+        const size_t cap = strlen(r->cfg.rains) + 8;
+
+        if (!(rains = malloc(cap))) {
+            fprintf(stderr, "[rank 0] out of memory\n");
+            return 1;
+        }
+        snprintf(rains, cap, "rains=%s", r->cfg.rains);
+    }
     snprintf(zrain, sizeof zrain, "zone_rain=%s", r->zone_rain_on ? r->cfg.zone_rain : "");
     {
         /* the pair histogram's soil codes are asked for where a mode counts pairs, and must be as many as its bins */
@@ -337,20 +366,25 @@ static int require(struct run *r)
               g->set_weights && g->grid_sums_weighted && g->grid_finish_weighted, "gcn10_gpu_grid_sums_weighted", storm },
             { r->grid_on && r->storms_key, g->set_weight_tables && g->grid_sums_storms && g->grid_finish_storms,
               "gcn10_gpu_grid_sums_storms", storm },
-            { r->rain_on, g->set_rain_tables && g->grid_sums_rain && g->grid_finish_rain, "gcn10_gpu_grid_sums_rain",
-              rain },
+            { r->rain_on && !r->rains_key, g->set_rain_tables && g->grid_sums_rain && g->grid_finish_rain,
+              "gcn10_gpu_grid_sums_rain", rain },
+            { r->rains_key, g->set_rain_tables && g->grid_sums_rains && g->grid_finish_rains,
+              "gcn10_gpu_grid_sums_rains", rains },
             { r->grid_on, g->grid_sums && g->grid_finish, "gcn10_gpu_grid_sums", grid },
             { r->verify, g->verify_strip && g->verify_buffers, "gcn10_gpu_verify_strip", "verify=1" },
             { r->lzw, g->lzw_strip && g->lzw_arena_bound, "gcn10_gpu_lzw_strip", "compress=lzw" },
         };
 
-        for (size_t i = 0; i < sizeof needs / sizeof needs[0]; i++)
+        for (size_t i = 0; rc == 0 && i < sizeof needs / sizeof needs[0]; i++)
             if (needs[i].on && !needs[i].present) {
                 fprintf(stderr, "[rank 0] %s lacks %s (needed by %s)\n", gcn10_gpu_library_path(), needs[i].symbol,
                         needs[i].needed_by);
-                return 1;
+                rc = 1;
             }
     }
+    free(rains);
+    if (rc)
+        return rc;
     r->inflate_codecs = GCN10_CODEC_DEFLATE | GCN10_CODEC_RAW;
     if (r->cfg.gpu_inflate_lzw && g->inflate_codecs && (g->inflate_codecs() & GCN10_CODEC_LZW))
         r->inflate_codecs |= GCN10_CODEC_LZW;
@@ -516,19 +550,23 @@ static int load(struct run *r)
         log0_line(r, "INFO", true, "storm: P = %.17g mm, lambda = %.17g, threshold CN %d (the smallest curve number that "
                   "sheds water)", r->storm_p[k], r->storm_lambda, threshold);
     }
-    if (r->rain_on) {
+    for (int j = 0; r->rain_on && j < r->n_rains; j++) {    /* two lines per raster, in the order given */
         const size_t n = (size_t)r->grid.nx * (size_t)r->grid.ny;
+        const uint8_t *rain = r->rain_layer[j];
         unsigned lo = 255, hi = 0;
         size_t dry = 0;
+        char tag[16] = "rain";
 
+        if (r->n_rains > 1)
+            snprintf(tag, sizeof tag, "rain[%d]", j + 1);
         for (size_t c = 0; c < n; c++) {
-            lo = r->rain[c] < lo ? r->rain[c] : lo;
-            hi = r->rain[c] > hi ? r->rain[c] : hi;
-            dry += r->rain[c] == 0;
+            lo = rain[c] < lo ? rain[c] : lo;
+            hi = rain[c] > hi ? rain[c] : hi;
+            dry += rain[c] == 0;
         }
-        log0_line(r, "INFO", true, "rain: %s, %d x %d cells, unit = %.17g mm, lambda = %.17g", r->cfg.rain, r->grid.nx,
-                  r->grid.ny, r->rain_unit, r->rain_lambda);
-        log0_line(r, "INFO", true, "rain: depths %u..%u counts, %zu cells without rain", lo, hi, dry);
+        log0_line(r, "INFO", true, "%s: %s, %d x %d cells, unit = %.17g mm, lambda = %.17g", tag, r->rain_file[j],
+                  r->grid.nx, r->grid.ny, r->rain_unit, r->rain_lambda);
+        log0_line(r, "INFO", true, "%s: depths %u..%u counts, %zu cells without rain", tag, lo, hi, dry);
     }
     if (r->zone_rain_on) {
         const gcn10_grid *zg = &r->zone_rain_grid;
@@ -765,6 +803,7 @@ done:
         r->mode->end(r);
     free(r->zone_rain);
     free(r->zone_rain_q);
+    free(r->rains_copy);
     free(r->block_ids);
     gcn10_blocks_free(&r->blocks);
     gcn10_config_free(&r->cfg);

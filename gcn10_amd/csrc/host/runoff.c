@@ -8,7 +8,9 @@
  * reaches that sum.
  *
  * A rainfall raster (config keys "rain" / "rain_unit") is 256 such storms, one per count of the raster's byte: the unit
- * parser and the 256 tables are here, the raster itself is read by grid.c (gcn10_rain_load).
+ * parser and the 256 tables are here, the raster itself is read by grid.c (gcn10_rain_load).  Several of them in one run
+ * (config key "rains") share the unit and the tables: the parser of the file list and the bytes of a cell from its 2 + K
+ * words are here too.
  */
 #include "gcn10_host.h"
 
@@ -16,6 +18,7 @@
 #include <math.h>
 #include <stdbool.h>
 #include <stdlib.h>
+#include <string.h>
 
 #if defined(__GNUC__) && !defined(__clang__)
 #define NO_CONTRACT __attribute__((optimize("fp-contract=off")))
@@ -129,6 +132,42 @@ int gcn10_parse_rain_unit(const char *text, double *unit, double *lambda)
     *unit = d[0];
     *lambda = d[1];
     return 0;
+}
+
+int gcn10_parse_rains(const char *text, char **copy, const char *files[GCN10_MAX_RAINS], int *k)
+{
+    size_t len, members = 1;
+    char *c;
+    int n = 0;
+
+    if (!text || !*text)
+        return -1;
+    len = strlen(text);
+    for (size_t i = 0; i < len; i++) {
+        const bool first = i == 0 || text[i - 1] == ':';
+
+        if (text[i] == ':' && (first || i + 1 == len))      /* an empty member, the last one included */
+            return -1;
+        members += text[i] == ':';
+    }
+    if (members > GCN10_MAX_RAINS || !(c = malloc(len + 1)))
+        return -1;
+    memcpy(c, text, len + 1);
+    for (size_t i = 0; i < len; i++) {
+        if (i == 0 || text[i - 1] == ':')
+            files[n++] = c + i;
+        if (c[i] == ':')
+            c[i] = '\0';
+    }
+    *copy = c;
+    *k = n;
+    return 0;
+}
+
+void gcn10_rains_cell(const uint64_t *words, int k, const uint8_t bytes[], const uint16_t q[256][256], uint8_t cn[])
+{
+    for (int j = 0; j < k; j++)
+        cn[j] = (uint8_t)gcn10_runoff_cn(words[0], words[1], words[2 + j], q[bytes[j]]);
 }
 
 NO_CONTRACT void gcn10_rain_tables(double unit, double lambda, uint16_t q[256][256])

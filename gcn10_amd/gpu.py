@@ -50,7 +50,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_set_weights", "gcn10_gpu_grid_sums_weighted", "gcn10_gpu_grid_finish_weighted",
     "gcn10_gpu_set_weight_tables", "gcn10_gpu_grid_sums_storms", "gcn10_gpu_grid_finish_storms",
     "gcn10_gpu_grid_rain_item", "gcn10_gpu_set_rain_tables", "gcn10_gpu_grid_sums_rain", "gcn10_gpu_grid_finish_rain",
-    "gcn10_gpu_zonal_sums_rain",
+    "gcn10_gpu_zonal_sums_rain", "gcn10_gpu_grid_sums_rains", "gcn10_gpu_grid_finish_rains",
 )
 
 
@@ -171,6 +171,8 @@ def lib():
             "gcn10_gpu_grid_sums_rain": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp, vp]),
             "gcn10_gpu_grid_finish_rain": (i, [vp, vp, i, sz, vp, vp, vp, vp, C.c_uint32, vp, vp]),
             "gcn10_gpu_zonal_sums_rain": (i, [vp, vp, i, i, vp, vp, vp, sz, i, u, u, vp, vp]),
+            "gcn10_gpu_grid_sums_rains": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, i, vp, vp]),
+            "gcn10_gpu_grid_finish_rains": (i, [vp, vp, i, sz, vp, i, vp, vp, vp, C.c_uint32, vp, vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -556,6 +558,26 @@ class Engine:
         self._chk(lib().gcn10_gpu_grid_finish_rain(self._ctx, acc_ptr, n_sel, n_cells, cell_table_ptr, means_ptr,
                                                    cnq_ptr, shared_idx_ptr or None, n_shared, shared_ptr or None,
                                                    stream), "gcn10_gpu_grid_finish_rain")
+
+    def grid_sums_rains(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, cellx_ptr: int, celly_ptr: int, ncx: int,
+                        ncy: int, cond_mask: int, table_mask: int, cell_tables_ptr: int, k: int, acc_ptr: int,
+                        stream=None):
+        """grid_sums_rain with k tables per cell, the pixels counted once: ADDS {s, n, sw_1 .. sw_k} to
+        acc[q][celly[y]][cellx[x]] (uint64 on the device, [n_sel][ncy][ncx][2 + k]), sw_j the sum of
+        w[cell_tables[j][cy][cx]][v] for the tables of set_rain_tables; cell_tables_ptr: uint8[k][ncy][ncx] on the
+        device, 1 <= k <= 8 (gcn10_gpu_grid_sums_rains).  Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_sums_rains(self._ctx, esa_ptr, W, rows, cj_ptr, cellx_ptr, celly_ptr, ncx, ncy,
+                                                  cond_mask, table_mask, cell_tables_ptr, k, acc_ptr, stream),
+                  "gcn10_gpu_grid_sums_rains")
+
+    def grid_finish_rains(self, acc_ptr: int, n_sel: int, n_cells: int, cell_tables_ptr: int, k: int, means_ptr: int,
+                          cnq_ptr: int, shared_idx_ptr, n_shared: int, shared_ptr, stream=None):
+        """means[q][c] as grid_finish, cnq[j][q][c] = host.runoff_cn of {word 0, word 1, word 2 + j} with table
+        cell_tables[j][c] of set_rain_tables, and the 2 + k words of the n_shared cells shared_idx names, packed into
+        shared[q][i] (gcn10_gpu_grid_finish_rains).  Asynchronous on `stream`."""
+        self._chk(lib().gcn10_gpu_grid_finish_rains(self._ctx, acc_ptr, n_sel, n_cells, cell_tables_ptr, k, means_ptr,
+                                                    cnq_ptr, shared_idx_ptr or None, n_shared, shared_ptr or None,
+                                                    stream), "gcn10_gpu_grid_finish_rains")
 
     def zonal_pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans, items, n_zones: int,
                              hist_ptr: int, stream=None):

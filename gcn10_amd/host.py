@@ -148,6 +148,12 @@ def lib():
         L.gcn10_rain_tables.argtypes = [C.c_double, C.c_double, np.ctypeslib.ndpointer(dtype=np.uint16,
                                                                                       flags="C_CONTIGUOUS")]
         L.gcn10_rain_tables.restype = None
+        L.gcn10_parse_rains.argtypes = [cp, C.POINTER(vp), C.POINTER(cp), C.POINTER(C.c_int)]
+        L.gcn10_parse_rains.restype = C.c_int
+        L.gcn10_rains_load.argtypes = [C.POINTER(cp), C.c_int, C.POINTER(Grid), C.POINTER(vp), cp, C.c_size_t]
+        L.gcn10_rains_load.restype = C.c_int
+        L.gcn10_rains_cell.argtypes = [vp, C.c_int, vp, vp, vp]
+        L.gcn10_rains_cell.restype = None
         L.gcn10_rain_load.argtypes = [cp, C.POINTER(Grid), C.POINTER(vp), cp, C.c_size_t]
         L.gcn10_rain_load.restype = C.c_int
         L.gcn10_zone_items_build.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(ZonePlan)]
@@ -225,6 +231,12 @@ class ConfigZoneRain(ConfigRain):
     """``gcn10_config`` with the keys of the rainfall raster under zones, appended behind ``ConfigRain`` as the C struct
     appends them."""
     _fields_ = [("zone_rain", C.c_char_p), ("zone_rain_unit", C.c_char_p)]
+
+
+class ConfigRains(ConfigZoneRain):
+    """``gcn10_config`` with the key of several rainfall rasters, appended behind ``ConfigZoneRain`` as the C struct
+    appends it."""
+    _fields_ = [("rains", C.c_char_p)]
 
 
 assert C.sizeof(Config) % 8 == 0
@@ -492,6 +504,56 @@ def rain_load(path: str, grid) -> np.ndarray:
         lib().free_(out)
 
 
+MAX_RAINS = 8       # GCN10_MAX_RAINS
+
+
+def parse_rains(text: str):
+    """"<file1>[:<file2>...]" -> [file1, file2, ...] (``gcn10_parse_rains``; 1 to 8 names, none empty); raises HostError
+    for any other text."""
+    copy, files, k = C.c_void_p(), (C.c_char_p * MAX_RAINS)(), C.c_int()
+    if lib().gcn10_parse_rains(os.fsencode(text), C.byref(copy), files, C.byref(k)) != 0:
+        raise HostError("bad value for rains: '%s' (file1[:file2...]: 1 to 8 files)" % text)
+    try:
+        return [os.fsdecode(files[j]) for j in range(k.value)]
+    finally:
+        lib().free_(copy)
+
+
+def rains_load(paths, grid) -> np.ndarray:
+    """The rainfall rasters of the grid, uint8[k][ny][nx] (``gcn10_rains_load``); raises HostError with the run's refusal
+    text ("rains: ...") for the first file that cannot be read, has another size or does not lie on the grid."""
+    g = Grid(**grid)
+    k = len(paths)
+    names = (C.c_char_p * max(k, 1))(*[os.fsencode(p) for p in paths])
+    out = (C.c_void_p * MAX_RAINS)()
+    err = C.create_string_buffer(8192)
+    rc = lib().gcn10_rains_load(names, k, C.byref(g), out, err, len(err))
+    if rc != 0:
+        e = HostError(err.value.decode(errors="replace"))
+        e.code = rc
+        raise e
+    try:
+        n = grid["nx"] * grid["ny"]
+        return np.stack([np.ctypeslib.as_array(C.cast(out[j], C.POINTER(C.c_uint8)), (n,)).copy()
+                         for j in range(k)]).reshape(k, grid["ny"], grid["nx"])
+    finally:
+        for j in range(k):
+            lib().free_(out[j])
+
+
+def rains_cell(words, bytes_of_layers, q) -> list:
+    """[cn_1 .. cn_k] of a cell with the words {s, n, sw_1 .. sw_k} and byte bytes_of_layers[j] in layer j, for the 256
+    tables q (``gcn10_rains_cell``)."""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    b = np.ascontiguousarray(bytes_of_layers, dtype=np.uint8)
+    t = np.ascontiguousarray(q, dtype=np.uint16).reshape(256, 256)
+    k = len(b)
+    assert len(w) == 2 + k
+    cn = np.zeros(k, np.uint8)
+    lib().gcn10_rains_cell(w.ctypes.data, k, b.ctypes.data, t.ctypes.data, cn.ctypes.data)
+    return cn.tolist()
+
+
 def zone_rain_load(path: str):
     """The rainfall raster of a zonal run: (grid, bytes) -- the raster as a model grid (the dict of parse_grid) and
     uint8[ny][nx] (``gcn10_zone_rain_load``); raises HostError with the run's refusal text."""
@@ -552,14 +614,14 @@ def zone_rain_cut(plan: dict, W: int, H: int, gplan: dict, rain, max_span_px: in
 
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = ConfigZoneRain()
+    cfg = ConfigRains()
     err = C.create_string_buffer(1024)
     rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
     out = {}
     for name, _t in (Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_ + ConfigStorm._fields_ +
-                     ConfigStorms._fields_ + ConfigRain._fields_ + ConfigZoneRain._fields_):
+                     ConfigStorms._fields_ + ConfigRain._fields_ + ConfigZoneRain._fields_ + ConfigRains._fields_):
         v = getattr(cfg, name)
         out[name] = v.decode() if isinstance(v, bytes) else list(v) if isinstance(v, C.Array) else v
     lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))

@@ -46,7 +46,8 @@ extern "C" {
  *    for several weight tables (gcn10_gpu_set_weight_tables, gcn10_gpu_grid_sums_storms, gcn10_gpu_grid_finish_storms);
  *    the sums with a weight table per cell (gcn10_gpu_set_rain_tables, gcn10_gpu_grid_sums_rain,
  *    gcn10_gpu_grid_finish_rain, gcn10_gpu_grid_rain_item); the sums per zone with a weight table per piece of a zone
- *    (gcn10_gpu_zonal_sums_rain).
+ *    (gcn10_gpu_zonal_sums_rain); the sums with several weight tables per cell (gcn10_gpu_grid_sums_rains,
+ *    gcn10_gpu_grid_finish_rains).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -521,6 +522,37 @@ int gcn10_gpu_grid_finish_rain(gcn10_gpu_ctx *ctx, const unsigned long long *acc
                                const uint8_t *cell_table_dev, uint8_t *means, uint8_t *cnq,
                                const uint32_t *shared_idx_dev, uint32_t n_shared, unsigned long long *shared,
                                gcn10_stream_t stream);
+
+/* Several weight tables per cell (config key rains=...: 1 to GCN10_GPU_MAX_RAIN_LAYERS rainfall rasters on the model
+ * grid, counted once).  Added in ABI 3 without a version change; the host looks them up for rains runs only.  The tables
+ * are those of gcn10_gpu_set_rain_tables, which serves both pairs of calls; only the byte of a cell differs from layer to
+ * layer.
+ *
+ * gcn10_gpu_grid_sums_rains: every word of gcn10_gpu_grid_sums_rain's contract -- the maps and the -1 rule, ADD
+ *   semantics, any maps are summed (those whose entries decrease too), nothing at or beyond W is read, nothing outside
+ *   acc is written, an entry >= the number of rain tables counts as table 0 --, for 2 + k words per (raster, cell): words
+ *   0 and 1 are exactly what gcn10_gpu_grid_sums adds, word 2 + j gets the sum of w[cell_tables[j][cy * ncx + cx]][v]
+ *   over the same pixels of cell (cx, cy).  cell_tables_dev holds k x ncy x ncx bytes and not one more is read.  The
+ *   pixels are counted once whatever k is; the items and the launch are those of gcn10_gpu_grid_sums_rain.  With k = 1
+ *   the call adds the words gcn10_gpu_grid_sums_rain adds.
+ * gcn10_gpu_grid_finish_rains: means[] as gcn10_gpu_grid_finish writes it; cnq[(j * n_sel + q) * n_cells + c] = the value
+ *   of {word 0, word 1, word 2 + j} by the rule of gcn10_runoff_cn with table cell_tables[j][c] (an entry >= the number
+ *   of tables counts as 0), bisection or the scan by the table's flag as gcn10_gpu_grid_finish_rain; and the 2 + k words
+ *   of the shared cells, packed as gcn10_gpu_grid_finish_storms packs them.  With k = 1 it writes the bytes and words of
+ *   gcn10_gpu_grid_finish_rain.
+ * Errors as the _rain calls'; k outside 1..GCN10_GPU_MAX_RAIN_LAYERS or null cell_tables: GCN10_E_INVAL naming the call;
+ * no rain tables: GCN10_E_STATE ("call gcn10_gpu_set_rain_tables first").  A refused call writes nothing. */
+#define GCN10_GPU_MAX_RAIN_LAYERS 8
+int gcn10_gpu_grid_sums_rains(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                              const int32_t *cellx_dev, const int32_t *celly_dev, int ncx, int ncy,
+                              unsigned cond_mask, unsigned table_mask,
+                              const uint8_t *cell_tables_dev /* [k][ncy][ncx] */, int k,
+                              unsigned long long *acc /* [n_sel][ncy][ncx][2 + k] */, gcn10_stream_t stream);
+int gcn10_gpu_grid_finish_rains(gcn10_gpu_ctx *ctx, const unsigned long long *acc, int n_sel, size_t n_cells,
+                                const uint8_t *cell_tables_dev /* [k][n_cells] */, int k, uint8_t *means,
+                                uint8_t *cnq /* [k][n_sel][n_cells] */, const uint32_t *shared_idx_dev,
+                                uint32_t n_shared, unsigned long long *shared /* [n_sel][n_shared][2 + k] */,
+                                gcn10_stream_t stream);
 
 /* A weight table per piece of a zone (config key zone_rain=...: a rainfall raster under the zones).  Added in ABI 3
  * without a version change; the host looks it up for zone_rain runs only.

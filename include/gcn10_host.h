@@ -157,6 +157,9 @@ typedef struct gcn10_config {
                                the zones of a zonal run (gcn10_zone_rain_load); not together with "storm" / "storms";
                                absent = off */
     char *zone_rain_unit;   /* "zone_rain_unit": <unit>[,<lambda>] as "rain_unit"; needs "zone_rain" */
+    char *rains;            /* "rains": <file1>[:<file2>...] (gcn10_parse_rains): 1 to GCN10_MAX_RAINS rainfall rasters as
+                               "rain" takes one, all in one grid run that counts its pixels once; "rain_unit" holds for
+                               all of them; not together with "rain"; absent = off */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -180,7 +183,7 @@ int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or
 int gcn10_parse_aggregate(const char *text, int *factor);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" / "rain_unit" / "zone_rain_unit" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" / "rain_unit" / "zone_rain_unit" / "rains" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -523,6 +526,27 @@ void gcn10_rain_tables(double unit, double lambda, uint16_t q[256][256]);
 enum { GCN10_RAIN_E_READ = -1, GCN10_RAIN_E_SIZE = -2, GCN10_RAIN_E_GEOTRANSFORM = -3 };
 int gcn10_rain_load(const char *path, const gcn10_grid *g, uint8_t **out, char *err, size_t errcap);
 
+/* Several rainfall rasters in one grid run (config key "rains", --rains): K = 1 to GCN10_MAX_RAINS files, each by every
+ * rule of "rain", one unit and one set of 256 tables (gcn10_rain_tables) for all -- only the byte of a cell differs from
+ * layer to layer.  The pixels of a block are counted once: the sums carry 2 + K words per (raster, cell), word 2 + j the
+ * sum of q[b_j][v] with b_j the cell's byte in file j.  With one file the run writes what "rain" writes, byte for byte
+ * and name for name; with K > 1, cnq_<hc>_<arc>_rain<j>.tif for j = 1..K in the order given, each the file "rain" alone
+ * writes for file j, and the means are those of the run without rain. */
+#define GCN10_MAX_RAINS 8
+/* "<file1>[:<file2>...]": 1 to GCN10_MAX_RAINS file names separated by ':' (so a name holds none), none of them empty.
+ * 0 with *copy = the text with every ':' replaced by a NUL (the caller frees it), files[0 .. *k) pointing into it; or -1
+ * for NULL, an empty text, an empty member or more than GCN10_MAX_RAINS members (nothing is written or allocated then),
+ * and for no memory. */
+int gcn10_parse_rains(const char *text, char **copy, const char *files[GCN10_MAX_RAINS], int *k);
+/* gcn10_rain_load for every file, in order: out[0 .. k) = nx * ny bytes each (the caller frees them).  Returns 0, or the
+ * GCN10_RAIN_E_* of the first file that fails, with gcn10_rain_load's message under the prefix "rains:" in err; nothing
+ * stays allocated then and out[] is all NULL. */
+int gcn10_rains_load(const char *const files[], int k, const gcn10_grid *g, uint8_t *out[GCN10_MAX_RAINS], char *err,
+                     size_t errcap);
+/* The bytes of one cell from its 2 + k words {s, n, sw_1 .. sw_k} (a cell that several blocks added to, after the last
+ * block): cn[j] = gcn10_runoff_cn(s, n, sw_j, q[bytes[j]]), bytes[j] the cell's byte in layer j. */
+void gcn10_rains_cell(const uint64_t *words, int k, const uint8_t bytes[], const uint16_t q[256][256], uint8_t cn[]);
+
 /* A rainfall raster under the zones (config keys "zone_rain" and "zone_rain_unit", --zone-rain / --zone-rain-unit; needs
  * zones): the runoff of every zone under a depth that varies across it.  "rain" stays "one byte per cell of grid" and
  * stays refused with zones; this raster carries its own georeferencing.
@@ -608,6 +632,7 @@ typedef struct gcn10_run_options {
     const char *rain_unit;      /* --rain-unit <unit>[,<lambda>]: overrides the config key "rain_unit" */
     const char *zone_rain;      /* --zone-rain <file>: overrides the config key "zone_rain" */
     const char *zone_rain_unit; /* --zone-rain-unit <unit>[,<lambda>]: overrides the config key "zone_rain_unit" */
+    const char *rains;          /* --rains <file1>[:<file2>...]: overrides the config key "rains" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -650,7 +675,9 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * several storms (opt->storms / "storms=<P1>[:<P2>...][,<lambda>]") add one such raster per storm, or the columns
  * runoff_mm_p<N>,cn_runoff_p<N> per storm (with one depth: exactly what storm adds).  A rainfall raster (opt->rain /
  * "rain=<file>", with opt->rain_unit / "rain_unit=<unit>[,<lambda>]") adds cn_grid_<cond>/cnq_<hc>_<arc>_rain.tif to a
- * grid run, every cell for its own depth; the means are byte for byte those of the run without it.  A rainfall raster
+ * grid run, every cell for its own depth; the means are byte for byte those of the run without it.  Several rainfall
+ * rasters (opt->rains / "rains=<file1>[:<file2>...]", with the same unit) add cnq_<hc>_<arc>_rain<j>.tif per file to a
+ * grid run that counts its pixels once (with one file: exactly what rain adds).  A rainfall raster
  * under the zones (opt->zone_rain / "zone_rain=<file>", with opt->zone_rain_unit / "zone_rain_unit=...") adds the columns
  * rain_pixels,rain_mm,rain_valid,runoff_mm_rain,cn_runoff_rain to a zonal run's table ("A rainfall raster under the
  * zones" above); the other columns are byte for byte those of the run without it. */

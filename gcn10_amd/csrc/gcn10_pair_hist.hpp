@@ -1,5 +1,5 @@
 // gcn10_pair_hist.hpp -- the pieces the pair-histogram kernels share (gcn10_stats.hip: a whole strip;
-// gcn10_zonal.hip and gcn10_zonal_rain.hip: the spans of zones; gcn10_grid_rain.hip and gcn10_grid_rains.hip: the cells of a grid): the bin of a soil code, the key of a pixel, and the run folding of a
+// gcn10_zonal.hip, gcn10_zonal_rain.hip and gcn10_zonal_rains.hip: the spans of zones; gcn10_grid_rain.hip and gcn10_grid_rains.hip: the cells of a grid): the bin of a soil code, the key of a pixel, and the run folding of a
 // lane's 16 pixels.  Why runs are folded: header comment of gcn10_stats.hip.
 #ifndef GCN10_PAIR_HIST_HPP
 #define GCN10_PAIR_HIST_HPP

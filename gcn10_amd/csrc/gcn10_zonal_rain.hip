@@ -17,15 +17,14 @@
 
 #include "gcn10_grid_internal.hpp"
 #include "gcn10_pair_hist.hpp"
+#include "gcn10_zonal_rain_walk.hpp"
 
 using namespace gcn10;
 using namespace gcn10::pair_hist;
+using namespace gcn10::zonal_rain_walk;
 
 namespace {
 
-// as gcn10_zonal.hip has it (the same workgroup, with the list of a flush 29 KiB of LDS)
-constexpr int kZonalRainGridPerCu = 4;
-constexpr uint32_t kWaves = kThreads / 64;
 constexpr uint32_t kSums = 2u * 9u * 3u;                    // (condition, table, word)
 
 struct ZonalRainParams {
@@ -44,9 +43,7 @@ struct ZonalRainParams {
 };
 
 // The workgroup's histogram against table `table`, added to the triples of `zone`; h is all zero afterwards.  The non-zero
-// bins -- a few dozen of the 4096 -- are listed first and dealt one (bin, condition) to a thread: the bins of one
-// landcover class lie 256 words apart, so a strided scan that reduced on the spot would leave all of a class's bins, each
-// with its chain of dependent loads (image row, then weights), to ONE thread.
+// bins are listed and dealt one (bin, condition) to a thread (list_bins says why).
 __device__ __forceinline__ void flush_piece(const ZonalRainParams &p, uint32_t *h, unsigned long long *sums,
                                             uint16_t *list, uint32_t *n_list, uint32_t zone, uint32_t table)
 {
@@ -56,27 +53,18 @@ __device__ __forceinline__ void flush_piece(const ZonalRainParams &p, uint32_t *
     if (tid == 0)
         *n_list = 0u;
     __syncthreads();            // the counts of every lane are in h, the sums and the list are empty
-    for (uint32_t j = 4u * tid; j < (uint32_t)kHistWords; j += 4u * kThreads) {
-        const u32x4 v = *reinterpret_cast<const u32x4 *>(h + j);
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++)
-            if (v[k])
-                list[atomicAdd(n_list, 1u)] = (uint16_t)(j + k);
-    }
+    list_bins(h, list, n_list);
     __syncthreads();
     const uint32_t m = *n_list, two = p.n_conds == 2u ? 1u : 0u;
     const uint16_t *const w = p.tables + 256u * (table < p.n_tables ? table : 0u);
     for (uint32_t u = tid; u < (m << two); u += kThreads) {
         const uint32_t i = list[u >> two], c = h[i];
-        const uint32_t lc = i & 255u, code = bin_code(i >> 8);
         const uint32_t cond = p.conds[u & two], sel9 = (p.sel >> (9u * cond)) & 0x1ffu;
-        const u32x4 r = *reinterpret_cast<const u32x4 *>(lut16_row(p.lut, (code >> (4u * cond)) & 15u, lc));
         uint32_t v[9], wv[9];
+        bin_values(p.lut, i, cond, v);
 #pragma unroll
-        for (uint32_t t = 0; t < 9; t++) {
-            v[t] = (r[t >> 2] >> (8u * (t & 3u))) & 255u;
-            wv[t] = w[v[t]];        // w[255] is there and never used
-        }
+        for (uint32_t t = 0; t < 9; t++)
+            wv[t] = w[v[t]];            // w[255] is there and never used
 #pragma unroll
         for (uint32_t t = 0; t < 9; t++)
             if ((sel9 >> t) & 1u && v[t] != GCN10_NODATA) {
@@ -106,11 +94,9 @@ __global__ __launch_bounds__(kThreads) void zonal_sums_rain_kernel(const ZonalRa
     __shared__ unsigned long long sums[kSums];
     __shared__ uint16_t list[kHistWords];           // the non-zero bins of a flush
     __shared__ uint32_t n_list;
-    __shared__ uint32_t pre[kThreads + 1];          // groups before span j of the spans at hand
-    __shared__ int32_t sy[kThreads], sx0[kThreads], sx1[kThreads];
-    __shared__ uint32_t wave_sum[kWaves];
+    __shared__ WalkLds walk;
 
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     for (uint32_t i = tid; i < (uint32_t)kHistWords; i += kThreads)
         h[i] = 0u;
     __syncthreads();
@@ -131,64 +117,7 @@ __global__ __launch_bounds__(kThreads) void zonal_sums_rain_kernel(const ZonalRa
             cur_zone = zone;
             cur_table = item.table;
         }
-        for (uint32_t s0 = 0; s0 < n_spans; s0 += kThreads) {
-            const uint32_t ns = min((uint32_t)kThreads, n_spans - s0);
-            // the spans at hand and the prefix sums of their group counts
-            uint32_t g = 0u;
-            if (tid < ns) {
-                const gcn10_zone_span sp = p.spans[first_span + s0 + tid];
-                sy[tid] = sp.y;
-                sx0[tid] = sp.x0;
-                sx1[tid] = sp.x1;
-                g = (((uint32_t)sp.x1 - 1u) >> 4) - ((uint32_t)sp.x0 >> 4) + 1u;
-            }
-#pragma unroll
-            for (uint32_t d = 1; d < 64u; d <<= 1) {
-                const uint32_t t = __shfl_up(g, d, 64);
-                if (lane >= d)
-                    g += t;
-            }
-            if (lane == 63u)
-                wave_sum[wave] = g;
-            __syncthreads();
-            for (uint32_t w = 0; w < wave; w++)
-                g += wave_sum[w];
-            pre[tid + 1] = g;
-            if (tid == 0)
-                pre[0] = 0u;
-            __syncthreads();
-            const uint32_t total = pre[ns];
-
-            for (uint32_t q = tid; q < total; q += kThreads) {
-                // the span of group q: the last j with pre[j] <= q
-                uint32_t lo = 0u, hi = ns;
-                while (hi - lo > 1u) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (pre[mid] <= q)
-                        lo = mid;
-                    else
-                        hi = mid;
-                }
-                const uint32_t x0 = (uint32_t)sx0[lo], x1 = (uint32_t)sx1[lo], y = (uint32_t)sy[lo];
-                const uint32_t gx = ((x0 >> 4) + (q - pre[lo])) << 4;       // first column of the group
-                const uint32_t a = max(gx, x0), b = min(gx + kPxPerLane, x1);
-                const uint8_t *erow = p.esa + (size_t)y * p.W + gx;
-                const uint8_t *srow = p.soil.ptr(y, gx);
-                if (gx + kPxPerLane <= p.W) {
-                    const u32x4 e = *reinterpret_cast<const u32x4_u *>(erow);
-                    const u32x4 s = *reinterpret_cast<const u32x4 *>(srow);
-                    if (b - a == kPxPerLane)
-                        count16(h, e, s);
-                    else
-                        count_masked(h, e, s, a - gx, b - gx);
-                }
-                else {
-                    // the row's last group, W no multiple of 16: bytes, nothing past the row end
-                    count_tail(h, erow + (a - gx), srow + (a - gx), b - a);
-                }
-            }
-            __syncthreads();        // sy / sx0 / sx1 / pre are rewritten by the next 256 spans
-        }
+        count_item(p.esa, p.soil, p.W, p.spans, first_span, n_spans, h, walk);
     }
     if (cur_zone >= 0)
         flush_piece(p, h, sums, list, &n_list, (uint32_t)cur_zone, cur_table);
@@ -232,7 +161,7 @@ int gcn10_gpu_zonal_sums_rain(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int
     p.n_items = (uint32_t)n_items;
     p.sel = select_rasters(cond_mask, table_mask, p.conds, p.n_conds);
     p.n_sel = (uint32_t)__builtin_popcount(p.sel);
-    const uint64_t cap = grid_cap(ctx, kZonalRainGridPerCu);
+    const uint64_t cap = grid_cap(ctx, kGridPerCu);
     const uint32_t grid = (uint32_t)(n_items < cap ? n_items : cap);
     p.items_per_wg = (p.n_items + grid - 1u) / grid;
     hipLaunchKernelGGL(zonal_sums_rain_kernel, dim3(grid), dim3(kThreads), 0, s, p);

@@ -357,6 +357,8 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             rc = set_str(&cfg->rains, val);
         else if (!strcmp(key, "zone_rain"))
             rc = set_str(&cfg->zone_rain, val);
+        else if (!strcmp(key, "zone_rains"))
+            rc = set_str(&cfg->zone_rains, val);
         else if (!strcmp(key, "zone_rain_unit")) {
             double unit, lambda;
 
@@ -433,5 +435,6 @@ void gcn10_config_free(gcn10_config *cfg)
     free(cfg->zone_rain);
     free(cfg->zone_rain_unit);
     free(cfg->rains);
+    free(cfg->zone_rains);
     memset(cfg, 0, sizeof *cfg);
 }

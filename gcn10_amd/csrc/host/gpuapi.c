@@ -118,6 +118,8 @@ static void load_once(void)
     *(void **)(&g_api.grid_finish_rains) = dlsym(h, "gcn10_gpu_grid_finish_rains");
     /* and the zonal sums with a weight table per item: needed by zone_rain=... runs only, which check for it */
     *(void **)(&g_api.zonal_sums_rain) = dlsym(h, "gcn10_gpu_zonal_sums_rain");
+    /* and with a tuple of tables per item: needed by zone_rains=... runs only, which check for it */
+    *(void **)(&g_api.zonal_sums_rains) = dlsym(h, "gcn10_gpu_zonal_sums_rains");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

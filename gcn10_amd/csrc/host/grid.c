@@ -343,6 +343,44 @@ int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char
     return *out ? 0 : -1;
 }
 
+int gcn10_zone_rains_load(const char *const files[], int k, gcn10_grid *grid, uint8_t *out[GCN10_MAX_RAINS], char *err,
+                          size_t errcap)
+{
+    char why[1024 + PATH_MAX] = "";
+    int rc = 0;
+
+    for (int j = 0; j < GCN10_MAX_RAINS; j++)
+        out[j] = NULL;
+    memset(grid, 0, sizeof *grid);
+    for (int j = 0; rc == 0 && j < k; j++) {
+        gcn10_grid g;
+
+        if (gcn10_zone_rain_load(files[j], j == 0 ? grid : &g, &out[j], why, sizeof why) != 0) {
+            snprintf(err, errcap, "zone_rains%s", why + strlen("zone_rain"));   /* "zone_rain: ..." as "zone_rains: ..." */
+            rc = -1;
+        }
+        else if (j > 0 && (g.nx != grid->nx || g.ny != grid->ny)) {
+            snprintf(err, errcap, "zone_rains: '%s' has %d x %d pixels, '%s' has %d x %d", files[j], g.nx, g.ny, files[0],
+                     grid->nx, grid->ny);
+            rc = -1;
+        }
+        else if (j > 0 && (memcmp(&g.xmin, &grid->xmin, sizeof g.xmin) != 0 || memcmp(&g.ymax, &grid->ymax, sizeof g.ymax) != 0 ||
+                           memcmp(&g.dx, &grid->dx, sizeof g.dx) != 0 || memcmp(&g.dy, &grid->dy, sizeof g.dy) != 0)) {
+            snprintf(err, errcap, "zone_rains: '%s' does not lie on the grid of '%s' (origin %.17g, %.17g, pixel %.17g x %.17g)",
+                     files[j], files[0], g.xmin, g.ymax, g.dx, -g.dy);     /* its gt[0], gt[3], gt[1], gt[5], as "rain" */
+            rc = -1;
+        }
+    }
+    if (rc != 0) {
+        for (int j = 0; j < GCN10_MAX_RAINS; j++) {
+            free(out[j]);
+            out[j] = NULL;
+        }
+        memset(grid, 0, sizeof *grid);
+    }
+    return rc;
+}
+
 /* ---------------------------------------------------------------------------------------------------------------- */
 /* the run                                                                                                           */
 /* ---------------------------------------------------------------------------------------------------------------- */

@@ -200,6 +200,10 @@ struct gcn10_gpu_api {
     int (*zonal_sums_rain)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const gcn10_zone_span *,
                            const gcn10_zone_rain_item *, size_t, int, unsigned, unsigned, unsigned long long *,
                            gcn10_stream_t);
+    /* optional: NULL when the library has none (needed by zone_rains=... only, with set_rain_tables) */
+    int (*zonal_sums_rains)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const gcn10_zone_span *,
+                            const gcn10_zone_rains_item *, size_t, int, unsigned, unsigned, int, unsigned long long *,
+                            gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -30,6 +30,7 @@ static void usage(FILE *fp)
             "        [--grid <xmin>,<ymax>,<dx>,<dy>,<nx>,<ny>] [--storm <P>[,<lambda>]]\n"
             "        [--storms <P1>[:<P2>...][,<lambda>]] [--rain <file> [--rain-unit <unit>[,<lambda>]]]\n"
             "        [--rains <file1>[:<file2>...]] [--zone-rain <file> [--zone-rain-unit <unit>[,<lambda>]]]\n"
+            "        [--zone-rains <file1>[:<file2>...]]\n"
             "  gcn10 --help | -h | --version | -v\n"
             "\n"
             "options:\n"
@@ -92,7 +93,13 @@ static void usage(FILE *fp)
             "\t\t\tthe field, reduced on the GPU, and the CN that yields it with the zone's mean depth\n"
             "\t\t\t(config key zone_rain=...); needs --zones, not with --storm or --storms\n"
             "  --zone-rain-unit <unit>[,<lambda>]\n"
-            "\t\t\tas --rain-unit, for --zone-rain (config key zone_rain_unit=...)\n"
+            "\t\t\tas --rain-unit, for --zone-rain and --zone-rains (config key zone_rain_unit=...)\n"
+            "  --zone-rains <file1>[:<file2>...]\n"
+            "\t\t\t1 to 8 rainfall rasters as --zone-rain takes one, on one grid, in ONE run: every block\n"
+            "\t\t\tis read, decoded, scan-converted and counted once.  rain_pixels,rain_valid, then\n"
+            "\t\t\train_mm_rain<j>,runoff_mm_rain<j>,cn_runoff_rain<j> per file, each what --zone-rain\n"
+            "\t\t\t<file_j> alone prints (one file: exactly the table of --zone-rain; config key\n"
+            "\t\t\tzone_rains=...); not with --zone-rain, otherwise as --zone-rain\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -159,6 +166,8 @@ int main(int argc, char **argv)
             opt.rains = argv[++i];
         else if (!strcmp(argv[i], "--zone-rain") && i + 1 < argc)
             opt.zone_rain = argv[++i];
+        else if (!strcmp(argv[i], "--zone-rains") && i + 1 < argc)
+            opt.zone_rains = argv[++i];
         else if (!strcmp(argv[i], "--zone-rain-unit") && i + 1 < argc)
             opt.zone_rain_unit = argv[++i];
         else if (!strcmp(argv[i], "--zonal"))

@@ -151,6 +151,7 @@ struct block_in {
     gcn10_grid_plan gplan;
     gcn10_grid_plan zr_gplan;               /* zone_rain: the block on the raster's grid, */
     gcn10_zone_rain_plan zr_cut;            /* ... and the zones' spans cut at its depth changes */
+    gcn10_zone_rains_plan zrs_cut;          /* zone_rains: the spans cut where the byte of any layer changes */
 };
 
 struct worker {
@@ -297,7 +298,11 @@ struct run {
     bool zone_rain_on;
     double zone_rain_unit, zone_rain_lambda;
     gcn10_grid zone_rain_grid;              /* the raster as a grid (gcn10_zone_rain_load) */
-    uint8_t *zone_rain;                     /* [ny][nx]: its counts */
+    bool zone_rains_key;                    /* the rasters come from "zone_rains": summed by the _rains call */
+    int n_zone_rains;                       /* how many: 1 with "zone_rain", 1 to GCN10_MAX_RAINS with "zone_rains" */
+    char *zone_rains_copy;                  /* gcn10_parse_rains' copy of the "zone_rains" value */
+    const char *zone_rain_file[GCN10_MAX_RAINS];    /* their names: cfg.zone_rain, or pointers into zone_rains_copy */
+    uint8_t *zone_rain_layer[GCN10_MAX_RAINS];      /* [ny][nx] each: the counts of every raster, all on zone_rain_grid */
     uint16_t (*zone_rain_q)[256];           /* [256][256]: gcn10_rain_tables */
 };
 

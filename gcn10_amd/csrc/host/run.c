@@ -153,20 +153,40 @@ static int resolve(struct run *r)
         free(r->cfg.zone_rain_unit);
         r->cfg.zone_rain_unit = strdup(opt->zone_rain_unit);
     }
-    r->zone_rain_on = r->cfg.zone_rain != NULL;
+    if (opt->zone_rains) {
+        free(r->cfg.zone_rains);
+        r->cfg.zone_rains = strdup(opt->zone_rains);
+    }
+    r->zone_rains_key = r->cfg.zone_rains != NULL;
+    r->zone_rain_on = r->cfg.zone_rain != NULL || r->zone_rains_key;
     if (r->cfg.zone_rain_unit && !r->zone_rain_on) {
         fprintf(stderr, "[rank 0] zone_rain_unit needs zone_rain\n");
         return 1;
     }
+    if (r->zone_rains_key && r->cfg.zone_rain) {
+        fprintf(stderr, "[rank 0] zone_rains cannot be combined with zone_rain\n");
+        return 1;
+    }
     if (r->zone_rain_on) {
+        const char *key = r->zone_rains_key ? "zone_rains" : "zone_rain";
+
         if (!r->cfg.zonal && !opt->zonal)
-            why = "zone_rain needs --zones";
+            why = "needs --zones";
         else if (opt->storm || r->cfg.storm)
-            why = "zone_rain cannot be combined with storm";
+            why = "cannot be combined with storm";
         else if (opt->storms || r->cfg.storms)
-            why = "zone_rain cannot be combined with storms";
+            why = "cannot be combined with storms";
         if (why) {
-            fprintf(stderr, "[rank 0] %s\n", why);
+            fprintf(stderr, "[rank 0] %s %s\n", key, why);
+            return 1;
+        }
+        if (!r->zone_rains_key) {
+            r->n_zone_rains = 1;
+            r->zone_rain_file[0] = r->cfg.zone_rain;
+        }
+        else if (gcn10_parse_rains(r->cfg.zone_rains, &r->zone_rains_copy, r->zone_rain_file, &r->n_zone_rains) != 0) {
+            fprintf(stderr, "[rank 0] bad value for zone_rains: '%s' (file1[:file2...]: 1 to %d files)\n", r->cfg.zone_rains,
+                    GCN10_MAX_RAINS);
             return 1;
         }
         r->zone_rain_unit = 1.0;
@@ -177,7 +197,10 @@ static int resolve(struct run *r)
                             "lambda < 1)\n", r->cfg.zone_rain_unit);
             return 1;
         }
-        if (gcn10_zone_rain_load(r->cfg.zone_rain, &r->zone_rain_grid, &r->zone_rain, err, sizeof err) != 0) {
+        if (r->zone_rains_key
+                ? gcn10_zone_rains_load(r->zone_rain_file, r->n_zone_rains, &r->zone_rain_grid, r->zone_rain_layer, err,
+                                        sizeof err) != 0
+                : gcn10_zone_rain_load(r->cfg.zone_rain, &r->zone_rain_grid, &r->zone_rain_layer[0], err, sizeof err) != 0) {
             fprintf(stderr, "[rank 0] %s\n", err);
             return 1;
         }
@@ -329,7 +352,7 @@ static int resolve(struct run *r)
 static int require(struct run *r)
 {
     const struct gcn10_gpu_api *g;
-    char err[2048] = "", agg[48], grid[600], storm[600], rain[PATH_MAX + 8], zrain[PATH_MAX + 16], *rains = NULL;
+    char err[2048] = "", agg[48], grid[600], storm[600], rain[PATH_MAX + 8], zrain[PATH_MAX + 16], *rains = NULL, *zrains = NULL;
     int rc = 0;
 
     r->gpu = g = gcn10_gpu_api_get(err, sizeof err);
@@ -351,7 +374,17 @@ static int require(struct run *r)
         }
         snprintf(rains, cap, "rains=%s", r->cfg.rains);
     }
-    snprintf(zrain, sizeof zrain, "zone_rain=%s", r->zone_rain_on ? r->cfg.zone_rain : "");
+    snprintf(zrain, sizeof zrain, "zone_rain=%s", r->zone_rain_on && !r->zone_rains_key ? r->cfg.zone_rain : "");
+    if (r->zone_rains_key) {
+        const size_t cap = strlen(r->cfg.zone_rains) + 16;
+
+        if (!(zrains = malloc(cap))) {
+            free(rains);
+            fprintf(stderr, "[rank 0] out of memory\n");
+            return 1;
+        }
+        snprintf(zrains, cap, "zone_rains=%s", r->cfg.zone_rains);
+    }
     {
         /* the pair histogram's soil codes are asked for where a mode counts pairs, and must be as many as its bins */
         const bool pairs = (r->stats || r->zonal) && g->pair_histogram_codes &&
@@ -359,7 +392,9 @@ static int require(struct run *r)
         const struct { bool on, present; const char *symbol, *needed_by; } needs[] = {
             { r->cog, g->overview_nearest && g->overview_average, "gcn10_gpu_overview_*", "cog=1" },
             { r->stats, g->pair_histogram && pairs, "gcn10_gpu_pair_histogram", "stats=1" },
-            { r->zone_rain_on, g->set_rain_tables && g->zonal_sums_rain, "gcn10_gpu_zonal_sums_rain", zrain },
+            { r->zone_rain_on && !r->zone_rains_key, g->set_rain_tables && g->zonal_sums_rain, "gcn10_gpu_zonal_sums_rain",
+              zrain },
+            { r->zone_rains_key, g->set_rain_tables && g->zonal_sums_rains, "gcn10_gpu_zonal_sums_rains", zrains },
             { r->zonal, g->zonal_pair_histogram && pairs, "gcn10_gpu_zonal_pair_histogram", "zonal=1" },
             { r->aggregate != 0, g->aggregate != NULL, "gcn10_gpu_aggregate", agg },
             { r->grid_on && r->storm_on && !r->storms_key,
@@ -383,6 +418,7 @@ static int require(struct run *r)
             }
     }
     free(rains);
+    free(zrains);
     if (rc)
         return rc;
     r->inflate_codecs = GCN10_CODEC_DEFLATE | GCN10_CODEC_RAW;
@@ -568,21 +604,25 @@ static int load(struct run *r)
                   r->grid.nx, r->grid.ny, r->rain_unit, r->rain_lambda);
         log0_line(r, "INFO", true, "%s: depths %u..%u counts, %zu cells without rain", tag, lo, hi, dry);
     }
-    if (r->zone_rain_on) {
+    for (int j = 0; r->zone_rain_on && j < r->n_zone_rains; j++) {      /* two lines per raster, in the order given */
         const gcn10_grid *zg = &r->zone_rain_grid;
         const size_t n = (size_t)zg->nx * (size_t)zg->ny;
+        const uint8_t *rain = r->zone_rain_layer[j];
         unsigned lo = 255, hi = 0;
         size_t dry = 0;
+        char tag[24] = "zone_rain";
 
+        if (r->n_zone_rains > 1)
+            snprintf(tag, sizeof tag, "zone_rain[%d]", j + 1);
         for (size_t c = 0; c < n; c++) {
-            lo = r->zone_rain[c] < lo ? r->zone_rain[c] : lo;
-            hi = r->zone_rain[c] > hi ? r->zone_rain[c] : hi;
-            dry += r->zone_rain[c] == 0;
+            lo = rain[c] < lo ? rain[c] : lo;
+            hi = rain[c] > hi ? rain[c] : hi;
+            dry += rain[c] == 0;
         }
-        log0_line(r, "INFO", true, "zone_rain: %s, %d x %d cells of %.17g x %.17g from (%.17g, %.17g), unit = %.17g mm, "
-                  "lambda = %.17g", r->cfg.zone_rain, zg->nx, zg->ny, zg->dx, zg->dy, zg->xmin, zg->ymax,
+        log0_line(r, "INFO", true, "%s: %s, %d x %d cells of %.17g x %.17g from (%.17g, %.17g), unit = %.17g mm, "
+                  "lambda = %.17g", tag, r->zone_rain_file[j], zg->nx, zg->ny, zg->dx, zg->dy, zg->xmin, zg->ymax,
                   r->zone_rain_unit, r->zone_rain_lambda);
-        log0_line(r, "INFO", true, "zone_rain: depths %u..%u counts, %zu cells without rain", lo, hi, dry);
+        log0_line(r, "INFO", true, "%s: depths %u..%u counts, %zu cells without rain", tag, lo, hi, dry);
     }
     if (r->n_workers > r->n_blocks) {       /* no worker (and no pinned memory) without a block */
         for (int i = r->n_blocks > 0 ? r->n_blocks : 1; i < r->n_workers; i++) {
@@ -801,7 +841,9 @@ done:
     free(r->verify_failed);
     if (r->mode->end)
         r->mode->end(r);
-    free(r->zone_rain);
+    for (int j = 0; j < GCN10_MAX_RAINS; j++)
+        free(r->zone_rain_layer[j]);
+    free(r->zone_rains_copy);
     free(r->zone_rain_q);
     free(r->rains_copy);
     free(r->block_ids);

@@ -19,6 +19,10 @@
  * the same kind of batches, clears nz x n_sel triples, runs gcn10_gpu_zonal_sums_rain -- the reduction against the 256
  * tables happens on the device -- and takes the triples back: 24 bytes per (zone, raster).  The table adds them, and
  * the cutter's rain_pixels and rain_sum per zone, under its mutex: integers again.
+ *
+ * With several such rasters (config key "zone_rains", "Several rainfall rasters under the zones" there) the spans are cut
+ * where the byte of ANY layer changes (gcn10_zone_rains_cut), the same batches run gcn10_gpu_zonal_sums_rains, and a
+ * (zone, raster) brings back 2 + K words: s and n once, sw_j per layer.  "zone_rain" keeps its own cut and call.
  */
 #include "pipeline_internal.h"
 
@@ -42,14 +46,16 @@ enum { ZONE_BATCH = 1024, SPAN_BATCH = 1 << 20 };
 struct zcell {
     uint64_t pixels, valid, sum, sum2;
     uint64_t runoff[GCN10_MAX_STORMS];      /* per storm, the sum of runoff_q[value] over the valid pixels */
-    uint64_t rain[3];                       /* zone_rain: {s, n, sw} over the valid pixels that lie in a rain cell */
+    uint64_t rain[2 + GCN10_MAX_RAINS];     /* zone_rain / zone_rains: {s, n, sw_1 .. sw_K} over the valid pixels that lie
+                                               in a rain cell */
     int min, max;
 };
 
 struct gcn10_zonal_table {
     pthread_mutex_t mu;
     struct zcell *cell;         /* [zones.n][n_sel] */
-    uint64_t *rain_pixels, *rain_sum;       /* zone_rain: [zones.n] pixels in a rain cell, and the sum of their bytes */
+    uint64_t *rain_pixels, *rain_sum;       /* zone_rain / zone_rains: [zones.n] pixels in a rain cell, and [K][zones.n]
+                                               the sum of every layer's bytes over them */
     int blocks;                 /* blocks counted */
 };
 
@@ -61,7 +67,7 @@ struct gcn10_zonal_state {
     struct zcell *part;                     /* [ZONE_BATCH][n_sel]: a batch, before it goes into the table */
     /* zone_rain: the cut spans, their items and the triples of a batch */
     gcn10_zone_span *h_rspans, *d_rspans;
-    gcn10_zone_rain_item *h_ritems, *d_ritems;
+    void *h_ritems, *d_ritems;              /* gcn10_zone_rain_item or gcn10_zone_rains_item: 16 bytes either way */
     unsigned long long *h_acc, *d_acc;
     size_t h_rspans_cap, d_rspans_cap, h_ritems_cap, d_ritems_cap, h_acc_cap, d_acc_cap;
     bool rain_tables_set;                   /* this worker's context holds the 256 tables */
@@ -81,7 +87,7 @@ int gcn10_zonal_start(struct run *r)
         t->cell = calloc((size_t)(r->zones.n > 0 ? r->zones.n : 1) * (size_t)(r->n_sel > 0 ? r->n_sel : 1), sizeof *t->cell);
     if (t && t->cell && r->zone_rain_on) {
         t->rain_pixels = calloc((size_t)(r->zones.n > 0 ? r->zones.n : 1), sizeof *t->rain_pixels);
-        t->rain_sum = calloc((size_t)(r->zones.n > 0 ? r->zones.n : 1), sizeof *t->rain_sum);
+        t->rain_sum = calloc((size_t)(r->zones.n > 0 ? r->zones.n : 1) * (size_t)r->n_zone_rains, sizeof *t->rain_sum);
     }
     if (!t || !t->cell || (r->zone_rain_on && (!t->rain_pixels || !t->rain_sum))) {
         fprintf(stderr, "[rank 0] out of memory for the table of %d zones\n", r->zones.n);
@@ -154,9 +160,14 @@ static int zonal_plan_block(struct worker *w, struct block_in *in, const double 
 
         gcn10_grid_plan_free(&in->zr_gplan);
         gcn10_zone_rain_plan_free(&in->zr_cut);
+        gcn10_zone_rains_plan_free(&in->zrs_cut);
         if (gcn10_grid_plan_block(zg, in->W, in->H, in->gt, NULL, &in->zr_gplan) != 0 ||
-            gcn10_zone_rain_cut(&in->zplan, in->W, in->H, in->zr_gplan.cellx, in->zr_gplan.celly, in->zr_gplan.cx0,
-                                in->zr_gplan.cy0, r->zone_rain, zg->nx, zg->ny, 0, 0, &in->zr_cut) != 0) {
+            (r->zone_rains_key
+                 ? gcn10_zone_rains_cut(&in->zplan, in->W, in->H, in->zr_gplan.cellx, in->zr_gplan.celly, in->zr_gplan.cx0,
+                                        in->zr_gplan.cy0, (const uint8_t *const *)r->zone_rain_layer, r->n_zone_rains,
+                                        zg->nx, zg->ny, 0, 0, &in->zrs_cut)
+                 : gcn10_zone_rain_cut(&in->zplan, in->W, in->H, in->zr_gplan.cellx, in->zr_gplan.celly, in->zr_gplan.cx0,
+                                       in->zr_gplan.cy0, r->zone_rain_layer[0], zg->nx, zg->ny, 0, 0, &in->zr_cut)) != 0) {
             wlog(w, "ERROR", true, "zonal block %d: out of memory for the spans under the rainfall raster", in->block_id);
             return -1;
         }
@@ -208,55 +219,73 @@ static void cells_of(const struct run *r, const uint64_t *pair, struct zcell *ce
     }
 }
 
-/* zone_rain: the triples of the block's local zones under the rainfall raster, in batches of at most ZONE_BATCH zones
- * and SPAN_BATCH cut spans (one item at least); the table adds them.  0, or -1: a GPU call failed (the caller logs
- * it), or memory ran out (logged). */
+/* first_span and n_spans of item i of either cut: both item structs begin with them */
+static void item_spans(const void *items, size_t i, uint32_t *first_span, uint32_t *n_spans)
+{
+    uint32_t two[2];
+
+    memcpy(two, (const char *)items + i * sizeof(gcn10_zone_rain_item), sizeof two);
+    *first_span = two[0];
+    *n_spans = two[1];
+}
+
+/* zone_rain / zone_rains: the words {s, n, sw_1 .. sw_K} of the block's local zones under the rainfall rasters, in batches
+ * of at most ZONE_BATCH zones and SPAN_BATCH cut spans (one item at least); the table adds them.  0, or -1: a GPU call
+ * failed (the caller logs it), or memory ran out (logged). */
 static int zonal_rain_block(struct worker *w, struct block_in *in, bool *prepared)
 {
     struct run *r = w->run;
     const struct gcn10_gpu_api *g = r->gpu;
-    const gcn10_zone_rain_plan *c = &in->zr_cut;
+    const bool many = r->zone_rains_key;
+    const size_t n_items = many ? in->zrs_cut.n_items : in->zr_cut.n_items;
+    const gcn10_zone_span *spans = many ? in->zrs_cut.spans : in->zr_cut.spans;
+    const void *items = many ? (const void *)in->zrs_cut.items : (const void *)in->zr_cut.items;
     const gcn10_zone_plan *p = &in->zplan;
     struct gcn10_zonal_table *t = r->zonal_table;
     struct gcn10_zonal_state *z = w->zonal;
-    const size_t row = (size_t)r->n_sel * 3u;
+    const size_t item_size = sizeof(gcn10_zone_rain_item);
+    const int words = many ? 2 + r->n_zone_rains : 3;
+    const size_t row = (size_t)r->n_sel * (size_t)words;
 
-    if (c->n_items && !z->rain_tables_set) {
+    _Static_assert(sizeof(gcn10_zone_rain_item) == sizeof(gcn10_zone_rains_item), "one batch code for both item forms");
+    if (n_items && !z->rain_tables_set) {
         if (g->set_rain_tables(w->ctx, r->zone_rain_q[0], 256) != 0)
             return -1;
         z->rain_tables_set = true;
     }
-    for (size_t i0 = 0; i0 < c->n_items;) {
-        const size_t s0 = c->items[i0].first_span;
-        const int zone0 = c->spans[s0].zone;
-        size_t i1 = i0, s1 = s0;
-        int nz;
+    for (size_t i0 = 0; i0 < n_items;) {
+        uint32_t first_span, n_spans;
+        size_t s0, i1 = i0, s1;
+        int zone0, nz;
 
-        while (i1 < c->n_items) {
-            const gcn10_zone_rain_item *it = &c->items[i1];
-
-            if (i1 > i0 && (c->spans[it->first_span].zone - zone0 >= ZONE_BATCH ||
-                            it->first_span + it->n_spans - s0 > SPAN_BATCH))
+        item_spans(items, i0, &first_span, &n_spans);
+        s0 = s1 = first_span;
+        zone0 = spans[s0].zone;
+        while (i1 < n_items) {
+            item_spans(items, i1, &first_span, &n_spans);
+            if (i1 > i0 && (spans[first_span].zone - zone0 >= ZONE_BATCH || first_span + n_spans - s0 > SPAN_BATCH))
                 break;
-            s1 = (size_t)it->first_span + it->n_spans;
+            s1 = (size_t)first_span + n_spans;
             i1++;
         }
-        nz = c->spans[s1 - 1].zone - zone0 + 1;
+        nz = spans[s1 - 1].zone - zone0 + 1;
 
         if (gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_rspans, &z->h_rspans_cap, (s1 - s0) * sizeof *z->h_rspans) != 0 ||
-            gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_ritems, &z->h_ritems_cap, (i1 - i0) * sizeof *z->h_ritems) != 0 ||
+            gcn10_ensure_pinned_on(w, w->ctx, &z->h_ritems, &z->h_ritems_cap, (i1 - i0) * item_size) != 0 ||
             gcn10_ensure_pinned_on(w, w->ctx, (void **)&z->h_acc, &z->h_acc_cap, (size_t)nz * row * sizeof *z->h_acc) != 0 ||
             gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_rspans, &z->d_rspans_cap, (s1 - s0) * sizeof *z->d_rspans) != 0 ||
-            gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_ritems, &z->d_ritems_cap, (i1 - i0) * sizeof *z->d_ritems) != 0 ||
+            gcn10_ensure_dev_on(w, w->ctx, &z->d_ritems, &z->d_ritems_cap, (i1 - i0) * item_size) != 0 ||
             gcn10_ensure_dev_on(w, w->ctx, (void **)&z->d_acc, &z->d_acc_cap, (size_t)nz * row * sizeof *z->d_acc) != 0)
             return -1;
         for (size_t s = s0; s < s1; s++) {
-            z->h_rspans[s - s0] = c->spans[s];
+            z->h_rspans[s - s0] = spans[s];
             z->h_rspans[s - s0].zone -= zone0;
         }
+        memcpy(z->h_ritems, (const char *)items + i0 * item_size, (i1 - i0) * item_size);
         for (size_t i = i0; i < i1; i++) {
-            z->h_ritems[i - i0] = c->items[i];
-            z->h_ritems[i - i0].first_span -= (uint32_t)s0;
+            item_spans(items, i, &first_span, &n_spans);
+            first_span -= (uint32_t)s0;
+            memcpy((char *)z->h_ritems + (i - i0) * item_size, &first_span, sizeof first_span);
         }
         if (!*prepared) {
             if (g->prepare_tile(w->ctx, in->d_coarse, in->hsx, in->hsy, in->d_ci, in->W, w->s_kernel) != 0)
@@ -264,10 +293,12 @@ static int zonal_rain_block(struct worker *w, struct block_in *in, bool *prepare
             *prepared = true;
         }
         if (g->memcpy_h2d(w->ctx, z->d_rspans, z->h_rspans, (s1 - s0) * sizeof *z->h_rspans, w->s_kernel) != 0 ||
-            g->memcpy_h2d(w->ctx, z->d_ritems, z->h_ritems, (i1 - i0) * sizeof *z->h_ritems, w->s_kernel) != 0 ||
+            g->memcpy_h2d(w->ctx, z->d_ritems, z->h_ritems, (i1 - i0) * item_size, w->s_kernel) != 0 ||
             g->memset(w->ctx, z->d_acc, 0, (size_t)nz * row * sizeof *z->d_acc, w->s_kernel) != 0 ||
-            g->zonal_sums_rain(w->ctx, in->d_block, in->W, in->H, in->d_cj, z->d_rspans, z->d_ritems, i1 - i0, nz,
-                               r->cond_mask, r->table_mask, z->d_acc, w->s_kernel) != 0 ||
+            (many ? g->zonal_sums_rains(w->ctx, in->d_block, in->W, in->H, in->d_cj, z->d_rspans, z->d_ritems, i1 - i0, nz,
+                                        r->cond_mask, r->table_mask, r->n_zone_rains, z->d_acc, w->s_kernel)
+                  : g->zonal_sums_rain(w->ctx, in->d_block, in->W, in->H, in->d_cj, z->d_rspans, z->d_ritems, i1 - i0, nz,
+                                       r->cond_mask, r->table_mask, z->d_acc, w->s_kernel)) != 0 ||
             g->memcpy_d2h(w->ctx, z->h_acc, z->d_acc, (size_t)nz * row * sizeof *z->h_acc, w->s_kernel) != 0)
             return -1;
         {
@@ -286,8 +317,8 @@ static int zonal_rain_block(struct worker *w, struct block_in *in, bool *prepare
                 const unsigned long long *src = z->h_acc + (size_t)k * row;
 
                 for (int q = 0; q < r->n_sel; q++)
-                    for (int word = 0; word < 3; word++)
-                        dst[q].rain[word] += src[3 * q + word];
+                    for (int word = 0; word < words; word++)
+                        dst[q].rain[word] += src[words * q + word];
             }
             pthread_mutex_unlock(&t->mu);
             w->t_zone_accum += gcn10_now_seconds() - t0;
@@ -412,9 +443,14 @@ static int zonal_block(struct worker *w, struct block_in *in)
     if (r->zone_rain_on && zonal_rain_block(w, in, &prepared) != 0)
         goto gpu_fail;
     pthread_mutex_lock(&t->mu);
-    for (int k = 0; r->zone_rain_on && k < in->zr_cut.n_local; k++) {
+    for (int k = 0; r->zone_rain_on && !r->zone_rains_key && k < in->zr_cut.n_local; k++) {
         t->rain_pixels[p->local_zone[k]] += in->zr_cut.rain_pixels[k];
         t->rain_sum[p->local_zone[k]] += in->zr_cut.rain_sum[k];
+    }
+    for (int k = 0; r->zone_rains_key && k < in->zrs_cut.n_local; k++) {
+        t->rain_pixels[p->local_zone[k]] += in->zrs_cut.rain_pixels[k];
+        for (int j = 0; j < r->n_zone_rains; j++)
+            t->rain_sum[(size_t)j * (size_t)r->zones.n + (size_t)p->local_zone[k]] += in->zrs_cut.rain_sum[j][k];
     }
     t->blocks++;
     pthread_mutex_unlock(&t->mu);
@@ -448,8 +484,13 @@ static int zonal_finish(struct run *r, gcn10_log *log0)
                 fprintf(f, ",runoff_mm,cn_runoff");
             else
                 fprintf(f, ",runoff_mm_p%u,cn_runoff_p%u", (unsigned)r->runoff_q[j][100], (unsigned)r->runoff_q[j][100]);
-        if (r->zone_rain_on)
+        if (r->zone_rain_on && r->n_zone_rains == 1)
             fprintf(f, ",rain_pixels,rain_mm,rain_valid,runoff_mm_rain,cn_runoff_rain");
+        else if (r->zone_rain_on) {         /* several rasters: what is counted once, then three columns per raster */
+            fprintf(f, ",rain_pixels,rain_valid");
+            for (int j = 1; j <= r->n_zone_rains; j++)
+                fprintf(f, ",rain_mm_rain%d,runoff_mm_rain%d,cn_runoff_rain%d", j, j, j);
+        }
         fprintf(f, "\n");
         for (int i = 0; i < r->zones.n; i++) {
             if (r->n_sel > 0 && t->cell[(size_t)i * (size_t)r->n_sel].pixels == 0)
@@ -476,7 +517,7 @@ static int zonal_finish(struct run *r, gcn10_log *log0)
                     for (int j = 0; j < n_storms; j++)
                         fprintf(f, ",,");
                 }
-                if (r->zone_rain_on) {      /* include/gcn10_host.h "A rainfall raster under the zones" */
+                if (r->zone_rain_on && r->n_zone_rains == 1) {  /* include/gcn10_host.h "A rainfall raster under the zones" */
                     double rain_mm, runoff_mm;
                     int cn;
                     const int have = gcn10_zone_rain_values(t->rain_pixels[i], t->rain_sum[i], r->zone_rain_unit,
@@ -491,6 +532,25 @@ static int zonal_finish(struct run *r, gcn10_log *log0)
                         fprintf(f, "%.14g,%d", runoff_mm, cn);
                     else
                         fprintf(f, ",");
+                }
+                else if (r->zone_rain_on) { /* ... "Several rainfall rasters under the zones" */
+                    fprintf(f, ",%llu,%llu", (unsigned long long)t->rain_pixels[i], (unsigned long long)c->rain[1]);
+                    for (int j = 0; j < r->n_zone_rains; j++) {
+                        double rain_mm, runoff_mm;
+                        int cn;
+                        const int have = gcn10_zone_rain_values(t->rain_pixels[i],
+                                                                t->rain_sum[(size_t)j * (size_t)r->zones.n + (size_t)i],
+                                                                r->zone_rain_unit, r->zone_rain_lambda, c->rain[0], c->rain[1],
+                                                                c->rain[2 + j], &rain_mm, &runoff_mm, &cn);
+
+                        fprintf(f, ",");
+                        if (have & 1)
+                            fprintf(f, "%.14g", rain_mm);
+                        if (have & 2)
+                            fprintf(f, ",%.14g,%d", runoff_mm, cn);
+                        else
+                            fprintf(f, ",,");
+                    }
                 }
                 fprintf(f, "\n");
             }
@@ -532,6 +592,7 @@ static void zonal_plan_free(struct block_in *in)
     gcn10_zone_plan_free(&in->zplan);
     gcn10_grid_plan_free(&in->zr_gplan);
     gcn10_zone_rain_plan_free(&in->zr_cut);
+    gcn10_zone_rains_plan_free(&in->zrs_cut);
 }
 
 const struct gcn10_mode gcn10_mode_zonal = {

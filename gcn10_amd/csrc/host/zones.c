@@ -645,7 +645,7 @@ oom:
 }
 
 /* ---------------------------------------------------------------------------------------------------------------- */
-/* spans cut at the depth changes of a rainfall raster (config key "zone_rain")                                      */
+/* spans cut at the depth changes of rainfall rasters (config keys "zone_rain" and "zone_rains")                     */
 /* ---------------------------------------------------------------------------------------------------------------- */
 
 void gcn10_zone_rain_plan_free(gcn10_zone_rain_plan *p)
@@ -657,47 +657,93 @@ void gcn10_zone_rain_plan_free(gcn10_zone_rain_plan *p)
     memset(p, 0, sizeof *p);
 }
 
-struct rain_items {
-    gcn10_zone_rain_item *v;
+void gcn10_zone_rains_plan_free(gcn10_zone_rains_plan *p)
+{
+    free(p->rain_pixels);
+    for (int j = 0; j < GCN10_MAX_RAINS; j++)
+        free(p->rain_sum[j]);
+    free(p->spans);
+    free(p->items);
+    memset(p, 0, sizeof *p);
+}
+
+/* a piece of a source span under one tuple: layer 0 in t[0], the bytes from k on zero */
+struct rain_piece {
+    int32_t y, x0, x1;
+    uint8_t t[8];
+};
+
+struct rain_pieces {
+    struct rain_piece *v;
     size_t n, cap;
 };
 
-static int rain_item_push(struct rain_items *l, uint32_t first, uint32_t n, uint32_t table)
+static int rain_piece_push(struct rain_pieces *l, int32_t y, int32_t x0, int32_t x1, const uint8_t t[8])
 {
     if (l->n == l->cap) {
-        const size_t cap = l->cap ? l->cap * 2 : 256;
-        gcn10_zone_rain_item *g = realloc(l->v, cap * sizeof *g);
+        const size_t cap = l->cap ? l->cap * 2 : 1024;
+        struct rain_piece *g = realloc(l->v, cap * sizeof *g);
 
         if (!g)
             return -1;
         l->v = g;
         l->cap = cap;
     }
-    l->v[l->n++] = (gcn10_zone_rain_item){ first, n, table, 0 };
+    l->v[l->n] = (struct rain_piece){ y, x0, x1, { 0 } };
+    memcpy(l->v[l->n++].t, t, 8);
     return 0;
 }
 
-int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t *cellx, const int32_t *celly, int cx0,
-                        int cy0, const uint8_t *rain, int nx, int ny, uint32_t max_span_px, uint32_t max_item_px,
-                        gcn10_zone_rain_plan *out)
+struct rains_items {
+    gcn10_zone_rains_item *v;
+    size_t n, cap;
+};
+
+static int rains_item_push(struct rains_items *l, uint32_t first, uint32_t n, const uint8_t t[8])
 {
-    struct span_list pieces = { NULL, 0, 0 }, cut = { NULL, 0, 0 };     /* a piece's `zone` is its byte */
-    struct rain_items items = { NULL, 0, 0 };
-    gcn10_zone_span *sorted = NULL;
+    if (l->n == l->cap) {
+        const size_t cap = l->cap ? l->cap * 2 : 256;
+        gcn10_zone_rains_item *g = realloc(l->v, cap * sizeof *g);
+
+        if (!g)
+            return -1;
+        l->v = g;
+        l->cap = cap;
+    }
+    l->v[l->n] = (gcn10_zone_rains_item){ first, n, { 0 } };
+    memcpy(l->v[l->n++].table, t, 8);
+    return 0;
+}
+
+int gcn10_zone_rains_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t *cellx, const int32_t *celly, int cx0,
+                         int cy0, const uint8_t *const rain[], int k, int nx, int ny, uint32_t max_span_px,
+                         uint32_t max_item_px, gcn10_zone_rains_plan *out)
+{
+    struct rain_pieces pieces = { NULL, 0, 0 };
+    struct span_list cut = { NULL, 0, 0 };
+    struct rains_items items = { NULL, 0, 0 };
+    struct rain_piece *sorted = NULL;
     size_t sorted_cap = 0;
     int32_t *next = NULL;       /* next[x]: the first column after x whose entry of cellx differs from cellx[x] */
+    bool layers = rain != NULL;
     int rc = -1;
 
     memset(out, 0, sizeof *out);
-    if (W <= 0 || H <= 0 || plan->n_local < 0 || plan->n_spans > 0xffffffffu)
+    if (W <= 0 || H <= 0 || plan->n_local < 0 || plan->n_spans > 0xffffffffu || k < 1 || k > GCN10_MAX_RAINS)
         return -1;
     bounds_of(&max_span_px, &max_item_px);
     out->n_local = plan->n_local;
+    out->k = k;
     out->rain_pixels = calloc((size_t)plan->n_local + 1, sizeof *out->rain_pixels);
-    out->rain_sum = calloc((size_t)plan->n_local + 1, sizeof *out->rain_sum);
-    if (!out->rain_pixels || !out->rain_sum)
+    if (!out->rain_pixels)
         goto done;
-    if (!cellx || !celly || !rain || nx <= 0 || ny <= 0 || plan->n_spans == 0) {
+    for (int j = 0; j < k; j++) {
+        out->rain_sum[j] = calloc((size_t)plan->n_local + 1, sizeof *out->rain_sum[j]);
+        if (!out->rain_sum[j])
+            goto done;
+        layers = layers && rain[j] != NULL;
+    }
+    if (!cellx || !celly || !layers || nx <= 0 || ny <= 0 || plan->n_spans == 0) {
         rc = 0;                 /* a block without rain cells, or without zones */
         goto done;
     }
@@ -710,15 +756,15 @@ int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t
 
     for (size_t i = 0; i < plan->n_spans;) {
         const int32_t zone = plan->spans[i].zone;
-        size_t count[257] = { 0 }, j = i;
+        size_t j = i;
 
         /* the pieces of the zone, in the order of its spans: (y, x0) */
         pieces.n = 0;
         for (; j < plan->n_spans && plan->spans[j].zone == zone; j++) {
             const gcn10_zone_span *sp = &plan->spans[j];
-            const uint8_t *row;
-            int32_t run0 = 0, run1 = 0;         /* the open run [run0, run1) of byte runb; empty: none */
-            uint8_t runb = 0;
+            int32_t run0 = 0, run1 = 0;         /* the open run [run0, run1) of tuple runt; empty: none */
+            uint8_t runt[8] = { 0 };
+            size_t row;
             int64_t cy;
 
             if (sp->y < 0 || sp->y >= H || sp->x0 < 0 || sp->x1 > W || sp->x0 >= sp->x1 || zone < 0 ||
@@ -727,28 +773,31 @@ int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t
             cy = (int64_t)celly[sp->y] + cy0;
             if (celly[sp->y] < 0 || cy >= ny)
                 continue;
-            row = rain + (size_t)cy * (size_t)nx;
+            row = (size_t)cy * (size_t)nx;
             for (int32_t x = sp->x0; x <= sp->x1;) {
                 const int32_t end = x < sp->x1 ? (next[x] < sp->x1 ? next[x] : sp->x1) : x + 1;
                 const int64_t cx = x < sp->x1 ? (int64_t)cellx[x] + cx0 : -1;
                 const bool in = x < sp->x1 && cellx[x] >= 0 && cx < nx;
+                uint8_t t[8] = { 0 };
 
-                if (in && run1 > run0 && run1 == x && row[cx] == runb) {
-                    run1 = end;         /* a neighbouring cell of equal byte */
+                for (int m = 0; in && m < k; m++)
+                    t[m] = rain[m][row + (size_t)cx];
+                if (in && run1 > run0 && run1 == x && memcmp(t, runt, 8) == 0) {
+                    run1 = end;         /* a neighbouring cell of equal tuple */
                 }
                 else {
                     if (run1 > run0) {
-                        if (span_push(&pieces, sp->y, run0, run1, runb, 0x40000000u) != 0)
+                        if (rain_piece_push(&pieces, sp->y, run0, run1, runt) != 0)
                             goto done;
-                        count[runb + 1]++;
                         out->rain_pixels[zone] += (uint64_t)(run1 - run0);
-                        out->rain_sum[zone] += (uint64_t)(run1 - run0) * runb;
+                        for (int m = 0; m < k; m++)
+                            out->rain_sum[m][zone] += (uint64_t)(run1 - run0) * runt[m];
                     }
                     run0 = run1 = 0;
                     if (in) {
                         run0 = x;
                         run1 = end;
-                        runb = row[cx];
+                        memcpy(runt, t, 8);
                     }
                 }
                 x = end;
@@ -758,39 +807,54 @@ int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t
         if (pieces.n == 0)
             continue;
 
-        /* a counting sort on the byte keeps (y, x0) within a byte */
+        /* a counting sort per layer, the last first, keeps (y, x0) within a tuple and leaves the tuples in
+         * lexicographic order; an even number of passes ends in pieces.v, an odd one in sorted */
         if (grow((void **)&sorted, &sorted_cap, pieces.n, sizeof *sorted) != 0)
             goto done;
-        for (int b = 0; b < 256; b++)
-            count[b + 1] += count[b];
-        for (size_t k = 0; k < pieces.n; k++)
-            sorted[count[pieces.v[k].zone]++] = pieces.v[k];
+        {
+            struct rain_piece *src = pieces.v, *dst = sorted;
 
-        /* the zone's spans, never longer than max_span_px, and items of one byte with at most max_item_px pixels */
-        for (size_t k = 0; k < pieces.n;) {
-            const int32_t b = sorted[k].zone;
-            size_t first = cut.n;
-            uint64_t px = 0;
+            for (int m = k - 1; m >= 0; m--) {
+                size_t count[257] = { 0 };
+                struct rain_piece *tmp;
 
-            for (; k < pieces.n && sorted[k].zone == b; k++) {
-                const size_t before = cut.n;
-
-                if (span_push(&cut, sorted[k].y, sorted[k].x0, sorted[k].x1, zone, max_span_px) != 0)
-                    goto done;
-                for (size_t m = before; m < cut.n; m++) {
-                    const uint64_t len = (uint64_t)(cut.v[m].x1 - cut.v[m].x0);
-
-                    if (m > first && px + len > max_item_px) {
-                        if (rain_item_push(&items, (uint32_t)first, (uint32_t)(m - first), (uint32_t)b) != 0)
-                            goto done;
-                        first = m;
-                        px = 0;
-                    }
-                    px += len;
-                }
+                for (size_t q = 0; q < pieces.n; q++)
+                    count[src[q].t[m] + 1]++;
+                for (int b = 0; b < 256; b++)
+                    count[b + 1] += count[b];
+                for (size_t q = 0; q < pieces.n; q++)
+                    dst[count[src[q].t[m]]++] = src[q];
+                tmp = src;
+                src = dst;
+                dst = tmp;
             }
-            if (cut.n > 0xffffffffu || rain_item_push(&items, (uint32_t)first, (uint32_t)(cut.n - first), (uint32_t)b) != 0)
-                goto done;
+
+            /* the zone's spans, never longer than max_span_px, and items of one tuple with at most max_item_px pixels */
+            for (size_t q = 0; q < pieces.n;) {
+                const uint8_t *t = src[q].t;
+                size_t first = cut.n;
+                uint64_t px = 0;
+
+                for (; q < pieces.n && memcmp(src[q].t, t, 8) == 0; q++) {
+                    const size_t before = cut.n;
+
+                    if (span_push(&cut, src[q].y, src[q].x0, src[q].x1, zone, max_span_px) != 0)
+                        goto done;
+                    for (size_t m = before; m < cut.n; m++) {
+                        const uint64_t len = (uint64_t)(cut.v[m].x1 - cut.v[m].x0);
+
+                        if (m > first && px + len > max_item_px) {
+                            if (rains_item_push(&items, (uint32_t)first, (uint32_t)(m - first), t) != 0)
+                                goto done;
+                            first = m;
+                            px = 0;
+                        }
+                        px += len;
+                    }
+                }
+                if (cut.n > 0xffffffffu || rains_item_push(&items, (uint32_t)first, (uint32_t)(cut.n - first), t) != 0)
+                    goto done;
+            }
         }
     }
     out->spans = cut.v;
@@ -802,11 +866,38 @@ int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t
     rc = 0;
 done:
     if (rc != 0)
-        gcn10_zone_rain_plan_free(out);
+        gcn10_zone_rains_plan_free(out);
     free(pieces.v);
     free(cut.v);
     free(items.v);
     free(sorted);
     free(next);
     return rc;
+}
+
+/* one layer: the same walk, its items and sums in the one-raster form */
+int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t *cellx, const int32_t *celly, int cx0,
+                        int cy0, const uint8_t *rain, int nx, int ny, uint32_t max_span_px, uint32_t max_item_px,
+                        gcn10_zone_rain_plan *out)
+{
+    gcn10_zone_rains_plan many;
+
+    memset(out, 0, sizeof *out);
+    if (gcn10_zone_rains_cut(plan, W, H, cellx, celly, cx0, cy0, &rain, 1, nx, ny, max_span_px, max_item_px, &many) != 0)
+        return -1;
+    out->items = many.n_items ? malloc(many.n_items * sizeof *out->items) : NULL;
+    if (many.n_items && !out->items) {
+        gcn10_zone_rains_plan_free(&many);
+        return -1;
+    }
+    for (size_t i = 0; i < many.n_items; i++)
+        out->items[i] = (gcn10_zone_rain_item){ many.items[i].first_span, many.items[i].n_spans, many.items[i].table[0], 0 };
+    out->n_local = many.n_local;
+    out->rain_pixels = many.rain_pixels;
+    out->rain_sum = many.rain_sum[0];
+    out->n_spans = many.n_spans;
+    out->n_items = many.n_items;
+    out->spans = many.spans;
+    free(many.items);
+    return 0;
 }

@@ -51,6 +51,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_set_weight_tables", "gcn10_gpu_grid_sums_storms", "gcn10_gpu_grid_finish_storms",
     "gcn10_gpu_grid_rain_item", "gcn10_gpu_set_rain_tables", "gcn10_gpu_grid_sums_rain", "gcn10_gpu_grid_finish_rain",
     "gcn10_gpu_zonal_sums_rain", "gcn10_gpu_grid_sums_rains", "gcn10_gpu_grid_finish_rains",
+    "gcn10_gpu_zonal_sums_rains",
 )
 
 
@@ -171,6 +172,7 @@ def lib():
             "gcn10_gpu_grid_sums_rain": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, vp, vp]),
             "gcn10_gpu_grid_finish_rain": (i, [vp, vp, i, sz, vp, vp, vp, vp, C.c_uint32, vp, vp]),
             "gcn10_gpu_zonal_sums_rain": (i, [vp, vp, i, i, vp, vp, vp, sz, i, u, u, vp, vp]),
+            "gcn10_gpu_zonal_sums_rains": (i, [vp, vp, i, i, vp, vp, vp, sz, i, u, u, i, vp, vp]),
             "gcn10_gpu_grid_sums_rains": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, i, vp, vp]),
             "gcn10_gpu_grid_finish_rains": (i, [vp, vp, i, sz, vp, i, vp, vp, vp, C.c_uint32, vp, vp]),
         }
@@ -648,6 +650,41 @@ class Engine:
         self._chk(lib().gcn10_gpu_zonal_sums_rain(self._ctx, esa_ptr, W, rows, cj_ptr, spans_ptr, items_ptr, n_items,
                                                   n_zones, cond_mask, table_mask, acc_ptr, stream),
                   "gcn10_gpu_zonal_sums_rain")
+
+    def zonal_sums_rains(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans, items, n_zones: int, cond_mask: int,
+                         table_mask: int, k: int, acc_ptr: int, stream=None):
+        """ADDS {s, n, sw_1 .. sw_k} of the pixels of every span to acc[zone][q] ([n_zones][n_sel][2 + k] uint64 on the
+        device), sw_j the sum of w[item.table[j]][v] for the tables of set_rain_tables (gcn10_gpu_zonal_sums_rains).  spans
+        (host.ZONE_SPAN_DTYPE) and items (host.ZONE_RAINS_ITEM_DTYPE: the spans of one zone under one tuple of tables
+        each), as host.zone_rains_cut makes them, are checked here -- the kernel trusts them --, uploaded, and freed
+        when the call has run."""
+        sp = np.ascontiguousarray(spans, dtype=_host.ZONE_SPAN_DTYPE)
+        it = np.ascontiguousarray(items, dtype=_host.ZONE_RAINS_ITEM_DTYPE)
+        if sp.size and not ((sp["y"] >= 0).all() and (sp["y"] < rows).all() and (sp["x0"] >= 0).all() and
+                            (sp["x0"] < sp["x1"]).all() and (sp["x1"] <= W).all() and (sp["zone"] >= 0).all() and
+                            (sp["zone"] < n_zones).all()):
+            raise ValueError("a span lies outside the %d x %d strip or its zone outside 0..%d" % (W, rows, n_zones - 1))
+        first, n = it["first_span"].astype(np.int64), it["n_spans"].astype(np.int64)
+        if it.size and not ((n > 0).all() and (first >= 0).all() and int((first + n).max()) <= sp.size and
+                            all(len(set(sp["zone"][a:a + m].tolist())) == 1 for a, m in zip(first, n))):
+            raise ValueError("an item names spans that are not there, or the spans of two zones")
+        bufs = [self.upload(sp), self.upload(it)] if it.size else []
+        try:
+            self.zonal_sums_rains_device(esa_ptr, W, rows, cj_ptr, bufs[0].ptr if bufs else None,
+                                         bufs[1].ptr if bufs else None, it.size, n_zones, cond_mask, table_mask, k,
+                                         acc_ptr, stream)
+            self.sync(stream)
+        finally:
+            for b in bufs:
+                b.close()
+
+    def zonal_sums_rains_device(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, spans_ptr, items_ptr, n_items: int,
+                                n_zones: int, cond_mask: int, table_mask: int, k: int, acc_ptr: int, stream=None):
+        """gcn10_gpu_zonal_sums_rains over spans and items that are on the device already: asynchronous on `stream` and
+        UNCHECKED (timing)."""
+        self._chk(lib().gcn10_gpu_zonal_sums_rains(self._ctx, esa_ptr, W, rows, cj_ptr, spans_ptr, items_ptr, n_items,
+                                                   n_zones, cond_mask, table_mask, k, acc_ptr, stream),
+                  "gcn10_gpu_zonal_sums_rains")
 
     def pair_histogram(self, esa_ptr: int, W: int, rows: int, cj_ptr: int, hist_ptr: int, stream=None):
         """Adds the (landcover, soil code) pair counts of a W x rows device strip to the device histogram hist_ptr

@@ -169,6 +169,13 @@ def lib():
         L.gcn10_zone_rain_cut.restype = C.c_int
         L.gcn10_zone_rain_plan_free.argtypes = [C.POINTER(ZoneRainPlan)]
         L.gcn10_zone_rain_plan_free.restype = None
+        L.gcn10_zone_rains_load.argtypes = [C.POINTER(cp), C.c_int, C.POINTER(Grid), C.POINTER(vp), cp, C.c_size_t]
+        L.gcn10_zone_rains_load.restype = C.c_int
+        L.gcn10_zone_rains_cut.argtypes = [C.POINTER(ZonePlan), C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(vp),
+                                           C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(ZoneRainsPlan)]
+        L.gcn10_zone_rains_cut.restype = C.c_int
+        L.gcn10_zone_rains_plan_free.argtypes = [C.POINTER(ZoneRainsPlan)]
+        L.gcn10_zone_rains_plan_free.restype = None
         L.gcn10_tiff_abort.argtypes = [vp]
         L.gcn10_tiff_abort.restype = None
         L.free_ = C.CDLL(None).free
@@ -239,6 +246,12 @@ class ConfigRains(ConfigZoneRain):
     _fields_ = [("rains", C.c_char_p)]
 
 
+class ConfigZoneRains(ConfigRains):
+    """``gcn10_config`` with the key of several rainfall rasters under zones, appended behind ``ConfigRains`` as the C
+    struct appends it."""
+    _fields_ = [("zone_rains", C.c_char_p)]
+
+
 assert C.sizeof(Config) % 8 == 0
 
 
@@ -271,6 +284,13 @@ class ZoneRainPlan(C.Structure):
                 ("n_spans", C.c_size_t), ("n_items", C.c_size_t), ("spans", C.c_void_p), ("items", C.c_void_p)]
 
 
+class ZoneRainsPlan(C.Structure):
+    """``gcn10_zone_rains_plan`` of include/gcn10_host.h."""
+    _fields_ = [("n_local", C.c_int), ("k", C.c_int), ("rain_pixels", C.POINTER(C.c_uint64)),
+                ("rain_sum", C.POINTER(C.c_uint64) * 8), ("n_spans", C.c_size_t), ("n_items", C.c_size_t),
+                ("spans", C.c_void_p), ("items", C.c_void_p)]
+
+
 class AggregateGeom(C.Structure):
     """``gcn10_aggregate_geom`` of include/gcn10_host.h."""
     _fields_ = [("x0", C.c_int), ("x1", C.c_int), ("y0", C.c_int), ("y1", C.c_int), ("Wa", C.c_int), ("Ha", C.c_int),
@@ -296,6 +316,8 @@ ZONE_SPAN_DTYPE = np.dtype([("y", "<i4"), ("x0", "<i4"), ("x1", "<i4"), ("zone",
 ZONE_ITEM_DTYPE = np.dtype([("first_span", "<u4"), ("n_spans", "<u4")])
 # struct gcn10_zone_rain_item
 ZONE_RAIN_ITEM_DTYPE = np.dtype([("first_span", "<u4"), ("n_spans", "<u4"), ("table", "<u4"), ("reserved", "<u4")])
+# struct gcn10_zone_rains_item: a tuple of up to eight tables, layer 0 first
+ZONE_RAINS_ITEM_DTYPE = np.dtype([("first_span", "<u4"), ("n_spans", "<u4"), ("table", "u1", (8,))])
 
 
 class HostError(RuntimeError):
@@ -612,16 +634,75 @@ def zone_rain_cut(plan: dict, W: int, H: int, gplan: dict, rain, max_span_px: in
     return res
 
 
+def zone_rains_load(paths):
+    """The rainfall rasters of a zonal run that takes several: (grid, uint8[k][ny][nx]), the grid that of the first file
+    (``gcn10_zone_rains_load``); raises HostError with the run's refusal text ("zone_rains: ...") for the first file that
+    cannot be taken, has another size than the first or does not lie on its grid."""
+    g = Grid()
+    k = len(paths)
+    names = (C.c_char_p * max(k, 1))(*[os.fsencode(p) for p in paths])
+    out = (C.c_void_p * MAX_RAINS)()
+    err = C.create_string_buffer(8192)
+    if lib().gcn10_zone_rains_load(names, k, C.byref(g), out, err, len(err)) != 0:
+        e = HostError(err.value.decode(errors="replace"))
+        e.left = [out[j] for j in range(MAX_RAINS)]     # what stayed allocated: all None
+        raise e
+    try:
+        grid = {name: getattr(g, name) for name, _t in Grid._fields_}
+        n = g.nx * g.ny
+        return grid, np.stack([np.ctypeslib.as_array(C.cast(out[j], C.POINTER(C.c_uint8)), (n,)).copy()
+                               for j in range(k)]).reshape(k, g.ny, g.nx)
+    finally:
+        for j in range(k):
+            lib().free_(out[j])
+
+
+def zone_rains_cut(plan: dict, W: int, H: int, gplan: dict, rains, max_span_px: int = 0, max_item_px: int = 0,
+                   n_local: int | None = None) -> dict:
+    """The spans of a block's zone plan cut where the byte of ANY of the k rainfall rasters changes
+    (``gcn10_zone_rains_cut``).  gplan: the dict of grid_plan_block for the block on the rasters' grid; rains:
+    uint8[k][ny][nx].  ``spans`` (ZONE_SPAN_DTYPE, sorted by (zone, tuple, y, x0)), ``items`` (ZONE_RAINS_ITEM_DTYPE),
+    ``rain_pixels`` (uint64 per local zone) and ``rain_sum`` (uint64[k][n_local])."""
+    sp = np.ascontiguousarray(plan["spans"], dtype=ZONE_SPAN_DTYPE)
+    if n_local is None:
+        n_local = len(plan["local_zone"]) if "local_zone" in plan else (int(sp["zone"].max()) + 1 if sp.size else 0)
+    zp = ZonePlan()
+    zp.n_local = int(n_local)
+    zp.n_spans = sp.size
+    zp.spans = sp.ctypes.data if sp.size else None
+    r = np.ascontiguousarray(rains, dtype=np.uint8)
+    cellx = np.ascontiguousarray(gplan["cellx"], dtype=np.int32)
+    celly = np.ascontiguousarray(gplan["celly"], dtype=np.int32)
+    if (cellx.size not in (0, W)) or (celly.size not in (0, H)) or r.ndim != 3:
+        raise ValueError("cellx / celly must have W / H entries (or none), the rasters three dimensions")
+    k = r.shape[0]
+    layers = (C.c_void_p * max(k, 1))(*[r[j].ctypes.data for j in range(k)])
+    out = ZoneRainsPlan()
+    rc = lib().gcn10_zone_rains_cut(C.byref(zp), int(W), int(H), cellx.ctypes.data if cellx.size else None,
+                                    celly.ctypes.data if celly.size else None, int(gplan["cx0"]), int(gplan["cy0"]),
+                                    layers, k, r.shape[2], r.shape[1], int(max_span_px), int(max_item_px), C.byref(out))
+    if rc != 0:
+        raise HostError("gcn10_zone_rains_cut: k outside 1..8, a span outside the block, a zone outside the plan, or out "
+                        "of memory")
+    res = {"spans": _copy(out.spans, out.n_spans, ZONE_SPAN_DTYPE),
+           "items": _copy(out.items, out.n_items, ZONE_RAINS_ITEM_DTYPE),
+           "rain_pixels": _copy(out.rain_pixels, out.n_local, np.uint64),
+           "rain_sum": np.stack([_copy(out.rain_sum[j], out.n_local, np.uint64) for j in range(k)])}
+    lib().gcn10_zone_rains_plan_free(C.byref(out))
+    return res
+
+
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = ConfigRains()
+    cfg = ConfigZoneRains()
     err = C.create_string_buffer(1024)
     rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
         raise HostError(err.value.decode(errors="replace"))
     out = {}
     for name, _t in (Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_ + ConfigStorm._fields_ +
-                     ConfigStorms._fields_ + ConfigRain._fields_ + ConfigZoneRain._fields_ + ConfigRains._fields_):
+                     ConfigStorms._fields_ + ConfigRain._fields_ + ConfigZoneRain._fields_ + ConfigRains._fields_ +
+                     ConfigZoneRains._fields_):
         v = getattr(cfg, name)
         out[name] = v.decode() if isinstance(v, bytes) else list(v) if isinstance(v, C.Array) else v
     lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))

@@ -580,6 +580,33 @@ int gcn10_gpu_zonal_sums_rain(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int
                               int n_zones, unsigned cond_mask, unsigned table_mask,
                               unsigned long long *acc /* [n_zones][n_sel][3] = {s, n, sw} */, gcn10_stream_t stream);
 
+/* A tuple of weight tables per piece of a zone (config key zone_rains=...: 1 to GCN10_GPU_MAX_RAIN_LAYERS rainfall rasters
+ * under the zones, counted once).  Added in ABI 3 without a version change; the host looks it up for zone_rains runs only.
+ *
+ * gcn10_gpu_zonal_sums_rains: every word of gcn10_gpu_zonal_sums_rain's contract -- esa, W, rows, cj, the prepared soil,
+ *   the spans, ADD semantics, any W and any alignment of esa, nothing at or beyond esa + W * rows is read, pixels named
+ *   twice count twice, the words do not depend on the launch shape, on how the spans are cut into items, or on order, a
+ *   (zone, tuple) run of a workgroup names fewer than 2^32 pixels, n_items == 0 is a successful no-op that reads no
+ *   pointer --, for 2 + k words per (zone, raster): words 0 and 1 are s and n, word 2 + j gets the sum of
+ *   w[items_dev[i].table[j]][v] over the item's pixels with v != 255.  items_dev[i] names n_spans consecutive spans of ONE
+ *   zone from first_span on, all under ONE tuple (gcn10_zone_rains_cut of gcn10_host.h makes spans and items, sorted by
+ *   (zone, tuple)).  A byte that is at least the number of rain tables counts as table 0.  Bytes k..7 of an item pick no
+ *   table, and the words never depend on them.  Nothing outside acc's n_zones * n_sel * (2 + k) words is written.  The
+ *   pixels are counted once whatever k is.  With k = 1 the call adds exactly the words gcn10_gpu_zonal_sums_rain adds for
+ *   table = table[0].  The grid is capped as that call's.
+ * GCN10_E_INVAL naming the call: k outside 1..GCN10_GPU_MAX_RAIN_LAYERS, or any argument the one-raster call refuses.
+ *   GCN10_E_STATE: no tables, no tile prepared for width W, or no rain tables.  A refused call writes nothing.
+ *   Asynchronous on `stream`. */
+#ifndef GCN10_ZONE_RAINS_ITEM_DEFINED
+#define GCN10_ZONE_RAINS_ITEM_DEFINED
+typedef struct gcn10_zone_rains_item { uint32_t first_span, n_spans; uint8_t table[8]; } gcn10_zone_rains_item;
+#endif
+int gcn10_gpu_zonal_sums_rains(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                               const gcn10_zone_span *spans_dev, const gcn10_zone_rains_item *items_dev, size_t n_items,
+                               int n_zones, unsigned cond_mask, unsigned table_mask, int k,
+                               unsigned long long *acc /* [n_zones][n_sel][2 + k] = {s, n, sw_1 .. sw_k} */,
+                               gcn10_stream_t stream);
+
 /* Verification of written rasters (config key verify=1): decoded file rasters compared on the GPU with the values
  * computed now.  Added in ABI 3 without a version change; the host looks them up for verify runs only.
  *

@@ -156,10 +156,13 @@ typedef struct gcn10_config {
     char *zone_rain;        /* "zone_rain": a one-band Byte GeoTIFF with a geotransform, the rainfall depth in counts under
                                the zones of a zonal run (gcn10_zone_rain_load); not together with "storm" / "storms";
                                absent = off */
-    char *zone_rain_unit;   /* "zone_rain_unit": <unit>[,<lambda>] as "rain_unit"; needs "zone_rain" */
+    char *zone_rain_unit;   /* "zone_rain_unit": <unit>[,<lambda>] as "rain_unit"; needs "zone_rain" or "zone_rains" */
     char *rains;            /* "rains": <file1>[:<file2>...] (gcn10_parse_rains): 1 to GCN10_MAX_RAINS rainfall rasters as
                                "rain" takes one, all in one grid run that counts its pixels once; "rain_unit" holds for
                                all of them; not together with "rain"; absent = off */
+    char *zone_rains;       /* "zone_rains": <file1>[:<file2>...] (gcn10_parse_rains): 1 to GCN10_MAX_RAINS rainfall rasters
+                               as "zone_rain" takes one, all in one zonal run that counts its pixels once (gcn10_zone_rains_load);
+                               "zone_rain_unit" holds for all of them; not together with "zone_rain"; absent = off */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -605,6 +608,57 @@ int gcn10_zone_rain_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t
                         gcn10_zone_rain_plan *out);
 void gcn10_zone_rain_plan_free(gcn10_zone_rain_plan *p);
 
+/* Several rainfall rasters under the zones in one run (config key "zone_rains=<file1>[:<file2>...]", --zone-rains; read by
+ * gcn10_parse_rains): K = 1 to GCN10_MAX_RAINS files, every one by every rule of "zone_rain" (Byte band, geotransform,
+ * north up, at most GCN10_GRID_MAX_CELLS pixels); files 2..K have the size of file 1 and its geotransform, bit for bit.
+ * One unit and lambda serve all layers ("zone_rain_unit" / --zone-rain-unit, accepted with either key), and so does one
+ * set of gcn10_rain_tables.  Not together with "zone_rain", "storm" or "storms"; needs zones.
+ *
+ * The sums, for zone z and selected raster r, over the pixels of z that lie in a rain cell and whose value v != 255:
+ * s = the sum of v and n = their count, both counted once; sw_j = the sum of q[b_j(pixel)][v] for each layer j.
+ * Independent of r: rain_pixels, counted once (the grid is shared, so it is the same for every layer), and rain_sum_j per
+ * layer.  All are integers, additive across blocks and workers.
+ *
+ * zonal_cn.csv: with K = 1, header and rows are byte for byte those of "zone_rain=<file1>".  With K > 1, after the columns
+ * of the run without the key come rain_pixels,rain_valid and then, for j = 1..K in the order given,
+ * rain_mm_rain<j>,runoff_mm_rain<j>,cn_runoff_rain<j>, each triple formed by gcn10_zone_rain_values(rain_pixels,
+ * rain_sum_j, unit, lambda, s, n, sw_j, ...): as text what "zone_rain=<file_j>" alone prints in
+ * rain_mm,runoff_mm_rain,cn_runoff_rain, empty fields included. */
+/* gcn10_zone_rain_load for every file, in order: *grid of file 1, out[0 .. k) = nx * ny bytes each (the caller frees
+ * them).  0, or -1 with the run's refusal in err: gcn10_zone_rain_load's message under the prefix "zone_rains:",
+ * "zone_rains: '<file>' has <w> x <h> pixels, '<file1>' has <nx> x <ny>", or "zone_rains: '<file>' does not lie on the grid
+ * of '<file1>' (origin %.17g, %.17g, pixel %.17g x %.17g)" with the file's own gt[0], gt[3], gt[1], gt[5]; nothing stays
+ * allocated then, out[] is all NULL and *grid all zero. */
+int gcn10_zone_rains_load(const char *const files[], int k, gcn10_grid *grid, uint8_t *out[GCN10_MAX_RAINS], char *err,
+                          size_t errcap);
+/* The spans of a block's plan cut wherever the byte of ANY of k layers changes -- the input of
+ * gcn10_gpu_zonal_sums_rains (the same item struct as in gcn10_gpu.h).  It is the walk of gcn10_zone_rain_cut with "one
+ * byte" replaced by "one k-tuple of bytes": rain[j] holds layer j's nx x ny bytes, k = 1..GCN10_MAX_RAINS; a tuple is 8
+ * bytes, layer 0 first, bytes k..7 zero.  Each cut span is a maximal run of columns of ONE source span, in cells, under
+ * one tuple (neighbouring cells of equal tuple merge), split at max_span_px; spans sorted by (zone, tuple, y, x0), tuples
+ * in lexicographic order; items: runs of consecutive spans of ONE zone and ONE tuple (`table`), at most max_item_px pixels
+ * each (0 = the builder's own bounds; results never depend on them).  rain_pixels[n_local]: the pixels of each local zone
+ * in a rain cell; rain_sum[j][n_local]: the sum of layer j's bytes over them (rain_sum[j] is NULL for j >= k).  With k
+ * identical layers, spans and items are those of gcn10_zone_rain_cut, with the byte repeated.  Cost: O(W + spans + rain
+ * cells crossed + k * pieces), the counting sort of gcn10_zone_rain_cut once per layer, last layer first.  0; -1 for k
+ * outside 1..GCN10_MAX_RAINS, a span outside the W x H block, a zone outside the plan, or out of memory. */
+#ifndef GCN10_ZONE_RAINS_ITEM_DEFINED
+#define GCN10_ZONE_RAINS_ITEM_DEFINED
+typedef struct gcn10_zone_rains_item { uint32_t first_span, n_spans; uint8_t table[8]; } gcn10_zone_rains_item;
+#endif
+typedef struct gcn10_zone_rains_plan {
+    int n_local, k;
+    uint64_t *rain_pixels;                  /* [n_local] */
+    uint64_t *rain_sum[GCN10_MAX_RAINS];    /* [k][n_local] */
+    size_t n_spans, n_items;
+    gcn10_zone_span *spans;
+    gcn10_zone_rains_item *items;
+} gcn10_zone_rains_plan;
+int gcn10_zone_rains_cut(const gcn10_zone_plan *plan, int W, int H, const int32_t *cellx, const int32_t *celly, int cx0,
+                         int cy0, const uint8_t *const rain[], int k, int nx, int ny, uint32_t max_span_px,
+                         uint32_t max_item_px, gcn10_zone_rains_plan *out);
+void gcn10_zone_rains_plan_free(gcn10_zone_rains_plan *p);
+
 /* ------------------------------------------------------------------------ */
 /* the run: src/main.c:58-203 + process_block, src/cn.c:134-384              */
 /* ------------------------------------------------------------------------ */
@@ -633,6 +687,7 @@ typedef struct gcn10_run_options {
     const char *zone_rain;      /* --zone-rain <file>: overrides the config key "zone_rain" */
     const char *zone_rain_unit; /* --zone-rain-unit <unit>[,<lambda>]: overrides the config key "zone_rain_unit" */
     const char *rains;          /* --rains <file1>[:<file2>...]: overrides the config key "rains" */
+    const char *zone_rains;     /* --zone-rains <file1>[:<file2>...]: overrides the config key "zone_rains" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
@@ -680,7 +735,9 @@ int gcn10_verify_structure(const char *path, int xsize, int ysize, const double 
  * grid run that counts its pixels once (with one file: exactly what rain adds).  A rainfall raster
  * under the zones (opt->zone_rain / "zone_rain=<file>", with opt->zone_rain_unit / "zone_rain_unit=...") adds the columns
  * rain_pixels,rain_mm,rain_valid,runoff_mm_rain,cn_runoff_rain to a zonal run's table ("A rainfall raster under the
- * zones" above); the other columns are byte for byte those of the run without it. */
+ * zones" above); the other columns are byte for byte those of the run without it.  Several such rasters
+ * (opt->zone_rains / "zone_rains=<file1>[:<file2>...]", with the same unit) add rain_pixels,rain_valid and three columns
+ * per file to a zonal run that counts its pixels once (with one file: exactly what zone_rain adds). */
 int gcn10_run(const gcn10_run_options *opt);
 
 /* Path of the HIP library this process would load (diagnostics). */

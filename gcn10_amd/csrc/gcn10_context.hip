@@ -221,6 +221,10 @@ void gcn10_gpu_destroy(gcn10_gpu_ctx *ctx)
         (void)hipFree(ctx->ws.inflate);
     if (ctx->ws.lzw)
         (void)hipFree(ctx->ws.lzw);
+    if (ctx->ws.cell_tables)
+        (void)hipFree(ctx->ws.cell_tables);
+    if (ctx->d_cell_byte_tables)
+        (void)hipFree(ctx->d_cell_byte_tables);
     if (ctx->d_class_of)
         (void)hipFree(ctx->d_class_of);
     delete ctx;

@@ -86,6 +86,10 @@ struct gcn10_gpu_ctx {
     uint16_t *d_rain_tables = nullptr;  // n_rain_tables tables w[256], then a byte per table: w[1..100] never decrease
     int n_rain_tables = 0;              // 0: not set
 
+    // ---- the byte tables of the per-cell strips (gcn10_runoff_strip.hip: gcn10_gpu_set_cell_byte_tables) ----
+    uint8_t *d_cell_byte_tables = nullptr;  // n_cell_byte_tables tables of 256 bytes, then 256 bytes 255 ("in no cell")
+    int n_cell_byte_tables = 0;             // 0: not set
+
     // ---- the prepared tile (gcn10_soil_tile.hip) ----
     struct Tile {
         // Soil workspace of the prepared tile (one allocation, grown by gcn10_gpu_prepare_tile):
@@ -143,6 +147,7 @@ struct gcn10_gpu_ctx {
     bool codes_ready = false;           // the per-thread form of pass B (gcn10_deflate_codes.hip)
     bool fused_stats_ready = false;     // pass F-A (gcn10_deflate_fused_stats.hpp)
     bool fused_emit_ready = false;      // pass F-C (gcn10_deflate_fused_emit.hpp)
+    bool runoff_strip_ready = false;    // gcn10_runoff_strip.hip
 
     // ---- device workspaces of the codecs, grown by gcn10::grow_workspace ----
     struct Workspaces {
@@ -152,6 +157,8 @@ struct gcn10_gpu_ctx {
         size_t inflate_cap = 0;
         void *lzw = nullptr;        // segment bit strings + their lengths of the LZW tile encoder (gcn10_lzw.hip)
         size_t lzw_cap = 0;
+        void *cell_tables = nullptr;    // the table of every (cell row, fine column) of a per-cell strip (gcn10_runoff_strip.hip)
+        size_t cell_tables_cap = 0;
     } ws;
 };
 

@@ -2,7 +2,8 @@
 // shares: the soil view, the all-tables lookup image, the 16-pixel gather and the raster selection test.  Readers:
 // the strip kernels (gcn10_strip.hip), the fused encoder (gcn10_deflate_fused.hip), verify_strip (gcn10_verify.hip),
 // the pair histograms (gcn10_stats.hip, gcn10_zonal.hip), the average overviews (gcn10_overview.hip), the area
-// means (gcn10_aggregate.hip) and the sums on a model grid (gcn10_grid.hip, gcn10_grid_rain.hip, gcn10_zonal_rain.hip).  Their host side is gcn10::bind_soil / check_masks / grid_cap of
+// means (gcn10_aggregate.hip) and the sums on a model grid (gcn10_grid.hip, gcn10_grid_rain.hip, gcn10_zonal_rain.hip) and
+// the strips through a byte table per cell (gcn10_runoff_strip.hip).  Their host side is gcn10::bind_soil / check_masks / grid_cap of
 // gcn10_gpu_internal.hpp.
 #ifndef GCN10_SOIL_READERS_HPP
 #define GCN10_SOIL_READERS_HPP

@@ -371,6 +371,31 @@ int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t er
             }
             rc = set_str(&cfg->zone_rain_unit, val);
         }
+        else if (!strcmp(key, "runoff_rain"))
+            rc = set_str(&cfg->runoff_rain, val);
+        else if (!strcmp(key, "runoff_rain_unit")) {
+            double unit, lambda;
+
+            if (gcn10_parse_rain_unit(val, &unit, &lambda) != 0) {
+                fclose(f);
+                snprintf(err, errcap, "bad value for runoff_rain_unit: '%s' (unit[,lambda]: 0 < unit, 255 unit <= 650 mm, "
+                                      "0 <= lambda < 1)", val);
+                gcn10_config_free(cfg);
+                return -3;
+            }
+            rc = set_str(&cfg->runoff_rain_unit, val);
+        }
+        else if (!strcmp(key, "runoff_unit")) {
+            unsigned u;
+
+            if (gcn10_parse_runoff_unit(val, &u) != 0) {
+                fclose(f);
+                snprintf(err, errcap, "bad value for runoff_unit: '%s' (millimetres per count, 0.01 to 650)", val);
+                gcn10_config_free(cfg);
+                return -3;
+            }
+            rc = set_str(&cfg->runoff_unit, val);
+        }
         else if (!strcmp(key, "zones_shp_path"))
             rc = set_str(&cfg->zones_shp_path, val);
         else if (!strcmp(key, "zonal_output"))
@@ -436,5 +461,8 @@ void gcn10_config_free(gcn10_config *cfg)
     free(cfg->zone_rain_unit);
     free(cfg->rains);
     free(cfg->zone_rains);
+    free(cfg->runoff_rain);
+    free(cfg->runoff_rain_unit);
+    free(cfg->runoff_unit);
     memset(cfg, 0, sizeof *cfg);
 }

@@ -120,6 +120,9 @@ static void load_once(void)
     *(void **)(&g_api.zonal_sums_rain) = dlsym(h, "gcn10_gpu_zonal_sums_rain");
     /* and with a tuple of tables per item: needed by zone_rains=... runs only, which check for it */
     *(void **)(&g_api.zonal_sums_rains) = dlsym(h, "gcn10_gpu_zonal_sums_rains");
+    /* and the strips through a byte table per cell: needed by runoff_rain=... runs only, which check for them */
+    *(void **)(&g_api.set_cell_byte_tables) = dlsym(h, "gcn10_gpu_set_cell_byte_tables");
+    *(void **)(&g_api.runoff_strip) = dlsym(h, "gcn10_gpu_runoff_strip");
     if (g_api.abi_version() != GCN10_GPU_ABI_VERSION) {
         snprintf(g_err, sizeof g_err, "%s has ABI version %d, expected %d", g_path,
                  g_api.abi_version(), GCN10_GPU_ABI_VERSION);

@@ -305,7 +305,8 @@ int gcn10_rains_load(const char *const files[], int k, const gcn10_grid *g, uint
     return 0;
 }
 
-int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char *err, size_t errcap)
+int gcn10_rain_raster_load(const char *prefix, const char *path, gcn10_grid *grid, uint8_t **out, char *err,
+                           size_t errcap)
 {
     char why[1024] = "";
     gcn10_raster *ra = gcn10_raster_open(path, NULL, why, sizeof why);
@@ -317,21 +318,21 @@ int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char
     *out = NULL;
     memset(grid, 0, sizeof *grid);
     if (!ra) {
-        snprintf(err, errcap, "zone_rain: cannot read '%s': %s", path, why);
+        snprintf(err, errcap, "%s: cannot read '%s': %s", prefix, path, why);
         return -1;
     }
     gcn10_raster_info(ra, &w, &h, gt);
     if (memcmp(gt, none, sizeof none) == 0)
-        snprintf(err, errcap, "zone_rain: '%s' carries no geotransform", path);
+        snprintf(err, errcap, "%s: '%s' carries no geotransform", prefix, path);
     else if (!(gt[1] > 0.0) || !(gt[5] < 0.0) || gt[2] != 0.0 || gt[4] != 0.0 || !isfinite(gt[0]) || !isfinite(gt[3]) ||
              !isfinite(gt[1]) || !isfinite(gt[5]))
-        snprintf(err, errcap, "zone_rain: '%s' is rotated or not north up", path);
+        snprintf(err, errcap, "%s: '%s' is rotated or not north up", prefix, path);
     else if (w < 1 || h < 1 || (uint64_t)w * (uint64_t)h > (uint64_t)GCN10_GRID_MAX_CELLS)
-        snprintf(err, errcap, "zone_rain: '%s' has more than %d pixels", path, GCN10_GRID_MAX_CELLS);
+        snprintf(err, errcap, "%s: '%s' has more than %d pixels", prefix, path, GCN10_GRID_MAX_CELLS);
     else {
         bytes = malloc((size_t)w * (size_t)h);
         if (!bytes || gcn10_raster_read(ra, 0, 0, w, h, bytes, why, sizeof why) != 0) {
-            snprintf(err, errcap, "zone_rain: cannot read '%s': %s", path, bytes ? why : "out of memory");
+            snprintf(err, errcap, "%s: cannot read '%s': %s", prefix, path, bytes ? why : "out of memory");
             free(bytes);
         }
         else {
@@ -341,6 +342,11 @@ int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char
     }
     gcn10_raster_close(ra);
     return *out ? 0 : -1;
+}
+
+int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char *err, size_t errcap)
+{
+    return gcn10_rain_raster_load("zone_rain", path, grid, out, err, errcap);
 }
 
 int gcn10_zone_rains_load(const char *const files[], int k, gcn10_grid *grid, uint8_t *out[GCN10_MAX_RAINS], char *err,

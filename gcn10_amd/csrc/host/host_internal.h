@@ -204,6 +204,10 @@ struct gcn10_gpu_api {
     int (*zonal_sums_rains)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const gcn10_zone_span *,
                             const gcn10_zone_rains_item *, size_t, int, unsigned, unsigned, int, unsigned long long *,
                             gcn10_stream_t);
+    /* optional: NULL when the library has none (needed by runoff_rain=... only) */
+    int (*set_cell_byte_tables)(gcn10_gpu_ctx *, const uint8_t *, int);
+    int (*runoff_strip)(gcn10_gpu_ctx *, const uint8_t *, int, int, const int32_t *, const int32_t *, const int32_t *, int,
+                        int, const uint8_t *, unsigned, unsigned, uint8_t *const[GCN10_N_RASTERS], gcn10_stream_t);
 };
 const struct gcn10_gpu_api *gcn10_gpu_api_get(char *err, size_t errcap);
 

@@ -100,6 +100,15 @@ static void usage(FILE *fp)
             "\t\t\train_mm_rain<j>,runoff_mm_rain<j>,cn_runoff_rain<j> per file, each what --zone-rain\n"
             "\t\t\t<file_j> alone prints (one file: exactly the table of --zone-rain; config key\n"
             "\t\t\tzone_rains=...); not with --zone-rain, otherwise as --zone-rain\n"
+            "  --runoff-rain <file>\twrite, instead of the curve numbers, the runoff depth of every 10 m pixel under a\n"
+            "\t\t\trainfall raster (one Byte band with a geotransform, as --zone-rain takes it):\n"
+            "\t\t\trunoff_rasters_<cond>/q_<hc>_<arc>_<id>.tif, 255 = no value or no rain cell (config key\n"
+            "\t\t\trunoff_rain=...); not with --verify, --aggregate, --zones, --grid, --storm(s), --rain(s),\n"
+            "\t\t\t--zone-rain(s), --cog or --stats\n"
+            "  --runoff-rain-unit <unit>[,<lambda>]\n"
+            "\t\t\tas --rain-unit, for --runoff-rain (config key runoff_rain_unit=...)\n"
+            "  --runoff-unit <mm>\tmillimetres per count of the written rasters, 0.01 to 650 (default: the rain unit;\n"
+            "\t\t\tconfig key runoff_unit=...)\n"
             "  --help, -h\t\tshow this help and exit\n"
             "  --version, -v\tprint version and exit\n"
             "\n"
@@ -170,6 +179,12 @@ int main(int argc, char **argv)
             opt.zone_rains = argv[++i];
         else if (!strcmp(argv[i], "--zone-rain-unit") && i + 1 < argc)
             opt.zone_rain_unit = argv[++i];
+        else if (!strcmp(argv[i], "--runoff-rain") && i + 1 < argc)
+            opt.runoff_rain = argv[++i];
+        else if (!strcmp(argv[i], "--runoff-rain-unit") && i + 1 < argc)
+            opt.runoff_rain_unit = argv[++i];
+        else if (!strcmp(argv[i], "--runoff-unit") && i + 1 < argc)
+            opt.runoff_unit = argv[++i];
         else if (!strcmp(argv[i], "--zonal"))
             opt.zonal = true;
         else if (!strcmp(argv[i], "--zones") && i + 1 < argc) {

@@ -58,16 +58,18 @@ void gcn10_wlog(struct worker *w, const char *level, bool console, const char *f
 
 /* output path with the reference's non-overwrite rule: an existing file is left
  * alone and the new one gets a trailing underscore (src/cn.c:320-360) */
-static void output_path(char *out, size_t cap, const char *cond, const char *suffix, const char *hc, const char *arc,
+static void output_path(char *out, size_t cap, const struct run *r, const char *cond, const char *hc, const char *arc,
                         int block_id, bool overwrite)
 {
-    snprintf(out, cap, "cn_rasters_%s%s/cn_%s_%s_%d.tif", cond, suffix, hc, arc, block_id);  /* src/cn.c:308 */
+    /* cn_rasters_<cond>/cn_<hc>_<arc>_<id>.tif, src/cn.c:308 */
+    snprintf(out, cap, "%s_%s%s/%s_%s_%s_%d.tif", r->out_dir, cond, r->out_suffix, r->out_name, hc, arc, block_id);
     if (!overwrite) {
         FILE *f = fopen(out, "r");
 
         if (f) {
             fclose(f);
-            snprintf(out, cap, "cn_rasters_%s%s/cn_%s_%s_%d_.tif", cond, suffix, hc, arc, block_id); /* :341 */
+            snprintf(out, cap, "%s_%s%s/%s_%s_%s_%d_.tif", r->out_dir, cond, r->out_suffix, r->out_name, hc, arc,
+                     block_id);                                                                 /* :341 */
         }
     }
 }
@@ -97,7 +99,7 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
 
         if (!(r->cond_mask & (1u << c)))
             continue;
-        snprintf(dir, sizeof dir, "cn_rasters_%s%s", gcn10_conds[c], r->out_suffix);
+        snprintf(dir, sizeof dir, "%s_%s%s", r->out_dir, gcn10_conds[c], r->out_suffix);
         if (mkdir(dir, 0755) != 0 && errno != EEXIST) {
             wlog(w, "ERROR", true, "failed to create output directory %s", dir);       /* src/cn.c:250 */
             return -1;
@@ -107,8 +109,8 @@ int gcn10_create_outputs(struct worker *w, struct block_in *in)
         const int k = r->sel[q];
         char path[PATH_MAX];
 
-        output_path(path, sizeof path, gcn10_conds[k / 9], r->out_suffix, gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3],
-                    in->block_id, r->opt.overwrite);
+        output_path(path, sizeof path, r, gcn10_conds[k / 9], gcn10_hcs[(k % 9) / 3], gcn10_arcs[k % 3], in->block_id,
+                    r->opt.overwrite);
         if (r->cog)
             in->tifs[k] = gcn10_tiff_create_cog(path, in->W, in->H, in->gt, gcn10_raster_georef(w->esa),
                                                 cog_levels_of(in->W, in->H), err, sizeof err);
@@ -197,8 +199,12 @@ int gcn10_run_strips(struct worker *w, int W, int H, const uint8_t *d_block, con
         else {
             for (int k = 0; k < GCN10_N_RASTERS; k++)
                 outs[k] = b->d_out[k];             /* NULL for a raster this run does not produce */
-            if (g->cn_strip(w->ctx, d_esa, W, rows, d_cj + y0, r->cond_mask, r->table_mask, outs,
-                            w->s_kernel) != 0)
+            /* (a runoff_rain run: every value through the byte table of the pixel's rain cell) */
+            if ((w->runoff ? g->runoff_strip(w->ctx, d_esa, W, rows, d_cj + y0, w->runoff->d_cellx,
+                                             w->runoff->d_celly + y0, w->runoff->ncx, w->runoff->ncy,
+                                             w->runoff->d_cells, r->cond_mask, r->table_mask, outs, w->s_kernel)
+                           : g->cn_strip(w->ctx, d_esa, W, rows, d_cj + y0, r->cond_mask, r->table_mask, outs,
+                                         w->s_kernel)) != 0)
                 goto gpu_fail;
             /* encode the selected strips where they are */
             if (r->gpu_deflate &&

@@ -1,7 +1,8 @@
 /* pipeline_internal.h -- the worker and run state shared by run.c (the run's steps), pipeline.c (workers, a block's
  * strips), sink.c (strip buffers, sink jobs), pipeline_input.c (landcover input through the GPU decoder), launcher.c and
  * the kinds of run, and what the writer and the verifier have in common: the chunk stager (stage.c) and the overview
- * levels (levels.c).  A run is of one kind -- write (pipeline.c), aggregate.c, verify.c, zonal.c or grid.c -- and each
+ * levels (levels.c).  A run is of one kind -- write (pipeline.c), aggregate.c, verify.c, zonal.c, grid.c or
+ * runoff_raster.c -- and each
  * is a struct gcn10_mode beside its code; resolve() (run.c) leaves the run's in run.mode and the driver calls through
  * it.  Every kind takes a staged block over with gcn10_block_take, the one reader of the decoder's status words. */
 #ifndef GCN10_PIPELINE_INTERNAL_H
@@ -25,6 +26,7 @@ struct gcn10_zonal_state;
 struct gcn10_zonal_table;
 struct gcn10_grid_state;
 struct gcn10_grid_result;
+struct gcn10_runoff_state;
 
 /* ---- stage.c: chunks as they lie in the files -> pinned ring -> device, for gcn10_gpu_inflate_tiles ---- */
 
@@ -152,6 +154,7 @@ struct block_in {
     gcn10_grid_plan zr_gplan;               /* zone_rain: the block on the raster's grid, */
     gcn10_zone_rain_plan zr_cut;            /* ... and the zones' spans cut at its depth changes */
     gcn10_zone_rains_plan zrs_cut;          /* zone_rains: the spans cut where the byte of any layer changes */
+    gcn10_grid_plan rr_gplan;               /* runoff_rain: the block on the raster's grid, every pixel of the window */
 };
 
 struct worker {
@@ -211,6 +214,14 @@ struct worker {
     struct gcn10_verify_state *verify;
     struct gcn10_zonal_state *zonal;
     struct gcn10_grid_state *gridst;
+    struct gcn10_runoff_state *runoffst;    /* map and cell-byte buffers (runoff_raster.c) */
+    /* runoff_rain: what gcn10_run_strips hands gcn10_gpu_runoff_strip in the place of cn_strip, set by the mode around its
+     * call (NULL: cn_strip): the block's maps and the bytes of its cell rectangle, on the device */
+    const struct gcn10_runoff_strip_args {
+        const int32_t *d_cellx, *d_celly;
+        const uint8_t *d_cells;
+        int ncx, ncy;
+    } *runoff;
     double t_zone_plan, t_zone_accum;       /* zonal: seconds of the input side building spans, of the worker adding up */
     long n_win_gpu, n_win_gpu_lzw, n_win_host;  /* landcover windows through the GPU decoder (of them with LZW chunks),
                                                    through the host reader */
@@ -304,6 +315,17 @@ struct run {
     const char *zone_rain_file[GCN10_MAX_RAINS];    /* their names: cfg.zone_rain, or pointers into zone_rains_copy */
     uint8_t *zone_rain_layer[GCN10_MAX_RAINS];      /* [ny][nx] each: the counts of every raster, all on zone_rain_grid */
     uint16_t (*zone_rain_q)[256];           /* [256][256]: gcn10_rain_tables */
+    /* runoff_rain=...: the runoff depth of every pixel under a rainfall raster, written in the place of the curve numbers
+     * (runoff_raster.c) */
+    bool runoff_on;
+    double runoff_rain_unit, runoff_lambda;
+    unsigned runoff_u;                      /* hundredths of a millimetre per count of the written rasters */
+    gcn10_grid runoff_grid;                 /* the raster as a grid (gcn10_rain_raster_load) */
+    uint8_t *runoff_layer;                  /* [ny][nx]: its counts */
+    uint8_t (*runoff_t)[256];               /* [256][256]: gcn10_runoff_bytes of gcn10_rain_tables */
+    /* the names of a block's files: <out_dir>_<cond><out_suffix>/<out_name>_<hc>_<arc>_<id>.tif ("cn_rasters" and "cn"
+     * unless the mode says otherwise) */
+    const char *out_dir, *out_name;
 };
 
 double gcn10_now_seconds(void);
@@ -399,12 +421,15 @@ struct gcn10_mode {
     void (*end)(struct run *r);                             /* frees what its start made */
 };
 extern const struct gcn10_mode gcn10_mode_write, gcn10_mode_aggregate, gcn10_mode_verify, gcn10_mode_zonal,
-    gcn10_mode_grid;
+    gcn10_mode_grid, gcn10_mode_runoff;
 /* run.c's resolve() before it chooses the mode, no GPU opened yet: the refused combinations, the zones, the grid's
  * result; 0, or -1 with a line on stderr and nothing left behind */
 int gcn10_aggregate_start(struct run *r);
 int gcn10_zonal_start(struct run *r);
 int gcn10_grid_start(struct run *r);
+/* runoff_raster.c: the keys of a runoff_rain run -- the refusals in the order of gcn10_host.h, the units, the raster and
+ * its 256 byte tables; 0 (r->runoff_on says whether the run is one), or -1 with a line on stderr */
+int gcn10_runoff_start(struct run *r);
 int gcn10_input_setup(struct worker *w);
 void gcn10_input_teardown(struct worker *w);
 int gcn10_input_start(struct worker *w);

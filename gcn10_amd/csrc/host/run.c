@@ -15,7 +15,8 @@
 #define now_seconds gcn10_now_seconds
 
 /* What the config and the command line ask for, and every combination that is refused, before any GPU is opened.  A
- * write run unless verify, zonal, aggregate or grid is asked for: they refuse each other, so r->mode is set once. */
+ * write run unless verify, zonal, aggregate, grid or runoff_rain is asked for: they refuse each other, so r->mode is set
+ * once. */
 static int resolve(struct run *r)
 {
     const gcn10_run_options *opt = &r->opt;
@@ -24,6 +25,8 @@ static int resolve(struct run *r)
     char err[2048] = "";
 
     r->mode = &gcn10_mode_write;
+    r->out_dir = "cn_rasters";
+    r->out_name = "cn";
     if (!opt->config_path) {
         fprintf(stderr, "[rank 0] missing -c/--config <file>; see 'gcn10 -h' for usage.\n");   /* src/main.c:103-106 */
         return 1;
@@ -80,6 +83,11 @@ static int resolve(struct run *r)
     for (int k = 0; k < GCN10_N_RASTERS; k++)
         if ((r->cond_mask >> (k / 9)) & 1u && (r->table_mask >> (k % 9)) & 1u)
             r->sel[r->n_sel++] = k;
+    /* runoff rasters under a rainfall raster: everything it cannot go with, before any of those starts */
+    if (gcn10_runoff_start(r) != 0)
+        return 1;
+    if (r->runoff_on)
+        r->mode = &gcn10_mode_runoff;
     /* a rainfall raster, or several ("rains"): the runs they cannot go with, tested before any of them starts, and their
      * unit; the rasters themselves are read once the grid is known (gcn10_grid_start) */
     if (opt->rain) {
@@ -320,6 +328,8 @@ static int resolve(struct run *r)
     r->stats = r->cfg.stats != 0;
     r->nodata = r->cfg.nodata;
     r->fused = r->cfg.gpu_deflate == 2 && !r->lzw;     /* the fused encoder is DEFLATE-only */
+    if (r->runoff_on)
+        r->fused = false;       /* ... and makes curve numbers: the runoff strips go through the per-raster encoder */
     if (r->aggregate) {
         /* the aggregated rasters are made on the device and go through the per-raster GPU encoder, whatever
          * "gpu_deflate" says; they carry neither overviews nor statistics */
@@ -353,6 +363,7 @@ static int require(struct run *r)
 {
     const struct gcn10_gpu_api *g;
     char err[2048] = "", agg[48], grid[600], storm[600], rain[PATH_MAX + 8], zrain[PATH_MAX + 16], *rains = NULL, *zrains = NULL;
+    char rrain[PATH_MAX + 16];
     int rc = 0;
 
     r->gpu = g = gcn10_gpu_api_get(err, sizeof err);
@@ -374,6 +385,7 @@ static int require(struct run *r)
         }
         snprintf(rains, cap, "rains=%s", r->cfg.rains);
     }
+    snprintf(rrain, sizeof rrain, "runoff_rain=%s", r->runoff_on ? r->cfg.runoff_rain : "");
     snprintf(zrain, sizeof zrain, "zone_rain=%s", r->zone_rain_on && !r->zone_rains_key ? r->cfg.zone_rain : "");
     if (r->zone_rains_key) {
         const size_t cap = strlen(r->cfg.zone_rains) + 16;
@@ -408,6 +420,7 @@ static int require(struct run *r)
             { r->grid_on, g->grid_sums && g->grid_finish, "gcn10_gpu_grid_sums", grid },
             { r->verify, g->verify_strip && g->verify_buffers, "gcn10_gpu_verify_strip", "verify=1" },
             { r->lzw, g->lzw_strip && g->lzw_arena_bound, "gcn10_gpu_lzw_strip", "compress=lzw" },
+            { r->runoff_on, g->set_cell_byte_tables && g->runoff_strip, "gcn10_gpu_runoff_strip", rrain },
         };
 
         for (size_t i = 0; rc == 0 && i < sizeof needs / sizeof needs[0]; i++)
@@ -623,6 +636,13 @@ static int load(struct run *r)
                   "lambda = %.17g", tag, r->zone_rain_file[j], zg->nx, zg->ny, zg->dx, zg->dy, zg->xmin, zg->ymax,
                   r->zone_rain_unit, r->zone_rain_lambda);
         log0_line(r, "INFO", true, "%s: depths %u..%u counts, %zu cells without rain", tag, lo, hi, dry);
+    }
+    if (r->runoff_on) {
+        const gcn10_grid *zg = &r->runoff_grid;
+
+        log0_line(r, "INFO", true, "runoff_rain: %s, %d x %d cells of %.17g x %.17g from (%.17g, %.17g), unit = %.17g mm, "
+                  "lambda = %.17g, 1 count = %u/100 mm", r->cfg.runoff_rain, zg->nx, zg->ny, zg->dx, zg->dy, zg->xmin,
+                  zg->ymax, r->runoff_rain_unit, r->runoff_lambda, r->runoff_u);
     }
     if (r->n_workers > r->n_blocks) {       /* no worker (and no pinned memory) without a block */
         for (int i = r->n_blocks > 0 ? r->n_blocks : 1; i < r->n_workers; i++) {

@@ -11,6 +11,9 @@
  * parser and the 256 tables are here, the raster itself is read by grid.c (gcn10_rain_load).  Several of them in one run
  * (config key "rains") share the unit and the tables: the parser of the file list and the bytes of a cell from its 2 + K
  * words are here too.
+ *
+ * Per-pixel runoff rasters (config key "runoff_rain"): the 256 tables as bytes in an output unit, and the parser of that
+ * unit, are here; the run mode is runoff_raster.c.
  */
 #include "gcn10_host.h"
 
@@ -224,4 +227,44 @@ NO_CONTRACT int gcn10_zone_rain_values(uint64_t rain_pixels, uint64_t rain_sum, 
     gcn10_runoff_table(*rain_mm, lambda, q);
     *cn = gcn10_runoff_cn(s, n, sw, q);
     return 3;
+}
+
+void gcn10_runoff_bytes(const uint16_t q[256][256], unsigned u, uint8_t t[256][256])
+{
+    for (int b = 0; b < 256; b++) {
+        for (int v = 0; v < 255; v++) {
+            const unsigned r = (2u * (unsigned)q[b][v] + u) / (2u * u);
+
+            t[b][v] = (uint8_t)(r < 254u ? r : 254u);
+        }
+        t[b][255] = 255;
+    }
+}
+
+NO_CONTRACT unsigned gcn10_runoff_unit_of(double mm)
+{
+    const double r = floor(100.0 * mm + 0.5);
+
+    return !(r >= 1.0) ? 1u : (r > 65000.0 ? 65000u : (unsigned)r);
+}
+
+NO_CONTRACT int gcn10_parse_runoff_unit(const char *text, unsigned *u)
+{
+    char *end;
+    double x, r;
+
+    if (!text)
+        return -1;
+    /* a field as gcn10_parse_storm takes it: a sign, a digit or a point first, nothing but the number */
+    if (!(*text == '-' || *text == '+' || *text == '.' || (*text >= '0' && *text <= '9')))
+        return -1;
+    errno = 0;
+    x = strtod(text, &end);
+    if (end == text || errno != 0 || *end != '\0' || !isfinite(x))
+        return -1;
+    r = floor(100.0 * x + 0.5);
+    if (!(r >= 1.0) || !(r <= 65000.0))
+        return -1;
+    *u = (unsigned)r;
+    return 0;
 }

@@ -51,7 +51,7 @@ ABI_SYMBOLS = (
     "gcn10_gpu_set_weight_tables", "gcn10_gpu_grid_sums_storms", "gcn10_gpu_grid_finish_storms",
     "gcn10_gpu_grid_rain_item", "gcn10_gpu_set_rain_tables", "gcn10_gpu_grid_sums_rain", "gcn10_gpu_grid_finish_rain",
     "gcn10_gpu_zonal_sums_rain", "gcn10_gpu_grid_sums_rains", "gcn10_gpu_grid_finish_rains",
-    "gcn10_gpu_zonal_sums_rains",
+    "gcn10_gpu_zonal_sums_rains", "gcn10_gpu_set_cell_byte_tables", "gcn10_gpu_runoff_strip",
 )
 
 
@@ -175,6 +175,8 @@ def lib():
             "gcn10_gpu_zonal_sums_rains": (i, [vp, vp, i, i, vp, vp, vp, sz, i, u, u, i, vp, vp]),
             "gcn10_gpu_grid_sums_rains": (i, [vp, vp, i, i, vp, vp, vp, i, i, u, u, vp, i, vp, vp]),
             "gcn10_gpu_grid_finish_rains": (i, [vp, vp, i, sz, vp, i, vp, vp, vp, C.c_uint32, vp, vp]),
+            "gcn10_gpu_set_cell_byte_tables": (i, [vp, vp, i]),
+            "gcn10_gpu_runoff_strip": (i, [vp, vp, i, i, vp, vp, vp, i, i, vp, u, u, C.POINTER(vp), vp]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(L, name)
@@ -403,6 +405,25 @@ class Engine:
             arr[r] = outs[r] if r < len(outs) and outs[r] else None
         self._chk(lib().gcn10_gpu_cn_strip(self._ctx, esa_d, W, rows, cj_d, cond_mask, table_mask,
                                            arr, stream), "gcn10_gpu_cn_strip")
+
+    def set_cell_byte_tables(self, t):
+        """k tables of 256 bytes ([k][256], 1 <= k <= 256) for runoff_strip, one of them named per cell
+        (gcn10_gpu_set_cell_byte_tables).  Independent of set_tables and of the weight and rain tables.  Synchronous."""
+        a = np.ascontiguousarray(t, np.uint8).reshape(-1, 256)
+        self._chk(lib().gcn10_gpu_set_cell_byte_tables(self._ctx, a.ctypes.data, a.shape[0]),
+                  "gcn10_gpu_set_cell_byte_tables")
+
+    def runoff_strip(self, esa_d: int, W: int, rows: int, cj_d: int, cellx_ptr: int, celly_ptr: int, ncx: int, ncy: int,
+                     cell_table_ptr: int, cond_mask: int, table_mask: int, outs: Sequence[Optional[int]], stream=None):
+        """cn_strip with every value v sent through T[cell_table[celly[y]][cellx[x]]][v] of set_cell_byte_tables, 255
+        where a map names no cell; cell_table_ptr: uint8[ncy][ncx] on the device (gcn10_gpu_runoff_strip).
+        Asynchronous on `stream`."""
+        arr = (C.c_void_p * N_RASTERS)()
+        for r in range(N_RASTERS):
+            arr[r] = outs[r] if r < len(outs) and outs[r] else None
+        self._chk(lib().gcn10_gpu_runoff_strip(self._ctx, esa_d, W, rows, cj_d, cellx_ptr, celly_ptr, ncx, ncy,
+                                               cell_table_ptr, cond_mask, table_mask, arr, stream),
+                  "gcn10_gpu_runoff_strip")
 
     # -- output encode (src/raster.c:204-219 on the GPU) ----------------------
     def _encode_into_arena(self, launch, where: str, n: int, W: int, rows: int, cap: int, stream, poison: Optional[int],

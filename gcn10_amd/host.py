@@ -148,6 +148,15 @@ def lib():
         L.gcn10_rain_tables.argtypes = [C.c_double, C.c_double, np.ctypeslib.ndpointer(dtype=np.uint16,
                                                                                       flags="C_CONTIGUOUS")]
         L.gcn10_rain_tables.restype = None
+        L.gcn10_runoff_bytes.argtypes = [np.ctypeslib.ndpointer(dtype=np.uint16, flags="C_CONTIGUOUS"), C.c_uint,
+                                         np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")]
+        L.gcn10_runoff_bytes.restype = None
+        L.gcn10_parse_runoff_unit.argtypes = [cp, C.POINTER(C.c_uint)]
+        L.gcn10_parse_runoff_unit.restype = C.c_int
+        L.gcn10_runoff_unit_of.argtypes = [C.c_double]
+        L.gcn10_runoff_unit_of.restype = C.c_uint
+        L.gcn10_rain_raster_load.argtypes = [cp, cp, C.POINTER(Grid), C.POINTER(vp), cp, C.c_size_t]
+        L.gcn10_rain_raster_load.restype = C.c_int
         L.gcn10_parse_rains.argtypes = [cp, C.POINTER(vp), C.POINTER(cp), C.POINTER(C.c_int)]
         L.gcn10_parse_rains.restype = C.c_int
         L.gcn10_rains_load.argtypes = [C.POINTER(cp), C.c_int, C.POINTER(Grid), C.POINTER(vp), cp, C.c_size_t]
@@ -250,6 +259,12 @@ class ConfigZoneRains(ConfigRains):
     """``gcn10_config`` with the key of several rainfall rasters under zones, appended behind ``ConfigRains`` as the C
     struct appends it."""
     _fields_ = [("zone_rains", C.c_char_p)]
+
+
+class ConfigRunoffRain(ConfigZoneRains):
+    """``gcn10_config`` with the keys of the runoff rasters under a rainfall raster, appended behind ``ConfigZoneRains``
+    as the C struct appends them."""
+    _fields_ = [("runoff_rain", C.c_char_p), ("runoff_rain_unit", C.c_char_p), ("runoff_unit", C.c_char_p)]
 
 
 assert C.sizeof(Config) % 8 == 0
@@ -508,6 +523,26 @@ def rain_tables(unit: float = 1.0, lam: float = 0.2) -> np.ndarray:
     return q
 
 
+def runoff_bytes(q: np.ndarray, u: int) -> np.ndarray:
+    """uint8[256][256]: the tables of rain_tables as bytes of an output unit of u hundredths of a millimetre, round half
+    up, saturating at 254, 255 kept (``gcn10_runoff_bytes``)."""
+    q = np.ascontiguousarray(q, np.uint16)
+    if q.shape != (256, 256) or int(u) < 1:
+        raise ValueError("runoff_bytes: q is uint16[256][256], u >= 1")
+    t = np.zeros((256, 256), np.uint8)
+    lib().gcn10_runoff_bytes(q, int(u), t)
+    return t
+
+
+def parse_runoff_unit(text: str) -> int:
+    """"<mm>" -> the output unit in hundredths of a millimetre (``gcn10_parse_runoff_unit``); raises HostError for any
+    other text."""
+    u = C.c_uint()
+    if lib().gcn10_parse_runoff_unit(text.encode(), C.byref(u)) != 0:
+        raise HostError("bad value for runoff_unit: '%s' (millimetres per count, 0.01 to 650)" % text)
+    return u.value
+
+
 def rain_load(path: str, grid) -> np.ndarray:
     """The rainfall raster of the grid (a dict as parse_grid returns it), uint8[ny][nx] (``gcn10_rain_load``); raises
     HostError with the run's refusal text when the file cannot be read, has another size or does not lie on the grid."""
@@ -590,6 +625,27 @@ def zone_rain_load(path: str):
         return grid, np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), (n,)).copy().reshape(g.ny, g.nx)
     finally:
         lib().free_(out)
+
+
+def rain_raster_load(prefix: str, path: str):
+    """zone_rain_load with the messages under the key name `prefix` (``gcn10_rain_raster_load``): a runoff_rain run
+    passes "runoff_rain"."""
+    g = Grid()
+    out = C.c_void_p()
+    err = C.create_string_buffer(4096 + 512)
+    if lib().gcn10_rain_raster_load(prefix.encode(), os.fsencode(path), C.byref(g), C.byref(out), err, len(err)) != 0:
+        raise HostError(err.value.decode(errors="replace"))
+    try:
+        grid = {name: getattr(g, name) for name, _t in Grid._fields_}
+        n = g.nx * g.ny
+        return grid, np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), (n,)).copy().reshape(g.ny, g.nx)
+    finally:
+        lib().free_(out)
+
+
+def runoff_unit_of(mm: float) -> int:
+    """The output unit, in hundredths of a millimetre, that stands for a rain unit of `mm` (``gcn10_runoff_unit_of``)."""
+    return lib().gcn10_runoff_unit_of(float(mm))
 
 
 def zone_rain_values(rain_pixels: int, rain_sum: int, unit: float, lam: float, s: int, n: int, sw: int):
@@ -694,7 +750,7 @@ def zone_rains_cut(plan: dict, W: int, H: int, gplan: dict, rains, max_span_px: 
 
 def parse_config(path: str) -> dict:
     """src/config.c:44-114 -> dict of the keys; raises HostError like the reference aborts."""
-    cfg = ConfigZoneRains()
+    cfg = ConfigRunoffRain()
     err = C.create_string_buffer(1024)
     rc = lib().gcn10_config_parse(os.fsencode(path), C.cast(C.pointer(cfg), C.POINTER(Config)), err, 1024)
     if rc != 0:
@@ -702,7 +758,7 @@ def parse_config(path: str) -> dict:
     out = {}
     for name, _t in (Config._fields_ + ConfigFull._fields_ + ConfigGrid._fields_ + ConfigStorm._fields_ +
                      ConfigStorms._fields_ + ConfigRain._fields_ + ConfigZoneRain._fields_ + ConfigRains._fields_ +
-                     ConfigZoneRains._fields_):
+                     ConfigZoneRains._fields_ + ConfigRunoffRain._fields_):
         v = getattr(cfg, name)
         out[name] = v.decode() if isinstance(v, bytes) else list(v) if isinstance(v, C.Array) else v
     lib().gcn10_config_free(C.cast(C.pointer(cfg), C.POINTER(Config)))

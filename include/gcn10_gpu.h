@@ -47,7 +47,8 @@ extern "C" {
  *    the sums with a weight table per cell (gcn10_gpu_set_rain_tables, gcn10_gpu_grid_sums_rain,
  *    gcn10_gpu_grid_finish_rain, gcn10_gpu_grid_rain_item); the sums per zone with a weight table per piece of a zone
  *    (gcn10_gpu_zonal_sums_rain); the sums with several weight tables per cell (gcn10_gpu_grid_sums_rains,
- *    gcn10_gpu_grid_finish_rains).
+ *    gcn10_gpu_grid_finish_rains); the rasters of a strip through a byte table per cell
+ *    (gcn10_gpu_set_cell_byte_tables, gcn10_gpu_runoff_strip).
  *    Removed within 3: the four timing-experiment options of gcn10_gpu_set_option (round 3); they are unknown names now. */
 #define GCN10_GPU_ABI_VERSION 3
 
@@ -648,6 +649,40 @@ int gcn10_gpu_verify_buffers(gcn10_gpu_ctx *ctx, const uint8_t *const want[GCN10
  * is hipEventSynchronize, which spins; n > 0: it queries the event and sleeps n microseconds in between -- what a
  * host pipeline's waiting threads want). */
 int gcn10_gpu_set_option(gcn10_gpu_ctx *ctx, const char *name, int value);
+
+/* The rasters of a strip through a byte table per cell of a coarse grid (config key runoff_rain=...: the per-pixel runoff
+ * depth under a rainfall raster).  Added in ABI 3 without a version change, as the rain calls were; the host looks them
+ * up for runoff_rain runs only.
+ *
+ * gcn10_gpu_set_cell_byte_tables: t[k][256], 1 <= k <= GCN10_GPU_MAX_CELL_BYTE_TABLES tables of bytes per raster value
+ *   (copied).  Synchronous.  Independent of the weight and the rain tables, and a later gcn10_gpu_set_tables does not
+ *   invalidate them -- they are functions of the value, not of the lookup tables.  A second call replaces the first.
+ * gcn10_gpu_runoff_strip: esa, W, rows, cj, the masks, out[] and the prepared tile are those of gcn10_gpu_cn_strip
+ *   (unselected entries of out[] are ignored; out[] must be ordinary device allocations).  cellx_dev[W] and
+ *   celly_dev[rows] are the maps of gcn10_gpu_grid_sums_rain, celly pointing at the strip's first row: an entry outside
+ *   0..ncx-1 or 0..ncy-1 means "in no cell"; no minimum cell size and no order are assumed -- entries may decrease or
+ *   repeat, and a cell may be one pixel wide.  For every selected raster r and pixel (x, y), with v what
+ *   gcn10_gpu_cn_strip writes there:
+ *       out[r][y * W + x] = T[cell_table[celly[y] * ncx + cellx[x]]][v]    if both maps name a cell,
+ *                           255                                            otherwise;
+ *   a cell_table entry >= k counts as table 0, the rule of the rain sums.  The library applies T as given, T[t][255]
+ *   included: it knows nothing about runoff.  Any W >= 1, any alignment of esa and out[]; nothing at or beyond W * rows
+ *   is read or written in any raster; cutting the rows into several calls gives the same bytes.  Asynchronous on
+ *   `stream`; the call expands cell_table through cellx into a workspace of the context first (2 bytes per column and
+ *   cell row, on `stream`), so the calls of one context are made on one stream or ordered by the caller.  Honours
+ *   gcn10_gpu_time_next_strip (the strip kernel, not the expansion).
+ *   Kernel names in profiles: runoff_strip_kernel<256> (k <= 32), runoff_strip_kernel<1024>, expand_cell_tables_kernel.
+ * Errors: GCN10_E_INVAL: bad masks, W, rows, ncx or ncy <= 0, more than 2^31-1 pixels, null pointers (a selected out[r]
+ *   among them), k outside 1..256 or null tables; GCN10_E_STATE: no lookup tables, no tile prepared for W, no byte tables
+ *   ("call gcn10_gpu_set_cell_byte_tables first"), or a device whose workgroups cannot hold the tables in LDS.  A
+ *   refused call writes nothing. */
+#define GCN10_GPU_MAX_CELL_BYTE_TABLES 256
+int gcn10_gpu_set_cell_byte_tables(gcn10_gpu_ctx *ctx, const uint8_t *t /* [k][256] */, int k);
+int gcn10_gpu_runoff_strip(gcn10_gpu_ctx *ctx, const uint8_t *esa, int W, int rows, const int32_t *cj,
+                           const int32_t *cellx_dev, const int32_t *celly_dev, int ncx, int ncy,
+                           const uint8_t *cell_table_dev /* [ncy][ncx] */,
+                           unsigned cond_mask, unsigned table_mask,
+                           uint8_t *const out[GCN10_N_RASTERS], gcn10_stream_t stream);
 
 /* Measurement: the next gcn10_gpu_cn_strip launch records `start` / `stop` as part of
  * the kernel dispatch itself (hipExtLaunchKernel), so gcn10_gpu_event_elapsed_ms gives

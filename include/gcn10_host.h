@@ -163,6 +163,12 @@ typedef struct gcn10_config {
     char *zone_rains;       /* "zone_rains": <file1>[:<file2>...] (gcn10_parse_rains): 1 to GCN10_MAX_RAINS rainfall rasters
                                as "zone_rain" takes one, all in one zonal run that counts its pixels once (gcn10_zone_rains_load);
                                "zone_rain_unit" holds for all of them; not together with "zone_rain"; absent = off */
+    char *runoff_rain;      /* "runoff_rain": a one-band Byte GeoTIFF with a geotransform, the rainfall depth in counts; the
+                               run writes the runoff depth of every pixel instead of its curve number ("Runoff rasters under
+                               a rainfall raster" below); absent = off */
+    char *runoff_rain_unit; /* "runoff_rain_unit": <unit>[,<lambda>] as "rain_unit"; needs "runoff_rain" */
+    char *runoff_unit;      /* "runoff_unit": <mm> per count of the written rasters (gcn10_parse_runoff_unit; default: the
+                               rain unit); needs "runoff_rain" */
 } gcn10_config;
 
 enum { GCN10_COMPRESS_DEFLATE = 0, GCN10_COMPRESS_LZW = 1 };
@@ -186,7 +192,7 @@ int gcn10_parse_zonal(const char *text, int *zonal);        /* "0" | "1".  0, or
 int gcn10_parse_aggregate(const char *text, int *factor);
 
 /* Returns 0; -1 cannot open (message in err); -3 a bad "lookups" / "conditions" / "compress" / "cog" /
- * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" / "rain_unit" / "zone_rain_unit" / "rains" value; -2 a required key is missing
+ * "overview_resampling" / "stats" / "nodata" / "verify" / "zonal" / "zones_id_field" / "aggregate" / "grid" / "storm" / "storms" / "rain_unit" / "zone_rain_unit" / "rains" / "runoff_rain_unit" / "runoff_unit" value; -2 a required key is missing
  * (the reference aborts in both cases, src/config.c:50-54, 107-113). */
 int gcn10_config_parse(const char *path, gcn10_config *cfg, char *err, size_t errcap);
 void gcn10_config_free(gcn10_config *cfg);
@@ -529,6 +535,36 @@ void gcn10_rain_tables(double unit, double lambda, uint16_t q[256][256]);
 enum { GCN10_RAIN_E_READ = -1, GCN10_RAIN_E_SIZE = -2, GCN10_RAIN_E_GEOTRANSFORM = -3 };
 int gcn10_rain_load(const char *path, const gcn10_grid *g, uint8_t **out, char *err, size_t errcap);
 
+/* Per-pixel runoff depth under a rainfall raster (config key "runoff_rain", --runoff-rain): the tables of
+ * gcn10_rain_tables as bytes of an output unit.  u: the unit in hundredths of a millimetre per count, u >= 1.  Integers
+ * only: t[b][255] = 255 (no value stays no value); for v < 255, t[b][v] = min(254, (2 * q[b][v] + u) / (2 * u)): round
+ * half up, saturating at 254.  q[b][v] <= q[b][100] = round(100 * b * unit), so with u = the rain unit in hundredths no
+ * entry of a table b < 255 saturates: its largest is b.  (Table 255 alone does: its largest entry would be 255.) */
+void gcn10_runoff_bytes(const uint16_t q[256][256], unsigned u, uint8_t t[256][256]);
+/* "<mm>": the output unit in millimetres per count, one field read as gcn10_parse_storm reads its own;
+ * *u = floor(100 * x + 0.5) in plain IEEE double, accepted iff 1 <= *u <= 65000.  0, or -1 for another text. */
+int gcn10_parse_runoff_unit(const char *text, unsigned *u);
+/* The output unit that stands for a rain unit of `mm` millimetres per count: floor(100 * mm + 0.5) by the same
+ * arithmetic, at least 1 (the default of "runoff_unit"). */
+unsigned gcn10_runoff_unit_of(double mm);
+
+/* Runoff rasters under a rainfall raster (config keys "runoff_rain", "runoff_rain_unit", "runoff_unit"; --runoff-rain,
+ * --runoff-rain-unit, --runoff-unit): a sixth kind of run, which writes for every block and selected raster
+ *     runoff_rasters_<cond>/q_<hc>_<arc>_<id>.tif
+ * with the size, geotransform, tiling, tags and overwrite rule of the block's CN raster.  The rainfall raster follows the
+ * rules of "zone_rain" (one Byte band, north-up geotransform, the landcover's CRS, at most GCN10_GRID_MAX_CELLS pixels;
+ * it IS a gcn10_grid; messages under "runoff_rain:") and is read once, before any GPU is opened.  A pixel's rain cell is
+ * the one gcn10_grid_plan_block(grid, W, H, gt_block, NULL, ...) names: there is no ownership box, every pixel of the
+ * window is written.  The value of a pixel with curve number v (what the CN raster holds) under a cell of byte b is
+ *     t[b][v],  t = gcn10_runoff_bytes(gcn10_rain_tables(unit, lambda), u),
+ * that is the runoff depth Q(b * unit, v) in counts of u / 100 mm, rounded half up, at most 254; 255 where the CN raster
+ * holds 255 and where the pixel lies in no rain cell.  A block that meets no rain cell still writes its files, all 255.
+ * Allowed with it: compress=lzw, nodata, lookups, conditions, direct_io, -l, -o, launcher ranks.  Refused, each with
+ * one "[rank 0] runoff_rain cannot be combined with <what>" line before any GPU is opened, tested in THIS order:
+ *     --verify, aggregate, --zonal, grid, storm, storms, rain, rains, zone_rain, zone_rains, cog, stats
+ * (the last two compute from CN, not from these bytes); before them "runoff_rain_unit needs runoff_rain" and
+ * "runoff_unit needs runoff_rain", then the bad values of the two units, then the raster's own four messages. */
+
 /* Several rainfall rasters in one grid run (config key "rains", --rains): K = 1 to GCN10_MAX_RAINS files, each by every
  * rule of "rain", one unit and one set of 256 tables (gcn10_rain_tables) for all -- only the byte of a cell differs from
  * layer to layer.  The pixels of a block are counted once: the sums carry 2 + K words per (raster, cell), word 2 + j the
@@ -582,6 +618,10 @@ int gcn10_zone_rain_values(uint64_t rain_pixels, uint64_t rain_sum, double unit,
  * reader reports 0, 1, 0, 0, 0, 1 then), "zone_rain: '<file>' is rotated or not north up", "zone_rain: '<file>' has
  * more than <GCN10_GRID_MAX_CELLS> pixels". */
 int gcn10_zone_rain_load(const char *path, gcn10_grid *grid, uint8_t **out, char *err, size_t errcap);
+/* The same reader with the four messages under another key's name ("<prefix>: cannot read ...", ...):
+ * gcn10_zone_rain_load is this with prefix "zone_rain", a runoff_rain run passes "runoff_rain". */
+int gcn10_rain_raster_load(const char *prefix, const char *path, gcn10_grid *grid, uint8_t **out, char *err,
+                           size_t errcap);
 /* The spans of a block's plan cut where the rainfall byte changes -- the input of gcn10_gpu_zonal_sums_rain (the same
  * item struct as in gcn10_gpu.h).  cellx[W], celly[H], cx0, cy0: the maps of gcn10_grid_plan_block for the block on the
  * raster's grid (column x lies in raster column cellx[x] + cx0; a negative entry: in none; both NULL: the block meets no
@@ -688,6 +728,9 @@ typedef struct gcn10_run_options {
     const char *zone_rain_unit; /* --zone-rain-unit <unit>[,<lambda>]: overrides the config key "zone_rain_unit" */
     const char *rains;          /* --rains <file1>[:<file2>...]: overrides the config key "rains" */
     const char *zone_rains;     /* --zone-rains <file1>[:<file2>...]: overrides the config key "zone_rains" */
+    const char *runoff_rain;    /* --runoff-rain <file>: overrides the config key "runoff_rain" */
+    const char *runoff_rain_unit;   /* --runoff-rain-unit <unit>[,<lambda>]: overrides the config key "runoff_rain_unit" */
+    const char *runoff_unit;    /* --runoff-unit <mm>: overrides the config key "runoff_unit" */
 } gcn10_run_options;
 
 /* ------------------------------------------------------------------------ */
